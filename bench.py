@@ -14,13 +14,19 @@ One process per GPU; the ranks all-gather the 13 floats / proposal (R, t, score)
 (fewer than 16 proposals per GPU) replay the step from a hipGraph (sam6d_hip.pem.PemGraph: one graph launch instead of ~250 kernel
 launches); at B = 32 the eager launch sequence is the faster one and is what is timed (--graph 1 / 0 force either).
 
-Prints ONE JSON line (rank 0).  Beside the contract's keys:
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints ONE JSON line (rank 0) with
+the headline keys (metric, value, unit, higher_is_better, dtype, ms_per_step, config) and
+  paths             which weight-guarded kernel routes this weight set takes
+  per_rank_ms, allgather_ms   (N > 1) every rank's own time per step and the all-gather's
+
+--dump-outputs DIR also writes the poses the last timed step computed (pred_R, pred_t, pred_pose_score, float32 .npy, global proposal
+order) for output-for-output comparisons of two builds; the inputs and weights are seeded, so the same arguments give the same inputs.
+
+--full adds everything else the line carries (each measured after the timed region):
   roofline          the dominant kernel (rpe_score_kernel): executed fp16-MFMA flops / dense fp16 peak, launch durations from HIP events
                     around the kernel in eager steps right behind the timed region (events cannot be recorded inside a captured graph);
                     the three-product yardstick of rounds 1-3 as `frac_three_product_yardstick`
   sustained         the same step for >= 3 s of continuous replays after the timed K steps (the chip lowers its clock under load)
-  paths             which weight-guarded kernel routes this weight set takes
-  per_rank_ms, allgather_ms   (N > 1) every rank's own time per step and the all-gather's
   latency           B = 1 and B = 25 (one proposal: config 1's shape; a strong-scaled shard of config 4), eager and graph
   config4           (config2 runs, N = 1) the 200-proposal scene in one call on this GPU
   fallbacks         the cost of the routes a different weight set may take (three-product stage 1, materialised embedding)
@@ -325,6 +331,14 @@ def bench_fallbacks(dev, sd, d, steps=5):
     return out
 
 
+def dump_outputs(dirname, R, t, score):
+    """--dump-outputs: what a caller of the timed path receives (Net's pred_R, pred_t, pred_pose_score) as float32 .npy files."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, x in (("pred_R", R), ("pred_t", t), ("pred_pose_score", score)):
+        np.save(os.path.join(dirname, name + ".npy"), x.detach().to("cpu", torch.float32).numpy())
+
+
 def _stub_match(inp):
     """--stub-compute (CPU test hook, tests/test_bench_launcher.py): a deterministic stand-in for pem_match that depends on every
     input of a proposal and on nothing else, so that the sharding / gather / unshard bookkeeping can be checked bit for bit without a GPU."""
@@ -345,21 +359,27 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", choices=("config2", "config4"), default="config2")
-    ap.add_argument("--cpu-proposals", type=int, default=8, help="proposals in the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--cpu-proposals", type=int, default=8, help="--full: proposals in the CPU-baseline sample (0 = skip)")
     ap.add_argument("--batch", type=int, default=B_PER_GPU, help="config2: proposals per GPU")
     ap.add_argument("--graph", type=int, default=-1, help="1: replay the step from a hipGraph; 0: eager launches; -1 (default): the graph "
                     "where the eager step is bound by the host's launch rate (fewer than 16 proposals per GPU), eager otherwise -- measured "
                     "in round 4: at B = 32 the replay is 1-2 %% SLOWER than the eager sequence (7.22 against 7.09 ms), at B = 1 it is what "
                     "removes the launch-rate bound (`latency` in the JSON line)")
     ap.add_argument("--microbatch", type=int, default=0, help="slices of the batch on concurrent streams (0 = the default for the mode)")
-    ap.add_argument("--sustained-seconds", type=float, default=3.0, help="continuous steps after the timed region (0 = skip)")
-    ap.add_argument("--no-ism", action="store_true", help="skip the ISM (config 3) leg reported beside the PEM metric")
-    ap.add_argument("--no-config5", action="store_true", help="skip the 4096-point (config 5) leg reported beside the PEM metric")
-    ap.add_argument("--no-extras", action="store_true", help="skip latency / config4 / fallback legs")
+    ap.add_argument("--sustained-seconds", type=float, default=3.0, help="--full: seconds of continuous steps after the timed region (0 = skip)")
+    ap.add_argument("--no-ism", action="store_true", help="--full: skip the ISM (config 3) leg reported beside the PEM metric")
+    ap.add_argument("--no-config5", action="store_true", help="--full: skip the 4096-point (config 5) leg reported beside the PEM metric")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip latency / config4 / fallback legs")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo for the CPU rehearsal)")
     ap.add_argument("--stub-compute", action="store_true", help="CPU test hook: replace the GPU path by a deterministic stand-in")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline: sustained clock, rooflines, "
+                    "latency / config4 / fallback legs, ISM (config 3), config 5 and the CPU baseline (each still subject to the --no-* / "
+                    "--cpu-proposals / --sustained-seconds switches)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the poses of the last timed step to DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher: become one -- N fresh children, started before anything in this process touches the GPU
@@ -392,7 +412,7 @@ def main():
     sync = (lambda: None) if stub else torch.cuda.synchronize
 
     from sam6d_hip import synth
-    from sam6d_hip.parallel import gather_poses, shard_indices, unshard, pack_poses
+    from sam6d_hip.parallel import gather_poses, shard_indices, unshard, pack_poses, unpack_poses
     pem = _lib = W = sd = None
     if not stub:
         import sam6d_hip
@@ -491,6 +511,8 @@ def main():
         g = pack_poses(*out).cpu() if world > 1 else pack_poses(*out).cpu()
         allp = unshard(g, CONFIG4_TOTAL, world) if world > 1 else g[:CONFIG4_TOTAL]
         poses_sha = hashlib.sha256(allp.contiguous().numpy().tobytes()).hexdigest()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *(unpack_poses(allp) if cfg4 else out))
 
     if stub:
         if rank == 0:
@@ -506,7 +528,7 @@ def main():
 
     # ------------------------------------------------------------------------------------------------ sustained clock
     sustained = None
-    if args.sustained_seconds > 0:
+    if args.full and args.sustained_seconds > 0:
         n = 0
         ts = time.perf_counter()
         while True:
@@ -541,7 +563,7 @@ def main():
         return pem.pem_match(*margs, W, d["rand"], cfg=cfg, template_ids=tids)
 
     prof = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         n_inst = max(1, min(args.steps, 5))
         pem.PROFILE_NAMES = {kname}
         pem.PROFILE = {}
@@ -557,7 +579,8 @@ def main():
         prof.update(pem.PROFILE)
         pem.PROFILE, pem.PROFILE_NAMES = None, None
 
-    if rank == 0:
+    roofline, extra = None, {}
+    if rank == 0 and args.full:
         ev = prof.get(kname, [])
         ms = sorted(a.elapsed_time(b) for a, b in ev)
         k_ms = sum(ms) / max(1, len(ms))
@@ -666,6 +689,7 @@ def main():
                 "traffic": (ft // mb) if ft else None, "traffic_recorded": _rec((ft // mb) if ft else None),
                 "launch_ms": ms1, "launches_timed": len(f_ms), "algorithmic_mb_per_launch": alg / 1e6}
 
+    if rank == 0:
         if cfg4:
             metric = "proposals/sec through PEM match+SVD (LM-O-style scene, 200 proposals of 8 objects round-robin over the GPUs); pose Δ vs CPU ref"
             workload = ("ONE scene of %d proposals of %d objects (SURVEY 8d config 4), proposal b on rank b %% %d: %d per GPU; unique "
@@ -689,8 +713,9 @@ def main():
                                   "weights, DESIGN 4 'Mode 2' -- config 5 is measured in the default mode, key `config5`)" if mode == 2 else
                                   "fp16x3 split-precision MFMA, fp32 accumulate (~1e-6 rel.)" if split else "exact fp32 MFMA")},
             "paths": paths,
-            "roofline": roofline,
         }
+        if args.full:
+            res["roofline"] = roofline
         if graph_error:
             res["config"]["graph_error"] = graph_error
         if sustained:
@@ -701,7 +726,7 @@ def main():
         if poses_sha:
             res["poses_sha256"] = poses_sha
         res.update(extra)
-        extras = world == 1 and not args.no_extras
+        extras = args.full and world == 1 and not args.no_extras
         if extras:
             try:
                 res["latency"] = bench_latency(dev, W, args.graph != 0)
@@ -716,17 +741,17 @@ def main():
                     res["fallbacks"] = bench_fallbacks(dev, sd, d)
                 except Exception as e:
                     res["fallbacks"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if world == 1 and not args.no_ism:
+        if args.full and world == 1 and not args.no_ism:
             try:
                 res["ism_config3"] = bench_ism(dev)
             except Exception as e:  # the headline line must not depend on the side measurement
                 res["ism_config3"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if world == 1 and not args.no_config5 and mode == 1:
+        if args.full and world == 1 and not args.no_config5 and mode == 1:
             try:
                 res["config5"] = bench_config5(dev, W)
             except Exception as e:
                 res["config5"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if args.cpu_proposals > 0 and world == 1:
+        if args.full and args.cpu_proposals > 0 and world == 1:
             # host cores for the baseline: the GPU box gives a 1-GPU job a share of 16 cores (more threads only
             # oversubscribe the shared host: 256 threads ran the same port 20x slower)
             threads = min(len(os.sched_getaffinity(0)), 16)

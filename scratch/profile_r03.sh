@@ -3,12 +3,12 @@
 # rocprofv3 run (kernel-trace only beside --pmc).  Raw output stays under /tmp on the GPU box; the summaries go to gpurun_out/.
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-CMD="python3 $R/bench.py --steps 10 --warmup 3 --cpu-proposals 0 --no-ism --no-config5"
+CMD="python3 $R/bench.py --full --steps 10 --warmup 3 --cpu-proposals 0 --no-ism --no-config5"
 rm -rf /tmp/p3 && mkdir -p /tmp/p3
 rocprofv3 --kernel-trace --stats -d /tmp/p3/stats -o out --output-format csv -- $CMD > /tmp/p3/stats.log 2>&1
 cp /tmp/p3/stats/out_kernel_stats.csv $R/gpurun_out/r03_kernel_stats.csv 2>/dev/null || find /tmp/p3/stats -name "*kernel_stats.csv" -exec cp {} $R/gpurun_out/r03_kernel_stats.csv \;
 tail -1 /tmp/p3/stats.log | cut -c1-400 > $R/gpurun_out/r03_bench_under_rocprof.json
-CMD2="python3 $R/bench.py --steps 2 --warmup 1 --cpu-proposals 0 --no-ism --no-config5"
+CMD2="python3 $R/bench.py --full --steps 2 --warmup 1 --cpu-proposals 0 --no-ism --no-config5"
 for set in "FETCH_SIZE" "WRITE_SIZE" "SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_INSTS_MFMA SQ_INSTS_VALU" "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY"; do
   tag=$(echo $set | cut -d' ' -f1)
   rocprofv3 --kernel-trace --pmc $set -d /tmp/p3/$tag -o out --output-format csv -- $CMD2 > /tmp/p3/$tag.log 2>&1

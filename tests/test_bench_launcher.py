@@ -65,3 +65,28 @@ def test_config4_two_gloo_ranks_equal_the_single_process_run(tmp_path):
     assert a["n_gpus"] == 1 and b["n_gpus"] == 2 and a["proposals_per_rank"] == 200 and b["proposals_per_rank"] == 100
     assert b["rows"] == 200 and len(b["per_rank_ms"]) == 2
     assert a["poses_sha256"] == b["poses_sha256"], "sharded poses differ from the single-process result"
+
+
+def test_dump_outputs_same_arguments_same_arrays(tmp_path):
+    """bench.py --dump-outputs DIR: the poses of the last timed step as float32 .npy files, identical from run to run with the same
+    arguments (seeded inputs), and --steps is the number of timed steps the line reports.  Compute: the --stub-compute stand-in."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--stub-compute", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, env=env)
+        assert p.returncode == 0, p.stderr[-2000:]
+        line = json.loads(p.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 3 and line["rows"] == 32
+        dumps.append({n: np.load(d / (n + ".npy")) for n in ("pred_R", "pred_t", "pred_pose_score")})
+    a, b = dumps
+    assert a["pred_R"].shape == (32, 3, 3) and a["pred_t"].shape == (32, 3) and a["pred_pose_score"].shape == (32,)
+    for n in a:
+        assert a[n].dtype == np.float32 and np.array_equal(a[n], b[n]), n
+    # the content: the stand-in's poses for rank 0's seeded proposals (every step computes the same, so this is the last step's)
+    from sam6d_hip import synth
+    want = dict(zip(("pred_R", "pred_t", "pred_pose_score"), _bench()._stub_match(synth.config2_inputs(B=32, seed=1))))
+    for n in a:
+        assert np.array_equal(a[n], want[n].numpy()), n

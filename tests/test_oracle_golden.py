@@ -1,7 +1,9 @@
 """Pins the CPU oracle (oracle/) to golden vectors captured from the REFERENCE ITSELF (oracle/gen_golden.py imported
 the reference's Python modules and its own compiled `_ext` in the build container).  CPU-only, no GPU, and nothing
 here reads /root/reference.  Integer/index outputs are bit-exact; float outputs that go through torch ops whose
-kernel choice can vary with the host CPU (GEMMs, softmax, sin/cos) use the tolerance stated per test."""
+kernel choice can vary with the host CPU (GEMMs, softmax, sin/cos) use the tolerance stated per test.  torch's CPU sqrt / exp /
+pow / sin run through oneMKL's vector-math kernels, and GEMM / SVD through its BLAS / LAPACK, which oneMKL picks per CPU vendor
+and ISA: the few outputs that such last bits decide (near-ties) carry a stated near-tie rule instead of bit equality."""
 import hashlib
 
 import numpy as np
@@ -75,12 +77,24 @@ def test_geo_embedding(sd):
     g = golden("geo_embedding")
     pts = _t(g["pts"])
     d_idx, a_idx, knn = O.geo_embedding_indices(pts)
-    assert np.array_equal(d_idx.numpy(), g["d_idx"])  # sqrt + division: exact
+    # sqrt + division: torch's CPU sqrt is not correctly rounded (1 ulp low on ~0.6 % of these inputs on the capture host, up to
+    # 2 ulp on ~14 % of them on an AMD EPYC host): <= 2 ulp of the capture
+    np.testing.assert_array_max_ulp(d_idx.numpy(), g["d_idx"], maxulp=2)
     assert np.array_equal(knn.numpy(), g["knn"].astype(np.int64))
     np.testing.assert_allclose(a_idx.numpy(), g["a_idx"], rtol=0, atol=2e-5)  # atan2/cross: libm-dependent
     out = O.geo_embedding(pts, sd)
     rows = g["rows"]
-    np.testing.assert_allclose(out[:, rows].numpy(), g["out_rows"], rtol=0, atol=2e-5)
+    # the embedding stage on the capture's own indices (a 1-ulp d_idx near 860 moves sin(w d) by up to 6e-5, more than the
+    # GEMM / sin / cos tolerance below covers); geo_embedding composes exactly that stage from its indices
+    assert torch.equal(out, _geo_embed(d_idx, a_idx, sd))
+    np.testing.assert_allclose(_geo_embed(_t(g["d_idx"]), _t(g["a_idx"]), sd)[:, rows].numpy(), g["out_rows"], rtol=0, atol=2e-5)
+
+
+def _geo_embed(d_idx, a_idx, sd, p="geo_embedding"):
+    """oracle/pem_oracle.py geo_embedding after its index stage."""
+    div = sd[p + ".embedding.div_term"]
+    d = O._lin(O.sinusoidal_embedding(d_idx, div), sd, p + ".proj_d")
+    return d + O._lin(O.sinusoidal_embedding(a_idx, div), sd, p + ".proj_a").max(dim=3)[0]
 
 
 def _layer_inputs(seed, B=1, n=197):
@@ -138,12 +152,32 @@ def test_coarse_rt_known_answer_and_flat():
     for tag in ("", "2"):
         att = _t(g["att" + tag])
         R, t, aux = O.compute_coarse_Rt(att, p1, p2, model, u, return_aux=True)
-        # discrete stages: bit-exact hypothesis indices and foreground mask
-        assert np.array_equal(aux["idx"].numpy().astype(np.int32), g["idx" + tag])
+        # discrete stages: bit-exact foreground mask; hypothesis indices = the first cumulative weight >= u, bit-exact except where u
+        # is a near-tie (within 1e-6) with the cumulative weight at the boundary: the weights pass through exp / pow, whose last bit
+        # is host-dependent; at most 0.5 % of the samples
         assert np.array_equal(aux["w1"].numpy(), g["w1" + ("_2" if tag else "")])
-        assert set(aux["top"][0].tolist()) == set(g["top" + tag][0].tolist())
-        np.testing.assert_allclose(R.numpy(), g["R" + tag], atol=1e-5, rtol=0)
-        np.testing.assert_allclose(t.numpy(), g["t" + tag], atol=1e-5, rtol=0)
+        idx, want = aux["idx"].numpy().astype(np.int64), g["idx" + tag].astype(np.int64)
+        cum = torch.cumsum(aux["weights"], dim=1)
+        cum = (cum / (cum[:, -1].unsqueeze(1) + 1e-8)).numpy().astype(np.float64)
+        off = np.argwhere(idx != want)
+        assert len(off) <= 0.005 * idx.size, "%d of %d sampled indices differ" % (len(off), idx.size)
+        for b, k in off:
+            edges = [cum[b, want[b, k]]] + ([cum[b, want[b, k] - 1]] if want[b, k] > 0 else [])
+            assert min(abs(e - float(u[b, k])) for e in edges) <= 1e-6, "index %d of row %d moved without a near-tie" % (k, b)
+        # the kept hypotheses = the 300 lowest residuals of 3-point Procrustes solutions (LAPACK SVD: host-dependent last bits, and
+        # for near-degenerate triples a host-dependent rotation): the capture's set wherever the residuals are the capture's
+        if np.array_equal(aux["dis"].numpy(), g["dis" + tag]):
+            assert set(aux["top"][0].tolist()) == set(g["top" + tag][0].tolist())
+        # the pose: the capture's within 1e-5 on the known-answer scene.  On flat attention the kept hypotheses include
+        # near-degenerate triples whose rotation is LAPACK rounding noise, and the scores follow it (an AMD EPYC host scores them up
+        # to 60 % apart and picks another pose): there the capture's pose wherever the residuals are the capture's, and always a
+        # proper rotation
+        same = tag == "" or np.array_equal(aux["dis"].numpy(), g["dis" + tag])
+        if same:
+            np.testing.assert_allclose(R.numpy(), g["R" + tag], atol=1e-5, rtol=0)
+            np.testing.assert_allclose(t.numpy(), g["t" + tag], atol=1e-5, rtol=0)
+        np.testing.assert_allclose((R @ R.transpose(1, 2)).numpy(), np.broadcast_to(np.eye(3), R.shape), atol=1e-5, rtol=0)
+        np.testing.assert_allclose(torch.linalg.det(R).numpy(), 1.0, atol=1e-5, rtol=0)
     # the known-answer scene recovers the ground-truth motion (SURVEY 8c KAT)
     R, t = O.compute_coarse_Rt(_t(g["att"]), p1, p2, model, u)
     np.testing.assert_allclose(R.numpy(), g["R_gt"], atol=2e-5, rtol=0)
@@ -307,7 +341,11 @@ def test_ism_scoring():
     masks, boxes = ism_masks(d["gen"], len(sel))
     assert np.array_equal(boxes.numpy().astype(np.int32), g["boxes"])
     vu = IO.project_template_to_image(best, obj, d["poses"], d["pc"], masks, d["depth"], d["K"], d["depth_scale"])
-    assert _sha(vu) == str(g["vu_sha"]) and np.array_equal(vu.numpy(), g["vu"].astype(np.int32))
+    # pixel coordinates truncate K (R p + t) / z computed with fp32 GEMMs (host-dependent last bits): a projection within rounding
+    # of an integer may land on the neighbouring pixel -- at most 1 px, on at most 1e-5 of the coordinates; otherwise the capture
+    off = np.abs(vu.numpy() - g["vu"].astype(np.int32))
+    assert off.max() <= 1 and (off > 0).sum() <= 1e-5 * off.size, "%d coordinates off, max %d px" % ((off > 0).sum(), off.max())
+    assert (off > 0).any() or _sha(vu) == str(g["vu_sha"])
     tr = IO.query_translation(masks, d["depth"], d["K"], d["depth_scale"])
     assert tr.dtype == torch.float32 and np.array_equal(tr.numpy(), g["translate"])  # float64 inside, one rounding at the end
     iou, vis = IO.geometric_score(vu, boxes, qa, ref_sel, 0.5)
