@@ -112,6 +112,26 @@ int sam6d_gemm_nt_w16(const float* A, const float* W, const void* Wh, const void
  * (the per-cloud, per-head q.k^T and P.v products of the attention: PEM/model/transformer.py:137-149, 408-419). */
 int sam6d_gemm_nt_b2(const float* A, const float* W, float* C, int M, int N, int K, long lda, long ldw, long ldc, int batch,
                      long sA, long sW, long sC, int batch2, long sA2, long sW2, long sC2, void* stream);
+#define SAM6D_GEMM_ROUTE_EXACT 0      /* bits 0-1: exact fp32 MFMA loop (mode 0, or K < 32) */
+#define SAM6D_GEMM_ROUTE_H3 1         /*           fp16 split, weight tile split per k-step */
+#define SAM6D_GEMM_ROUTE_H3_W16 2     /*           fp16 split, pre-split weight halves */
+#define SAM6D_GEMM_ROUTE_TILE128 4    /* 128 x 128 workgroup tiles (else 64 x 64) */
+#define SAM6D_GEMM_ROUTE_FAST 8       /* whole-tile pre-split specialisation (no bounds checks) */
+#define SAM6D_GEMM_ROUTE_WIDE 16      /* 16-byte epilogue (split kernels only) */
+#define SAM6D_GEMM_ROUTE_HALF 32      /* single hi.hi product (matmul mode 2) */
+#define SAM6D_GEMM_ROUTE_PLAIN 0      /* bits 6-7: workgroup order -- plain row-tile-major */
+#define SAM6D_GEMM_ROUTE_COLGROUP 64  /*           column tiles of 8 row tiles grouped per XCD, last group padded */
+#define SAM6D_GEMM_ROUTE_FOLD 128     /*           batch folded into grid.x, one element per XCD, last group of 8 padded */
+#define SAM6D_GEMM_ROUTE_NONE 256     /* M, N or batch is 0: no launch */
+/* The kernel route a GEMM launch with these arguments takes (the launch decision itself, shared with the launch; nothing is launched
+ * and no pointer is dereferenced) for the nn.Linear / similarity call sites of sam6d_gemm_nt (PEM/model/transformer.py:127-129;
+ * PEM/utils/model_utils.py:144-150).  Arguments: those of sam6d_gemm_nt_w16 (Wh = Wl = NULL: sam6d_gemm_nt) plus the inner batch
+ * level of sam6d_gemm_nt_b2 (batch2 = 1, sA2 = sW2 = sC2 = 0 otherwise).  Reads the calling thread's matmul mode and SAM6D_GEMM_FAST
+ * as the launch does.  Returns a bit code >= 0 (SAM6D_GEMM_ROUTE_* above), or < 0 with the error the launch would report. */
+int sam6d_gemm_route(const float* A, const float* W, const void* Wh, const void* Wl, float w_scale, const float* bias,
+                     const float* colscale, const float* residual, const float* C, int M, int N, int K, long lda, long ldw, long ldc,
+                     long ldr, int batch, long sA, long sW, long sC, long sR, float divisor, int act, int batch2, long sA2, long sW2,
+                     long sC2);
 
 /* Matrix-core arithmetic of gemm_nt / geo_embed: 0 = exact fp32 MFMA (v_mfma_f32_32x32x2_f32, a k-ordered fmaf chain),
  * 1 = fp16 x3 split (x = hi + lo in fp16, 3 MFMAs, ~1e-6 relative; default), 2 = fp16 single product (hi . hi only, fp32

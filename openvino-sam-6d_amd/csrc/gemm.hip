@@ -553,10 +553,24 @@ static bool gemm_fast_enabled() {  // SAM6D_GEMM_FAST=0: the general kernel also
   return on != 0;
 }
 
-static int gemm_launch(const float* A, const float* W, const float* bias, const float* colscale, const float* residual,
-                       float* C, int M, int N, int K, long lda, long ldw, long ldc, long ldr, int batch, long sA, long sW,
-                       long sC, long sR, Batch2 b2, float divisor, int act, void* stream, const void* Wh = nullptr,
-                       const void* Wl = nullptr, float w_scale = 1.0f) {
+// The launch decision of gemm_launch, factored out so that sam6d_gemm_route reports exactly what a launch with the same arguments runs.
+struct GemmRoute {
+  int kernel;      // SAM6D_GEMM_ROUTE_EXACT / _H3 / _H3_W16
+  bool big, fast, wide, half;
+  int order;       // SAM6D_GEMM_ROUTE_PLAIN / _COLGROUP / _FOLD: the workgroup order gemm_tile decodes
+  bool empty;      // M, N or batch is 0: nothing is launched
+  int tm, tn, nz;  // row tiles, column tiles, batch elements (batch * batch2)
+  long tiles;      // grid.x
+  int code() const {
+    if (empty) return SAM6D_GEMM_ROUTE_NONE;
+    return kernel | (big ? SAM6D_GEMM_ROUTE_TILE128 : 0) | (fast ? SAM6D_GEMM_ROUTE_FAST : 0) | (wide ? SAM6D_GEMM_ROUTE_WIDE : 0) |
+           (half ? SAM6D_GEMM_ROUTE_HALF : 0) | order;
+  }
+};
+
+static int gemm_pick(GemmRoute& r, const float* A, const float* W, const float* bias, const float* colscale, const float* residual,
+                     const float* C, int M, int N, int K, long lda, long ldw, long ldc, long ldr, int batch, long sA, long sW, long sC,
+                     long sR, const Batch2& b2, float divisor, int act, const void* Wh, const void* Wl) {
   SAM6D_REQUIRE(A && W && C, "gemm_nt: null pointer");
   SAM6D_REQUIRE(M >= 0 && N >= 0 && K > 0 && batch >= 0 && b2.n2 >= 1, "gemm_nt: bad sizes M=%d N=%d K=%d batch=%d x %d", M, N,
                 K, batch, b2.n2);
@@ -565,51 +579,89 @@ static int gemm_launch(const float* A, const float* W, const float* bias, const 
   act &= ~16;
   SAM6D_REQUIRE(act == 0 || act == 1, "gemm_nt: act must be 0 (none) or 1 (ReLU), optionally + 16");
   SAM6D_REQUIRE((long)batch * b2.n2 <= 65535, "gemm_nt: batch (x batch2) must be <= 65535");
-  if (M == 0 || N == 0 || batch == 0) return 0;
-  const int nz = batch * b2.n2;
-  const long blocks128 = (long)cdiv(M, 128) * cdiv(N, 128) * nz;
+  r = GemmRoute{};
+  r.empty = (M == 0 || N == 0 || batch == 0);
+  if (r.empty) return 0;
+  r.nz = batch * b2.n2;
+  const long blocks128 = (long)cdiv(M, 128) * cdiv(N, 128) * r.nz;
   // big tiles when they fill the chip (>= 4 workgroups per CU) and do not mostly pad (M = 197 would waste 42 % of a 2 x 128 split)
-  const bool big = blocks128 >= 1024 && (M > 256 || M % 128 == 0);
+  r.big = blocks128 >= 1024 && (M > 256 || M % 128 == 0);
   // (64 x 256 tiles -- the whole output row in one workgroup, every A row read and split once -- were measured on the fine in_proj,
   // M = 131 136, N = K = 256 with pre-split weights: 128 us against 115 us for 128 x 128 tiles; the epilogue keeps its two-pass form)
-  const int bm = big ? 128 : 64, bn = big ? 128 : 64;
-  const int tm = cdiv(M, bm), tn = cdiv(N, bn);
+  const int bm = r.big ? 128 : 64, bn = r.big ? 128 : 64;
+  r.tm = cdiv(M, bm);
+  r.tn = cdiv(N, bn);
   // all tiles on x (2^31 limit) in the XCD-aware order the kernels decode; groups of 8 row tiles are padded
-  const bool fold = nz >= 8;  // batch elements folded into grid.x, one XCD per element (gemm_tile)
-  const long tiles = fold ? (long)cdiv(nz, 8) * 8 * tm * tn : (tn <= 8 && tm >= 32) ? (long)cdiv(tm, 8) * 8 * tn : (long)tm * tn;
-  SAM6D_REQUIRE(tiles < 2147483647L, "gemm_nt: too many tiles for one launch");
-  dim3 grid((unsigned)tiles, 1, fold ? 1 : nz);
-  b2.fold_nz = fold ? nz : 0;
+  const bool fold = r.nz >= 8;  // batch elements folded into grid.x, one XCD per element (gemm_tile)
+  const bool colgroup = !fold && r.tn <= 8 && r.tm >= 32;
+  r.order = fold ? SAM6D_GEMM_ROUTE_FOLD : colgroup ? SAM6D_GEMM_ROUTE_COLGROUP : SAM6D_GEMM_ROUTE_PLAIN;
+  r.tiles = fold ? (long)cdiv(r.nz, 8) * 8 * r.tm * r.tn : colgroup ? (long)cdiv(r.tm, 8) * 8 * r.tn : (long)r.tm * r.tn;
+  SAM6D_REQUIRE(r.tiles < 2147483647L, "gemm_nt: too many tiles for one launch");
+  if (sam6d_get_matmul_mode() >= 1 && K >= 32) {
+    r.half = sam6d_half_for(0) && !keep_split;
+    // 16-byte epilogue accesses need 4-float alignment of every row start and of the per-column vectors
+    r.wide = (N & 3) == 0 && (ldc & 3) == 0 && (sC & 3) == 0 && (b2.sC2 & 3) == 0 && (((size_t)C) & 15) == 0 &&
+             (!residual || ((ldr & 3) == 0 && (sR & 3) == 0 && (b2.sR2 & 3) == 0 && (((size_t)residual) & 15) == 0)) &&
+             (!bias || (((size_t)bias) & 15) == 0) && (!colscale || (((size_t)colscale) & 15) == 0);
+    if (Wh && Wl) {
+      r.kernel = SAM6D_GEMM_ROUTE_H3_W16;
+      r.fast = r.big && r.wide && !r.half && (M % 128) == 0 && (N % 128) == 0 && (K % 32) == 0 && (lda & 3) == 0 && (ldw & 3) == 0 &&
+               ((((size_t)A | (size_t)W) & 15) == 0) && ((((size_t)Wh | (size_t)Wl) & 7) == 0) && (sA & 3) == 0 && (b2.sA2 & 3) == 0 &&
+               (sW & 3) == 0 && (b2.sW2 & 3) == 0 && divisor == 1.0f && !colscale && act == 0 && gemm_fast_enabled();
+    } else {
+      r.kernel = SAM6D_GEMM_ROUTE_H3;
+    }
+  } else {
+    r.kernel = SAM6D_GEMM_ROUTE_EXACT;
+  }
+  return 0;
+}
+
+static int gemm_launch(const float* A, const float* W, const float* bias, const float* colscale, const float* residual,
+                       float* C, int M, int N, int K, long lda, long ldw, long ldc, long ldr, int batch, long sA, long sW,
+                       long sC, long sR, Batch2 b2, float divisor, int act, void* stream, const void* Wh = nullptr,
+                       const void* Wl = nullptr, float w_scale = 1.0f) {
+  GemmRoute r;
+  const int rc = gemm_pick(r, A, W, bias, colscale, residual, C, M, N, K, lda, ldw, ldc, ldr, batch, sA, sW, sC, sR, b2, divisor, act,
+                           Wh, Wl);
+  if (rc != 0) return rc;
+  if (r.empty) return 0;
+  act &= ~16;
+  const bool fold = r.order == SAM6D_GEMM_ROUTE_FOLD;
+  dim3 grid((unsigned)r.tiles, 1, fold ? 1 : r.nz);
+  b2.fold_nz = fold ? r.nz : 0;
   hipStream_t st = (hipStream_t)stream;
+  const int wide = r.wide ? 1 : 0, half = r.half ? 1 : 0;
+  const _Float16* wh = reinterpret_cast<const _Float16*>(Wh);
+  const _Float16* wl = reinterpret_cast<const _Float16*>(Wl);
+  const float wu = 1.0f / w_scale;
 #define GEMM_LAUNCH(KERNEL, ...)                                                                                         \
   hipLaunchKernelGGL(KERNEL, grid, dim3(256), 0, st, A, W, bias, colscale, residual, C, M, N, K, lda, ldw, ldc, ldr, sA, sW, \
                      sC, sR, divisor, act, b2, ##__VA_ARGS__)
-  if (sam6d_get_matmul_mode() >= 1 && K >= 32) {
-    const int half = (sam6d_half_for(0) && !keep_split) ? 1 : 0;
-    // 16-byte epilogue accesses need 4-float alignment of every row start and of the per-column vectors
-    const int wide = ((N & 3) == 0 && (ldc & 3) == 0 && (sC & 3) == 0 && (b2.sC2 & 3) == 0 && (((size_t)C) & 15) == 0 &&
-                      (!residual || ((ldr & 3) == 0 && (sR & 3) == 0 && (b2.sR2 & 3) == 0 && (((size_t)residual) & 15) == 0)) &&
-                      (!bias || (((size_t)bias) & 15) == 0) && (!colscale || (((size_t)colscale) & 15) == 0))
-                         ? 1 : 0;
-    const _Float16* wh = reinterpret_cast<const _Float16*>(Wh);
-    const _Float16* wl = reinterpret_cast<const _Float16*>(Wl);
-    const float wu = 1.0f / w_scale;
-    if (wh && wl) {
-      const bool fast = big && wide && !half && (M % 128) == 0 && (N % 128) == 0 && (K % 32) == 0 && (lda & 3) == 0 && (ldw & 3) == 0 &&
-                        ((((size_t)A | (size_t)W) & 15) == 0) && ((((size_t)Wh | (size_t)Wl) & 7) == 0) && (sA & 3) == 0 && (b2.sA2 & 3) == 0 &&
-                        (sW & 3) == 0 && (b2.sW2 & 3) == 0 && divisor == 1.0f && !colscale && act == 0 && gemm_fast_enabled();
-      if (fast) GEMM_LAUNCH((gemm_nt_h3_kernel<128, 128, true, true>), wide, half, wh, wl, wu);
-      else if (big) GEMM_LAUNCH((gemm_nt_h3_kernel<128, 128, true>), wide, half, wh, wl, wu);
-      else GEMM_LAUNCH((gemm_nt_h3_kernel<64, 64, true>), wide, half, wh, wl, wu);
-    } else {
-      if (big) GEMM_LAUNCH((gemm_nt_h3_kernel<128, 128, false>), wide, half, wh, wl, wu);
-      else GEMM_LAUNCH((gemm_nt_h3_kernel<64, 64, false>), wide, half, wh, wl, wu);
-    }
+  if (r.kernel == SAM6D_GEMM_ROUTE_H3_W16) {
+    if (r.fast) GEMM_LAUNCH((gemm_nt_h3_kernel<128, 128, true, true>), wide, half, wh, wl, wu);
+    else if (r.big) GEMM_LAUNCH((gemm_nt_h3_kernel<128, 128, true>), wide, half, wh, wl, wu);
+    else GEMM_LAUNCH((gemm_nt_h3_kernel<64, 64, true>), wide, half, wh, wl, wu);
+  } else if (r.kernel == SAM6D_GEMM_ROUTE_H3) {
+    if (r.big) GEMM_LAUNCH((gemm_nt_h3_kernel<128, 128, false>), wide, half, wh, wl, wu);
+    else GEMM_LAUNCH((gemm_nt_h3_kernel<64, 64, false>), wide, half, wh, wl, wu);
   } else {
-    if (big) GEMM_LAUNCH((gemm_nt_kernel<128, 128>)); else GEMM_LAUNCH((gemm_nt_kernel<64, 64>));
+    if (r.big) GEMM_LAUNCH((gemm_nt_kernel<128, 128>)); else GEMM_LAUNCH((gemm_nt_kernel<64, 64>));
   }
 #undef GEMM_LAUNCH
   SAM6D_LAUNCH_CHECK("gemm_nt");
+}
+
+extern "C" int sam6d_gemm_route(const float* A, const float* W, const void* Wh, const void* Wl, float w_scale, const float* bias,
+                                const float* colscale, const float* residual, const float* C, int M, int N, int K, long lda, long ldw,
+                                long ldc, long ldr, int batch, long sA, long sW, long sC, long sR, float divisor, int act, int batch2,
+                                long sA2, long sW2, long sC2) {
+  SAM6D_REQUIRE(!Wh == !Wl, "gemm_route: Wh and Wl are given together or not at all");
+  SAM6D_REQUIRE(!Wh || w_scale > 0.f, "gemm_route: the pre-split weight halves need their scale");
+  GemmRoute r;
+  const int rc = gemm_pick(r, A, W, bias, colscale, residual, C, M, N, K, lda, ldw, ldc, ldr, batch, sA, sW, sC, sR,
+                           Batch2{batch2, sA2, sW2, sC2, 0, 0}, divisor, act, Wh, Wl);
+  return rc != 0 ? rc : r.code();
 }
 
 extern "C" int sam6d_gemm_nt(const float* A, const float* W, const float* bias, const float* colscale,

@@ -40,6 +40,7 @@ SIGNATURES = {
     "sam6d_split_f16": [c_p, c_l, c_f, c_p, c_p, c_p],
     "sam6d_geo_embed_h3": [c_p, c_l, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p],
     "sam6d_gemm_nt_b2": [c_p, c_p, c_p, c_i, c_i, c_i, c_l, c_l, c_l, c_i, c_l, c_l, c_l, c_i, c_l, c_l, c_l, c_p],
+    "sam6d_gemm_route": [c_p] * 4 + [c_f] + [c_p] * 4 + [c_i] * 3 + [c_l] * 4 + [c_i] + [c_l] * 4 + [c_f, c_i, c_i, c_l, c_l, c_l],
     "sam6d_geo_outliers": [c_p, c_l, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
     "sam6d_rpe_scores": [c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_l, c_i, c_i, c_p],
     "sam6d_rpe_geo_scores": [c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_i, c_p, c_p, c_p, c_l, c_i, c_i, c_p],

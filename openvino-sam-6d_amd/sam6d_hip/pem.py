@@ -449,6 +449,23 @@ def gemm(A, W, bias, out, M, N, K, lda, ldw, ldc, *, a_off=0, w_off=0, c_off=0, 
         launch()
 
 
+def gemm_route(A, W, bias, out, M, N, K, lda, ldw, ldc, *, a_off=0, w_off=0, c_off=0, residual=None, r_off=0, ldr=0, colscale=None,
+               batch=1, sA=0, sW=0, sC=0, sR=0, divisor=1.0, act=0, w16=None, batch2=1, sA2=0, sW2=0, sC2=0):
+    """The SAM6D_GEMM_ROUTE_* bit code of the kernel `gemm` (batch2 > 1: `gemm_b2`) launches with these arguments, in the calling
+    thread's matmul mode (sam6d_gemm_route; nothing is launched).  The pre-split weights count as `gemm` would use them."""
+    wh = wl = None
+    sc = 0.0
+    if w16 is not None and K >= 32 and _flags().w16:
+        hi, lo, sc = w16
+        wh, wl = hi.data_ptr() + 2 * w_off, lo.data_ptr() + 2 * w_off
+    rc = _lib.load().sam6d_gemm_route(_p(A, a_off), _p(W, w_off), wh, wl, float(sc), _p(bias), _p(colscale), _p(residual, r_off),
+                                      _p(out, c_off), M, N, K, lda, ldw, ldc, ldr, batch, sA, sW, sC, sR, float(divisor), act, batch2,
+                                      sA2, sW2, sC2)
+    if rc < 0:
+        raise RuntimeError("sam6d_gemm_route failed (rc=%d): %s" % (rc, _lib.load().sam6d_last_error().decode()))
+    return rc
+
+
 def linear(x2d, lin, *, act=0, residual=None, out=None, cloud_rows=0):
     """x2d (M,K) contiguous -> (M,N) = act(x W^T + b) (+ residual).  cloud_rows: tokens per cloud when the rows are the sparse tokens of
     whole clouds (<= 512 each): the projection then runs on the panel kernel."""
