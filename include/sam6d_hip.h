@@ -126,8 +126,8 @@ int sam6d_gemm_nt_b2(const float* A, const float* W, float* C, int M, int N, int
 /* The kernel route a GEMM launch with these arguments takes (the launch decision itself, shared with the launch; nothing is launched
  * and no pointer is dereferenced) for the nn.Linear / similarity call sites of sam6d_gemm_nt (PEM/model/transformer.py:127-129;
  * PEM/utils/model_utils.py:144-150).  Arguments: those of sam6d_gemm_nt_w16 (Wh = Wl = NULL: sam6d_gemm_nt) plus the inner batch
- * level of sam6d_gemm_nt_b2 (batch2 = 1, sA2 = sW2 = sC2 = 0 otherwise).  Reads the calling thread's matmul mode and SAM6D_GEMM_FAST
- * as the launch does.  Returns a bit code >= 0 (SAM6D_GEMM_ROUTE_* above), or < 0 with the error the launch would report. */
+ * level of sam6d_gemm_nt_b2 (batch2 = 1, sA2 = sW2 = sC2 = 0 otherwise).  Reads the calling thread's matmul mode as the
+ * launch does.  Returns a bit code >= 0 (SAM6D_GEMM_ROUTE_* above), or < 0 with the error the launch would report. */
 int sam6d_gemm_route(const float* A, const float* W, const void* Wh, const void* Wl, float w_scale, const float* bias,
                      const float* colscale, const float* residual, const float* C, int M, int N, int K, long lda, long ldw, long ldc,
                      long ldr, int batch, long sA, long sW, long sC, long sR, float divisor, int act, int batch2, long sA2, long sW2,

@@ -286,20 +286,8 @@ extern "C" int sam6d_linattn_kv_image(const float* kv, const float* scale, int B
                     (((size_t)kv | (size_t)scale) & 15) == 0,
                 "linattn_kv_image: bad arguments (kv rows = 256 k | 256 v channels, 16-byte aligned)");
   if (B == 0) return 0;
-  static int shape = -1;  // SAM6D_KV_THREADS = 256 / 512 / 1024 (A/B runs)
-  if (shape < 0) {
-    const char* e = getenv("SAM6D_KV_THREADS");
-    shape = e ? atoi(e) : 1024;
-  }
-  if (shape == 256)
-    hipLaunchKernelGGL(tb_kv_fused_kernel<256>, dim3(4, B), dim3(256), 0, (hipStream_t)stream, kv, scale, J, ld, stride,
-                       (unsigned char*)image, inv, ksum);
-  else if (shape == 512)
-    hipLaunchKernelGGL(tb_kv_fused_kernel<512>, dim3(4, B), dim3(512), 0, (hipStream_t)stream, kv, scale, J, ld, stride,
-                       (unsigned char*)image, inv, ksum);
-  else
-    hipLaunchKernelGGL(tb_kv_fused_kernel<1024>, dim3(4, B), dim3(1024), 0, (hipStream_t)stream, kv, scale, J, ld, stride,
-                       (unsigned char*)image, inv, ksum);
+  hipLaunchKernelGGL(tb_kv_fused_kernel<1024>, dim3(4, B), dim3(1024), 0, (hipStream_t)stream, kv, scale, J, ld, stride,
+                     (unsigned char*)image, inv, ksum);
   SAM6D_LAUNCH_CHECK("linattn_kv_image");
 }
 
@@ -917,13 +905,11 @@ struct RfArgs {
 };
 
 // VT: the values go to vT (8 scattered 4-byte stores per value panel) instead of the v third of qkv (2 float4 stores).
-// Stores are issued for every lane -- rows past M are clamped to row M - 1 and rewrite its values -- so that the number of vector-memory
-// operations between two panel DMAs is a compile-time constant: the wait at the head of a panel then lets the previous panel's STORES
-// stay in flight (s_waitcnt vmcnt(#stores)) instead of draining them (vmcnt(0) cost a store round trip per panel: 36 per workgroup).
-// LOADERS (0 / 4) extra waves issue the panel DMA, as in token_block_kernel; the computing waves then never wait on the vector-memory
-// counter at all (their stores stay in flight across panels without the counted waits below).
-template <bool VT, int LOADERS = 0>
-__global__ __launch_bounds__((4 + LOADERS) * 64, LOADERS ? 1 : 2) void rpe_front_kernel(RfArgs a) {
+// Stores are issued for every lane: rows past M are clamped to row M - 1 and rewrite its values.
+// Four loader waves beside the four computing ones issue the panel DMA, as in token_block_kernel; the computing waves then never wait on
+// the vector-memory counter (their stores stay in flight across panels).
+template <bool VT>
+__global__ __launch_bounds__(512, 1) void rpe_front_kernel(RfArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   unsigned char* pan = lds;  // 2 x TB_PANEL_BYTES
   const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6), fr = lane & 15, fg = lane >> 4;
@@ -945,34 +931,26 @@ __global__ __launch_bounds__((4 + LOADERS) * 64, LOADERS ? 1 : 2) void rpe_front
       unsigned char* dst = pan + (I & 1) * TB_PANEL_BYTES;
 #pragma unroll
       for (int k = 0; k < NP; ++k) {
-        const int pc = (LOADERS ? wave - 4 : wave) + 4 * k;
+        const int pc = (wave - 4) + 4 * k;
         __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)(src + (size_t)pc * 1024 + lane * 16),
                                          (void __attribute__((address_space(3)))*)(dst + pc * 1024), 16, 0, 0);
       }
     }
   };
-  // panel I's DMA was issued at the head of panel I - 1; younger than it are only the NST stores of panel I - 1's epilogue
-  auto next_panel = [&](auto IC, auto NSTC) -> unsigned {
+  // the computing waves' side of the loader waves' barrier of unit I
+  auto next_panel = [&](auto IC) -> unsigned {
     constexpr int I = decltype(IC)::value;
-    constexpr int NST = decltype(NSTC)::value;
-    if constexpr (LOADERS == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NST) : "memory");
     __syncthreads();
-    if constexpr (LOADERS == 0) dma(std::integral_constant<int, I + 1>{});
     return pan_lds + (I & 1) * TB_PANEL_BYTES;
   };
-  if constexpr (LOADERS > 0) {
-    static_assert(LOADERS == 4, "the DMA pieces are dealt to four waves");
-    if (wave >= 4) {  // a loader wave: unit I + 1 goes out once unit I has landed and every wave has left unit I - 1
-      dma(std::integral_constant<int, 0>{});
-      tb_static_for<0, NPAN>([&](auto IC) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        dma(std::integral_constant<int, decltype(IC)::value + 1>{});
-      });
-      return;
-    }
-  } else {
+  if (wave >= 4) {  // a loader wave: unit I + 1 goes out once unit I has landed and every wave has left unit I - 1
     dma(std::integral_constant<int, 0>{});
+    tb_static_for<0, NPAN>([&](auto IC) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      dma(std::integral_constant<int, decltype(IC)::value + 1>{});
+    });
+    return;
   }
 
   half8 xh[8], xl[8];
@@ -1014,9 +992,7 @@ __global__ __launch_bounds__((4 + LOADERS) * 64, LOADERS ? 1 : 2) void rpe_front
   float* orow = a.qkv + (size_t)row * 768;
   tb_static_for<0, 24>([&](auto J) {
     constexpr int j = decltype(J)::value;
-    // stores of the previous panel: none before panel 0 (the wait also covers the x rows), 8 after a transposed value panel, else 2
-    constexpr int prev_st = j == 0 ? 0 : ((VT && j - 1 >= 16) ? 8 : 2);
-    const unsigned p = next_panel(std::integral_constant<int, j>{}, std::integral_constant<int, prev_st>{});
+    const unsigned p = next_panel(std::integral_constant<int, j>{});
     f32x4 c0 = f32x4{0.f, 0.f, 0.f, 0.f}, c1 = f32x4{0.f, 0.f, 0.f, 0.f};
     tb_mma<8>(c0, c1, p, xh, xl, fr, fg, false);
     const float4 b0 = *reinterpret_cast<const float4*>(a.bias + 32 * j + 4 * fg);
@@ -1051,9 +1027,7 @@ __global__ __launch_bounds__((4 + LOADERS) * 64, LOADERS ? 1 : 2) void rpe_front
     f32x4 pa[16];
     tb_static_for<0, 2>([&](auto GG) {
       constexpr int gq = decltype(GG)::value;
-      // younger than this unit's DMA: the last qkv panel's stores (h = 0), the 2 qd stores of the previous head, or nothing (gq = 1)
-      constexpr int prev_st = gq == 1 ? 0 : (h == 0 ? (VT ? 8 : 2) : 2);
-      const unsigned p4 = next_panel(std::integral_constant<int, 24 + 3 * h + gq>{}, std::integral_constant<int, prev_st>{});
+      const unsigned p4 = next_panel(std::integral_constant<int, 24 + 3 * h + gq>{});
       tb_static_for<0, 4>([&](auto U) {
         constexpr int j = 4 * gq + decltype(U)::value;
         f32x4 c0 = f32x4{0.f, 0.f, 0.f, 0.f}, c1 = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -1069,7 +1043,7 @@ __global__ __launch_bounds__((4 + LOADERS) * 64, LOADERS ? 1 : 2) void rpe_front
     }
     half8 ph[8], pl[8];
     const float sp = tb_split_rows<16>(pa, ph, pl);
-    const unsigned p = next_panel(std::integral_constant<int, 24 + 3 * h + 2>{}, std::integral_constant<int, 16>{});  // the 16 qp stores
+    const unsigned p = next_panel(std::integral_constant<int, 24 + 3 * h + 2>{});
     f32x4 c0 = f32x4{0.f, 0.f, 0.f, 0.f}, c1 = f32x4{0.f, 0.f, 0.f, 0.f};
     tb_mma<8>(c0, c1, p, ph, pl, fr, fg, false);
     {
@@ -1104,8 +1078,6 @@ static int rpe_front_launch(const float* x, const void* wimage, const float* bia
   if (sam6d_first_use_on_device(&done)) {
     hipError_t e = hipFuncSetAttribute((const void*)rpe_front_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * TB_PANEL_BYTES);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)rpe_front_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * TB_PANEL_BYTES);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)rpe_front_kernel<false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * TB_PANEL_BYTES);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)rpe_front_kernel<true, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * TB_PANEL_BYTES);
     if (e != hipSuccess) {
       sam6d_set_error("rpe_front: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
       return (int)e;
@@ -1113,20 +1085,11 @@ static int rpe_front_launch(const float* x, const void* wimage, const float* bia
     sam6d_setup_done_on_device(&done);
   }
   RfArgs a{x, (const unsigned char*)wimage, bias_qkv, qkv, qp, qd, M, inv_qkv, inv_wp, inv_dc, vT, n, ldp};
-  static int loaders = -1;  // four loader waves beside the four computing ones (SAM6D_FRONT_LOADERS=0: the plain shape, for A/B runs)
-  if (loaders < 0) {
-    const char* e = getenv("SAM6D_FRONT_LOADERS");
-    loaders = (e && e[0] == '0') ? 0 : 4;
-  }
   const dim3 g((unsigned)((M + 63) / 64));
-  if (vT && loaders)
-    hipLaunchKernelGGL((rpe_front_kernel<true, 4>), g, dim3(512), 2 * TB_PANEL_BYTES, (hipStream_t)stream, a);
-  else if (vT)
-    hipLaunchKernelGGL((rpe_front_kernel<true, 0>), g, dim3(256), 2 * TB_PANEL_BYTES, (hipStream_t)stream, a);
-  else if (loaders)
-    hipLaunchKernelGGL((rpe_front_kernel<false, 4>), g, dim3(512), 2 * TB_PANEL_BYTES, (hipStream_t)stream, a);
+  if (vT)
+    hipLaunchKernelGGL(rpe_front_kernel<true>, g, dim3(512), 2 * TB_PANEL_BYTES, (hipStream_t)stream, a);
   else
-    hipLaunchKernelGGL((rpe_front_kernel<false, 0>), g, dim3(256), 2 * TB_PANEL_BYTES, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(rpe_front_kernel<false>, g, dim3(512), 2 * TB_PANEL_BYTES, (hipStream_t)stream, a);
   SAM6D_LAUNCH_CHECK("rpe_front");
 }
 
@@ -1135,8 +1098,8 @@ static int rpe_front_launch(const float* x, const void* wimage, const float* bia
 // (FinePointMatching.forward: out_proj, PEM/model/fine_point_matching.py:70-72; compute_feature_similarity: F.normalize(dim=2),
 // PEM/utils/model_utils.py:141-142):   y = x W^T + b;   fh | fl = fp16 hi / lo of (y / max(|y|, 1e-12)) * 2^10
 // -- what sam6d_gemm_nt followed by finematch.hip's fm_prep_kernel produce (a 134 MB fp32 intermediate written and read back at
-// B = 32).  One workgroup = 64 token rows on four computing waves + four loader waves (8 panels, two per ring slot), the same
-// register-chained transposed product as token_block_kernel; rows are read non-temporally (each exactly once).
+// B = 32).  One workgroup = 64 token rows on four waves, the same register-chained transposed product as token_block_kernel; rows are
+// read non-temporally (each exactly once).
 struct OsArgs {
   const float* x;            // (M, 256)
   const unsigned char* wimg; // sam6d_pack_panels(W, 256 rows, k0 = 0, ksteps = 8): 8 panels
@@ -1148,39 +1111,23 @@ struct OsArgs {
   int half;
 };
 
-// LOADERS = 4, PSTEP = 2: four loader waves, two panels per ring slot (one workgroup per CU: 128 KB of LDS); LOADERS = 0, PSTEP = 1:
-// the computing waves issue their own DMA, one panel per slot (64 KB: two workgroups per CU, one's row loads / stores beside the
+// The four waves issue their own DMA, one panel per slot (64 KB of LDS: two workgroups per CU, one's row loads / stores beside the
 // other's products) -- the shape for this pure streaming pass.
-template <int LOADERS, int PSTEP>
-__global__ __launch_bounds__((4 + LOADERS) * 64, LOADERS ? 1 : 2) void out_split_kernel(OsArgs a) {
+__global__ __launch_bounds__(256, 2) void out_split_kernel(OsArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6), fr = lane & 15, fg = lane >> 4;
   const unsigned pan_lds = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)lds;
-  constexpr int SLOT = PSTEP * TB_PANEL_BYTES, NSTEP = 8 / PSTEP;
-  auto dma_step = [&](int T) {  // step T = PSTEP panels into slot T & 1, dealt to the four issuing waves
-    const unsigned char* src = a.wimg + (size_t)T * SLOT;
-    unsigned char* dst = lds + (T & 1) * SLOT;
+  auto dma_step = [&](int T) {  // panel T into slot T & 1, dealt to the four waves
+    const unsigned char* src = a.wimg + (size_t)T * TB_PANEL_BYTES;
+    unsigned char* dst = lds + (T & 1) * TB_PANEL_BYTES;
 #pragma unroll
-    for (int k = 0; k < 8 * PSTEP; ++k) {
-      const int pc = (LOADERS ? wave - 4 : wave) + 4 * k;
+    for (int k = 0; k < 8; ++k) {
+      const int pc = wave + 4 * k;
       __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)(src + (size_t)pc * 1024 + lane * 16),
                                        (void __attribute__((address_space(3)))*)(dst + pc * 1024), 16, 0, 0);
     }
   };
-  if constexpr (LOADERS > 0) {
-    if (wave >= 4) {
-      dma_step(0);
-#pragma unroll
-      for (int T = 0; T < NSTEP; ++T) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (T + 1 < NSTEP) dma_step(T + 1);
-      }
-      return;
-    }
-  } else {
-    dma_step(0);
-  }
+  dma_step(0);
   const long r0 = (long)blockIdx.x * 64 + wave * 16 + fr;
   const bool valid = r0 < a.M;
   const long row = valid ? r0 : a.M - 1;
@@ -1222,12 +1169,11 @@ __global__ __launch_bounds__((4 + LOADERS) * 64, LOADERS ? 1 : 2) void out_split
   const bool half = a.half != 0;
   tb_static_for<0, 8>([&](auto J) {
     constexpr int j = decltype(J)::value;
-    if constexpr (j % PSTEP == 0) {  // step j / PSTEP has landed and is published; the slot of the step before is free
-      if constexpr (LOADERS == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if constexpr (LOADERS == 0 && j / PSTEP + 1 < NSTEP) dma_step(j / PSTEP + 1);
-    }
-    const unsigned p = pan_lds + ((j / PSTEP) & 1) * SLOT + (j % PSTEP) * TB_PANEL_BYTES;
+    // panel j has landed and is published; the slot of panel j - 1 is free
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if constexpr (j + 1 < 8) dma_step(j + 1);
+    const unsigned p = pan_lds + (j & 1) * TB_PANEL_BYTES;
     tb_mma<8>(acc[2 * j], acc[2 * j + 1], p, xh, xl, fr, fg, half);
   });
   const float inv = a.inv_w * (1.0f / sx);
@@ -1272,9 +1218,7 @@ extern "C" int sam6d_linear_norm_split(const float* x, const void* wimage, const
   if (M == 0) return 0;
   static unsigned long long done = 0;
   if (sam6d_first_use_on_device(&done)) {
-    hipError_t e = hipFuncSetAttribute((const void*)out_split_kernel<4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TB_PANEL_BYTES);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void*)out_split_kernel<0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * TB_PANEL_BYTES);
+    hipError_t e = hipFuncSetAttribute((const void*)out_split_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * TB_PANEL_BYTES);
     if (e != hipSuccess) {
       sam6d_set_error("linear_norm_split: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
       return (int)e;
@@ -1282,16 +1226,7 @@ extern "C" int sam6d_linear_norm_split(const float* x, const void* wimage, const
     sam6d_setup_done_on_device(&done);
   }
   OsArgs a{x, (const unsigned char*)wimage, bias, (_Float16*)fh, (_Float16*)fl, M, inv_w_scale, sam6d_half_for(1)};
-  static int shape = -1;  // SAM6D_OUT_SPLIT_LOADERS=1: the one-workgroup-per-CU shape with loader waves (A/B runs)
-  if (shape < 0) {
-    const char* e = getenv("SAM6D_OUT_SPLIT_LOADERS");
-    shape = (e && e[0] == '1') ? 1 : 0;
-  }
-  const dim3 g((unsigned)((M + 63) / 64));
-  if (shape)
-    hipLaunchKernelGGL((out_split_kernel<4, 2>), g, dim3(512), 4 * TB_PANEL_BYTES, (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL((out_split_kernel<0, 1>), g, dim3(256), 2 * TB_PANEL_BYTES, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(out_split_kernel, dim3((unsigned)((M + 63) / 64)), dim3(256), 2 * TB_PANEL_BYTES, (hipStream_t)stream, a);
   SAM6D_LAUNCH_CHECK("linear_norm_split");
 }
 
@@ -1431,20 +1366,9 @@ extern "C" int sam6d_rows_linear(const float* x, const void* wimage, int npanels
 #define TB_LDS_BYTES(NBUF) ((NBUF) * TB_PANEL_BYTES + (TC_N + 256) * 4)
 #define TB_LDS_BYTES2(NBUF, PSTEP) ((NBUF) * (PSTEP) * TB_PANEL_BYTES + (TC_N + 256) * 4)
 
-// Two shapes of the same kernel: 4 waves x 16 tokens with a 2-slot panel ring (77 KB of LDS: two workgroups per CU, which run out
-// of step, so one's row epilogues overlap the other's MFMAs), and 8 waves x 16 tokens with a 4-slot ring (one workgroup per CU).
-// SAM6D_BLOCK_SHAPE=8 selects the latter (kept for A/B measurements).
-// The 197-token layers (sam6d_token_block) default to 4 computing + 4 loader waves with two panels per ring slot (shape 142); "4" is the
-// plain 4-wave shape there, "4L" / "4P" loader waves / two-panel steps alone.
-static int tb_shape() {
-  static int shape = 0;
-  if (!shape) {
-    const char* e = getenv("SAM6D_BLOCK_SHAPE");
-    shape = !e ? 142 : e[0] == '8' ? 8 : (e[0] == '4' && e[1] == '4') ? 44 : (e[0] == '4' && e[1] == 'L') ? 141 :
-            (e[0] == '4' && e[1] == 'P') ? 42 : e[0] == '4' ? 4 : 142;
-  }
-  return shape;
-}
+// The launched shapes: the dense layer (sam6d_linattn_layer) runs 4 waves x 16 tokens with a 2-slot panel ring (77 KB of LDS: two
+// workgroups per CU, which run out of step, so one's row epilogues overlap the other's MFMAs); the 197-token layers (sam6d_token_block)
+// run 4 (or 2) computing + 4 loader waves with two panels per ring slot.
 
 template <class K>
 static int tb_attr(K kernel, int bytes) {
@@ -1459,16 +1383,9 @@ static int tb_attr(K kernel, int bytes) {
 static int tb_set_attr() {
   static unsigned long long done0 = 0;
   if (sam6d_first_use_on_device(&done0)) {
-    int rc = tb_attr(token_block_kernel<0, 4, 2>, TB_LDS_BYTES(2));
-    if (!rc) rc = tb_attr(token_block_kernel<1, 4, 2>, TB_LDS_BYTES(2));
-    if (!rc) rc = tb_attr(token_block_kernel<0, 8, 4>, TB_LDS_BYTES(4));
-    if (!rc) rc = tb_attr(token_block_kernel<0, 4, 4>, TB_LDS_BYTES(4));
-    if (!rc) rc = tb_attr(token_block_kernel<1, 8, 4>, TB_LDS_BYTES(4));
+    int rc = tb_attr(token_block_kernel<1, 4, 2>, TB_LDS_BYTES(2));
     if (!rc) rc = tb_attr(token_block_kernel<0, 4, 2, TB_FD, 4, 2>, TB_LDS_BYTES2(2, 2));
-    if (!rc) rc = tb_attr(token_block_kernel<0, 4, 2, TB_FD, 4, 1>, TB_LDS_BYTES2(2, 1));
-    if (!rc) rc = tb_attr(token_block_kernel<0, 4, 2, TB_FD, 0, 2>, TB_LDS_BYTES2(2, 2));
     if (!rc) rc = tb_attr(token_block_kernel<0, 2, 2, TB_FD, 4, 2>, TB_LDS_BYTES2(2, 2));
-    if (!rc) rc = tb_attr(token_block_kernel<0, 2, 2, TB_FD, 2, 2>, TB_LDS_BYTES2(2, 2));
     if (rc) return rc;
     sam6d_setup_done_on_device(&done0);
   }
@@ -1484,17 +1401,11 @@ extern "C" int sam6d_token_block(const float* hidden, const float* x, const void
   if (rc) return rc;
   TbArgs a{hidden, x, out, (const unsigned char*)wimage, consts, nullptr, nullptr, nullptr, M, 0, 0, 0, eps,
            sam6d_half_for(1)};
-  const dim3 g64((unsigned)((M + 63) / 64));
   // Round 4: 32-token workgroups (two computing waves) while they all fit the chip at once.  A wave's chain -- 56 weight panels through
   // the LDS ring -- is what a launch takes whatever the number of workgroups; the 6304-row launches (the cross layers: 32 clouds x 197)
   // filled 99 of the 256 CUs with four computing waves each, which contend for the LDS reads of every panel (4 x 32 KB per panel) and
   // leave 157 CUs idle; with two computing waves per workgroup the same rows use 197 CUs and a panel is read twice, not four times.
   // A token's arithmetic does not depend on the workgroup shape (everything is per 16-token wave), so the results are bit-identical.
-  static int narrow = -1;
-  if (narrow < 0) {
-    const char* e = getenv("SAM6D_TB_NARROW");  // A/B: 0 = always 64-token workgroups; 2 = two loader waves instead of four
-    narrow = e ? atoi(e) : 1;
-  }
   int dev_ = 0, cus = 256;
   if (hipGetDevice(&dev_) == hipSuccess) {
     static int cu_cache[SAM6D_MAX_DEVICES];
@@ -1503,24 +1414,12 @@ extern "C" int sam6d_token_block(const float* hidden, const float* x, const void
       cus = cu_cache[dev_];
     }
   }
-  if (narrow && tb_shape() == 142 && (M + 31) / 32 <= cus) {
-    const dim3 g32((unsigned)((M + 31) / 32));
-    if (narrow == 2)
-      hipLaunchKernelGGL((token_block_kernel<0, 2, 2, TB_FD, 2, 2>), g32, dim3(256), TB_LDS_BYTES2(2, 2), (hipStream_t)stream, a);
-    else
-      hipLaunchKernelGGL((token_block_kernel<0, 2, 2, TB_FD, 4, 2>), g32, dim3(384), TB_LDS_BYTES2(2, 2), (hipStream_t)stream, a);
-  } else if (tb_shape() == 142)
-    hipLaunchKernelGGL((token_block_kernel<0, 4, 2, TB_FD, 4, 2>), g64, dim3(512), TB_LDS_BYTES2(2, 2), (hipStream_t)stream, a);
-  else if (tb_shape() == 141)
-    hipLaunchKernelGGL((token_block_kernel<0, 4, 2, TB_FD, 4, 1>), g64, dim3(512), TB_LDS_BYTES2(2, 1), (hipStream_t)stream, a);
-  else if (tb_shape() == 42)
-    hipLaunchKernelGGL((token_block_kernel<0, 4, 2, TB_FD, 0, 2>), g64, dim3(256), TB_LDS_BYTES2(2, 2), (hipStream_t)stream, a);
-  else if (tb_shape() == 44)
-    hipLaunchKernelGGL((token_block_kernel<0, 4, 4>), dim3((unsigned)((M + 63) / 64)), dim3(256), TB_LDS_BYTES(4), (hipStream_t)stream, a);
-  else if (tb_shape() == 8)
-    hipLaunchKernelGGL((token_block_kernel<0, 8, 4>), dim3((unsigned)((M + 127) / 128)), dim3(512), TB_LDS_BYTES(4), (hipStream_t)stream, a);
+  if ((M + 31) / 32 <= cus)
+    hipLaunchKernelGGL((token_block_kernel<0, 2, 2, TB_FD, 4, 2>), dim3((unsigned)((M + 31) / 32)), dim3(384), TB_LDS_BYTES2(2, 2),
+                       (hipStream_t)stream, a);
   else
-    hipLaunchKernelGGL((token_block_kernel<0, 4, 2>), dim3((unsigned)((M + 63) / 64)), dim3(256), TB_LDS_BYTES(2), (hipStream_t)stream, a);
+    hipLaunchKernelGGL((token_block_kernel<0, 4, 2, TB_FD, 4, 2>), dim3((unsigned)((M + 63) / 64)), dim3(512), TB_LDS_BYTES2(2, 2),
+                       (hipStream_t)stream, a);
   SAM6D_LAUNCH_CHECK("token_block");
 }
 
@@ -1532,15 +1431,10 @@ extern "C" int sam6d_linattn_layer(const float* D, const void* wimage, const flo
   if (B == 0) return 0;
   int rc = tb_set_attr();
   if (rc) return rc;
-  const int dshape = tb_shape() == 8 ? 8 : 4;  // (128-token workgroups for the dense layer alone: 0.342 ms against 0.341 ms)
-  const int tok = dshape == 8 ? 128 : 64;  // tokens per workgroup of the kernel shape launched below
-  const int tiles = (I - row0 + tok - 1) / tok;
+  const int tiles = (I - row0 + 63) / 64;  // 64-token workgroups
   SAM6D_REQUIRE((long)B * tiles < 2147483647L, "linattn_layer: too many tiles");
   TbArgs a{D, nullptr, Dout, (const unsigned char*)wimage, consts, (const unsigned char*)kvimage, kvinv, ksum, 0, I, row0, tiles, eps,
            sam6d_half_for(1)};
-  if (dshape == 8)
-    hipLaunchKernelGGL((token_block_kernel<1, 8, 4>), dim3((unsigned)(B * tiles)), dim3(512), TB_LDS_BYTES(4), (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL((token_block_kernel<1, 4, 2>), dim3((unsigned)(B * tiles)), dim3(256), TB_LDS_BYTES(2), (hipStream_t)stream, a);
+  hipLaunchKernelGGL((token_block_kernel<1, 4, 2>), dim3((unsigned)(B * tiles)), dim3(256), TB_LDS_BYTES(2), (hipStream_t)stream, a);
   SAM6D_LAUNCH_CHECK("linattn_layer");
 }

@@ -544,15 +544,6 @@ extern "C" int sam6d_set_thread_matmul_mode(int mode) {
 extern "C" int sam6d_get_matmul_mode(void) { return t_matmul_mode >= 0 ? t_matmul_mode : g_matmul_mode; }
 extern "C" int sam6d_get_thread_matmul_mode(void) { return t_matmul_mode; }
 
-static bool gemm_fast_enabled() {  // SAM6D_GEMM_FAST=0: the general kernel also for whole-tile launches (A/B runs)
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("SAM6D_GEMM_FAST");
-    on = (e && e[0] == '0') ? 0 : 1;
-  }
-  return on != 0;
-}
-
 // The launch decision of gemm_launch, factored out so that sam6d_gemm_route reports exactly what a launch with the same arguments runs.
 struct GemmRoute {
   int kernel;      // SAM6D_GEMM_ROUTE_EXACT / _H3 / _H3_W16
@@ -607,7 +598,7 @@ static int gemm_pick(GemmRoute& r, const float* A, const float* W, const float* 
       r.kernel = SAM6D_GEMM_ROUTE_H3_W16;
       r.fast = r.big && r.wide && !r.half && (M % 128) == 0 && (N % 128) == 0 && (K % 32) == 0 && (lda & 3) == 0 && (ldw & 3) == 0 &&
                ((((size_t)A | (size_t)W) & 15) == 0) && ((((size_t)Wh | (size_t)Wl) & 7) == 0) && (sA & 3) == 0 && (b2.sA2 & 3) == 0 &&
-               (sW & 3) == 0 && (b2.sW2 & 3) == 0 && divisor == 1.0f && !colscale && act == 0 && gemm_fast_enabled();
+               (sW & 3) == 0 && (b2.sW2 & 3) == 0 && divisor == 1.0f && !colscale && act == 0;
     } else {
       r.kernel = SAM6D_GEMM_ROUTE_H3;
     }

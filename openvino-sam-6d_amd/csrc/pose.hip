@@ -904,13 +904,8 @@ __global__ __launch_bounds__(SR_T) void select_radix_kernel(const float* __restr
 extern "C" int sam6d_select_smallest(const float* dis, int B, int n, int k, int* sel, void* stream) {
   SAM6D_REQUIRE(dis && sel && B >= 0 && n > 0 && k > 0 && k <= n && n <= 15000 && B <= 65535, "select_smallest: bad arguments (n <= 15000)");
   if (B == 0) return 0;
-  static int use_radix = -1;
-  if (use_radix < 0) {
-    const char* e = getenv("SAM6D_SELECT_RADIX");  // A/B switch: 0 = the all-pairs rank counting
-    use_radix = (e && e[0] == '0') ? 0 : 1;
-  }
   // dynamic + static LDS (hist[2048] + 3 words, rounded up) within the default 64 KB limit; longer rows keep the all-pairs kernel
-  if (use_radix && (size_t)(n + 2 * k) * 4 + SR_STATIC_LDS <= 65536)
+  if ((size_t)(n + 2 * k) * 4 + SR_STATIC_LDS <= 65536)
     hipLaunchKernelGGL(select_radix_kernel, dim3(B), dim3(SR_T), (size_t)(n + 2 * k) * 4, (hipStream_t)stream, dis, n, k, sel);
   else
     hipLaunchKernelGGL(select_smallest_kernel, dim3(cdiv(n, 256), B), dim3(256), (size_t)((n + 3) & ~3) * 4, (hipStream_t)stream, dis, n, k,
@@ -1543,10 +1538,9 @@ extern "C" int sam6d_fine_score(const float* pts1, const float* R, float* t, con
     sam6d_setup_done_on_device(&fn_done);
   }
   hipLaunchKernelGGL(zero_kernel, dim3(cdiv(2 * B, 256)), dim3(256), 0, s, cnt_ws, 2 * B);
-  const char* fn_env = getenv("SAM6D_FINE_NEAR_MFMA");  // A/B switch, read per call (one call per step): 0 = the vector-ALU kernel
-  const int use_mfma = (fn_env && fn_env[0] == '0') ? 0 : 1;
+  // the matrix-core kernel while its Ppad * 20 bytes of CAD points fit the default 64 KB of LDS (P <= 3264); the vector-ALU kernel beyond
   const int Ppad = (P + 31) & ~31;
-  if (use_mfma && (size_t)Ppad * 20 <= 65536 - 64)
+  if ((size_t)Ppad * 20 <= 65536 - 64)
     hipLaunchKernelGGL(fine_near_mfma_kernel, dim3(cdiv(N, 4 * FN_CT * 32), B), dim3(256), (size_t)Ppad * 20, s, pts1, R, t, model, radius,
                        label1, N, P, Ppad, dis_thres, cnt_ws);
   else

@@ -466,12 +466,6 @@ __global__ __launch_bounds__(XA_WAVES * 64) void xattn_kernel(XaArgs a) {
 static int xa_cu_count[SAM6D_MAX_DEVICES];
 // query split of a launch: two workgroups per (cloud, head) while they all fit the chip at once (the results do not depend on it)
 static int xa_qsplit(int B, int n) {
-  static int allow = -1;  // SAM6D_XATTN_QSPLIT=0: always one workgroup per (cloud, head) (A/B runs)
-  if (allow < 0) {
-    const char* e = getenv("SAM6D_XATTN_QSPLIT");
-    allow = (e && e[0] == '0') ? 0 : 1;
-  }
-  if (!allow) return 1;
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= SAM6D_MAX_DEVICES) return 1;
   const int cu = xa_cu_count[dev];

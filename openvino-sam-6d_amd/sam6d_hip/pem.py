@@ -25,71 +25,55 @@ def _s():
 
 
 class Options:
-    """The explicit choice of arithmetic and kernel routes for a launch sequence -- what used to be a process-global matmul mode plus
-    a dozen SAM6D_* environment switches.  An Options object travels with a weight set (`PemWeights(sd, dev, options=...)`) or with one
-    call (`pem_match(..., options=...)`, any @on_tensor_device entry point); two weight sets in one process can therefore run different
-    arithmetic.  Without one, `Options.from_env()` is resolved once per outermost entry point (the A/B switches of earlier rounds keep
-    working from the environment).  Fields:
-      matmul_mode   None = the library's process default (sam6d_set_matmul_mode / SAM6D_MATMUL_MODE), else 0 exact fp32 MFMA,
-                    1 fp16 x3 split, 2 fp16 single product (experimental); applied as the calling thread's mode for the duration of
-                    the entry point (sam6d_set_thread_matmul_mode)
-      fused_rpe / fused_fine / overlap / microbatch / pe_side_wgs   pipeline shape of pem_match (cfg keys of the same name win)
-      the rest      A/B routes between bit- or tolerance-equivalent kernels (see the comments below)."""
+    """The explicit choice of arithmetic and kernel routes for a launch sequence.  An Options object travels with a weight set
+    (`PemWeights(sd, dev, options=...)`) or with one call (`pem_match(..., options=...)`, any @on_tensor_device entry point); two weight
+    sets in one process can therefore run different arithmetic.  Without one, `Options.from_env()` is resolved once per outermost entry
+    point.  Fields (environment variable in ENV):
+      matmul_mode   None = the library's process default (sam6d_set_matmul_mode / SAM6D_MATMUL_MODE), resolved into `mode` when the
+                    object is built; else 0 exact fp32 MFMA, 1 fp16 x3 split, 2 fp16 single product (experimental).  Applied as the
+                    calling thread's mode for the duration of the entry point (sam6d_set_thread_matmul_mode)
+      fused_block   fused transformer-block kernels (csrc/block.hip); off = the launch-per-op path
+      fused_rpe / rpe_products / fused_fine / overlap / microbatch   pipeline shape of pem_match (cfg keys of the same name win)
+    The object keeps the values it was given; the split-precision routes (fused_block, fused_rpe) read as off in mode 0, so
+    `replace(matmul_mode=1)` starts again from what the caller asked for.  Read-only routes that follow from the fields: w16 (pre-split
+    fp16 weight halves in the GEMMs: modes 1 and 2) and fused_front / fused_out / rows_linear (the RPE front kernel, the fine out_proj
+    + normalize + split pass and the sparse-token panel kernel: with fused_block)."""
     DEFAULTS = dict(
         matmul_mode=None,
-        w16=True,           # pre-split fp16 weight halves in the large GEMMs
         fused_block=True,   # fused transformer-block kernels (csrc/block.hip)
-        fused_ln=False,     # projection + residual + LayerNorm in one launch on the unfused path (measured 1 % slower)
-        fused_front=True,   # qkv projection + proj_p fold + D_c fold of an RPE self layer in one launch
-        score_mfma=True,    # hypothesis scoring: distance products on the fp32 matrix cores
-        bq_grid=True,       # ball queries through the cell grid (identical indices)
-        xattn_kv=True,      # key / value projection inside the cross-attention kernel
-        self_attn=True,     # q.k^T + softmax + P.v of the RPE self layers in one launch per (cloud, head)
-        fused_out=True,     # fine out_proj + normalize + operand split in one pass
-        rows_linear=True,   # sparse-token projections on the panel kernel
         rpe_products=0,     # 0: what the weight set allows (geo_cheb_a_packed); 3: always three stage-1 products
         fused_rpe=True,     # RPE attention without the embedding tensor
         fused_fine=True,    # fine similarity + soft assignment as one pipeline (finematch.hip)
         overlap=True,       # pose-independent fine work on a second HIP stream
         microbatch=1,
-        pe_side_wgs=512,    # bound on the side stream's persistent PE-MLP workgroups
     )
-    ENV = dict(matmul_mode="SAM6D_MATMUL_MODE", w16="SAM6D_W16", fused_block="SAM6D_FUSED_BLOCK", fused_ln="SAM6D_FUSED_LN",
-               fused_front="SAM6D_FUSED_FRONT", score_mfma="SAM6D_SCORE_MFMA", bq_grid="SAM6D_BQ_GRID", xattn_kv="SAM6D_XATTN_KV",
-               self_attn="SAM6D_SELF_ATTN", fused_out="SAM6D_FUSED_OUT", rows_linear="SAM6D_ROWS_LINEAR",
-               rpe_products="SAM6D_RPE_PRODUCTS", fused_rpe="SAM6D_FUSED_RPE", fused_fine="SAM6D_FUSED_FINE", overlap="SAM6D_OVERLAP",
-               microbatch="SAM6D_MICROBATCH", pe_side_wgs="SAM6D_PE_SIDE_WGS")
-    __slots__ = tuple(DEFAULTS) + ("mode",)
+    ENV = dict(matmul_mode="SAM6D_MATMUL_MODE", fused_block="SAM6D_FUSED_BLOCK", rpe_products="SAM6D_RPE_PRODUCTS",
+               fused_rpe="SAM6D_FUSED_RPE", fused_fine="SAM6D_FUSED_FINE", overlap="SAM6D_OVERLAP", microbatch="SAM6D_MICROBATCH")
+    __slots__ = ("_kw", "mode")
 
     def __init__(self, **kw):
         bad = set(kw) - set(self.DEFAULTS)
         if bad:
             raise TypeError("Options: unknown field(s) %s" % sorted(bad))
-        for k, v in self.DEFAULTS.items():
-            setattr(self, k, kw.get(k, v))
-        self._resolve()
-
-    def _resolve(self):
-        """Resolve the arithmetic mode and gate the routes that exist only in the split-precision modes."""
-        m = self.matmul_mode
+        self._kw = dict(self.DEFAULTS, **kw)
+        m = self._kw["matmul_mode"]
         self.mode = int(_lib.load().sam6d_get_matmul_mode()) if m is None else int(m)
         if self.mode not in (0, 1, 2):
             raise ValueError("Options.matmul_mode must be None, 0, 1 or 2")
-        split = self.mode >= 1
-        self.w16 = bool(self.w16) and split
-        self.fused_block = bool(self.fused_block) and split
-        self.fused_ln = bool(self.fused_ln) and split
-        self.fused_front = bool(self.fused_front) and self.fused_block
-        self.fused_out = bool(self.fused_out) and self.fused_block
-        self.rows_linear = bool(self.rows_linear) and self.fused_block
-        self.fused_rpe = bool(self.fused_rpe) and split
-        self.rpe_products = int(self.rpe_products)
-        self.microbatch = int(self.microbatch)
-        self.pe_side_wgs = int(self.pe_side_wgs)
+
+    matmul_mode = property(lambda self: self._kw["matmul_mode"])
+    fused_block = property(lambda self: bool(self._kw["fused_block"]) and self.mode >= 1)
+    fused_rpe = property(lambda self: bool(self._kw["fused_rpe"]) and self.mode >= 1)
+    rpe_products = property(lambda self: int(self._kw["rpe_products"]))
+    fused_fine = property(lambda self: self._kw["fused_fine"])
+    overlap = property(lambda self: self._kw["overlap"])
+    microbatch = property(lambda self: int(self._kw["microbatch"]))
+    w16 = property(lambda self: self.mode >= 1)
+    fused_front = fused_out = rows_linear = fused_block
 
     @classmethod
     def from_env(cls, **over):
-        """The environment's A/B switches (read now), overridden by keyword arguments."""
+        """The environment's switches (read now), overridden by keyword arguments."""
         kw = {}
         for k, name in cls.ENV.items():
             v = os.environ.get(name)
@@ -101,21 +85,18 @@ class Options:
         return cls(**kw)
 
     def replace(self, **over):
-        kw = {k: getattr(self, k) for k in self.DEFAULTS}
-        kw["matmul_mode"] = self.matmul_mode
-        kw.update(over)
-        return Options(**kw)
+        """A copy with some fields changed, built from the values this object was given."""
+        return Options(**dict(self._kw, **over))
 
     def describe(self):
         return {k: getattr(self, k) for k in self.DEFAULTS if k != "matmul_mode"} | {"matmul_mode": self.mode}
 
 
 class _Tls(threading.local):
-    """Per-thread state of the entry points: the Options of the outermost call in flight, its nesting depth and the micro-batch pipeline
-    slot -- the library's matmul mode is per thread too (sam6d_set_thread_matmul_mode), so two threads may drive two models at once."""
+    """Per-thread state of the entry points: the Options of the outermost call in flight and its nesting depth -- the library's matmul
+    mode is per thread too (sam6d_set_thread_matmul_mode), so two threads may drive two models at once."""
     flags = None
     depth = 0
-    pipe = None
 
 
 _TLS = _Tls()
@@ -516,16 +497,6 @@ def _post_attention(hidden, x2d, L, out=None):
         with _Timed("token_block"):
             _lib.call("sam6d_token_block", _p(hidden), _p(x2d), tb["img"].data_ptr(), _p(tb["cst"]), _p(out), M, 1e-5, _s())
         return out
-    # SAM6D_FUSED_LN=1: projection + residual + LayerNorm in one launch (sam6d_gemm_ln256).  Off by default: measured 1 % slower
-    # than the two launches (64-row tiles at 184 registers and 4-byte stores cost what the saved LayerNorm pass gives back).
-    if _flags().fused_ln:
-        y = gemm_ln(hidden, L["lin"], x2d, L["n1"])
-        h = linear(y, L["exp"], act=1)
-        r = gemm_ln(h, L["sq"], y, L["n2"])
-        if out is not None:
-            _lib.call("sam6d_copy_f32", _p(r), _p(out), r.numel(), _s())
-            return out
-        return r
     y = layernorm(linear(hidden, L["lin"], residual=x2d), L["n1"])
     h = linear(y, L["exp"], act=1)
     return layernorm(linear(h, L["sq"], residual=y), L["n2"], out=out)
@@ -538,7 +509,8 @@ def _fused_block():
 
 
 def gemm_ln(x, lin, residual, norm, eps=1e-5):
-    """LayerNorm(x @ lin.w^T + lin.b + residual) for 256 output channels (sam6d_gemm_ln256)."""
+    """LayerNorm(x @ lin.w^T + lin.b + residual) for 256 output channels (sam6d_gemm_ln256).  Not on the path: the two launches of
+    _post_attention measured 1 % faster."""
     M, K = x.shape
     out = _empty((M, C), x)
     _lib.call("sam6d_gemm_ln256", _p(x), _p(lin.w), _p(lin.b), _p(residual), _p(norm[0]), _p(norm[1]), _p(out), M, K, K, K, C, C,
@@ -554,32 +526,14 @@ PROFILE = None
 PROFILE_NAMES = None
 
 
-# Micro-batch pipeline (pem_match with microbatch > 1): the slices run the same launch chain on their own streams.  Started together they
-# stay in lock-step -- both in a throughput-bound kernel (which then share the chip: no gain) or both in a latency-bound one (whose time
-# does not depend on the batch size: no gain either).  What pays is a slice's latency-bound chain (197-token layers, pose solver) BESIDE
-# another slice's throughput-bound kernel, so the big kernels take turns: occurrence k of a big kernel in slice s waits for occurrence k
-# of the same kernel in slice s - 1 (an event recorded earlier in program order: slices are issued one after the other).  Slice 0 runs
-# free, slice 1 trails it by one big kernel, and so on: at any time at most one slice is inside a given big kernel while the others are
-# in their latency-bound stretches.  _TLS.pipe = (events, slice index, per-slice occurrence counters) while a slice is being issued.
-_BIG = frozenset(("rpe_score_kernel", "linattn_layer", "score_hyp", "fine_match", "linear_norm_split", "pe_mlp", "gemm_big"))
-
-
 class _Timed:
+    """Profiling events around a launch site (PROFILE); nothing is recorded when PROFILE is None."""
+
     def __init__(self, name):
         self.name = name
 
     def __enter__(self):
         self.on = PROFILE is not None and (PROFILE_NAMES is None or self.name in PROFILE_NAMES)
-        self.turn = None
-        if _TLS.pipe is not None and self.name in _BIG:
-            ev, s, counts = _TLS.pipe
-            k = counts.get(self.name, 0)
-            counts[self.name] = k + 1
-            self.turn = (s, self.name, k)
-            if s > 0:
-                e = ev.get((s - 1, self.name, k))
-                if e is not None:
-                    torch.cuda.current_stream().wait_event(e)
         if self.on:
             self.a = torch.cuda.Event(enable_timing=True)
             self.b = torch.cuda.Event(enable_timing=True)
@@ -589,10 +543,6 @@ class _Timed:
         if self.on:
             self.b.record()
             PROFILE.setdefault(self.name, []).append((self.a, self.b))
-        if self.turn is not None and _TLS.pipe is not None:
-            e = torch.cuda.Event()
-            e.record(torch.cuda.current_stream())
-            _TLS.pipe[0][self.turn] = e
 
 
 @on_tensor_device
@@ -806,9 +756,19 @@ def pack_rpe_front(L, dcT):
     return dict(img=img, inv=(1.0 / s_qkv, 1.0 / s_wp, 1.0 / s_dc))
 
 
+# the longest cloud the one-launch self attention (xattn.hip sattn_kernel) takes; longer clouds run q.k^T and P.v as batched GEMMs
+SATTN_MAX_N = 208
+
+
 def rpe_self_layer_fused(x, G, L):
-    """rpe_self_layer without the embedding tensor (rpe.hip): q.k^T and P.v as batched GEMMs, the geometric term rebuilt from
-    the Chebyshev basis inside the score kernel."""
+    """rpe_self_layer without the embedding tensor (rpe.hip): the geometric term rebuilt from the Chebyshev basis inside the score
+    kernel."""
+    return _rpe_self_tail(x, G, L, *_rpe_self_front(x, G, L))
+
+
+def _rpe_self_front(x, G, L):
+    """(qkv, qp, qd, vT) of rpe_self_layer_fused: the q | k | v rows, the query folded into proj_p per head and qp folded into D_c;
+    vT = the values transposed per cloud where the GEMM tail takes them (else None)."""
     Bp, n, _ = x.shape
     M = Bp * n
     x2 = x.reshape(M, C)
@@ -821,39 +781,51 @@ def rpe_self_layer_fused(x, G, L):
         qp = _empty((M, H * C), x)
         qd = _empty((M * H, 32), x)
         ldp = (n + 3) // 4 * 4
-        if _flags().self_attn and n <= 208:  # the attention kernel cuts k and v into its LDS images itself: plain q | k | v rows
+        if n <= SATTN_MAX_N:  # the attention kernel cuts k and v into its LDS images itself: plain q | k | v rows
             with _Timed("rpe_front"):
                 _lib.call("sam6d_rpe_front", _p(x2), fr["img"].data_ptr(), _p(L["qkv"].b), fr["inv"][0], fr["inv"][1], fr["inv"][2],
                           _p(qkv), _p(qp), _p(qd), M, _s())
-            return _rpe_self_tail(x, x2, G, L, qkv, qp, qd)
+            return qkv, qp, qd, None
         vT = _empty((Bp, C, ldp), x)  # the values land transposed per cloud (the P.v operand): no transpose pass
         with _Timed("rpe_front"):
             _lib.call("sam6d_rpe_front_vt", _p(x2), fr["img"].data_ptr(), _p(L["qkv"].b), fr["inv"][0], fr["inv"][1], fr["inv"][2], _p(qkv),
                       _p(qp), _p(qd), M, _p(vT), n, ldp, _s())
-        return _rpe_self_tail(x, x2, G, L, qkv, qp, qd, vT)
+        return qkv, qp, qd, vT
     qkv = linear(x2, L["qkv"])  # (M, 768): q | k | v
     qp = _empty((M, H * C), x)
     # (act 16: the two folds of the geometric embedding into the query stay at fp16 x3 in matmul mode 2 -- "fp32 geometry")
     gemm(qkv, L["wpT"], None, qp, M, C, 64, 3 * C, C, H * C, batch=H, sA=64, sW=64, sC=C, act=16, w16=L.get("wpT16"))
     qd = _empty((M * H, 32), x)
     gemm(qp, G.dcT, None, qd, M * H, 32, C, C, C, 32, act=16, w16=G.dcT16)
-    return _rpe_self_tail(x, x2, G, L, qkv, qp, qd)
+    return qkv, qp, qd, None
 
 
-def _rpe_self_tail(x, x2, G, L, qkv, qp, qd, vT=None):
+def _rpe_self_tail(x, G, L, qkv, qp, qd, vT=None):
     """q.k^T, geometric scores + softmax, P.v and the layer tail of rpe_self_layer_fused."""
+    if x.shape[1] <= SATTN_MAX_N:
+        return _rpe_self_tail_attention(x, G, L, qkv, qp, qd)
+    return _rpe_self_tail_gemm(x, G, L, qkv, qp, qd, vT)
+
+
+def _rpe_self_tail_attention(x, G, L, qkv, qp, qd):
+    """The geometric score term alone, then q.k^T + softmax + P.v per (cloud, head) in one launch (xattn.hip sattn_kernel)."""
     Bp, n, _ = x.shape
     M = Bp * n
     ldp = (n + 3) // 4 * 4
-    if _flags().self_attn and n <= 208:
-        # geometric score term alone, then q.k^T + softmax + P.v per (cloud, head) in one launch (xattn.hip sattn_kernel)
-        Gs = _empty((M, H, ldp), x)
-        with _Timed("rpe_score_kernel"):
-            _lib.call("sam6d_rpe_geo_scores", _p(G.idx), _p(G.pos), _p(G.keep[1]), _p(G.rows), G.wa_cheb, float(GEO_XMAX),
-                      float(G.xmax_a), int(G.products), _p(qp), _p(qd), _p(Gs), M, n, ldp, _s())
-        hid = _empty((M, C), x)
-        _lib.call("sam6d_rpe_self_attention", _p(qkv), _p(Gs), _p(hid), Bp, n, ldp, _s())
-        return _post_attention(hid, x2, L).reshape(Bp, n, C)
+    Gs = _empty((M, H, ldp), x)
+    with _Timed("rpe_score_kernel"):
+        _lib.call("sam6d_rpe_geo_scores", _p(G.idx), _p(G.pos), _p(G.keep[1]), _p(G.rows), G.wa_cheb, float(GEO_XMAX),
+                  float(G.xmax_a), int(G.products), _p(qp), _p(qd), _p(Gs), M, n, ldp, _s())
+    hid = _empty((M, C), x)
+    _lib.call("sam6d_rpe_self_attention", _p(qkv), _p(Gs), _p(hid), Bp, n, ldp, _s())
+    return _post_attention(hid, x.reshape(M, C), L).reshape(Bp, n, C)
+
+
+def _rpe_self_tail_gemm(x, G, L, qkv, qp, qd, vT=None):
+    """q.k^T and P.v as batched GEMMs, the softmax inside the score kernel; vT None: the values are transposed out of qkv."""
+    Bp, n, _ = x.shape
+    M = Bp * n
+    ldp = (n + 3) // 4 * 4
     qk = _empty((M, H, ldp), x)
     P = _empty((M, H, ldp), x)
     gemm_b2(qkv, qkv, qk, n, n, 64, 3 * C, 3 * C, H * ldp, Bp, n * 3 * C, n * 3 * C, n * H * ldp, H, 64, 64, ldp, w_off=C)
@@ -865,7 +837,7 @@ def _rpe_self_tail(x, x2, G, L, qkv, qp, qd, vT=None):
         _lib.call("sam6d_transpose", _p(qkv, 2 * C), 3 * C, n * 3 * C, Bp, n, C, _p(vT), ldp, C * ldp, _s())
     hid = _empty((M, C), x)
     gemm_b2(P, vT, hid, n, 64, n, H * ldp, ldp, C, Bp, n * H * ldp, C * ldp, n * C, H, ldp, 64 * ldp, 64)
-    return _post_attention(hid, x2, L).reshape(Bp, n, C)
+    return _post_attention(hid, x.reshape(M, C), L).reshape(Bp, n, C)
 
 
 def rpe_self_layer(x, E, L):
@@ -895,7 +867,7 @@ def cross_layer(x, mem, L, out=None):
     if _fused_block() and "xq" in L and n <= 256 and m <= 208:
         # proj_q, proj_k, proj_v + softmax attention of all four heads in one launch on the matrix cores (xattn.hip)
         with _Timed("cross_attention"):
-            if "xkv" in L and _flags().xattn_kv:
+            if "xkv" in L:
                 _lib.call("sam6d_cross_attention_kv", _p(x2), _p(mem), L["xq"]["img"].data_ptr(), _p(L["q"].b), float(L["xq"]["inv"]),
                           L["xkv"]["img"].data_ptr(), _p(L["kv"].b), float(L["xkv"]["inv"]), _p(hid), B, n, m, _s())
             else:
@@ -1060,15 +1032,11 @@ def pe_group(pts, r1=0.1, r2=0.2, ns1=32, ns2=64):
     q = _empty((Bp, N, 3), pts)
     _lib.call("sam6d_add_scalar", _p(pts), 0.00000001, Bp * N * 3, _p(q), _s())
     idx12 = (_empty((Bp, N, ns1), pts, torch.int32), _empty((Bp, N, ns2), pts, torch.int32))
-    if _flags().bq_grid:
-        nbytes = int(_lib.load().sam6d_ball_query2_grid_workspace_bytes(Bp, N))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=pts.device)
-        with _Timed("ball_query"):
-            _lib.call("sam6d_ball_query2_grid", _p(q), _p(pts), Bp, N, N, float(r1), ns1, _p(idx12[0]), float(r2), ns2, _p(idx12[1]),
-                      ws.data_ptr(), nbytes, _s())
-        return idx12
+    nbytes = int(_lib.load().sam6d_ball_query2_grid_workspace_bytes(Bp, N))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=pts.device)
     with _Timed("ball_query"):
-        _lib.call("sam6d_ball_query2", _p(q), _p(pts), Bp, N, N, float(r1), ns1, _p(idx12[0]), float(r2), ns2, _p(idx12[1]), _s())
+        _lib.call("sam6d_ball_query2_grid", _p(q), _p(pts), Bp, N, N, float(r1), ns1, _p(idx12[0]), float(r2), ns2, _p(idx12[1]),
+                  ws.data_ptr(), nbytes, _s())
     return idx12
 
 
@@ -1150,7 +1118,7 @@ def compute_coarse_Rt(att, pts1, pts2, model, radius, rand, n_proposal1=6000, n_
     Rb = _empty((B, 3, 3), att)
     tb = _empty((B, 3), att)
     best = _empty((B,), att, torch.int32)
-    if model.shape[1] <= 4096 and _flags().score_mfma:
+    if model.shape[1] <= 4096:
         # the K = 3 distance contraction on the fp32 matrix cores (same bits), weighted distances staged in a workspace
         ws = _empty((B * N1 * n_proposal2,), att)
         with _Timed("score_hyp"):
@@ -1421,12 +1389,9 @@ def fine_point_matching(dp, df, E, fps_idx, radius, model, init_R, init_t, W, cf
         D, lead = sparse_to_dense_transformer(D, E, fps_idx, blk, lead=lead, write_bg=(k == len(blocks) - 1), return_sparse=True)
     if fused_fine and N in (2048, 4096) and _fused_block():
         # similarity + soft assignment as one pipeline: the (B, 2049, 2049) matrix is written once and read twice (finematch.hip)
-        if _flags().fused_out and _flags().mode >= 1:
-            if "out_img" not in W.fine:
-                W.fine["out_img"] = pack_cross_query(W.fine["out_proj"])
-            f = linear_norm_split(D.reshape(2 * B * (N + 1), C), W.fine["out_proj"], W.fine["out_img"])
-        else:
-            f = linear(D.reshape(2 * B * (N + 1), C), W.fine["out_proj"])
+        if "out_img" not in W.fine:
+            W.fine["out_img"] = pack_cross_query(W.fine["out_proj"])
+        f = linear_norm_split(D.reshape(2 * B * (N + 1), C), W.fine["out_proj"], W.fine["out_img"])
         return compute_fine_Rt_fused(f, B, N + 1, cfg["temp"], dp[:B], dp[B:], model, radius, cfg["dis_thres"], return_aux)
     att = feature_similarity(D, B, N + 1, W.fine["out_proj"], cfg["temp"])
     R, t, score = compute_fine_Rt(att, dp[:B], dp[B:], model, radius, cfg["dis_thres"])
@@ -1467,6 +1432,8 @@ def _ensure_w16(W):
 
 
 _SIDE_STREAMS = {}
+# bound on the persistent PE-MLP workgroups of the side stream (they run beside the coarse pose solver)
+PE_SIDE_WGS = 512
 
 
 def _side_stream(dev, key=0):
@@ -1474,8 +1441,7 @@ def _side_stream(dev, key=0):
     streams and ("mb", i, "side") their side streams)."""
     s = _SIDE_STREAMS.get((dev, key))
     if s is None:
-        prio = os.environ.get("SAM6D_SIDE_PRIO")  # A/B: HIP stream priority of the auxiliary streams (default: the default priority)
-        s = _SIDE_STREAMS[(dev, key)] = torch.cuda.Stream(device=dev) if prio is None else torch.cuda.Stream(device=dev, priority=int(prio))
+        s = _SIDE_STREAMS[(dev, key)] = torch.cuda.Stream(device=dev)
     return s
 
 
@@ -1496,9 +1462,7 @@ def pem_match(dense_pm, dense_fm, dense_po, dense_fo, radius, model, W, rand, cf
 
     cfg["microbatch"] = k (env SAM6D_MICROBATCH, default 1 = off): the batch is cut into k slices whose coarse / fine stages run
     on k HIP streams (one slice's latency-bound chains beside another's dense kernels, +2 % at k = 2, twice the host launch work).
-    FPS, gathers and the geometric indices of every slice are computed first, serially, on the caller's stream -- defence in
-    depth for the packed-fp32 / f16-MFMA hazard described in DESIGN "Concurrency caveat" (the library is built without packed
-    fp32 instructions since).  scratch/dbg_ov.py: 0 of 60 two-slice runs differ from the serial result.
+    Each slice runs its own FPS, gathers and geometric indices on its own stream and forks no further stream.
 
     return_aux=True adds a dict of intermediates (coarse attention, sampled indices, hypotheses, scores, the coarse pose, FPS indices,
     fine labels / weights) WITHOUT changing which kernels run.  Kernel choice is cfg's: cfg["fused_rpe"] (env SAM6D_FUSED_RPE, default on)
@@ -1610,8 +1574,8 @@ def pem_match(dense_pm, dense_fm, dense_po, dense_fo, radius, model, W, rand, cf
                 ev.record(cur)
                 with torch.cuda.stream(side):
                     side.wait_event(ev)
-                    fine_static_b(dpu, D, grp, W, shared_template, max_wg=opts.pe_side_wgs)
-        elif overlap and (mb <= 1 or cfg.get("mb_overlap", False)):
+                    fine_static_b(dpu, D, grp, W, shared_template, max_wg=PE_SIDE_WGS)
+        elif overlap and mb <= 1:
             # (inside a micro-batch slice the pipeline of slices provides the overlap; a second level of forked streams is also what
             #  hipStreamEndCapture crashed on when the slices were captured into a graph: scratch/graph_probe2.py)
             D, side = fork_fine_static(dpu, df, side_key)
@@ -1647,25 +1611,12 @@ def pem_match(dense_pm, dense_fm, dense_po, dense_fo, radius, model, W, rand, cf
     # (until round 4 the slices' FPS / gathers / geometric indices ran serially on the caller's stream first -- defence in depth for the
     #  packed-fp32 hazard, which the build flags have removed since; FPS is latency-bound, 0.17 ms whatever the batch, so k serial
     #  prologues cost k times that: each slice now runs its own prologue on its own stream)
-    serial_prep = bool(cfg.get("mb_serial_prepare", False))
-    preps = [prepare(lo, hi) for lo, hi in spans] if serial_prep else [None] * len(spans)
     outs = []
-    events = {}
     for i, (lo, hi) in enumerate(spans):
         st = _side_stream(dense_pm.device, ("mb", i))
         st.wait_stream(main)
-        _TLS.pipe = (events, i, {}) if cfg.get("mb_pipeline", False) else None
-        try:
-            with torch.cuda.stream(st):
-                if preps[i] is None:
-                    preps[i] = prepare(lo, hi)
-                outs.append(rest(preps[i], lo, hi, ("mb", i, "side")))
-        finally:
-            _TLS.pipe = None
-        if serial_prep:
-            for tns in preps[i][:5]:
-                for x in (tns if isinstance(tns, tuple) else (tns,)):
-                    x.record_stream(st)
+        with torch.cuda.stream(st):
+            outs.append(rest(prepare(lo, hi), lo, hi, ("mb", i, "side")))
     R = _empty((B, 3, 3), dense_pm)
     t = _empty((B, 3), dense_pm)
     sc = _empty((B,), dense_pm)
@@ -1700,17 +1651,15 @@ def describe_paths(W, cfg=DEFAULT_CFG, options=None):
         "fused_rpe_guard_passed": fused_ok if split else None,
         "embedding_rows": ("geo_cheb_kernel + geo_embed_h3_kernel (split-precision images in range)" if img_ok else
                            "geo_embed_kernel (exact fp32: weight images leave the fp16 range)") if split else "geo_embed_kernel (exact fp32)",
-        "gemm_route": ("gemm_nt_h3_kernel, pre-split fp16 weight halves" if o.w16 else "gemm_nt_h3_kernel, weights split per tile") if split
-                      else "gemm_nt_kernel (v_mfma_f32_32x32x2_f32)",
+        "gemm_route": "gemm_nt_h3_kernel, pre-split fp16 weight halves" if split else "gemm_nt_kernel (v_mfma_f32_32x32x2_f32)",
         "layer_tails": "token_block_kernel (one launch per tail)" if o.fused_block else "GEMM + LayerNorm launches",
-        "cross_layers": ("xattn_kernel<kv inside> + token_block kernel" if o.xattn_kv else "kv GEMM + xattn_kernel + token_block kernel") if o.fused_block
-                        else "GEMM / attention_kernel launches",
-        "self_attention": "sattn_kernel (q.k^T + softmax + P.v per (cloud, head))" if (o.self_attn and fused) else "batched GEMMs",
+        "cross_layers": "xattn_kernel<kv inside> + token_block kernel" if o.fused_block else "GEMM / attention_kernel launches",
+        "self_attention": "sattn_kernel (q.k^T + softmax + P.v per (cloud, head))" if fused else "batched GEMMs",
         "fine_match": "finematch.hip pipeline (E written once, read twice)" if (bool(cfg.get("fused_fine", o.fused_fine)) and o.fused_block)
                       else "materialised (B,N+1,N+1) attention + soft-assignment passes",
-        "fine_out_proj": "out_split_kernel (out_proj + normalize + fp16 split)" if (o.fused_out and split) else "GEMM + fm_prep_kernel",
-        "hypothesis_scoring": "score_hyp_mfma_kernel (fp32 matrix cores)" if o.score_mfma else "score_hyp_kernel (vector ALU)",
-        "ball_query": "cell grid" if o.bq_grid else "all pairs",
+        "fine_out_proj": "out_split_kernel (out_proj + normalize + fp16 split)" if o.fused_out else "GEMM + fm_prep_kernel",
+        "hypothesis_scoring": "score_hyp_mfma_kernel (fp32 matrix cores)",
+        "ball_query": "cell grid",
         "overlap_side_stream": bool(cfg.get("overlap", o.overlap)),
         "microbatch": int(cfg.get("microbatch", o.microbatch)),
     }

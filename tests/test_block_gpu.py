@@ -221,8 +221,9 @@ def test_fine_match_equals_unfused_path(dev, B, n):
 
 
 # --------------------------------------------------------------------------------------------------- fused cross attention
+# (33, 197, 197): 8B > 256 CUs, so xa_qsplit launches one workgroup per (cloud, head) instead of two
 @pytest.mark.parametrize("B,n,m,xs", [(2, 197, 197, 1.0), (3, 50, 208, 1.0), (1, 16, 1, 1.0), (2, 64, 32, 1.0), (2, 197, 197, 3.0e4),
-                                      (2, 130, 197, 1.0e-5)])
+                                      (2, 130, 197, 1.0e-5), (33, 197, 197, 1.0)])
 def test_cross_attention_vs_fp64(dev, B, n, m, xs):
     """sam6d_cross_attention (proj_q + 4-head softmax attention, xattn.hip) against a float64 recompute of MultiHeadAttention
     (PEM/model/transformer.py:95-150); xs scales the query-side tokens and 1 / xs the keys (operands far outside fp16's range, logits
@@ -256,7 +257,7 @@ def test_cross_attention_vs_fp64(dev, B, n, m, xs):
 
 
 @pytest.mark.parametrize("B,n,m,xs", [(2, 197, 197, 1.0), (3, 50, 208, 1.0), (1, 16, 1, 1.0), (2, 64, 32, 1.0), (2, 197, 197, 3.0e4),
-                                      (2, 130, 197, 1.0e-5), (1, 197, 100, 1.0)])
+                                      (2, 130, 197, 1.0e-5), (1, 197, 100, 1.0), (33, 197, 197, 1.0)])
 def test_cross_attention_kv_vs_fp64(dev, B, n, m, xs):
     """sam6d_cross_attention_kv -- proj_q, proj_k, proj_v and the 4-head softmax attention of MultiHeadAttention in ONE launch
     (PEM/model/transformer.py:111-150), the memory tokens as input -- against a float64 recompute; xs scales the query-side tokens and

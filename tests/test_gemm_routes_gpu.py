@@ -51,11 +51,6 @@ T128, FAST, WIDE, HALF = R["TILE128"], R["FAST"], R["WIDE"], R["HALF"]
 PLAIN, CG, FOLD, NONE = R["PLAIN"], R["COLGROUP"], R["FOLD"], R["NONE"]
 
 
-def _fast_enabled():
-    e = os.environ.get("SAM6D_GEMM_FAST")
-    return not (e and e[0] == "0")
-
-
 def _half_enabled():
     return bool(int(os.environ.get("SAM6D_HALF_MASK", "15")) & 1)
 
@@ -280,14 +275,17 @@ def _check(got, ref, bound, what):
     return worst
 
 
-def _skip_if_unreachable(c):
+def _presplit_used():
+    """pem.gemm passes pre-split weights in the split-precision modes of the environment's Options (not under SAM6D_MATMUL_MODE=0)."""
     from sam6d_hip import pem
-    if c["code"] & FAST and not _fast_enabled():
-        pytest.skip("SAM6D_GEMM_FAST=0 in the environment: the whole-tile kernel is switched off")
+    return pem._flags().w16
+
+
+def _skip_if_unreachable(c):
     if c["code"] & HALF and not _half_enabled():
         pytest.skip("SAM6D_HALF_MASK clears the GEMM family: mode 2 keeps the split")
-    if c["w16"] and not pem._flags().w16:
-        pytest.skip("SAM6D_W16=0 in the environment: pem.gemm does not use pre-split weights")
+    if c["w16"] and not _presplit_used():
+        pytest.skip("SAM6D_MATMUL_MODE=0 in the environment: pem.gemm does not use pre-split weights")
 
 
 @pytest.mark.parametrize("c", CASES, ids=[c["name"] for c in CASES])
@@ -335,13 +333,11 @@ def test_route_query_matches_launch_decision(dev):
         assert pem.gemm_route(A, W, None, out, M, N, 64, 64, 64, 1024, batch=b) == NONE
 
 
-@pytest.mark.skipif(not _fast_enabled(), reason="SAM6D_GEMM_FAST=0 in the environment: the whole-tile kernel is switched off")
 @pytest.mark.parametrize("layout", ["bg_rows_fold32", "single_colgroup"])
 def test_fast_bits_equal_general_presplit(dev, layout):
     """FAST and the general pre-split 128 x 128 kernel on the same inputs: the same bits (colscale = ones forces the general one)."""
-    from sam6d_hip import pem
-    if not pem._flags().w16:
-        pytest.skip("SAM6D_W16=0 in the environment")
+    if not _presplit_used():
+        pytest.skip("SAM6D_MATMUL_MODE=0 in the environment: pem.gemm does not use pre-split weights")
     if layout == "bg_rows_fold32":
         c = _case(layout, 1, 2048, 256, 256, 0, batch=32, ldc=256, sC=2049 * 256, c_off=256, bias=True, w16=True, res="sep")
         order = FOLD

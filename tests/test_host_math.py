@@ -58,28 +58,36 @@ def test_chebyshev_range_covers_normalised_clouds():
 
 def test_options_object_resolves_env_and_gates_routes(monkeypatch):
     """pem.Options: the explicit replacement of the process-global matmul mode + SAM6D_* switches.  Environment switches resolve into it
-    once; routes that exist only in the split-precision arithmetic are gated by the mode; the thread-local mode of the library follows
-    an explicit override and falls back to the process default."""
+    once; routes that exist only in the split-precision arithmetic are gated by the mode, from the values the caller gave (replace()
+    starts again from them); retired fields are refused; the thread-local mode of the library follows an explicit override and falls
+    back to the process default."""
     from sam6d_hip import _lib
     lib = _lib.load()
     assert lib.sam6d_get_thread_matmul_mode() == -1
     base = lib.sam6d_get_matmul_mode()
     o = pem.Options()
-    assert o.mode == base and o.fused_block == (base >= 1) and o.microbatch == 1 and o.rpe_products == 0
+    assert o.mode == base and o.fused_block == (base >= 1) and o.fused_rpe == (base >= 1) and o.microbatch == 1 and o.rpe_products == 0
+    assert o.fused_fine and o.overlap and o.matmul_mode is None
     monkeypatch.setenv("SAM6D_FUSED_BLOCK", "0")
     monkeypatch.setenv("SAM6D_RPE_PRODUCTS", "3")
     monkeypatch.setenv("SAM6D_MICROBATCH", "2")
     e = pem.Options.from_env()
     assert not e.fused_block and not e.fused_front and not e.rows_linear and e.rpe_products == 3 and e.microbatch == 2
+    assert e.fused_rpe == (base >= 1)
     assert pem.Options.from_env(fused_block=True).fused_block == (base >= 1)
     x = pem.Options(matmul_mode=0)
     assert x.mode == 0 and not (x.w16 or x.fused_block or x.fused_rpe or x.fused_out)
-    assert x.replace(matmul_mode=1).mode == 1
-    try:
-        pem.Options(no_such_switch=1)
-        assert False, "unknown field accepted"
-    except TypeError:
-        pass
+    # replace() starts from the caller's values, not from the mode-gated ones
+    y, z = x.replace(matmul_mode=1), pem.Options(matmul_mode=1)
+    assert y.mode == 1 and y.describe() == z.describe() and y.fused_block and y.fused_rpe and y.w16 and y.fused_out
+    assert y.replace(matmul_mode=0).describe() == x.describe()
+    assert x.replace(fused_block=False, matmul_mode=1).describe() == pem.Options(matmul_mode=1, fused_block=False).describe()
+    for bad in (dict(no_such_switch=1), dict(self_attn=False)):  # (self_attn: a retired A/B field)
+        try:
+            pem.Options(**bad)
+            assert False, "unknown field accepted: %s" % bad
+        except TypeError:
+            pass
     # thread override: visible through sam6d_get_matmul_mode, gone after -1
     assert lib.sam6d_set_thread_matmul_mode(0) == 0
     assert lib.sam6d_get_matmul_mode() == 0 and pem.Options().mode == 0

@@ -545,9 +545,11 @@ def test_fine_score_large_model_cloud(dev, P):
     assert torch.allclose(tt.cpu(), t * (radius.reshape(B, 1) + 1e-6), rtol=1e-6, atol=0)
 
 
-def test_fine_score_matrix_core_kernel_equals_vector_kernel(dev, monkeypatch):
+def test_fine_score_matrix_core_kernel_equals_vector_kernel(dev):
     """The nearest-CAD-point count on the fp32 matrix cores (fine_near_mfma_kernel) and on the vector ALU (fine_near_kernel) evaluate the
-    same pairwise-distance bit recipe: identical counts, hence identical scores, at the step's shape."""
+    same pairwise-distance bit recipe: identical counts, hence identical scores, at the step's shape.  The matrix-core kernel takes the
+    P = 1024 CAD points; the same points tiled to P = 3328 (beyond its 3264-point LDS bound) take the vector kernel -- exact duplicates
+    leave every nearest-point minimum unchanged."""
     from sam6d_hip import _lib
     gen = torch.Generator().manual_seed(77)
     B, N, P = 4, 2048, 1024
@@ -558,16 +560,16 @@ def test_fine_score_matrix_core_kernel_equals_vector_kernel(dev, monkeypatch):
     t = (torch.rand(B, 3, generator=gen) - 0.5) * 0.1
     l1 = (torch.rand(B, N, generator=gen) > 0.3).to(torch.int32)
     d = [x.to(dev).contiguous() for x in (p1, R, t, model, radius, l1)]
+    tiled = torch.cat([model] * 4, dim=1)[:, :3328].to(dev).contiguous()
     out = {}
-    for flag in ("1", "0"):
-        monkeypatch.setenv("SAM6D_FINE_NEAR_MFMA", flag)
+    for kernel, m in (("mfma", d[3]), ("vector", tiled)):
         cnt = torch.empty(2 * B, device=dev); score = torch.empty(B, device=dev); tt = d[2].clone()
-        _lib.call("sam6d_fine_score", d[0].data_ptr(), d[1].data_ptr(), tt.data_ptr(), d[3].data_ptr(), d[4].data_ptr(), d[5].data_ptr(), B, N,
-                  P, 0.02, cnt.data_ptr(), score.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        _lib.call("sam6d_fine_score", d[0].data_ptr(), d[1].data_ptr(), tt.data_ptr(), m.data_ptr(), d[4].data_ptr(), d[5].data_ptr(), B, N,
+                  m.shape[1], 0.02, cnt.data_ptr(), score.data_ptr(), torch.cuda.current_stream().cuda_stream)
         torch.cuda.synchronize()
-        out[flag] = (cnt.cpu(), score.cpu())
-    assert torch.equal(out["1"][0], out["0"][0]) and torch.equal(out["1"][1], out["0"][1])
-    assert 0.0 < float(out["1"][1].min()) and float(out["1"][1].max()) < 1.0
+        out[kernel] = (cnt.cpu(), score.cpu())
+    assert torch.equal(out["mfma"][0], out["vector"][0]) and torch.equal(out["mfma"][1], out["vector"][1])
+    assert 0.0 < float(out["mfma"][1].min()) and float(out["mfma"][1].max()) < 1.0
 
 
 def test_procrustes_golden(dev):
@@ -859,9 +861,9 @@ def test_rpe_stage1_two_and_three_products(dev, W, sigma_a, forced):
 
 
 def test_rpe_self_layer_one_launch_attention_equals_gemm_path(dev, W):
-    """The default RPE self layer (geometric scores, then q.k^T + softmax + P.v in one launch per (cloud, head)) against the same
-    layer with the q.k^T / P.v GEMMs and the softmax inside the score kernel (SAM6D_SELF_ATTN=0)."""
-    import os
+    """The default RPE self layer tail (geometric scores, then q.k^T + softmax + P.v in one launch per (cloud, head)) against the tail
+    with the q.k^T / P.v GEMMs and the softmax inside the score kernel (the form of clouds longer than SATTN_MAX_N), on the same
+    front results."""
     from sam6d_hip import _lib, pem
     if _lib.load().sam6d_get_matmul_mode() != 1:
         pytest.skip("the fused RPE path is the default (fp16x3) mode")
@@ -872,20 +874,32 @@ def test_rpe_self_layer_one_launch_attention_equals_gemm_path(dev, W):
     x = torch.randn(B, n, 256, generator=gen).to(dev)
     L = W.coarse["blocks"][0]["self"]
     G = pem.geo_context(pts.to(dev), W)
-    outs = []
-    old = os.environ.get("SAM6D_SELF_ATTN")
-    try:
-        for v in ("1", "0"):
-            os.environ["SAM6D_SELF_ATTN"] = v
-            outs.append(pem.rpe_self_layer(x, G, L).cpu())
-    finally:
-        if old is None:
-            os.environ.pop("SAM6D_SELF_ATTN", None)
-        else:
-            os.environ["SAM6D_SELF_ATTN"] = old
+    qkv, qp, qd, vT = pem._rpe_self_front(x, G, L)
+    assert vT is None and n <= pem.SATTN_MAX_N
+    outs = [pem._rpe_self_tail_attention(x, G, L, qkv, qp, qd).cpu(), pem._rpe_self_tail_gemm(x, G, L, qkv, qp, qd).cpu()]
     d = float((outs[0] - outs[1]).abs().max())
     print("\none-launch attention vs GEMM path: max abs diff %.2e (scale %.1f)" % (d, float(outs[1].abs().max())))
     assert torch.isfinite(outs[0]).all() and d < 1e-5
+
+
+def test_rpe_self_layer_long_cloud_gemm_path(dev, W):
+    """A cloud longer than SATTN_MAX_N takes the fused front with transposed values and the GEMM tail; against the materialised
+    layer rpe_self_layer(x, geo_embedding(...), L)."""
+    from sam6d_hip import _lib, pem
+    if _lib.load().sam6d_get_matmul_mode() != 1:
+        pytest.skip("the fused RPE path is the default (fp16x3) mode")
+    gen = torch.Generator().manual_seed(23)
+    B, n = 3, 240
+    assert n > pem.SATTN_MAX_N
+    pts = (torch.rand(B, n, 3, generator=gen) - 0.5) * 1.2
+    pts[:, 0] = 100.0
+    x = torch.randn(B, n, 256, generator=gen).to(dev)
+    L = W.coarse["blocks"][1]["self"]
+    want = pem.rpe_self_layer(x, pem.geo_embedding(pts.to(dev), W), L).cpu()
+    got = pem.rpe_self_layer(x, pem.geo_context(pts.to(dev), W), L).cpu()
+    d = float((got - want).abs().max())
+    print("\nfused RPE layer, n = %d: max abs diff %.2e (scale %.1f)" % (n, d, float(want.abs().max())))
+    assert torch.isfinite(got).all() and d < 2e-5
 
 
 def test_rpe_fused_range_guard(dev, sd):
