@@ -1,4 +1,6 @@
 """Drop-in for PEM/model/coarse_point_matching.py (inference)."""
+import types
+
 import torch
 import torch.nn as nn
 
@@ -35,7 +37,7 @@ class CoarsePointMatching(_Packed):
 
     def _build(self, sd, dev):
         sd = {"coarse_point_matching." + k: v for k, v in sd.items()}
-        W = _pem.PemWeights.__new__(_pem.PemWeights)
+        W = types.SimpleNamespace()
         g = _pem._getter(sd, dev)
         W.coarse = _pem.PemWeights._matching(g, "coarse_point_matching")
         W.coarse["blocks"] = [_pem.pack_geo_transformer(sd, dev, "coarse_point_matching.transformers.%d" % i)

@@ -63,14 +63,12 @@ class Net(nn.Module):
                        angle_k=self.geo_embedding.angle_k)
             # the reference's caller repeats one object's template tensors per instance (run_inference_custom_pytorch.py:445-446):
             # recognised here (bitwise comparison on the device), their pose-independent work then runs once
-            if template_ids is not None:
-                return _pem.pem_match(dense_pm.contiguous(), dense_fm.contiguous(), dense_po.contiguous(), dense_fo.contiguous(),
-                                      radius.reshape(-1).contiguous(), model.contiguous(), W, rand.contiguous(), cfg=cfg,
-                                      template_ids=template_ids)
-            shared = _pem.template_is_shared(dense_po, dense_fo) if self.shared_template is None else bool(self.shared_template)
+            shared = False
+            if template_ids is None:
+                shared = _pem.template_is_shared(dense_po, dense_fo) if self.shared_template is None else bool(self.shared_template)
             return _pem.pem_match(dense_pm.contiguous(), dense_fm.contiguous(), dense_po.contiguous(), dense_fo.contiguous(),
                                   radius.reshape(-1).contiguous(), model.contiguous(), W, rand.contiguous(), cfg=cfg,
-                                  shared_template=shared)
+                                  shared_template=shared, template_ids=template_ids)
         if template_ids is not None:  # module-by-module path: the repeated form
             ids = template_ids.to(dense_po.device).long()
             dense_po, dense_fo = dense_po[ids], dense_fo[ids]

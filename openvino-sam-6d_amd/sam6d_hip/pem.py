@@ -11,6 +11,7 @@ Citations: PEM = SAM-6D/Pose_Estimation_Model in the reference.
 import math
 import os
 import threading
+import types
 
 import torch
 
@@ -285,7 +286,7 @@ class PemWeights:
 
     def __init__(self, sd, device, nblock=3, options=None):
         """options: the Options every launch sequence on this weight set runs with (None: the environment's, per call)."""
-        g = lambda k: sd[k].detach().to(device=device, dtype=torch.float32).contiguous()
+        g = _getter(sd, device)
         self.dev = device
         self.options = options
         self.nblock = nblock
@@ -295,33 +296,8 @@ class PemWeights:
         self.coarse = self._matching(g, "coarse_point_matching")
         self.fine = self._matching(g, "fine_point_matching")
         self.coarse["blocks"] = [self._geo_transformer(g, "coarse_point_matching.transformers.%d" % i) for i in range(nblock)]
-        self.fine["blocks"] = []
-        for i in range(nblock):
-            t = "fine_point_matching.transformers.%d" % i
-            blk = self._geo_transformer(g, t + ".sparse_layer")
-            d = t + ".dense_layer"
-            a = d + ".attention.attention"
-            blk["dense"] = dict(
-                scale=g(a + ".scale").reshape(-1),
-                q=Linear(g(a + ".proj_q.weight"), g(a + ".proj_q.bias")),
-                kv=Linear(torch.cat([g(a + ".proj_k.weight"), g(a + ".proj_v.weight")], 0),
-                          torch.cat([g(a + ".proj_k.bias"), g(a + ".proj_v.bias")], 0)),
-                **self._post(g, d))
-            blk["dense"]["tbd"] = pack_token_block(blk["dense"], blk["dense"]["q"], blk["dense"]["scale"])
-            self.fine["blocks"].append(blk)
-        pe = "fine_point_matching.PE"
-        self.pe = dict(mlp=[], mlp3=Linear(g(pe + ".mlp3.conv.weight").reshape(C, C), g(pe + ".mlp3.conv.bias")))
-        for k in (1, 2):
-            layers = []
-            for l in range(3):
-                q = "%s.mlp%d.layer%d" % (pe, k, l)
-                w = g(q + ".conv.weight")
-                w = w.reshape(w.shape[0], w.shape[1]).contiguous()
-                bn = q + ".normlayer.bn"
-                scale = g(bn + ".weight") / torch.sqrt(g(bn + ".running_var") + 1e-5)
-                shift = g(bn + ".bias") - g(bn + ".running_mean") * scale
-                layers.append(dict(w=w, scale=scale.contiguous(), shift=shift.contiguous()))
-            self.pe["mlp"].append(layers)
+        self.fine["blocks"] = [self._sparse_to_dense(g, "fine_point_matching.transformers.%d" % i) for i in range(nblock)]
+        self.pe = self._pe(g, "fine_point_matching.PE")
 
     @staticmethod
     def _matching(g, p):
@@ -338,7 +314,8 @@ class PemWeights:
         L["tb"] = pack_token_block(L)  # the fused layer tail's weight image (csrc/block.hip)
         return L
 
-    def _geo_transformer(self, g, p):
+    @staticmethod
+    def _geo_transformer(g, p):
         s, c = p + ".layers.0", p + ".layers.1"
         sa, ca = s + ".attention.attention", c + ".attention.attention"
         self_l = dict(
@@ -346,65 +323,73 @@ class PemWeights:
                        torch.cat([g(sa + ".proj_q.bias"), g(sa + ".proj_k.bias"), g(sa + ".proj_v.bias")], 0)),
             # proj_p folded into the query (attention.hip header): WpT[j, k] = Wp[k, j]; its bias cancels in softmax
             wpT=g(sa + ".proj_p.weight").t().contiguous(),
-            **self._post(g, s))
+            **PemWeights._post(g, s))
         self_l["wpT16"] = split_w16(self_l["wpT"])
         cross_l = dict(
             q=Linear(g(ca + ".proj_q.weight"), g(ca + ".proj_q.bias")),
             kv=Linear(torch.cat([g(ca + ".proj_k.weight"), g(ca + ".proj_v.weight")], 0),
                       torch.cat([g(ca + ".proj_k.bias"), g(ca + ".proj_v.bias")], 0)),
-            **self._post(g, c))
+            **PemWeights._post(g, c))
         cross_l["xq"] = pack_cross_query(cross_l["q"])
         cross_l["xkv"] = pack_cross_kv(cross_l["kv"])
         return dict(self=self_l, cross=cross_l)
+
+    @staticmethod
+    def _sparse_to_dense(g, p):
+        """A SparseToDenseTransformer block: the geometric transformer of its sparse layer + the dense linear-attention layer (q, [k; v],
+        the focusing scale, the layer tail and the whole layer's fused image)."""
+        blk = PemWeights._geo_transformer(g, p + ".sparse_layer")
+        d = p + ".dense_layer"
+        a = d + ".attention.attention"
+        L = dict(scale=g(a + ".scale").reshape(-1), q=Linear(g(a + ".proj_q.weight"), g(a + ".proj_q.bias")),
+                 kv=Linear(torch.cat([g(a + ".proj_k.weight"), g(a + ".proj_v.weight")], 0),
+                           torch.cat([g(a + ".proj_k.bias"), g(a + ".proj_v.bias")], 0)), **PemWeights._post(g, d))
+        L["tbd"] = pack_token_block(L, L["q"], L["scale"])
+        blk["dense"] = L
+        return blk
+
+    @staticmethod
+    def _pe(g, pe):
+        """PositionalEncoding's MLPs: the 1x1 convolutions of mlp1 / mlp2 with their eval-mode BatchNorm folded into a per-channel
+        scale / shift, and mlp3."""
+        mlp = []
+        for k in (1, 2):
+            layers = []
+            for l in range(3):
+                q = "%s.mlp%d.layer%d" % (pe, k, l)
+                w = g(q + ".conv.weight")
+                w = w.reshape(w.shape[0], w.shape[1]).contiguous()
+                bn = q + ".normlayer.bn"
+                scale = g(bn + ".weight") / torch.sqrt(g(bn + ".running_var") + 1e-5)
+                shift = g(bn + ".bias") - g(bn + ".running_mean") * scale
+                layers.append(dict(w=w, scale=scale.contiguous(), shift=shift.contiguous()))
+            mlp.append(layers)
+        return dict(mlp=mlp, mlp3=Linear(g(pe + ".mlp3.conv.weight").reshape(C, C), g(pe + ".mlp3.conv.bias")))
 
 
 def _getter(sd, device):
     return lambda k: sd[k].detach().to(device=device, dtype=torch.float32).contiguous()
 
 
+# The drop-in sub-modules pack only their own part of the weights, into a plain namespace holding the PemWeights attributes their
+# launches read (pem/transformer.py, pem/coarse_point_matching.py, pem/fine_point_matching.py).
 def pack_geo(sd, device, p="geo_embedding"):
     g = _getter(sd, device)
-    w = PemWeights.__new__(PemWeights)
-    w.dev = device
-    w.div_term = g(p + ".embedding.div_term")
-    w.geo_d = Linear(g(p + ".proj_d.weight"), g(p + ".proj_d.bias"))
-    w.geo_a = Linear(g(p + ".proj_a.weight"), g(p + ".proj_a.bias"))
-    return w
+    return types.SimpleNamespace(dev=device, div_term=g(p + ".embedding.div_term"),
+                                 geo_d=Linear(g(p + ".proj_d.weight"), g(p + ".proj_d.bias")),
+                                 geo_a=Linear(g(p + ".proj_a.weight"), g(p + ".proj_a.bias")))
 
 
 def pack_geo_transformer(sd, device, p):
-    return PemWeights._geo_transformer(PemWeights.__new__(PemWeights), _getter(sd, device), p)
+    return PemWeights._geo_transformer(_getter(sd, device), p)
 
 
 def pack_sparse_to_dense(sd, device, p):
-    g = _getter(sd, device)
-    blk = pack_geo_transformer(sd, device, p + ".sparse_layer")
-    d = p + ".dense_layer"
-    a = d + ".attention.attention"
-    blk["dense"] = dict(scale=g(a + ".scale").reshape(-1), q=Linear(g(a + ".proj_q.weight"), g(a + ".proj_q.bias")),
-                        kv=Linear(torch.cat([g(a + ".proj_k.weight"), g(a + ".proj_v.weight")], 0),
-                                  torch.cat([g(a + ".proj_k.bias"), g(a + ".proj_v.bias")], 0)), **PemWeights._post(g, d))
-    blk["dense"]["tbd"] = pack_token_block(blk["dense"], blk["dense"]["q"], blk["dense"]["scale"])
-    return blk
+    return PemWeights._sparse_to_dense(_getter(sd, device), p)
 
 
 def pack_pe(sd, device, pe):
-    g = _getter(sd, device)
-    w = PemWeights.__new__(PemWeights)
-    w.dev = device
-    w.pe = dict(mlp=[], mlp3=Linear(g(pe + ".mlp3.conv.weight").reshape(C, C), g(pe + ".mlp3.conv.bias")))
-    for k in (1, 2):
-        layers = []
-        for l in range(3):
-            q = "%s.mlp%d.layer%d" % (pe, k, l)
-            wt = g(q + ".conv.weight")
-            wt = wt.reshape(wt.shape[0], wt.shape[1]).contiguous()
-            bn = q + ".normlayer.bn"
-            scale = g(bn + ".weight") / torch.sqrt(g(bn + ".running_var") + 1e-5)
-            shift = g(bn + ".bias") - g(bn + ".running_mean") * scale
-            layers.append(dict(w=wt, scale=scale.contiguous(), shift=shift.contiguous()))
-        w.pe["mlp"].append(layers)
-    return w
+    return types.SimpleNamespace(dev=device, pe=PemWeights._pe(_getter(sd, device), pe))
 
 
 # ------------------------------------------------------------------------------------------------- primitives
@@ -555,28 +540,21 @@ def geo_embedding(points_bg, W, sigma_d=0.2, sigma_a=15, angle_k=3):
     flag = knn.data_ptr() + 4 * B * n * angle_k
     factor_a = 180.0 / (sigma_a * math.pi)
     _lib.call("sam6d_geo_indices", _p(points_bg), B, n, float(sigma_d), float(factor_a), angle_k, _p(knn), _p(idx), _s())
-    if _flags().mode >= 1 and not geo_images_in_range(W):
-        # proj_d / proj_a (or their Chebyshev coefficients) x 1024 leave the fp16 range: the split-precision images of this weight set
-        # would hold inf.  The exact fp32 kernel (mode 0's) computes the embedding instead -- slower, never wrong.
+    exact = lambda redo: _lib.call("sam6d_geo_embed", _p(idx), B * n * n, _p(W.div_term), _p(W.geo_d.w), _p(W.geo_d.b), _p(W.geo_a.w),
+                                   _p(W.geo_a.b), C, flag, redo, _p(out), _s())
+    if _flags().mode == 0 or not geo_images_in_range(W):
+        # the exact fp32 kernel: mode 0's arithmetic, and the split-precision modes' when proj_d / proj_a (or their Chebyshev
+        # coefficients) x 1024 leave the fp16 range -- the split-precision images of this weight set would hold inf; slower, never wrong
         with _Timed("geo_embed_kernel"):
-            _lib.call("sam6d_geo_embed", _p(idx), B * n * n, _p(W.div_term), _p(W.geo_d.w), _p(W.geo_d.b), _p(W.geo_a.w),
-                      _p(W.geo_a.b), C, flag, 0, _p(out), _s())
+            exact(0)
         return out
-    if _flags().mode >= 1:
-        lst = _empty((B * n * n + 1,), points_bg, torch.int32)  # [count | pair ids outside the Chebyshev range]
-        pos = _empty((B * n * n,), points_bg, torch.int32)  # pair -> list slot or -1
-        with _Timed("geo_embed_kernel"):
-            _lib.call("sam6d_geo_embed_cheb", _p(idx), B * n * n, geo_cheb_packed(W).data_ptr(), float(GEO_XMAX), _p(W.div_term),
-                      geo_packed(W).data_ptr(), _p(W.geo_d.b), _p(W.geo_a.b), C, flag, _p(pos), _p(lst), _p(out), _s())
-    if _flags().mode >= 1:
-        # indices beyond the fast sincos range (flag set on the device): this launch redoes the call exactly; otherwise
-        # it returns immediately
-        _lib.call("sam6d_geo_embed", _p(idx), B * n * n, _p(W.div_term), _p(W.geo_d.w), _p(W.geo_d.b), _p(W.geo_a.w),
-                  _p(W.geo_a.b), C, flag, 1, _p(out), _s())
-    else:
-        with _Timed("geo_embed_kernel"):
-            _lib.call("sam6d_geo_embed", _p(idx), B * n * n, _p(W.div_term), _p(W.geo_d.w), _p(W.geo_d.b), _p(W.geo_a.w),
-                      _p(W.geo_a.b), C, flag, 0, _p(out), _s())
+    lst = _empty((B * n * n + 1,), points_bg, torch.int32)  # [count | pair ids outside the Chebyshev range]
+    pos = _empty((B * n * n,), points_bg, torch.int32)  # pair -> list slot or -1
+    with _Timed("geo_embed_kernel"):
+        _lib.call("sam6d_geo_embed_cheb", _p(idx), B * n * n, geo_cheb_packed(W).data_ptr(), float(GEO_XMAX), _p(W.div_term),
+                  geo_packed(W).data_ptr(), _p(W.geo_d.b), _p(W.geo_a.b), C, flag, _p(pos), _p(lst), _p(out), _s())
+    # indices beyond the fast sincos range (flag set on the device): this launch redoes the call exactly; otherwise it returns immediately
+    exact(1)
     return out
 
 
@@ -1299,78 +1277,56 @@ def coarse_point_matching(sp, sf, E, radius, model, W, rand, cfg, return_aux=Fal
     return out
 
 
-def fine_static_a(dp, df, W, cfg, shared_template=False):
+def fine_static_a(dp, df, W, cfg, templates=None):
     """First half of fine_static: token buffer D with in_proj of both clouds + the template cloud's ball queries (ordinary
-    grids that share the chip well).  df: stacked (2B,N,256) or the (scene, template) pair.  shared_template: every proposal carries the SAME template cloud (one object's dense_po /
-    dense_fo `.repeat`ed per instance, PEM/run_inference_custom_pytorch.py:445-446): its tokens are computed once, in slot B."""
-    if isinstance(shared_template, tuple):
-        # (B, T, gidx, ids): dp = [B scene clouds; T UNIQUE template clouds], df = (scene (B,N,256), template (T,N,256)).  The scene tokens go
-        # to slots 0 .. B-1 of D (2B slots); the T template token blocks are finished in their own buffer Dt (in_proj here, the PE MLPs
-        # in fine_static_b) and then handed to the template slot of every proposal (fine_static_b).
-        B, T = shared_template[:2]
-        N, K = df[0].shape[1], df[0].shape[2]
-        lin = W.fine["in_proj"]
-        D = _empty((2 * B, N + 1, C), df[0])
-        Dt = _empty((T, N + 1, C), df[0])
-        gemm(df[0], lin.w, lin.b, D, N, C, K, K, K, C, c_off=C, batch=B, sA=N * K, sC=(N + 1) * C, w16=lin.w16())
-        gemm(df[1], lin.w, lin.b, Dt, N, C, K, K, K, C, c_off=C, batch=T, sA=N * K, sC=(N + 1) * C, w16=lin.w16())
-        _lib.call("sam6d_put_rows", _p(W.fine["bg"]), 0, C, _p(D), (N + 1) * C, C, B, 1, C, _s())
-        _lib.call("sam6d_put_rows", _p(W.fine["bg"]), 0, C, _p(Dt), (N + 1) * C, C, T, 1, C, _s())
-        grp = pe_group(dp[B:], cfg["pe_radius1"], cfg["pe_radius2"], cfg["pe_nsample1"], cfg["pe_nsample2"])
-        return (D, Dt), grp
-    if isinstance(df, tuple):
-        B, N, K = df[0].shape
-        Bp = 2 * B
-    else:
-        Bp, N, K = df.shape
-        B = Bp // 2
-    if shared_template and B > 1:
-        lin = W.fine["in_proj"]
-        if isinstance(df, tuple):
-            D = _empty((Bp, N + 1, C), df[0])
-            gemm(df[0], lin.w, lin.b, D, N, C, K, K, K, C, c_off=C, batch=B, sA=N * K, sC=(N + 1) * C, w16=lin.w16())
-            gemm(df[1], lin.w, lin.b, D, N, C, K, K, K, C, c_off=C + B * (N + 1) * C, batch=1, sA=N * K, sC=(N + 1) * C, w16=lin.w16())
-        else:
-            D = _empty((Bp, N + 1, C), df)
-            gemm(df, lin.w, lin.b, D, N, C, K, K, K, C, c_off=C, batch=B + 1, sA=N * K, sC=(N + 1) * C, w16=lin.w16())  # scene clouds + template slot B
-        _lib.call("sam6d_put_rows", _p(W.fine["bg"]), 0, C, _p(D), (N + 1) * C, C, B + 1, 1, C, _s())
-        grp = pe_group(dp[B:B + 1], cfg["pe_radius1"], cfg["pe_radius2"], cfg["pe_nsample1"], cfg["pe_nsample2"])
+    grids that share the chip well).  df: stacked (2B,N,256) or the (scene, template) pair.
+    templates = (B, T, gidx, ids) (pem_match's unique-template form): dp = [B scene clouds; T UNIQUE template clouds], df = (scene
+    (B,N,256), template (T,N,256)).  The scene tokens go to slots 0 .. B-1 of D (2B slots); the T template token blocks are finished in
+    their own buffer Dt (in_proj here, the PE MLPs in fine_static_b), which fine_static_b then hands to the template slot of every
+    proposal.  Returns (D, grp), with D = (D, Dt) in that form."""
+    if templates is None:
+        D = _tokens_with_bg(df, W.fine["in_proj"], W.fine["bg"])
+        grp = pe_group(dp[dp.shape[0] // 2:], cfg["pe_radius1"], cfg["pe_radius2"], cfg["pe_nsample1"], cfg["pe_nsample2"])
         return D, grp
-    D = _tokens_with_bg(df, W.fine["in_proj"], W.fine["bg"])
+    B, T = templates[:2]
+    N, K = df[0].shape[1], df[0].shape[2]
+    lin = W.fine["in_proj"]
+    D = _empty((2 * B, N + 1, C), df[0])
+    Dt = _empty((T, N + 1, C), df[0])
+    gemm(df[0], lin.w, lin.b, D, N, C, K, K, K, C, c_off=C, batch=B, sA=N * K, sC=(N + 1) * C, w16=lin.w16())
+    gemm(df[1], lin.w, lin.b, Dt, N, C, K, K, K, C, c_off=C, batch=T, sA=N * K, sC=(N + 1) * C, w16=lin.w16())
+    _lib.call("sam6d_put_rows", _p(W.fine["bg"]), 0, C, _p(D), (N + 1) * C, C, B, 1, C, _s())
+    _lib.call("sam6d_put_rows", _p(W.fine["bg"]), 0, C, _p(Dt), (N + 1) * C, C, T, 1, C, _s())
     grp = pe_group(dp[B:], cfg["pe_radius1"], cfg["pe_radius2"], cfg["pe_nsample1"], cfg["pe_nsample2"])
-    return D, grp
+    return (D, Dt), grp
 
 
-def fine_static_b(dp, D, grp, W, shared_template=False, max_wg=0):
-    """Second half: the PE MLPs of the template cloud (persistent workgroups that hold most of every CU's LDS while they run).
-    shared_template: one cloud's worth, then the finished token block of slot B is copied to the other template slots."""
-    if isinstance(shared_template, tuple):
-        B, T, _, ids = shared_template
-        D, Dt = D
-        N = dp.shape[1]
-        pe_apply(dp[B:], grp, W, Dt, C, (N + 1) * C, max_wg)
-        _lib.call("sam6d_take_rows", Dt.data_ptr(), ids.data_ptr(), T, B, (N + 1) * C * 4, _p(D, B * (N + 1) * C), _s())
+def fine_static_b(dp, D, grp, W, templates=None, max_wg=0):
+    """Second half: the PE MLPs of the template clouds (persistent workgroups that hold most of every CU's LDS while they run).
+    templates: once per unique template, into Dt; its finished token blocks are then copied to the template slot of every proposal."""
+    if templates is None:
+        Bp, N, _ = dp.shape
+        B = Bp // 2
+        pe_apply(dp[B:], grp, W, D, B * (N + 1) * C + C, (N + 1) * C, max_wg)
         return D
-    Bp, N, _ = dp.shape
-    B = Bp // 2
-    if shared_template and B > 1:
-        pe_apply(dp[B:B + 1], grp, W, D, B * (N + 1) * C + C, (N + 1) * C, max_wg)
-        _lib.call("sam6d_put_rows", _p(D, B * (N + 1) * C), 0, C, _p(D, (B + 1) * (N + 1) * C), (N + 1) * C, C, B - 1, N + 1, C, _s())
-        return D
-    pe_apply(dp[B:], grp, W, D, B * (N + 1) * C + C, (N + 1) * C, max_wg)
+    B, T, _, ids = templates
+    D, Dt = D
+    N = dp.shape[1]
+    pe_apply(dp[B:], grp, W, Dt, C, (N + 1) * C, max_wg)
+    _lib.call("sam6d_take_rows", Dt.data_ptr(), ids.data_ptr(), T, B, (N + 1) * C * 4, _p(D, B * (N + 1) * C), _s())
     return D
 
 
-def fine_static(dp, df, W, cfg, shared_template=False):
+def fine_static(dp, df, W, cfg, templates=None):
     """The part of FinePointMatching.forward that does not depend on the coarse pose: in_proj of both clouds' dense
     features into the token buffer D (2B,N+1,256) with the bg token, and the positional encoding of the TEMPLATE cloud
-    (PEM/model/fine_point_matching.py:47-51).  pem_match issues it on a side stream, under the latency-bound coarse stage."""
-    D, grp = fine_static_a(dp, df, W, cfg, shared_template)
-    return fine_static_b(dp, D, grp, W, shared_template)
+    (PEM/model/fine_point_matching.py:47-51).  pem_match issues it on a side stream, under the latency-bound coarse stage.
+    templates: as in fine_static_a."""
+    D, grp = fine_static_a(dp, df, W, cfg, templates)
+    return fine_static_b(dp, D, grp, W, templates)
 
 
-def fine_point_matching(dp, df, E, fps_idx, radius, model, init_R, init_t, W, cfg, return_aux=False, D=None, shared_template=False,
-                        fused_fine=True):
+def fine_point_matching(dp, df, E, fps_idx, radius, model, init_R, init_t, W, cfg, return_aux=False, D=None, fused_fine=True):
     """dp (2B,N,3) stacked [scene; template], df the dense features: (2B,N,256) stacked the same way, or the pair (scene (B,N,256),
     template (B,N,256)) left where the caller holds them  (PEM/model/fine_point_matching.py:42-79, eval).
     D: the result of fine_static() when the caller has already produced it.  fused_fine=False: the (B,N+1,N+1) attention matrix is
@@ -1378,7 +1334,7 @@ def fine_point_matching(dp, df, E, fps_idx, radius, model, init_R, init_t, W, cf
     Bp, N, _ = dp.shape
     B = Bp // 2
     if D is None:
-        D = fine_static(dp, df, W, cfg, shared_template)
+        D = fine_static(dp, df, W, cfg)
     p1 = _empty((B, N, 3), dp)
     _lib.call("sam6d_rigid_inverse", _p(dp), _p(init_R), _p(init_t), B, N, _p(p1), _s())  # p1_ = (p1 - t) @ R
     positional_encoding_add(p1, W, D, C, (N + 1) * C, cfg["pe_radius1"], cfg["pe_radius2"], cfg["pe_nsample1"],
@@ -1437,8 +1393,8 @@ PE_SIDE_WGS = 512
 
 
 def _side_stream(dev, key=0):
-    """A per-device pool of auxiliary HIP streams (key 0: the side stream of the default pipeline; ("mb", i) the micro-batch
-    streams and ("mb", i, "side") their side streams)."""
+    """A per-device pool of auxiliary HIP streams (key 0: the side stream of the single-slice pipeline; ("mb", i) the micro-batch
+    streams)."""
     s = _SIDE_STREAMS.get((dev, key))
     if s is None:
         s = _SIDE_STREAMS[(dev, key)] = torch.cuda.Stream(device=dev)
@@ -1449,77 +1405,83 @@ DEFAULT_CFG = dict(coarse_npoint=196, sigma_d=0.2, sigma_a=15, angle_k=3, temp=0
                    pe_radius1=0.1, pe_radius2=0.2, pe_nsample1=32, pe_nsample2=64, dis_thres=0.15)
 
 
+def resolve_routes(W, cfg, options):
+    """The pipeline shape pem_match takes for this weight set, cfg and Options (a cfg key wins over the Options field of its name):
+      fused_rpe        RPE attention without the embedding tensor: asked for, a split-precision mode, and the weight set's guard passed
+      fused_rpe_guard  that guard (fused_rpe_in_range at cfg's sigma_a, which sets the range of the angular indices); None in mode 0
+      fused_fine       the fine similarity + soft-assignment pipeline of finematch.hip (it runs on the fused block kernels)
+      overlap          the pose-independent fine work on a side stream
+      microbatch       slices of the batch on concurrent streams"""
+    split = options.mode >= 1
+    guard = bool(fused_rpe_in_range(W, cfg.get("sigma_a", 15))) if split else None
+    return dict(fused_rpe=bool(cfg.get("fused_rpe", options.fused_rpe)) and split and guard,
+                fused_rpe_guard=guard,
+                fused_fine=bool(cfg.get("fused_fine", options.fused_fine)) and options.fused_block,
+                overlap=bool(cfg.get("overlap", options.overlap)),
+                microbatch=int(cfg.get("microbatch", options.microbatch)))
+
+
 @on_tensor_device
 def pem_match(dense_pm, dense_fm, dense_po, dense_fo, radius, model, W, rand, cfg=DEFAULT_CFG, return_aux=False,
               shared_template=False, init_pose=None, template_ids=None):
     """Net.forward after feature extraction (PEM/model/pose_estimation_model.py:29-55):
     FPS x2 -> geo-embedding x2 -> CoarsePointMatching -> FinePointMatching -> (pred_R, pred_t, pred_pose_score).
     rand (B, 3*nproposal1) uniforms for the hypothesis sampling (the reference draws them inside, model_utils.py:292).
-    shared_template=True: the caller guarantees dense_po[b] == dense_po[0] and dense_fo[b] == dense_fo[0] for every proposal (the
-    reference's caller repeats one object's template tensors per instance, run_inference_custom_pytorch.py:445-446): the template
-    side of the pose-independent fine work (in_proj of 2048 dense tokens, both ball queries, both PE MLPs, mlp3) then runs once
-    instead of B times; the result is bit-identical to the repeated form.
 
     cfg["microbatch"] = k (env SAM6D_MICROBATCH, default 1 = off): the batch is cut into k slices whose coarse / fine stages run
     on k HIP streams (one slice's latency-bound chains beside another's dense kernels, +2 % at k = 2, twice the host launch work).
     Each slice runs its own FPS, gathers and geometric indices on its own stream and forks no further stream.
 
     return_aux=True adds a dict of intermediates (coarse attention, sampled indices, hypotheses, scores, the coarse pose, FPS indices,
-    fine labels / weights) WITHOUT changing which kernels run.  Kernel choice is cfg's: cfg["fused_rpe"] (env SAM6D_FUSED_RPE, default on)
-    = RPE attention without the embedding tensor, cfg["fused_fine"] (env SAM6D_FUSED_FINE, default on) = the similarity + soft-assignment
-    pipeline of finematch.hip; off = the materialised launch-per-op forms.
+    fine labels / weights) WITHOUT changing which kernels run.  Kernel choice is cfg's (resolve_routes): cfg["fused_rpe"] (env
+    SAM6D_FUSED_RPE, default on) = RPE attention without the embedding tensor, cfg["fused_fine"] (env SAM6D_FUSED_FINE, default on) = the
+    similarity + soft-assignment pipeline of finematch.hip; off = the materialised launch-per-op forms.
     template_ids (B,) integer tensor: a MULTI-OBJECT batch (a BOP scene mixes objects per batch: PEM/provider/bop_test_dataset.py:107,156
     returns an `obj` index per instance).  dense_po (T,N,3) / dense_fo (T,N,256) then hold the T UNIQUE templates and proposal b uses
     template template_ids[b] -- the form the reference's caller would have BEFORE it `.repeat`s / indexes the template tensors per
     instance (run_inference_custom_pytorch.py:445-446).  Template-side work that does not depend on the proposal -- FPS and the row
     gathers of the sparse points / features, in_proj of the dense tokens, both ball queries, both PE MLPs, mlp3 -- runs once per
     template and its result is handed to every proposal of that template (device copies); every kernel treats a cloud independently of
-    its batch neighbours, so the result is bit-identical to the repeated form (tests/test_configs_gpu.py).
+    its batch neighbours, so the result is bit-identical to the repeated form (tests/test_configs_gpu.py).  The batch runs as one slice.
+    shared_template=True: the case T = 1 of template_ids -- the caller guarantees dense_po[b] == dense_po[0] and dense_fo[b] ==
+    dense_fo[0] for every proposal (the reference's caller repeats one object's template tensors per instance,
+    run_inference_custom_pytorch.py:445-446), and the call runs on dense_po[:1] / dense_fo[:1] with every id 0.
     init_pose = (R0 (B,3,3), t0 (B,3)): the fine stage starts from this pose instead of the coarse stage's own result (which is still
     computed and returned in aux) -- the seam FinePointMatching.forward takes its init_R / init_t through
     (PEM/model/fine_point_matching.py:42-46); used by the staged parity tests."""
     B = dense_pm.shape[0]
     opts = _flags()
-    mb = int(cfg.get("microbatch", opts.microbatch))
-    fused = cfg.get("fused_rpe", opts.fused_rpe) and opts.mode >= 1
-    fused = fused and fused_rpe_in_range(W, cfg["sigma_a"])  # (the range of the angular indices, hence the guard, depends on sigma_a)
-    fused_fine = bool(cfg.get("fused_fine", opts.fused_fine))
-    overlap = cfg.get("overlap", opts.overlap)
-    tmpl = None
-    if template_ids is not None:
+    routes = resolve_routes(W, cfg, opts)
+    mb, fused, overlap = routes["microbatch"], routes["fused_rpe"], routes["overlap"]
+    if shared_template and template_ids is not None:
+        raise ValueError("pem_match: template_ids and shared_template are alternatives")
+    tmpl = None  # the unique-template form: (B, T, gidx, ids)
+    if shared_template or template_ids is not None:
         if shared_template:
-            raise ValueError("pem_match: template_ids and shared_template are alternatives")
-        T = dense_po.shape[0]
-        if dense_fo.shape[0] != T or template_ids.numel() != B:
-            raise ValueError("pem_match: template_ids (B,) indexes dense_po / dense_fo (T, ...)")
-        ids = template_ids.to(device=dense_pm.device, dtype=torch.int64).reshape(B)
-        # one host read-back per call (an out-of-range id would otherwise read a zero block); not while a hipGraph is being captured --
-        # PemGraph validates the ids it is built with on the host
-        if not torch.cuda.is_current_stream_capturing() and bool(((ids < 0) | (ids >= T)).any()):
-            raise ValueError("pem_match: template_ids out of range [0, %d)" % T)
+            dense_po, dense_fo = dense_po[:1], dense_fo[:1]
+            ids = torch.zeros(B, dtype=torch.int64, device=dense_pm.device)
+        else:
+            T = dense_po.shape[0]
+            if dense_fo.shape[0] != T or template_ids.numel() != B:
+                raise ValueError("pem_match: template_ids (B,) indexes dense_po / dense_fo (T, ...)")
+            ids = template_ids.to(device=dense_pm.device, dtype=torch.int64).reshape(B)
+            # one host read-back per call (an out-of-range id would otherwise read a zero block); not while a hipGraph is being
+            # captured -- PemGraph validates the ids it is built with on the host
+            if not torch.cuda.is_current_stream_capturing() and bool(((ids < 0) | (ids >= T)).any()):
+                raise ValueError("pem_match: template_ids out of range [0, %d)" % T)
         # block b of a stacked (2B, ...) tensor comes from block gidx[b] of the unique (B + T, ...) one
         gidx = torch.cat([torch.arange(B, device=ids.device, dtype=torch.int64), ids + B]).contiguous()
-        tmpl = (B, T, gidx, ids.contiguous())
-        shared_template = tmpl
+        tmpl = (B, dense_po.shape[0], gidx, ids.contiguous())
         mb = 1
 
-    def fork_fine_static(dp, df, side_key):
-        """The pose-independent part of the fine stage (dense in_proj, template-cloud ball queries + PE MLP) on a second HIP
-        stream; the caller joins it (cur.wait_stream(side)) before the fine transformer."""
-        cur = torch.cuda.current_stream()
-        side = _side_stream(dp.device, side_key)
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):
-            D = fine_static(dp, df, W, cfg, shared_template)
-        D.record_stream(cur)
-        return D, side
-
-    def prepare(lo, hi, side_key=None):
-        """FPS, gathers and the geometric indices of proposals [lo, hi) on the caller's stream.  With side_key (the default,
-        single-slice pipeline) the first half of the fine stage's static part (in_proj GEMM, ball queries) is forked BEFORE
+    def prepare(lo, hi, fork):
+        """FPS, gathers and the geometric indices of proposals [lo, hi) on the caller's stream.  fork (the single-slice pipeline with
+        overlap on): the first half of the fine stage's static part (in_proj GEMM, ball queries) is forked onto the side stream BEFORE
         these kernels and fills the chip while FPS (one workgroup per cloud, 196 sequential rounds) runs; its second half (the
-        persistent PE-MLP workgroups, which would keep the LDS-heavy outlier-embedding kernels of this phase waiting) is queued
-        by rest() beside the coarse pose solver.  The micro-batch mode keeps this phase serial."""
+        persistent PE-MLP workgroups, which would keep the LDS-heavy outlier-embedding kernels of this phase waiting) is queued by
+        rest() beside the coarse pose solver.  A micro-batch slice forks no second stream: inside a slice the pipeline of slices
+        provides the overlap, and a second level of forked streams is also what hipStreamEndCapture crashed on when the slices were
+        captured into a graph (scratch/graph_probe2.py)."""
         b = hi - lo
         if tmpl is not None:
             dp = _cat0(dense_pm, dense_po)  # (B + T, N, 3): the unique clouds
@@ -1530,12 +1492,12 @@ def pem_match(dense_pm, dense_fm, dense_po, dense_fo, radius, model, W, rand, cf
             # two halves with one launch each (a stacked copy cost 0.27 GB of traffic at the head of every step)
             df = (dense_fm[lo:hi], dense_fo[lo:hi])
         early = None
-        if side_key is not None and overlap:
+        if fork:
             cur = torch.cuda.current_stream()
-            side = _side_stream(dp.device, side_key)
+            side = _side_stream(dp.device)
             side.wait_stream(cur)
             with torch.cuda.stream(side):
-                D, grp = fine_static_a(dp, df, W, cfg, shared_template)
+                D, grp = fine_static_a(dp, df, W, cfg, tmpl)
         n = cfg["coarse_npoint"]
         sp, sf, idx = sample_pts_feats(dp, df, n)
         dpu = dp
@@ -1549,19 +1511,19 @@ def pem_match(dense_pm, dense_fm, dense_po, dense_fo, radius, model, W, rand, cf
             E = geo_context(pb, W, cfg["sigma_d"], cfg["sigma_a"], cfg["angle_k"])
         else:
             E = geo_embedding(pb, W, cfg["sigma_d"], cfg["sigma_a"], cfg["angle_k"])
-        if side_key is not None and overlap:
+        if fork:
             for x in (D if isinstance(D, tuple) else (D,)):
                 x.record_stream(cur)
             early = (D, side, grp)
         return dp, df, sp, sf, idx, E, early, dpu
 
-    def rest(prep, lo, hi, side_key):
+    def rest(prep, lo, hi):
         dp, df, sp, sf, idx, E, early, dpu = prep
         rad, mod, rnd = radius[lo:hi].contiguous(), model[lo:hi].contiguous(), rand[lo:hi].contiguous()
         # The coarse stage is a chain of small launches (197-token layers, 6000 hypotheses) that leaves most of the chip
-        # idle; the static part of the fine stage runs beside it (forked here unless prepare already did).
-        D = side = None
-        hook = None
+        # idle; the static part of the fine stage runs beside it when prepare forked it.  Without the fork the unique-template form
+        # finishes it here and the per-proposal form inside fine_point_matching.
+        D = side = hook = None
         if early is not None:
             D, side, grp = early
 
@@ -1574,13 +1536,9 @@ def pem_match(dense_pm, dense_fm, dense_po, dense_fo, radius, model, W, rand, cf
                 ev.record(cur)
                 with torch.cuda.stream(side):
                     side.wait_event(ev)
-                    fine_static_b(dpu, D, grp, W, shared_template, max_wg=PE_SIDE_WGS)
-        elif overlap and mb <= 1:
-            # (inside a micro-batch slice the pipeline of slices provides the overlap; a second level of forked streams is also what
-            #  hipStreamEndCapture crashed on when the slices were captured into a graph: scratch/graph_probe2.py)
-            D, side = fork_fine_static(dpu, df, side_key)
+                    fine_static_b(dpu, D, grp, W, tmpl, max_wg=PE_SIDE_WGS)
         elif tmpl is not None:
-            D = fine_static(dpu, df, W, cfg, shared_template)
+            D = fine_static(dpu, df, W, cfg, tmpl)
         c = coarse_point_matching(sp, sf, E, rad, mod, W, rnd, cfg, return_aux, before_pose=hook)
         R0, t0 = c[0], c[1]
         if side is not None:
@@ -1588,8 +1546,7 @@ def pem_match(dense_pm, dense_fm, dense_po, dense_fo, radius, model, W, rand, cf
         if isinstance(D, tuple):
             D = D[0]  # (fine_static_b has filled the template slots from the per-template buffer)
         Ri, ti = (R0, t0) if init_pose is None else (init_pose[0][lo:hi].contiguous(), init_pose[1][lo:hi].contiguous())
-        f = fine_point_matching(dp, df, E, idx, rad, mod, Ri, ti, W, cfg, return_aux, D=D,
-                                shared_template=(False if tmpl is not None else shared_template), fused_fine=fused_fine)
+        f = fine_point_matching(dp, df, E, idx, rad, mod, Ri, ti, W, cfg, return_aux, D=D, fused_fine=routes["fused_fine"])
         if return_aux:
             b = hi - lo
             return f[0], f[1], f[2], dict(coarse=c[2], fine=f[3], init_R=R0, init_t=t0, fps_idx_m=idx[:b], fps_idx_o=idx[b:],
@@ -1597,15 +1554,12 @@ def pem_match(dense_pm, dense_fm, dense_po, dense_fo, radius, model, W, rand, cf
         return f
 
     dense_pm, dense_fm, dense_po, dense_fo = [x.contiguous() for x in (dense_pm, dense_fm, dense_po, dense_fo)]
-    if mb <= 1 or B < 8 * mb or return_aux:
-        if opts.mode >= 1:
-            geo_packed(W), geo_cheb_packed(W), geo_dcT(W), geo_dcT16(W)  # lazily built weight images: finish them before the streams fork
-            _ensure_w16(W)
-        return rest(prepare(0, B, side_key=0), 0, B, 0)
-    main = torch.cuda.current_stream()
     if opts.mode >= 1:
-        geo_packed(W), geo_cheb_packed(W), geo_dcT(W), geo_dcT16(W)  # lazily built weight images: finish them before the streams fork
+        geo_packed(W), geo_cheb_packed(W), geo_dcT(W), geo_dcT16(W)  # lazily built weight images: finish them before a stream forks
         _ensure_w16(W)
+    if mb <= 1 or B < 8 * mb or return_aux:
+        return rest(prepare(0, B, overlap), 0, B)
+    main = torch.cuda.current_stream()
     per = (B + mb - 1) // mb
     spans = [(i * per, min(B, (i + 1) * per)) for i in range(mb)]
     # (until round 4 the slices' FPS / gathers / geometric indices ran serially on the caller's stream first -- defence in depth for the
@@ -1616,7 +1570,7 @@ def pem_match(dense_pm, dense_fm, dense_po, dense_fo, radius, model, W, rand, cf
         st = _side_stream(dense_pm.device, ("mb", i))
         st.wait_stream(main)
         with torch.cuda.stream(st):
-            outs.append(rest(prepare(lo, hi), lo, hi, ("mb", i, "side")))
+            outs.append(rest(prepare(lo, hi, False), lo, hi))
     R = _empty((B, 3, 3), dense_pm)
     t = _empty((B, 3), dense_pm)
     sc = _empty((B,), dense_pm)
@@ -1635,33 +1589,32 @@ def describe_paths(W, cfg=DEFAULT_CFG, options=None):
     split-precision embedding images need proj_d / proj_a x 1024 finite in fp16) -- with the released checkpoint any of them may route
     to the slower three-product or materialised kernels.  Returned as a plain dict (bench.py prints it as `paths`)."""
     o = options if options is not None else (getattr(W, "options", None) or Options.from_env())
+    routes = resolve_routes(W, cfg, o)
     split = o.mode >= 1
     img_ok = bool(geo_images_in_range(W)) if split else None
-    sigma_a = cfg.get("sigma_a", 15)
-    fused_ok = bool(fused_rpe_in_range(W, sigma_a)) if split else False
-    fused = bool(cfg.get("fused_rpe", o.fused_rpe)) and split and fused_ok
+    fused = routes["fused_rpe"]
     products = None
     if fused:
-        products = 3 if o.rpe_products == 3 else int(geo_cheb_a_packed(W, sigma_a)[2])
+        products = 3 if o.rpe_products == 3 else int(geo_cheb_a_packed(W, cfg.get("sigma_a", 15))[2])
     return {
         "matmul_mode": {0: "exact fp32 MFMA", 1: "fp16x3 split", 2: "fp16 single product (experimental)"}[o.mode],
         "rpe_attention": ("fused score kernel (Chebyshev basis, no embedding tensor), stage 1 = rpe_score_kernel<%d>" % products) if fused
                          else "materialised embedding + attention_kernel<RPE>",
         "rpe_stage1_products": products,
-        "fused_rpe_guard_passed": fused_ok if split else None,
+        "fused_rpe_guard_passed": routes["fused_rpe_guard"],
         "embedding_rows": ("geo_cheb_kernel + geo_embed_h3_kernel (split-precision images in range)" if img_ok else
                            "geo_embed_kernel (exact fp32: weight images leave the fp16 range)") if split else "geo_embed_kernel (exact fp32)",
         "gemm_route": "gemm_nt_h3_kernel, pre-split fp16 weight halves" if split else "gemm_nt_kernel (v_mfma_f32_32x32x2_f32)",
         "layer_tails": "token_block_kernel (one launch per tail)" if o.fused_block else "GEMM + LayerNorm launches",
         "cross_layers": "xattn_kernel<kv inside> + token_block kernel" if o.fused_block else "GEMM / attention_kernel launches",
         "self_attention": "sattn_kernel (q.k^T + softmax + P.v per (cloud, head))" if fused else "batched GEMMs",
-        "fine_match": "finematch.hip pipeline (E written once, read twice)" if (bool(cfg.get("fused_fine", o.fused_fine)) and o.fused_block)
+        "fine_match": "finematch.hip pipeline (E written once, read twice)" if routes["fused_fine"]
                       else "materialised (B,N+1,N+1) attention + soft-assignment passes",
         "fine_out_proj": "out_split_kernel (out_proj + normalize + fp16 split)" if o.fused_out else "GEMM + fm_prep_kernel",
         "hypothesis_scoring": "score_hyp_mfma_kernel (fp32 matrix cores)",
         "ball_query": "cell grid",
-        "overlap_side_stream": bool(cfg.get("overlap", o.overlap)),
-        "microbatch": int(cfg.get("microbatch", o.microbatch)),
+        "overlap_side_stream": routes["overlap"],
+        "microbatch": routes["microbatch"],
     }
 
 
@@ -1677,8 +1630,8 @@ class PemGraph:
     R, t, score = g(dense_pm, dense_fm, dense_po, dense_fo, radius, model, rand)                   # copies into the static inputs, replays
     R, t, score = g.replay()                                                                      # inputs already written to g.inputs
 
-    The outputs are the graph's static tensors (overwritten by the next replay).  template_ids (fixed at capture) / shared_template
-    as in pem_match.  The reference has no counterpart (eager PyTorch: PEM/run_inference_custom_pytorch.py:447-454 calls the model
+    The outputs are the graph's static tensors (overwritten by the next replay).  template_ids (fixed at capture) and shared_template
+    (its case T = 1) as in pem_match; either runs the batch as one slice.  The reference has no counterpart (eager PyTorch: PEM/run_inference_custom_pytorch.py:447-454 calls the model
     once per batch)."""
 
     KEYS = ("dense_pm", "dense_fm", "dense_po", "dense_fo", "radius", "model", "rand")
