@@ -557,6 +557,26 @@ int sam6d_radius_filter(int N, int cap, const int* n_valid, float radius, int* c
                         void* stream);
 int sam6d_choose_points(int N, int cap, const int* choose, const float* cloud, const int* bbox, const int* sel, int ns, int img_size,
                         float* pts, long long* rgb_choose, void* stream);
+/* Template geometry of _get_template (PEM/run_inference_custom_pytorch.py:199-219); masks (T,H,W) u8, one per render.
+ * sam6d_template_bbox: bbox (T,4) i32 = get_bbox(mask == 255) (:201-203, PEM/utils/data_utils.py:125-160), no depth condition;
+ *   count (T) = mask pixels in the image.
+ * sam6d_template_crop_points: the mask pixels of each crop in row-major order (:214): choose (T,cap) i32 flat crop indices,
+ *   xyz (T,cap,3) f32 = xyz_mm[y1:y2, x1:x2] / 1000 (:200, :219) with xyz_mm (T,H,W,3) f32, n_valid (T) = min(count in crop, cap).
+ *   The caller's choice (:215-218) then goes through sam6d_choose_points (xyz[sel] and get_resize_rgb_choose, :221). */
+int sam6d_template_bbox(const unsigned char* masks, int T, int H, int W, int* bbox, int* count, void* stream);
+int sam6d_template_crop_points(const unsigned char* masks, const float* xyz_mm, int T, int H, int W, const int* bbox, int cap, int* choose,
+                               float* xyz, int* n_valid, void* stream);
+/* The rgb input (PEM/run_inference_custom_pytorch.py:344-350 proposals, :207-212 templates): img[y1:y2, x1:x2][:, :, ::-1], times the
+ * mask bit, cv2.resize to (img_size, img_size) with INTER_LINEAR (OpenCV 4.x fixed point, restated; a 2*img_size crop takes OpenCV's
+ * INTER_AREA fast path), then ToTensor + Normalize (:151-153).  N items in one launch.
+ * images: (H,W,channels) u8 per item at byte stride image_stride (0: all items share one image); channels 1 (grayscale, as :293-294)
+ * or 3.  bbox (N,4) i32 = (y1, y2, x1, x2).  mask_mode 0: no mask (rgb_mask_flag False); 1: (masks[i] > 0) & (depth > 0) (:318);
+ * 2: masks[i] == 255 (:201).  masks (N,H,W) u8, depth (H,W) f32.
+ * out (N,3,img_size,img_size) f32; out_u8 (N,img_size,img_size,3) u8 the resized crops, or NULL; status (N) i32, or NULL: 1 where
+ * bbox[i] is not inside the image (that item is written as an all-masked crop), else 0.  img_size <= 1024; W <= 8191. */
+int sam6d_rgb_crop_resize(const unsigned char* images, long image_stride, int channels, int H, int W, const unsigned char* masks,
+                          const float* depth, int mask_mode, int N, const int* bbox, int img_size, float* out, unsigned char* out_u8,
+                          int* status, void* stream);
 
 #ifdef __cplusplus
 }

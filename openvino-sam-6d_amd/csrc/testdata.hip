@@ -9,6 +9,8 @@
 // ---- 1. valid-pixel count and crop box --------------------------------------------------------------------------------
 // bbox[i] = {rmin, rmax, cmin, cmax} exactly as get_bbox computes it from (mask > 0) & (depth > 0); count[i] = number of
 // valid pixels (the caller skips proposals with count <= 32, run_inference_custom_pytorch.py:320-324).
+// kTem: a template render instead (_get_template :201-203): one mask per item, valid = mask == 255, no depth.
+template <bool kTem>
 __global__ __launch_bounds__(256) void mask_bbox_kernel(const unsigned char* __restrict__ masks, const float* __restrict__ depth, int H,
                                                         int W, int* __restrict__ bbox, int* __restrict__ count) {
   __shared__ int s_rmin, s_rmax, s_cmin, s_cmax, s_cnt;
@@ -26,7 +28,7 @@ __global__ __launch_bounds__(256) void mask_bbox_kernel(const unsigned char* __r
   for (int r = wave; r < H; r += 4) {  // one wave per image row, lanes over columns (coalesced)
     for (int c0 = 0; c0 < W; c0 += 64) {
       const int c = c0 + lane;
-      const bool v = c < W && m[(size_t)r * W + c] != 0 && depth[(size_t)r * W + c] > 0.f;
+      const bool v = c < W && (kTem ? m[(size_t)r * W + c] == 255 : (m[(size_t)r * W + c] != 0 && depth[(size_t)r * W + c] > 0.f));
       if (v) {
         cmin = min(cmin, c);
         cmax = max(cmax, c);
@@ -86,13 +88,16 @@ extern "C" int sam6d_mask_bbox(const unsigned char* masks, const float* depth, i
   SAM6D_REQUIRE(masks && depth && bbox && count, "mask_bbox: null pointer");
   SAM6D_REQUIRE(N >= 0 && H > 0 && W > 0, "mask_bbox: bad sizes");
   if (N == 0) return 0;
-  hipLaunchKernelGGL(mask_bbox_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, masks, depth, H, W, bbox, count);
+  hipLaunchKernelGGL(mask_bbox_kernel<false>, dim3(N), dim3(256), 0, (hipStream_t)stream, masks, depth, H, W, bbox, count);
   SAM6D_LAUNCH_CHECK("mask_bbox");
 }
 
 // ---- 2. masked pixels of the crop, in row-major order, with their back-projected points -------------------------------
 // choose[i, k] = flat index (row * crop_w + col) of the k-th valid pixel inside bbox[i]; cloud[i, k] = its 3-D point in the
 // get_point_cloud_from_depth recipe ((col - cx) * z / fx, (row - cy) * z / fy, z; fp32, in that order).  n_valid[i] = how many.
+// kTem: a template render (_get_template :201-219): valid = mask == 255, `depth` is the item's (H,W,3) xyz map in millimetres and
+// cloud[i, k] = xyz / 1000 (fp32 division, np.float32 array / 1000.0).
+template <bool kTem>
 __global__ __launch_bounds__(1024) void crop_points_kernel(const unsigned char* __restrict__ masks, const float* __restrict__ depth,
                                                            int H, int W, const int* __restrict__ bbox, float fx, float fy, float cx,
                                                            float cy, int cap, int* __restrict__ choose, float* __restrict__ cloud,
@@ -114,8 +119,12 @@ __global__ __launch_bounds__(1024) void crop_points_kernel(const unsigned char* 
     if (p < npix) {
       r = r0 + (int)(p / cw);
       c = c0 + (int)(p % cw);
-      z = depth[(size_t)r * W + c];
-      v = m[(size_t)r * W + c] != 0 && z > 0.f;
+      if (kTem) {
+        v = m[(size_t)r * W + c] == 255;
+      } else {
+        z = depth[(size_t)r * W + c];
+        v = m[(size_t)r * W + c] != 0 && z > 0.f;
+      }
     }
     const unsigned long long bal = __ballot(v);
     if (lane == 0) s_wave[wave] = __popcll(bal);
@@ -127,9 +136,16 @@ __global__ __launch_bounds__(1024) void crop_points_kernel(const unsigned char* 
       if (k < cap) {
         choose[(size_t)i * cap + k] = (int)p;
         float* o = cloud + ((size_t)i * cap + k) * 3;
-        o[0] = ((float)c - cx) * z / fx;
-        o[1] = ((float)r - cy) * z / fy;
-        o[2] = z;
+        if (kTem) {
+          const float* x = depth + ((size_t)i * H * W + (size_t)r * W + c) * 3;
+          o[0] = x[0] / 1000.f;
+          o[1] = x[1] / 1000.f;
+          o[2] = x[2] / 1000.f;
+        } else {
+          o[0] = ((float)c - cx) * z / fx;
+          o[1] = ((float)r - cy) * z / fy;
+          o[2] = z;
+        }
       }
     }
     __syncthreads();
@@ -208,9 +224,30 @@ extern "C" int sam6d_crop_masked_points(const unsigned char* masks, const float*
   SAM6D_REQUIRE(masks && depth && bbox && choose && cloud && n_valid, "crop_masked_points: null pointer");
   SAM6D_REQUIRE(N >= 0 && H > 0 && W > 0 && cap > 0, "crop_masked_points: bad sizes");
   if (N == 0) return 0;
-  hipLaunchKernelGGL(crop_points_kernel, dim3(N), dim3(1024), 0, (hipStream_t)stream, masks, depth, H, W, bbox, fx, fy, cx, cy, cap,
+  hipLaunchKernelGGL(crop_points_kernel<false>, dim3(N), dim3(1024), 0, (hipStream_t)stream, masks, depth, H, W, bbox, fx, fy, cx, cy, cap,
                      choose, cloud, n_valid);
   SAM6D_LAUNCH_CHECK("crop_masked_points");
+}
+
+// The template side of the same two steps (_get_template, PEM/run_inference_custom_pytorch.py:199-219): masks (T,H,W) u8, one per
+// render, valid = mask == 255 without a depth condition; xyz_mm (T,H,W,3) f32.  The chosen points and their resized-crop indices then
+// come from sam6d_choose_points, as for proposals.
+extern "C" int sam6d_template_bbox(const unsigned char* masks, int T, int H, int W, int* bbox, int* count, void* stream) {
+  SAM6D_REQUIRE(masks && bbox && count, "template_bbox: null pointer");
+  SAM6D_REQUIRE(T >= 0 && H > 0 && W > 0, "template_bbox: bad sizes");
+  if (T == 0) return 0;
+  hipLaunchKernelGGL(mask_bbox_kernel<true>, dim3(T), dim3(256), 0, (hipStream_t)stream, masks, nullptr, H, W, bbox, count);
+  SAM6D_LAUNCH_CHECK("template_bbox");
+}
+
+extern "C" int sam6d_template_crop_points(const unsigned char* masks, const float* xyz_mm, int T, int H, int W, const int* bbox, int cap,
+                                          int* choose, float* xyz, int* n_valid, void* stream) {
+  SAM6D_REQUIRE(masks && xyz_mm && bbox && choose && xyz && n_valid, "template_crop_points: null pointer");
+  SAM6D_REQUIRE(T >= 0 && H > 0 && W > 0 && cap > 0, "template_crop_points: bad sizes");
+  if (T == 0) return 0;
+  hipLaunchKernelGGL(crop_points_kernel<true>, dim3(T), dim3(1024), 0, (hipStream_t)stream, masks, xyz_mm, H, W, bbox, 0.f, 0.f, 0.f,
+                     0.f, cap, choose, xyz, n_valid);
+  SAM6D_LAUNCH_CHECK("template_crop_points");
 }
 
 extern "C" int sam6d_radius_filter(int N, int cap, const int* n_valid, float radius, int* choose, float* cloud, int* n_keep,

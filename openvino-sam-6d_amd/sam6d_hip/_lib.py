@@ -104,6 +104,9 @@ SIGNATURES = {
     "sam6d_crop_masked_points": [c_p, c_p, c_i, c_i, c_i, c_p, c_f, c_f, c_f, c_f, c_i, c_p, c_p, c_p, c_p],
     "sam6d_radius_filter": [c_i, c_i, c_p, c_f, c_p, c_p, c_p, c_p, c_p],
     "sam6d_choose_points": [c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p],
+    "sam6d_template_bbox": [c_p, c_i, c_i, c_i, c_p, c_p, c_p],
+    "sam6d_template_crop_points": [c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p],
+    "sam6d_rgb_crop_resize": [c_p, c_l, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p],
     "sam6d_pairwise_distance": [c_p, c_p, c_i, c_i, c_i, c_p, c_p],
     "sam6d_fine_score": [c_p] * 6 + [c_i] * 3 + [c_f, c_p, c_p, c_p],
     "sam6d_fine_match_workspace_bytes": [c_i],

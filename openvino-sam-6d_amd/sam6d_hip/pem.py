@@ -1773,6 +1773,110 @@ def proposal_choose(geom, sel, img_size=224):
     return pts, rc
 
 
+def _rgb_crop_resize(images, stride, C, masks, depth, mask_mode, bbox, img_size, return_uint8, check):
+    """sam6d_rgb_crop_resize over bbox.shape[0] items of images (..., H, W, C) u8 (stride: 1 = one image per item, 0 = shared)."""
+    from .ops import _chk
+    bbox = bbox.contiguous()
+    _chk(bbox, "bbox", torch.int32, 2)
+    N = bbox.shape[0]
+    H, Wd = images.shape[-3:-1] if C == 3 else images.shape[-2:]
+    S = int(img_size)
+    out = _empty((N, 3, S, S), images)
+    u8 = _empty((N, S, S, 3), images, torch.uint8) if return_uint8 else None
+    status = _empty((N,), images, torch.int32) if check else None
+    _lib.call("sam6d_rgb_crop_resize", images.data_ptr(), stride * H * Wd * C, C, H, Wd, masks.data_ptr() if masks is not None else None,
+              depth.data_ptr() if depth is not None else None, mask_mode, N, _p(bbox), S, _p(out), u8.data_ptr() if u8 is not None else None,
+              _p(status), _s())
+    if check and N and bool(status.any()):
+        bad = [i for i, v in enumerate(status.cpu().tolist()) if v]
+        raise RuntimeError("rgb crop: the bbox of item(s) %s is not inside the %dx%d image" % (bad[:8], H, Wd))
+    return (out, u8) if return_uint8 else out
+
+
+def _image_channels(img, name, lead):
+    """3 for (..., H, W, 3), 1 for a grayscale (..., H, W) u8 stack with `lead` leading dimensions"""
+    from .ops import _chk
+    _chk(img, name, torch.uint8)
+    if img.dim() == lead + 3 and img.shape[-1] == 3:
+        return 3
+    if img.dim() == lead + 2:
+        return 1
+    raise RuntimeError("%s must be %s(H, W, 3) or %s(H, W) uint8, got %s" % (name, "(T, " * lead, "(T, " * lead, tuple(img.shape)))
+
+
+@on_tensor_device
+def proposal_rgb(image, masks, depth, geom, img_size=224, rgb_mask_flag=True, return_uint8=False, check=True):
+    """The rgb input of get_test_data (PEM/run_inference_custom_pytorch.py:344-350) for every proposal in one launch: the crop
+    geom["bbox"] (from proposal_geometry, or any (N,4) i32 (y1, y2, x1, x2)) of image (H,W,3) u8 RGB or (H,W) grayscale (:293-294),
+    channels reversed, times (mask > 0) & (depth > 0) (:318) when rgb_mask_flag, cv2.resize INTER_LINEAR to img_size, ToTensor +
+    Normalize.  -> rgb (N,3,S,S) f32, and with return_uint8 also the resized crops (N,S,S,3) u8.  check: one read-back of a status
+    vector, RuntimeError for a bbox outside the image (boxes from proposal_geometry always lie inside; inputs.test_data skips it)."""
+    from .ops import _chk
+    image = image.contiguous()
+    masks = masks.to(torch.uint8).contiguous()
+    depth = depth.contiguous()
+    C = _image_channels(image, "image", 0)
+    _chk(masks, "masks", torch.uint8, 3)
+    _chk(depth, "depth", torch.float32, 2)
+    if tuple(depth.shape) != tuple(masks.shape[1:]) or tuple(image.shape[:2]) != tuple(depth.shape):
+        raise RuntimeError("image %s, masks %s and depth %s disagree on (H, W)" % (tuple(image.shape), tuple(masks.shape), tuple(depth.shape)))
+    if geom["bbox"].shape[0] != masks.shape[0]:
+        raise RuntimeError("geom has %d boxes for %d masks" % (geom["bbox"].shape[0], masks.shape[0]))
+    if rgb_mask_flag:
+        return _rgb_crop_resize(image, 0, C, masks, depth, 1, geom["bbox"], img_size, return_uint8, check)
+    return _rgb_crop_resize(image, 0, C, None, None, 0, geom["bbox"], img_size, return_uint8, check)
+
+
+@on_tensor_device
+def template_geometry(masks, xyz_mm, cap=None):
+    """The crop of each template before the random choice (_get_template, PEM/run_inference_custom_pytorch.py:199-214): masks (T,H,W)
+    u8 (mask == 255 is the object, :201), xyz_mm (T,H,W,3) f32 millimetres.  -> dict(bbox (T,4) i32 = get_bbox(mask == 255),
+    count (T) mask pixels, choose (T,cap) i32 raster-order mask pixels of the crop, cloud (T,cap,3) = their xyz / 1000, n_valid (T),
+    cap).  cap defaults to min(H, W)^2, the largest crop; n_valid[t] is the len(choose) the caller draws from (0: the reference's
+    get_bbox would fail on that template)."""
+    from .ops import _chk
+    masks = masks.to(torch.uint8).contiguous()
+    xyz_mm = xyz_mm.contiguous()
+    _chk(masks, "masks", torch.uint8, 3)
+    _chk(xyz_mm, "xyz_mm", torch.float32, 4)
+    T, H, Wd = masks.shape
+    if tuple(xyz_mm.shape) != (T, H, Wd, 3):
+        raise RuntimeError("xyz_mm must be (%d, %d, %d, 3), got %s" % (T, H, Wd, tuple(xyz_mm.shape)))
+    bbox = _empty((T, 4), masks, torch.int32)
+    count = _empty((T,), masks, torch.int32)
+    _lib.call("sam6d_template_bbox", _p(masks), T, H, Wd, _p(bbox), _p(count), _s())
+    cap = int(cap) if cap is not None else min(H, Wd) ** 2
+    choose = _empty((T, cap), masks, torch.int32)
+    cloud = _empty((T, cap, 3), masks)
+    n_valid = _empty((T,), masks, torch.int32)
+    _lib.call("sam6d_template_crop_points", _p(masks), _p(xyz_mm), T, H, Wd, _p(bbox), cap, _p(choose), _p(cloud), _p(n_valid), _s())
+    return dict(bbox=bbox, count=count, choose=choose, cloud=cloud, n_valid=n_valid, cap=cap)
+
+
+@on_tensor_device
+def template_inputs(images, masks, xyz_mm, sel, img_size=224, rgb_mask_flag=True, geom=None):
+    """rgb, rgb_choose, xyz of _get_template (PEM/run_inference_custom_pytorch.py:199-222) for T templates at once: images (T,H,W,3)
+    u8 RGB (or (T,H,W) grayscale), masks (T,H,W) u8 (mask == 255 is the object), xyz_mm (T,H,W,3) f32 millimetres, sel (T,ns) the
+    caller's random choice into each template's n_valid crop pixels (:215-218).  -> rgb (T,3,S,S) f32, rgb_choose (T,ns) i64, xyz
+    (T,ns,3) f32 metres.  geom: template_geometry(masks, xyz_mm) when the caller already has it (it draws sel from n_valid)."""
+    images = images.contiguous()
+    C = _image_channels(images, "images", 1)
+    if geom is None:
+        geom = template_geometry(masks, xyz_mm)
+    masks = masks.to(torch.uint8).contiguous()
+    T, H, Wd = masks.shape
+    if tuple(images.shape[:3]) != (T, H, Wd):
+        raise RuntimeError("images %s do not match masks %s" % (tuple(images.shape), tuple(masks.shape)))
+    if not torch.is_tensor(sel) or sel.dim() != 2 or sel.shape[0] != T:
+        raise RuntimeError("sel must be a (%d, ns) tensor" % T)
+    xyz, rgb_choose = proposal_choose(geom, sel.to(masks.device), img_size)
+    if rgb_mask_flag:
+        rgb = _rgb_crop_resize(images, 1, C, masks, None, 2, geom["bbox"], img_size, False, False)
+    else:
+        rgb = _rgb_crop_resize(images, 1, C, None, None, 0, geom["bbox"], img_size, False, False)
+    return rgb, rgb_choose, xyz
+
+
 def _cat0(a, b):
     """stack two (B,N,K) tensors along the batch -- a device copy, no arithmetic"""
     a = a.contiguous()
