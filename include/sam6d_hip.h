@@ -30,7 +30,7 @@ const char* sam6d_last_error(void);
  *   1  rounds 1-3
  *   2  sam6d_set_thread_matmul_mode added; round 3's layout change made visible: sam6d_linattn_kv_pack / sam6d_linattn_kv_image write 4*B floats to `inv` (one image
  *      scale per head), sam6d_linattn_layer reads kvinv as (B,4) -- a version-1 consumer allocated B floats */
-#define SAM6D_ABI_VERSION 2
+#define SAM6D_ABI_VERSION 3
 int sam6d_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -94,8 +94,8 @@ int sam6d_gather_rows_lead(const float* feats, const int* idx, int B, int N, int
 /* C = act(((A . W^T) / divisor) * colscale + bias) + residual  on the fp32 matrix cores.
  * replaces nn.Linear / 1x1-conv call sites (PEM/model/transformer.py:127-129,186-188,390-393,548-550;
  * PEM/model/coarse_point_matching.py:35-38) and the similarity contraction (PEM/utils/model_utils.py:144-150).
- * A (M,K) lda; W (N,K) ldw; C (M,N) ldc; residual (M,N) ldr or NULL; bias/colscale (N) or NULL; act 0 none / 1 ReLU,
- * + 16 marks a geometric operand (the proj_p / Chebyshev folds of the RPE query) that keeps the fp16 x3 split in matmul mode 2;
+ * A (M,K) lda; W (N,K) ldw; C (M,N) ldc; residual (M,N) ldr or NULL; bias/colscale (N) or NULL; act 0 none / 1 ReLU /
+ * 2 exact erf GELU (nn.GELU of the ViT MLP, PEM/model/feature_extraction.py:21-35), + 16 marks a geometric operand (the proj_p / Chebyshev folds of the RPE query) that keeps the fp16 x3 split in matmul mode 2;
  * `batch` independent problems with strides sA/sW/sC/sR (floats).  divisor = 1 disables the division. */
 int sam6d_gemm_nt(const float* A, const float* W, const float* bias, const float* colscale, const float* residual,
                   float* C, int M, int N, int K, long lda, long ldw, long ldc, long ldr, int batch, long sA, long sW,
@@ -577,6 +577,25 @@ int sam6d_template_crop_points(const unsigned char* masks, const float* xyz_mm, 
 int sam6d_rgb_crop_resize(const unsigned char* images, long image_stride, int channels, int H, int W, const unsigned char* masks,
                           const float* depth, int mask_mode, int N, const int* bbox, int img_size, float* out, unsigned char* out_u8,
                           int* status, void* stream);
+
+/* ViT-B/16 image encoder of the feature extraction (PEM/model/feature_extraction.py:21-35, :98-118, :141-142); the residual stream is
+ * X (B*197, 768) f32 row-major, row 0 of each image the cls token.  The dense projections are sam6d_gemm_nt / _w16 (fc1 with act 2).
+ * sam6d_vit_patch_rows: images (B,3,224,224) -> A (B*196, 768), row 14 py + px = the 16 x 16 patch in the Conv2d weight's (c, kh, kw)
+ *   order (patch_embed.proj, feature_extraction.py:21-35), and the cls rows X[197 b] = cls_token + pos_embed[0] (768 floats each). */
+int sam6d_vit_patch_rows(const float* img, const float* cls_token, const float* pos_embed, float* A, float* X, int B, void* stream);
+/* nn.LayerNorm(768, eps) over `rows` rows of each of nimg images (feature_extraction.py:21-35 norm1 / norm2 / norm): row r of image b
+ * is x + b sx + r ldx -> y + b sy + r ldy (floats; strides multiples of 4, pointers 16-byte aligned).  Also writes the pyramid taps
+ * into their concat buffer (:98-118). */
+int sam6d_vit_layernorm768(const float* x, const float* gamma, const float* beta, float* y, int nimg, int rows, long ldx, long sx,
+                           long ldy, long sy, float eps, void* stream);
+/* Multi-head self-attention of a ViT-B block (feature_extraction.py:21-35): qkv (B*n, 2304) = [q | k | v], head h at columns
+ * 64h .. 64h+63 of each part -> out (B*n, 768) = softmax(q_h k_h^T / 8) v_h per head, in x.transpose(1,2).reshape(B,n,768) order.
+ * n <= 208.  fp16 x3 split MFMA products with power-of-two operand scales (fp32 softmax); the probabilities stay on chip. */
+int sam6d_vit_attention(const float* qkv, float* out, int B, int n, void* stream);
+/* output_upscaling -> F.interpolate(56 -> 224, bilinear, align_corners=False) -> get_chosen_pixel_feats (feature_extraction.py:98-118,
+ * PEM/utils/model_utils.py:86-98) without the dense map: U (B*196, 4096) = the output_upscaling GEMM output (bias included),
+ * choose (B,N) i64 pixel indices -> out (B,N,256).  An index outside [0, 224*224) yields a NaN row. */
+int sam6d_vit_upsample_gather(const float* U, const long long* choose, float* out, int B, int N, void* stream);
 
 #ifdef __cplusplus
 }

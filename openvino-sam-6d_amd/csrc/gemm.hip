@@ -13,6 +13,10 @@
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+// act = 2: exact (erf) GELU, x * 0.5 * (1 + erf(x / sqrt 2)) as nn.GELU() / F.gelu compute it (the ViT MLP's fc1,
+// PEM/model/feature_extraction.py:21-35 through timm's Mlp)
+__device__ __forceinline__ float gelu_erf(float x) { return x * 0.5f * (1.0f + erff(x * 0.70710678118654752f)); }
+
 #define GM_BK 16
 #define GM_LD 17
 
@@ -190,6 +194,7 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const float* __restrict__ 
           if (divisor != 1.0f) v = v / divisor;
           v = colscale ? fmaf(v, cs, bv) : v + bv;
           if (act == 1) v = v > 0.f ? v : 0.f;
+          else if (act == 2) v = gelu_erf(v);
           v += rv[r];
           C[(size_t)row * ldc + col] = v;
         }
@@ -485,6 +490,7 @@ __global__ __launch_bounds__(256, FAST ? 3 : 2) void gemm_nt_h3_kernel(const flo
             if (divisor != 1.0f) x = x / divisor;
             x = colscale ? fmaf(x, cc[q], bb[q]) : x + bb[q];
             if (act == 1) x = x > 0.f ? x : 0.f;
+            else if (act == 2) x = gelu_erf(x);
             e[q] = x + rz[q];
           }
           *reinterpret_cast<float4*>(C + (size_t)row * ldc + col) = make_float4(e[0], e[1], e[2], e[3]);
@@ -518,6 +524,7 @@ __global__ __launch_bounds__(256, FAST ? 3 : 2) void gemm_nt_h3_kernel(const flo
           if (divisor != 1.0f) v = v / divisor;
           v = colscale ? fmaf(v, cs, bv) : v + bv;
           if (act == 1) v = v > 0.f ? v : 0.f;
+          else if (act == 2) v = gelu_erf(v);
           v += rv[r];
           C[(size_t)row * ldc + col] = v;
         }
@@ -568,7 +575,7 @@ static int gemm_pick(GemmRoute& r, const float* A, const float* W, const float* 
   SAM6D_REQUIRE(lda >= K && ldw >= K && ldc >= N, "gemm_nt: leading dimension smaller than the row length");
   const int keep_split = act & 16;  // geometric operand: stays at fp16 x3 in matmul mode 2 (sam6d_hip.h)
   act &= ~16;
-  SAM6D_REQUIRE(act == 0 || act == 1, "gemm_nt: act must be 0 (none) or 1 (ReLU), optionally + 16");
+  SAM6D_REQUIRE(act == 0 || act == 1 || act == 2, "gemm_nt: act must be 0 (none), 1 (ReLU) or 2 (erf GELU), optionally + 16");
   SAM6D_REQUIRE((long)batch * b2.n2 <= 65535, "gemm_nt: batch (x batch2) must be <= 65535");
   r = GemmRoute{};
   r.empty = (M == 0 || N == 0 || batch == 0);

@@ -543,9 +543,9 @@ extern "C" int sam6d_sattn_debug_stamps(void* dst) {
 #define SA_ST(i)
 #endif
 struct SaArgs {
-  const float* qkv;   // (B n, 768): q | k | v
-  const float* G;     // (B n, 4, ldp) geometric score term (raw, not yet / 8)
-  float* out;         // (B n, 256)
+  const float* qkv;   // (B n, 3 * SaLayout::C): q | k | v
+  const float* G;     // (B n, 4, ldp) geometric score term (raw, not yet / 8); RPE layout only
+  float* out;         // (B n, SaLayout::C)
   int n, ldp;
   int half;
 };
@@ -582,7 +582,19 @@ __device__ __forceinline__ void xa_rows_step(f32x4* acc, unsigned kb, int fr, in
   if constexpr (S + 1 < 2 * NT) xa_rows_step<NT, S + 1>(acc, kb, fr, fg, xh, xl, fh, fl, half);
 }
 
+// Token layout of the self-attention kernel: C channels (C / 64 heads) per token, qkv rows of 3 C floats.  VIT = false: the RPE layers
+// (4 heads, plus the geometric score term G); VIT = true: the ViT-B encoder's blocks (12 heads, scores q k^T / 8 alone,
+// PEM/model/feature_extraction.py:21-35 through timm's Attention) -- sam6d_vit_attention.
+template <bool VIT>
+struct SaLayout {
+  static constexpr int C = VIT ? 768 : 256;
+  static constexpr int LDQ = 3 * C;
+  static constexpr bool G = !VIT;
+};
+
+template <bool VIT>
 __global__ __launch_bounds__(XA_WAVES * 64) void sattn_kernel(SaArgs a) {
+  using L = SaLayout<VIT>;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   unsigned char* regA = lds;                    // v_h^T image
   unsigned char* kimg = lds + XA_WQ_BYTES;      // k_h image
@@ -605,6 +617,7 @@ __global__ __launch_bounds__(XA_WAVES * 64) void sattn_kernel(SaArgs a) {
   float4 qa[2][2], qb[2][2];
   // G tiles of the lane's query: keys 16 i + 4 g .. + 3 (a row of ldp = 4 ceil(n / 4) floats, so a started float4 stays inside it)
   auto load_g = [&](int gi) {
+    if (!L::G) return;
     const int grp = wave + XA_WAVES * gi;
     const int tok = min(grp * 16 + fr, n - 1);
     const float* grow = a.G + (((size_t)b * n + tok) * 4 + h) * a.ldp + 4 * fg;
@@ -615,7 +628,7 @@ __global__ __launch_bounds__(XA_WAVES * 64) void sattn_kernel(SaArgs a) {
   auto load_q = [&](int gi) {
     const int grp = wave + XA_WAVES * gi;
     const int tok = min(grp * 16 + fr, n - 1);
-    const float* src = a.qkv + ((size_t)b * n + tok) * 768 + 64 * h;
+    const float* src = a.qkv + ((size_t)b * n + tok) * L::LDQ + 64 * h;
 #pragma unroll
     for (int s2 = 0; s2 < 2; ++s2) {
       qa[gi][s2] = *reinterpret_cast<const float4*>(src + 32 * s2 + 4 * fg);
@@ -624,14 +637,14 @@ __global__ __launch_bounds__(XA_WAVES * 64) void sattn_kernel(SaArgs a) {
   };
   constexpr int XA_KT = (XA_MAXKEY * 16 + XA_WAVES * 64 - 1) / (XA_WAVES * 64);        // 7 float4 of k per thread
   constexpr int XA_VT = ((XA_MAXKEY / 4) * 64 + XA_WAVES * 64 - 1) / (XA_WAVES * 64);  // 7 key quads of v per thread
-  const float* kb = a.qkv + (size_t)b * n * 768 + 256 + 64 * h;
-  const float* vb = kb + 256;
+  const float* kb = a.qkv + (size_t)b * n * L::LDQ + L::C + 64 * h;
+  const float* vb = kb + L::C;
   float4 kreg[XA_KT];
   float vreg[XA_VT][4];
 #pragma unroll
   for (int i = 0; i < XA_KT; ++i) {
     const int e = t + XA_WAVES * 64 * i, j = e >> 4, c4 = e & 15;
-    kreg[i] = (j < m) ? *reinterpret_cast<const float4*>(kb + (size_t)j * 768 + 4 * c4) : make_float4(0.f, 0.f, 0.f, 0.f);
+    kreg[i] = (j < m) ? *reinterpret_cast<const float4*>(kb + (size_t)j * L::LDQ + 4 * c4) : make_float4(0.f, 0.f, 0.f, 0.f);
   }
 #pragma unroll
   for (int i = 0; i < XA_VT; ++i) {
@@ -639,7 +652,7 @@ __global__ __launch_bounds__(XA_WAVES * 64) void sattn_kernel(SaArgs a) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int j = 4 * jq + r;
-      vreg[i][r] = (j < m) ? vb[(size_t)j * 768 + d] : 0.f;
+      vreg[i][r] = (j < m) ? vb[(size_t)j * L::LDQ + d] : 0.f;
     }
   }
   // (behind the key / value loads: the vector-memory counter retires in order, and the images are built first)
@@ -743,7 +756,8 @@ __global__ __launch_bounds__(XA_WAVES * 64) void sattn_kernel(SaArgs a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int key = 16 * i + 4 * fg + r;
-          s[i][r] = key < m ? s[i][r] * inv + gv[r] * 0.125f : -INFINITY;
+          if (L::G) s[i][r] = key < m ? s[i][r] * inv + gv[r] * 0.125f : -INFINITY;
+          else s[i][r] = key < m ? s[i][r] * inv : -INFINITY;
           mx = fmaxf(mx, s[i][r]);
         }
       }
@@ -782,7 +796,7 @@ __global__ __launch_bounds__(XA_WAVES * 64) void sattn_kernel(SaArgs a) {
       }
       SA_ST(8 + 5 * gi);
       if (grp * 16 + fr < n) {
-        float* dst = a.out + ((size_t)b * n + tok) * 256 + 64 * h;
+        float* dst = a.out + ((size_t)b * n + tok) * L::C + 64 * h;
 #pragma unroll
         for (int i = 0; i < 4; ++i)
           *reinterpret_cast<float4*>(dst + 16 * i + 4 * fg) = make_float4(o[i][0] * inv_v, o[i][1] * inv_v, o[i][2] * inv_v, o[i][3] * inv_v);
@@ -808,7 +822,7 @@ extern "C" int sam6d_rpe_self_attention(const float* qkv, const float* G, float*
   if (B == 0) return 0;
   static unsigned long long done = 0;
   if (sam6d_first_use_on_device(&done)) {
-    hipError_t e = hipFuncSetAttribute((const void*)sattn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, XA_LDS);
+    hipError_t e = hipFuncSetAttribute((const void*)sattn_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, XA_LDS);
     if (e != hipSuccess) {
       sam6d_set_error("rpe_self_attention: cannot reserve %d bytes of LDS: %s", XA_LDS, hipGetErrorString(e));
       return (int)e;
@@ -816,6 +830,28 @@ extern "C" int sam6d_rpe_self_attention(const float* qkv, const float* G, float*
     sam6d_setup_done_on_device(&done);
   }
   SaArgs a{qkv, G, hidden, n, ldp, sam6d_half_for(2)};
-  hipLaunchKernelGGL(sattn_kernel, dim3(4, B), dim3(XA_WAVES * 64), XA_LDS, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(sattn_kernel<false>, dim3(4, B), dim3(XA_WAVES * 64), XA_LDS, (hipStream_t)stream, a);
   SAM6D_LAUNCH_CHECK("rpe_self_attention");
+}
+
+// The ViT-B encoder's multi-head self-attention (PEM/model/feature_extraction.py:21-35 -> timm Attention: softmax(q k^T / 8) v over
+// 12 heads of 64 channels): sattn_kernel<true>, one workgroup per (image, head), the probabilities stay in registers.
+extern "C" int sam6d_vit_attention(const float* qkv, float* out, int B, int n, void* stream) {
+  SAM6D_REQUIRE(qkv && out && B >= 0, "vit_attention: null pointer");
+  SAM6D_REQUIRE(n > 0 && n <= XA_MAXKEY, "vit_attention: needs 0 < n <= %d tokens per image (n = %d)", XA_MAXKEY, n);
+  SAM6D_REQUIRE(((((size_t)qkv) | ((size_t)out)) & 15) == 0, "vit_attention: pointers must be 16-byte aligned");
+  SAM6D_REQUIRE(B <= 65535, "vit_attention: B <= 65535");
+  if (B == 0) return 0;
+  static unsigned long long done = 0;
+  if (sam6d_first_use_on_device(&done)) {
+    hipError_t e = hipFuncSetAttribute((const void*)sattn_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, XA_LDS);
+    if (e != hipSuccess) {
+      sam6d_set_error("vit_attention: cannot reserve %d bytes of LDS: %s", XA_LDS, hipGetErrorString(e));
+      return (int)e;
+    }
+    sam6d_setup_done_on_device(&done);
+  }
+  SaArgs a{qkv, nullptr, out, n, 0, sam6d_half_for(2)};
+  hipLaunchKernelGGL(sattn_kernel<true>, dim3(12, B), dim3(XA_WAVES * 64), XA_LDS, (hipStream_t)stream, a);
+  SAM6D_LAUNCH_CHECK("vit_attention");
 }

@@ -1,5 +1,6 @@
-"""Drop-in for PEM/model/feature_extraction.py.  The ViT backbone is OUTSIDE the matching hot path:
-it stays plain PyTorch-ROCm.  timm is used when importable; otherwise a local ViT-B/16 with timm-compatible state_dict
+"""Drop-in for PEM/model/feature_extraction.py.  The ViT backbone below is plain PyTorch-ROCm (the default, and the reference the
+library path is tested against); with Options.hip_vit (SAM6D_HIP_VIT=1) ViTEncoder's image features run on the library instead
+(sam6d_hip/vit.py: HIP kernels, the dense 224 x 224 feature map never formed).  timm is used when importable; otherwise a local ViT-B/16 with timm-compatible state_dict
 keys (patch_embed.proj, cls_token, pos_embed, blocks.N.{norm1,attn.qkv,attn.proj,norm2,mlp.fc1,mlp.fc2}, norm) so the
 released checkpoint still loads.  No network access: a missing MAE checkpoint is skipped with a message instead of
 being downloaded (feature_extraction.py:78-97)."""
@@ -12,6 +13,8 @@ from torch.nn import functional as F
 
 from model_utils import get_chosen_pixel_feats, sample_pts_feats
 from sam6d_hip import pem as _pem
+from sam6d_hip import vit as _vit
+from transformer import _sig
 
 
 class _Attn(nn.Module):
@@ -138,11 +141,33 @@ class ViTEncoder(nn.Module):
         dense_pm, dense_po, radius = _pem.radius_normalize(pts, dense_po)  # feature_extraction.py:133-137, on the GPU
         return dense_pm, dense_fm, dense_po, dense_fo, radius
 
+    def _vit_weights(self):
+        """The library's weight pack of rgb_net (sam6d_hip.vit.VitWeights), rebuilt when any parameter is replaced or modified."""
+        sig = _sig(self.rgb_net)
+        if getattr(self, "_vit_sig", None) != sig:
+            dev = self.rgb_net.output_upscaling.weight.device
+            if dev.type != "cuda":
+                raise RuntimeError("ViTEncoder: hip_vit needs the parameters on a HIP device (model.to('cuda'))")
+            object.__setattr__(self, "_vit_pack", _vit.VitWeights(self.rgb_net.state_dict(), dev, cfg=self.rgb_net.cfg))
+            object.__setattr__(self, "_vit_sig", sig)
+        return self._vit_pack
+
     def get_img_feats(self, img, choose):
+        if _pem._flags().hip_vit:
+            return _vit.image_features(img, choose, self._vit_weights())
         return get_chosen_pixel_feats(self.rgb_net(img)[0], choose)
 
     def get_obj_feats(self, tem_rgb_list, tem_pts_list, tem_choose_list, npoint=None):
         npoint = npoint or self.npoint
+        if isinstance(tem_rgb_list, list) and _pem._flags().hip_vit:
+            # the T template images in one batch (each keeps its own choose); features in the list form's (B, T*N) order
+            T, B = len(tem_rgb_list), tem_rgb_list[0].shape[0]
+            ns = [c.shape[1] for c in tem_choose_list]
+            nmax = max(ns)
+            ch = torch.cat([F.pad(c.long(), (0, nmax - c.shape[1])) for c in tem_choose_list], 0)
+            f = self.get_img_feats(torch.cat(tem_rgb_list, 0), ch).view(T, B, nmax, -1)
+            feats = torch.cat([f[t, :, :n] for t, n in enumerate(ns)], dim=1)
+            return sample_pts_feats(torch.cat(tem_pts_list, dim=1), feats, npoint)
         if isinstance(tem_rgb_list, list):
             feats = [self.get_img_feats(t, c) for t, c in zip(tem_rgb_list, tem_choose_list)]
             return sample_pts_feats(torch.cat(tem_pts_list, dim=1), torch.cat(feats, dim=1), npoint)

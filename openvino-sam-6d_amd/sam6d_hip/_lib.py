@@ -11,7 +11,7 @@ LIB_PATH = os.environ.get("SAM6D_LIB") or os.path.join(os.path.dirname(_HERE), "
 
 c_f = ctypes.c_float
 c_i = ctypes.c_int
-ABI_VERSION = 2  # include/sam6d_hip.h SAM6D_ABI_VERSION (tests/test_abi.py keeps the two equal)
+ABI_VERSION = 3  # include/sam6d_hip.h SAM6D_ABI_VERSION (tests/test_abi.py keeps the two equal)
 c_l = ctypes.c_long
 c_p = ctypes.c_void_p
 
@@ -128,6 +128,10 @@ SIGNATURES = {
     "sam6d_linattn_kv_image": [c_p, c_p, c_i, c_i, c_l, c_l, c_p, c_p, c_p, c_p],
     "sam6d_token_block": [c_p, c_p, c_p, c_p, c_p, c_l, c_f, c_p],
     "sam6d_linattn_layer": [c_p] * 7 + [c_i, c_i, c_i, c_f, c_p],
+    "sam6d_vit_patch_rows": [c_p] * 5 + [c_i, c_p],
+    "sam6d_vit_layernorm768": [c_p] * 4 + [c_i, c_i, c_l, c_l, c_l, c_l, c_f, c_p],
+    "sam6d_vit_attention": [c_p, c_p, c_i, c_i, c_p],
+    "sam6d_vit_upsample_gather": [c_p, c_p, c_p, c_i, c_i, c_p],
 }
 
 _lib = None

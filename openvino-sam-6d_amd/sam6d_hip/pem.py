@@ -35,6 +35,7 @@ class Options:
                     calling thread's mode for the duration of the entry point (sam6d_set_thread_matmul_mode)
       fused_block   fused transformer-block kernels (csrc/block.hip); off = the launch-per-op path
       fused_rpe / rpe_products / fused_fine / overlap / microbatch   pipeline shape of pem_match (cfg keys of the same name win)
+      hip_vit       the drop-in ViTEncoder's image features on the library (sam6d_hip/vit.py) instead of eager PyTorch (off by default)
     The object keeps the values it was given; the split-precision routes (fused_block, fused_rpe) read as off in mode 0, so
     `replace(matmul_mode=1)` starts again from what the caller asked for.  Read-only routes that follow from the fields: w16 (pre-split
     fp16 weight halves in the GEMMs: modes 1 and 2) and fused_front / fused_out / rows_linear (the RPE front kernel, the fine out_proj
@@ -47,9 +48,11 @@ class Options:
         fused_fine=True,    # fine similarity + soft assignment as one pipeline (finematch.hip)
         overlap=True,       # pose-independent fine work on a second HIP stream
         microbatch=1,
+        hip_vit=False,      # ViTEncoder.get_img_feats / get_obj_feats through sam6d_hip.vit
     )
     ENV = dict(matmul_mode="SAM6D_MATMUL_MODE", fused_block="SAM6D_FUSED_BLOCK", rpe_products="SAM6D_RPE_PRODUCTS",
-               fused_rpe="SAM6D_FUSED_RPE", fused_fine="SAM6D_FUSED_FINE", overlap="SAM6D_OVERLAP", microbatch="SAM6D_MICROBATCH")
+               fused_rpe="SAM6D_FUSED_RPE", fused_fine="SAM6D_FUSED_FINE", overlap="SAM6D_OVERLAP", microbatch="SAM6D_MICROBATCH",
+               hip_vit="SAM6D_HIP_VIT")
     __slots__ = ("_kw", "mode")
 
     def __init__(self, **kw):
@@ -69,6 +72,7 @@ class Options:
     fused_fine = property(lambda self: self._kw["fused_fine"])
     overlap = property(lambda self: self._kw["overlap"])
     microbatch = property(lambda self: int(self._kw["microbatch"]))
+    hip_vit = property(lambda self: bool(self._kw["hip_vit"]))
     w16 = property(lambda self: self.mode >= 1)
     fused_front = fused_out = rows_linear = fused_block
 
