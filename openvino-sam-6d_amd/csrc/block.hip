@@ -13,9 +13,11 @@
 // Before: 8 GEMM launches + 2 LayerNorm + focus passes per dense layer = twelve passes over 134 MB tensors (~3.2 GB of HBM traffic
 // per layer); now D is read once and D' written once (268 MB).
 //
-// Layout: one workgroup = 8 waves (two per SIMD), one wave = 16 tokens, and every product is computed TRANSPOSED:
+// (The layer tail of the 197-token layers -- mode 0 as launched by sam6d_token_block -- has a data flow of its own, see
+// token_tail_kernel; what follows describes token_block_kernel, the dense layer.)
+// Layout: one workgroup = 4 waves, one wave = 16 tokens, and every product is computed TRANSPOSED:
 //     Y^T (out-channel x token) = W (out-channel x k) . X^T (k x token)          v_mfma_f32_16x16x32_f16
-// so the weights are the A operand (streamed through LDS by LDS-DMA, shared by the eight waves) and a wave's activations are the B
+// so the weights are the A operand (streamed through LDS by LDS-DMA, shared by the waves of a workgroup) and a wave's activations are the B
 // operand, held in registers for the whole K extent (8 k-steps x {hi, lo} x 4 VGPRs = 64 VGPRs).  In the 16x16 accumulator a lane
 // (token = lane & 15, g = lane >> 4) holds out-channels 4g .. 4g+3 of ITS OWN token; two such tiles give the 8 values the B operand of
 // the next product wants from that lane, up to a fixed permutation inside every 32-channel block (slot 8g + e <-> channel
@@ -515,17 +517,18 @@ extern "C" int sam6d_tb_debug_stamps(void* dst) {
 #define TB_ST(i)
 #endif
 
-// LOADERS > 0: that many extra waves do nothing but the panel DMA (wait for their pieces, join the barrier, issue the next step), so
-// the ~45 issue cycles of each 1 KiB piece (8 per wave and K = 256 panel) leave the computing waves' instruction streams; PSTEP = 2:
-// a ring slot holds two consecutive panels and the barrier comes every other panel.  Both only where one workgroup per CU runs anyway
-// (the 197-token layers: 197 workgroups on 256 CUs).
-template <int MODE, int WAVES, int NBUF, int FD = TB_FD, int LOADERS = 0, int PSTEP = 1>
-__global__ __launch_bounds__((WAVES + LOADERS) * 64, 2) void token_block_kernel(TbArgs a) {  // (2 waves per SIMD: <= 256 VGPR + AGPR)
+// (Until the layer tail of the 197-token layers got a kernel of its own, token_tail_kernel below, this kernel also ran it, with extra
+// loader waves that did nothing but the panel DMA and ring slots of two panels; only the dense layer, MODE 1, is instantiated now.)
+template <int MODE, int WAVES, int NBUF, int FD = TB_FD>
+__global__ __launch_bounds__(WAVES * 64, 2) void token_block_kernel(TbArgs a) {  // (2 waves per SIMD: <= 256 VGPR + AGPR)
+  // Only the dense layer is launched.  The MODE == 0 branches below are the layer tail on its own as this kernel ran it before
+  // token_tail_kernel; they are kept because the tail INSIDE the dense layer shares every line with them, not as a route.
+  static_assert(MODE == 1, "token_block_kernel is the dense layer; the layer tail on its own is token_tail_kernel");
   constexpr int TB_TOK = 16 * WAVES, TB_NBUF = NBUF;
-  constexpr int NTHREADS = (WAVES + LOADERS) * 64;
-  constexpr int SLOT_BYTES = PSTEP * TB_PANEL_BYTES;
+  constexpr int NTHREADS = WAVES * 64;
+  constexpr int SLOT_BYTES = TB_PANEL_BYTES;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-  unsigned char* pan = lds;                                                   // TB_NBUF slots of PSTEP panels
+  unsigned char* pan = lds;                                                   // TB_NBUF panel slots
   float* cst = reinterpret_cast<float*>(lds + TB_NBUF * SLOT_BYTES);          // TC_N floats
   float* ksm = cst + TC_N;                                                    // 256 floats (mode 1)
   const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6), fr = lane & 15, fg = lane >> 4;
@@ -554,10 +557,8 @@ __global__ __launch_bounds__((WAVES + LOADERS) * 64, 2) void token_block_kernel(
   }
 
   const unsigned char* kvp = MODE ? a.kvimg + (size_t)b * (8 * TB_P64) : nullptr;
-  static_assert(SCH::NPAN % PSTEP == 0, "whole steps");
-  constexpr int NW = LOADERS ? LOADERS : WAVES;        // waves that issue the DMA
-  const bool issuer = LOADERS ? wave >= WAVES : true;
-  const int lw = LOADERS ? wave - WAVES : wave;        // index among the issuing waves
+  constexpr int NW = WAVES;   // every wave issues its share of the DMA
+  const int lw = wave;
   // LDS-DMA of panel I into its ring slot: SCH::per_issuer(I, NW) pieces of 1 KiB per issuing wave (the global image IS the LDS image)
   auto dma = [&](auto IC) {
     constexpr int I = decltype(IC)::value;
@@ -573,7 +574,7 @@ __global__ __launch_bounds__((WAVES + LOADERS) * 64, 2) void token_block_kernel(
         constexpr size_t base = 8 * (size_t)TB_P256 + c * (size_t)TB_CHUNK_BYTES;
         src = a.wimg + (u < 4 ? base + u * (size_t)TB_P256 : base + 4 * (size_t)TB_P256 + (u - 4) * (size_t)TB_P128);
       }
-      unsigned char* dst = pan + ((I / PSTEP) % TB_NBUF) * SLOT_BYTES + (I % PSTEP) * TB_PANEL_BYTES;
+      unsigned char* dst = pan + (I % TB_NBUF) * SLOT_BYTES;
 #pragma unroll
       for (int k = 0; k < NP; ++k) {
         const int pc = lw + NW * k;
@@ -588,44 +589,34 @@ __global__ __launch_bounds__((WAVES + LOADERS) * 64, 2) void token_block_kernel(
   // pieces per issuing wave of the steps T+1 .. T+NBUF-2 (in flight while step T is awaited)
   auto step_in_flight = [](int T) constexpr {
     int n = 0;
-    for (int k = 1; k <= NBUF - 2; ++k)
-      for (int p = 0; p < PSTEP; ++p) n += SCH::per_issuer((T + k) * PSTEP + p, NW);
+    for (int k = 1; k <= NBUF - 2; ++k) n += SCH::per_issuer(T + k, NW);
     return n;
   };
-  auto dma_step = [&](auto TC) {  // all panels of step T
-    constexpr int T = decltype(TC)::value;
-    tb_static_for<0, PSTEP>([&](auto PC) { dma(std::integral_constant<int, T * PSTEP + decltype(PC)::value>{}); });
-  };
+  auto dma_step = [&](auto TC) { dma(TC); };  // a step = one panel
   auto step_sync = [&](auto TC) {  // start of step T: its panels have landed and are published; the slot of step T-1 is free
     constexpr int T = decltype(TC)::value;
     static_assert(NBUF == 2 || (32 % NW) == 0, "counted waits need the same number of pieces in every wave");
     constexpr int N = step_in_flight(T);
     TB_ST(4 + 3 * T);
-    if (issuer) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
     TB_ST(5 + 3 * T);
 #ifndef TB_ABL_NOBAR
     __syncthreads();
 #endif
     TB_ST(6 + 3 * T);
 #ifndef TB_ABL_NODMA
-    if (issuer) dma_step(std::integral_constant<int, T + NBUF - 1>{});
+    dma_step(std::integral_constant<int, T + NBUF - 1>{});
 #endif
   };
   auto next_panel = [&](auto IC) -> unsigned {
     constexpr int I = decltype(IC)::value;
-    if constexpr (I % PSTEP == 0) step_sync(std::integral_constant<int, I / PSTEP>{});
-    return pan_lds + ((I / PSTEP) % TB_NBUF) * SLOT_BYTES + (I % PSTEP) * TB_PANEL_BYTES;
+    step_sync(IC);
+    return pan_lds + (I % TB_NBUF) * SLOT_BYTES;
   };
 
-  if (issuer) tb_static_for<0, NBUF - 1>([&](auto TC) { dma_step(TC); });
+  tb_static_for<0, NBUF - 1>([&](auto TC) { dma_step(TC); });
   for (int i = t; i < TC_N; i += NTHREADS) cst[i] = a.consts[i];
   if (MODE && t < 256) ksm[t] = a.ksum[(size_t)b * 256 + t];
-  if constexpr (LOADERS > 0) {
-    if (wave >= WAVES) {  // a loader wave: the barrier sequence of the computing waves, nothing else
-      tb_static_for<0, SCH::NPAN / PSTEP>([&](auto TC) { step_sync(TC); });
-      return;
-    }
-  }
 
   // ---- X: the input rows, split (mode 0: hidden; mode 1: D)
   half8 xh[8], xl[8];
@@ -862,6 +853,346 @@ __global__ __launch_bounds__((WAVES + LOADERS) * 64, 2) void token_block_kernel(
   if (blockIdx.x < 512)
     for (int i = lane; i < TB_NSTAMP; i += 64) st_base[i] = st_lds[wave][i];
 #endif
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The layer tail (mode 0) of the 197-token layers: output channels dealt to eight waves per tile.
+//
+// token_block_kernel gives a wave 16 tokens and ALL output channels: a launch takes one wave's serial chain of 1920 MFMAs + every row
+// epilogue on 64 values per lane, behind 56 weight panels that go L2 -> LDS ring -> fragment reads with a workgroup barrier per step,
+// whatever the number of workgroups -- and these launches have one small workgroup per CU.  Here a workgroup of eight waves (two per
+// SIMD) owns TT x 16 tokens and wave w computes ALL tokens of the tile for its own 1/8 of the output channels of every product:
+//     lin:  out channels 32 w .. 32 w + 31                       = panel w of the linear part            (K = 256)
+//     exp:  hidden channels 32 e .. 32 e + 31, e = 8 hf + w      = expand panel e & 3 of chunk e >> 2    (K = 256; hf = 0, 1: two halves)
+//     sq:   out channels 32 w .. 32 w + 31 over all 512 hidden   = squeeze panel w of the chunks 0 .. 3  (4 x K = 128, ascending)
+//   * weights never touch LDS: a wave reads the A fragments of its own 32 rows from the packed image (the XOR-swizzled panels of
+//     tb_pack_kernel, unchanged) straight into a register ring D k-steps ahead of the MFMAs; the ring runs on across the epilogues and
+//     barriers (one stream of 40 k-steps per wave).  Per load instruction a row's four chunks are one aligned 64-byte segment, and the
+//     k-steps 2 j, 2 j + 1 share their 128-byte lines.
+//   * activations live in LDS as fp16 hi / lo in B-fragment order -- block (k-step, plane, token tile) = 1 KiB, lane l's 16 bytes at
+//     16 l, so that writes and ds_read_b128 are linear -- written once by the epilogue that produces them (wave w's 32 channels ARE
+//     k-step w of the next product), read by all eight waves: y 16 KiB per token tile, and one buffer of the same size that holds the
+//     split input rows and then the two 256-wide halves of the FFN hidden row.
+//   * a row statistic that needs all 256 channels is exchanged through LDS: per-wave partials red[w][token], one barrier, every lane
+//     sums the eight partials in WAVE ORDER.  Five exchanges (LayerNorm mean / variance twice, the row maximum that fixes y's split
+//     scale) + five publishing barriers = ten barriers per launch instead of 28 ring steps.  The hidden row keeps its pack-time scale.
+// A token is one MFMA column: its result depends on its own row only -- not on M, its place in the tile, TT or its neighbours.
+// Same arithmetic class as token_block_kernel (fp16 x3, fp32 accumulate, power-of-two scales undone exactly); the second residual adds
+// y rebuilt from its hi + lo halves.
+template <int G>
+struct TtStep {  // k-step G (0 .. 39) of a wave's weight stream
+  static constexpr bool sq = (G >= 16 && G < 24) || G >= 32;
+  static constexpr int KS = sq ? 4 : 8;
+  static constexpr int S = sq ? (G & 3) : (G & 7);                 // k-step inside its panel
+  static constexpr int P = G < 8 ? 0 : G < 16 ? 1 : G < 24 ? 3 + ((G - 16) >> 2) : G < 32 ? 2 : 5 + ((G - 32) >> 2);  // pointer index
+};
+#define TT_NSTEP 40
+#define TT_D2 6  // k-steps of weight fragments in flight: 32-token tiles
+#define TT_D4 3  //                                          64-token tiles (4: 246 registers, 34.3 against 34.0 us -- no gain)
+#define TT_LDS_BYTES(TT) ((TT) * (32768 + 25 * 16 * 4))
+
+template <int TT, int D, bool HALF>
+__global__ __launch_bounds__(512) void token_tail_kernel(TbArgs a) {
+  constexpr int NTOK = 16 * TT, ACT = TT * 16384, RPW = NTOK / 8;
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+  unsigned char* yb = lds;                                  // y
+  unsigned char* hb = lds + ACT;                            // the split input rows, then the hidden row's halves
+  float* red = reinterpret_cast<float*>(lds + 2 * ACT);     // [3][8][NTOK] partial row statistics
+  float* sxs = red + 3 * 8 * NTOK;                          // [NTOK] split scale of the input rows
+  const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6), fr = lane & 15, fg = lane >> 4;
+  const long tile0 = (long)blockIdx.x * NTOK;
+  const float* cst = a.consts;
+  // LDS addresses as one lane-dependent base + immediate offsets; the bases are made opaque, or the compiler rebuilds every address of
+  // the unrolled stream in a register of its own (and spills them)
+  typedef __attribute__((address_space(3))) unsigned char lds_u8;
+  typedef __attribute__((address_space(3))) float lds_f32;
+  typedef __attribute__((address_space(3))) half8 lds_h8;
+  typedef __attribute__((address_space(3))) tb_u32x4 lds_u4;
+  lds_u8* ybl = (lds_u8*)yb + lane * 16;
+  lds_u8* hbl = (lds_u8*)hb + lane * 16;
+  lds_f32* redl = (lds_f32*)red + fr;
+  asm volatile("" : "+v"(ybl), "+v"(hbl), "+v"(redl));
+  auto row_of = [&](int tok) -> long { return tile0 + tok < a.M ? tile0 + tok : a.M - 1; };
+
+  // ---- requests first: this wave's input rows (whole rows: the row maximum needs no exchange) and its residual slices
+  float4 xv[RPW];
+#pragma unroll
+  for (int i = 0; i < RPW; ++i) xv[i] = *reinterpret_cast<const float4*>(a.in + (size_t)row_of(wave * RPW + i) * 256 + lane * 4);
+  f32x4 rv[TT][2];
+#pragma unroll
+  for (int tt = 0; tt < TT; ++tt)
+#pragma unroll
+    for (int rt = 0; rt < 2; ++rt)
+      rv[tt][rt] = *reinterpret_cast<const f32x4*>(a.resid + (size_t)row_of(16 * tt + fr) * 256 + 32 * wave + 16 * rt + 4 * fg);
+
+  // ---- the weight stream: pointers of this wave's panels, the lane part of a fragment address (see TbChunk), a ring of D + 1 k-steps
+  // (buffer loads: one descriptor over the image, the panel in the scalar offset, the lane part in the 32-bit vector offset -- and a
+  // fragment address outside the image would read zeros instead of faulting)
+  const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(a.wimg), 0, TB_IMAGE_BYTES(0), 0x00020000);
+  constexpr unsigned chunk0 = 8 * TB_P256;
+  const unsigned wp[7] = {(unsigned)wave * TB_P256,
+                          chunk0 + (unsigned)(wave >> 2) * TB_CHUNK_BYTES + (unsigned)(wave & 3) * TB_P256,
+                          chunk0 + (unsigned)(2 + (wave >> 2)) * TB_CHUNK_BYTES + (unsigned)(wave & 3) * TB_P256,
+                          chunk0 + 0 * TB_CHUNK_BYTES + 4 * TB_P256 + (unsigned)wave * TB_P128,
+                          chunk0 + 1 * TB_CHUNK_BYTES + 4 * TB_P256 + (unsigned)wave * TB_P128,
+                          chunk0 + 2 * TB_CHUNK_BYTES + 4 * TB_P256 + (unsigned)wave * TB_P128,
+                          chunk0 + 3 * TB_CHUNK_BYTES + 4 * TB_P256 + (unsigned)wave * TB_P128};
+  unsigned o8[4], o4[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    o8[q] = fr * TB_ROWB(8) + (((4 * q + fg) ^ fr) << 4);
+    o4[q] = fr * TB_ROWB(4) + (((4 * q + fg) ^ fr) << 4);
+  }
+  tb_u32x4 ar[D + 1][4];
+  auto wload = [&](auto GC) {
+    constexpr int G = decltype(GC)::value;
+    if constexpr (G < TT_NSTEP) {
+      typedef TtStep<G> ST;
+      typedef TbChunk<ST::KS, 0, ST::S> H;
+      typedef TbChunk<ST::KS, 1, ST::S> L;
+      constexpr int R1 = 16 * TB_ROWB(ST::KS);
+      const unsigned o = ST::KS == 8 ? o8[H::q] : o4[H::q];
+      tb_u32x4* f = ar[G % (D + 1)];
+      f[0] = __builtin_amdgcn_raw_buffer_load_b128(wr, o + H::off, wp[ST::P], 0);
+      f[1] = __builtin_amdgcn_raw_buffer_load_b128(wr, o + L::off, wp[ST::P], 0);
+      f[2] = __builtin_amdgcn_raw_buffer_load_b128(wr, o + H::off, wp[ST::P] + R1, 0);
+      f[3] = __builtin_amdgcn_raw_buffer_load_b128(wr, o + L::off, wp[ST::P] + R1, 0);
+    }
+  };
+  tb_static_for<0, D>([&](auto GC) { wload(GC); });
+
+  // NS k-steps starting at stream step G0: acc[rt][tt] += W(rows 16 rt ..) . B(token tile tt); B fragments one step ahead
+  auto product = [&](auto G0C, auto NSC, f32x4 (&acc)[2][TT], const lds_u8* bbase) {
+    constexpr int G0 = decltype(G0C)::value, NS = decltype(NSC)::value;
+    half8 bq[2][TT][2];
+    auto bload = [&](int s, half8 (&b)[TT][2]) {
+#pragma unroll
+      for (int tt = 0; tt < TT; ++tt) {
+        b[tt][0] = *reinterpret_cast<const lds_h8*>(bbase + ((s * 2 + 0) * TT + tt) * 1024);
+        b[tt][1] = *reinterpret_cast<const lds_h8*>(bbase + ((s * 2 + 1) * TT + tt) * 1024);
+      }
+    };
+    bload(0, bq[0]);
+    tb_static_for<0, NS>([&](auto SC) {
+      constexpr int S = decltype(SC)::value, G = G0 + S;
+      wload(std::integral_constant<int, G + D>{});
+      if constexpr (S + 1 < NS) bload(S + 1, bq[(S + 1) & 1]);
+      __builtin_amdgcn_sched_barrier(0);
+      const tb_u32x4* f = ar[G % (D + 1)];
+      const half8 ah[2] = {__builtin_bit_cast(half8, f[0]), __builtin_bit_cast(half8, f[2])};
+      const half8 al[2] = {__builtin_bit_cast(half8, f[1]), __builtin_bit_cast(half8, f[3])};
+      const half8(&b)[TT][2] = bq[S & 1];
+      if constexpr (!HALF) {  // matmul mode 2 keeps the hi . hi product only
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+          for (int tt = 0; tt < TT; ++tt) acc[rt][tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[rt], b[tt][0], acc[rt][tt], 0, 0, 0);
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+          for (int tt = 0; tt < TT; ++tt) acc[rt][tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[rt], b[tt][1], acc[rt][tt], 0, 0, 0);
+      }
+#pragma unroll
+      for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+        for (int tt = 0; tt < TT; ++tt) acc[rt][tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[rt], b[tt][0], acc[rt][tt], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+    });
+  };
+  auto zero = [&](f32x4 (&acc)[2][TT]) {
+#pragma unroll
+    for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+      for (int tt = 0; tt < TT; ++tt) acc[rt][tt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  };
+  // row statistics over all channels: this wave's partial per token (in p) -> the total, the eight partials combined in wave order
+  auto xsum = [&](float (&p)[TT], int k) {  // k: which of the three buffers
+    lds_f32* buf = redl + k * 8 * NTOK;
+#pragma unroll
+    for (int tt = 0; tt < TT; ++tt) {
+      const float s = tok_sum(p[tt]);
+      if (fg == 0) buf[wave * NTOK + 16 * tt] = s;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int tt = 0; tt < TT; ++tt) {
+      float s = buf[16 * tt];
+#pragma unroll
+      for (int w = 1; w < 8; ++w) s += buf[w * NTOK + 16 * tt];
+      p[tt] = s;
+    }
+  };
+  auto xmax = [&](float (&p)[TT], int k) {
+    lds_f32* buf = redl + k * 8 * NTOK;
+#pragma unroll
+    for (int tt = 0; tt < TT; ++tt) {
+      const float s = tok_max(p[tt]);
+      if (fg == 0) buf[wave * NTOK + 16 * tt] = s;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int tt = 0; tt < TT; ++tt) {
+      float s = buf[16 * tt];
+#pragma unroll
+      for (int w = 1; w < 8; ++w) s = fmaxf(s, buf[w * NTOK + 16 * tt]);
+      p[tt] = s;
+    }
+  };
+  // LayerNorm of v (this wave's 32 channels of every token) over the token's 256 channels
+  auto layernorm = [&](f32x4 (&v)[2][TT], int goff, int boff) {
+    float s[TT], q[TT];
+#pragma unroll
+    for (int tt = 0; tt < TT; ++tt)
+      s[tt] = ((v[0][tt][0] + v[0][tt][1]) + (v[0][tt][2] + v[0][tt][3])) + ((v[1][tt][0] + v[1][tt][1]) + (v[1][tt][2] + v[1][tt][3]));
+    xsum(s, 0);
+#pragma unroll
+    for (int tt = 0; tt < TT; ++tt) {
+      const float mean = s[tt] * (1.0f / 256.0f);
+      q[tt] = 0.f;
+#pragma unroll
+      for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          v[rt][tt][r] -= mean;
+          q[tt] += v[rt][tt][r] * v[rt][tt][r];
+        }
+    }
+    xsum(q, 1);
+#pragma unroll
+    for (int rt = 0; rt < 2; ++rt) {
+      const float4 gg = *reinterpret_cast<const float4*>(cst + goff + 32 * wave + 16 * rt + 4 * fg);
+      const float4 bb = *reinterpret_cast<const float4*>(cst + boff + 32 * wave + 16 * rt + 4 * fg);
+#pragma unroll
+      for (int tt = 0; tt < TT; ++tt) {
+        const float rstd = 1.0f / sqrtf(q[tt] * (1.0f / 256.0f) + a.eps);
+        v[rt][tt][0] = v[rt][tt][0] * rstd * gg.x + bb.x;
+        v[rt][tt][1] = v[rt][tt][1] * rstd * gg.y + bb.y;
+        v[rt][tt][2] = v[rt][tt][2] * rstd * gg.z + bb.z;
+        v[rt][tt][3] = v[rt][tt][3] * rstd * gg.w + bb.w;
+      }
+    }
+  };
+  // this wave's 32 channels of token tile tt (already scaled) -> k-step `ks` of an activation buffer
+  auto put = [&](lds_u8* buf, int ks, int tt, const f32x4& v0, const f32x4& v1) {
+    unsigned h0, l0, h1, l1, h2, l2, h3, l3;
+    sam6d_split2_f16(v0[0], v0[1], h0, l0);
+    sam6d_split2_f16(v0[2], v0[3], h1, l1);
+    sam6d_split2_f16(v1[0], v1[1], h2, l2);
+    sam6d_split2_f16(v1[2], v1[3], h3, l3);
+    *reinterpret_cast<lds_u4*>(buf + ((ks * 2 + 0) * TT + tt) * 1024) = tb_u32x4{h0, h1, h2, h3};
+    *reinterpret_cast<lds_u4*>(buf + ((ks * 2 + 1) * TT + tt) * 1024) = tb_u32x4{l0, l1, l2, l3};
+  };
+
+  // ---- the input rows, split: lane l holds channels 4 l .. 4 l + 3 = k-step l >> 3, lane group l & 3, slots 4 ((l >> 2) & 1) ..
+#pragma unroll
+  for (int i = 0; i < RPW; ++i) {
+    const int tok = wave * RPW + i;
+    const float m = wave_max_dpp(fmaxf(fmaxf(fabsf(xv[i].x), fabsf(xv[i].y)), fmaxf(fabsf(xv[i].z), fabsf(xv[i].w))));
+    const float sx = pow2_scale_for(m);
+    if (lane == 0) sxs[tok] = sx;
+    unsigned h0, l0, h1, l1;
+    sam6d_split2_f16(xv[i].x * sx, xv[i].y * sx, h0, l0);
+    sam6d_split2_f16(xv[i].z * sx, xv[i].w * sx, h1, l1);
+    unsigned char* dst = hb + (size_t)(tok >> 4) * 1024 + ((lane & 3) * 16 + (tok & 15)) * 16 + 8 * ((lane >> 2) & 1);
+    *reinterpret_cast<tb_u2*>(dst + ((lane >> 3) * 2 + 0) * TT * 1024) = tb_u2{h0, h1};
+    *reinterpret_cast<tb_u2*>(dst + ((lane >> 3) * 2 + 1) * TT * 1024) = tb_u2{l0, l1};
+  }
+  __syncthreads();
+
+  // ---- y = LayerNorm(hidden Wlin^T + b + x)
+  float sy[TT];
+  {
+    f32x4 y[2][TT];
+    zero(y);
+    product(std::integral_constant<int, 0>{}, std::integral_constant<int, 8>{}, y, hbl);
+    const float iw = cst[TC_SC + 1];
+#pragma unroll
+    for (int rt = 0; rt < 2; ++rt) {
+      const float4 bl = *reinterpret_cast<const float4*>(cst + TC_BLIN + 32 * wave + 16 * rt + 4 * fg);
+#pragma unroll
+      for (int tt = 0; tt < TT; ++tt) {
+        const float inv = iw * (1.0f / sxs[16 * tt + fr]);
+        y[rt][tt][0] = (y[rt][tt][0] * inv + bl.x) + rv[tt][rt][0];
+        y[rt][tt][1] = (y[rt][tt][1] * inv + bl.y) + rv[tt][rt][1];
+        y[rt][tt][2] = (y[rt][tt][2] * inv + bl.z) + rv[tt][rt][2];
+        y[rt][tt][3] = (y[rt][tt][3] * inv + bl.w) + rv[tt][rt][3];
+      }
+    }
+    layernorm(y, TC_G1, TC_BE1);
+#pragma unroll
+    for (int tt = 0; tt < TT; ++tt) {
+      float m = 0.f;
+#pragma unroll
+      for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) m = fmaxf(m, fabsf(y[rt][tt][r]));
+      sy[tt] = m;
+    }
+    xmax(sy, 2);
+#pragma unroll
+    for (int tt = 0; tt < TT; ++tt) {
+      const float sc = sy[tt] = pow2_scale_for(sy[tt]);
+      put(ybl, wave, tt, f32x4{y[0][tt][0] * sc, y[0][tt][1] * sc, y[0][tt][2] * sc, y[0][tt][3] * sc},
+          f32x4{y[1][tt][0] * sc, y[1][tt][1] * sc, y[1][tt][2] * sc, y[1][tt][3] * sc});
+    }
+    __syncthreads();
+  }
+
+  // ---- out = LayerNorm(relu(y Wexp^T + b) Wsq^T + b + y), the hidden row in two halves of 256 channels
+  f32x4 acc[2][TT];
+  zero(acc);
+  tb_static_for<0, 2>([&](auto HC) {
+    constexpr int hf = decltype(HC)::value;
+    f32x4 ha[2][TT];
+    zero(ha);
+    product(std::integral_constant<int, 8 + 16 * hf>{}, std::integral_constant<int, 8>{}, ha, ybl);
+    const float ie = cst[TC_SC + 2], sh = cst[TC_SC + 4];
+    if constexpr (hf == 1) __syncthreads();  // every wave has left the first half of the hidden row
+#pragma unroll
+    for (int tt = 0; tt < TT; ++tt) {
+      const float inv = ie * (1.0f / sy[tt]);
+      f32x4 hv[2];
+#pragma unroll
+      for (int rt = 0; rt < 2; ++rt) {
+        const float4 be = *reinterpret_cast<const float4*>(cst + TC_BEXP + 32 * (8 * hf + wave) + 16 * rt + 4 * fg);
+        const float bb[4] = {be.x, be.y, be.z, be.w};
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float v = ha[rt][tt][r] * inv + bb[r];
+          hv[rt][r] = (v > 0.f ? v : 0.f) * sh;
+        }
+      }
+      put(hbl, wave, tt, hv[0], hv[1]);
+    }
+    __syncthreads();
+    product(std::integral_constant<int, 16 + 16 * hf>{}, std::integral_constant<int, 8>{}, acc, hbl);
+  });
+  {
+    const float inv = cst[TC_SC + 3];
+#pragma unroll
+    for (int rt = 0; rt < 2; ++rt) {
+      const float4 bs = *reinterpret_cast<const float4*>(cst + TC_BSQ + 32 * wave + 16 * rt + 4 * fg);
+#pragma unroll
+      for (int tt = 0; tt < TT; ++tt) {
+        // y = (hi + lo) / scale, read back from this lane's own fragment chunk (22 significand bits, as in token_block_kernel)
+        const half8 yh = *reinterpret_cast<const lds_h8*>(ybl + ((wave * 2 + 0) * TT + tt) * 1024);
+        const half8 yl = *reinterpret_cast<const lds_h8*>(ybl + ((wave * 2 + 1) * TT + tt) * 1024);
+        const float isy = 1.0f / sy[tt];
+        const float bb[4] = {bs.x, bs.y, bs.z, bs.w};
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[rt][tt][r] = (acc[rt][tt][r] * inv + bb[r]) + ((float)yh[4 * rt + r] + (float)yl[4 * rt + r]) * isy;
+      }
+    }
+    layernorm(acc, TC_G2, TC_BE2);
+  }
+#pragma unroll
+  for (int tt = 0; tt < TT; ++tt)
+    if (tile0 + 16 * tt + fr < a.M) {
+      float* o = a.out + (size_t)(tile0 + 16 * tt + fr) * 256 + 32 * wave + 4 * fg;
+#pragma unroll
+      for (int rt = 0; rt < 2; ++rt)
+        *reinterpret_cast<float4*>(o + 16 * rt) = make_float4(acc[rt][tt][0], acc[rt][tt][1], acc[rt][tt][2], acc[rt][tt][3]);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1233,8 +1564,8 @@ extern "C" int sam6d_linear_norm_split(const float* x, const void* wimage, const
 // ---------------------------------------------------------------------------------------------------------------------
 // y = x W^T + b for a few thousand 256-channel token rows (the sparse-token projections: in_proj / out_proj of the coarse stage,
 // [proj_k; proj_v] of the dense layers' memory tokens -- PEM/model/coarse_point_matching.py:35-38, 61; PEM/model/transformer.py:556-558):
-// 197 workgroups of 64 rows on the panel machinery of token_block_kernel (four computing + four loader waves, two panels per ring
-// slot) instead of the generic GEMM's 64 x 64 tiles, whose ~1600 single-k-chunk workgroups are launch-latency-bound at this size.
+// 197 workgroups of 64 rows on panel machinery like token_block_kernel's, with loader waves of its own (four computing + four loader
+// waves, two panels per ring slot) instead of the generic GEMM's 64 x 64 tiles, whose ~1600 single-k-chunk workgroups are launch-latency-bound at this size.
 // Rows may be strided per cloud on both sides (row R = cloud R / rpb, token R % rpb): the bg slot of a token buffer is skipped in place.
 struct RlArgs {
   const float* x;
@@ -1364,11 +1695,10 @@ extern "C" int sam6d_rows_linear(const float* x, const void* wimage, int npanels
 }
 
 #define TB_LDS_BYTES(NBUF) ((NBUF) * TB_PANEL_BYTES + (TC_N + 256) * 4)
-#define TB_LDS_BYTES2(NBUF, PSTEP) ((NBUF) * (PSTEP) * TB_PANEL_BYTES + (TC_N + 256) * 4)
 
 // The launched shapes: the dense layer (sam6d_linattn_layer) runs 4 waves x 16 tokens with a 2-slot panel ring (77 KB of LDS: two
 // workgroups per CU, which run out of step, so one's row epilogues overlap the other's MFMAs); the 197-token layers (sam6d_token_block)
-// run 4 (or 2) computing + 4 loader waves with two panels per ring slot.
+// run token_tail_kernel: eight waves per 32- or 64-token tile, output channels dealt to the waves.
 
 template <class K>
 static int tb_attr(K kernel, int bytes) {
@@ -1384,8 +1714,10 @@ static int tb_set_attr() {
   static unsigned long long done0 = 0;
   if (sam6d_first_use_on_device(&done0)) {
     int rc = tb_attr(token_block_kernel<1, 4, 2>, TB_LDS_BYTES(2));
-    if (!rc) rc = tb_attr(token_block_kernel<0, 4, 2, TB_FD, 4, 2>, TB_LDS_BYTES2(2, 2));
-    if (!rc) rc = tb_attr(token_block_kernel<0, 2, 2, TB_FD, 4, 2>, TB_LDS_BYTES2(2, 2));
+    if (!rc) rc = tb_attr(token_tail_kernel<2, TT_D2, false>, TT_LDS_BYTES(2));
+    if (!rc) rc = tb_attr(token_tail_kernel<4, TT_D4, false>, TT_LDS_BYTES(4));
+    if (!rc) rc = tb_attr(token_tail_kernel<2, TT_D2, true>, TT_LDS_BYTES(2));
+    if (!rc) rc = tb_attr(token_tail_kernel<4, TT_D4, true>, TT_LDS_BYTES(4));
     if (rc) return rc;
     sam6d_setup_done_on_device(&done0);
   }
@@ -1401,11 +1733,11 @@ extern "C" int sam6d_token_block(const float* hidden, const float* x, const void
   if (rc) return rc;
   TbArgs a{hidden, x, out, (const unsigned char*)wimage, consts, nullptr, nullptr, nullptr, M, 0, 0, 0, eps,
            sam6d_half_for(1)};
-  // Round 4: 32-token workgroups (two computing waves) while they all fit the chip at once.  A wave's chain -- 56 weight panels through
-  // the LDS ring -- is what a launch takes whatever the number of workgroups; the 6304-row launches (the cross layers: 32 clouds x 197)
-  // filled 99 of the 256 CUs with four computing waves each, which contend for the LDS reads of every panel (4 x 32 KB per panel) and
-  // leave 157 CUs idle; with two computing waves per workgroup the same rows use 197 CUs and a panel is read twice, not four times.
-  // A token's arithmetic does not depend on the workgroup shape (everything is per 16-token wave), so the results are bit-identical.
+  // The tile shape is a function of M and the CU count only: 32-token tiles while they all fit the chip in one round (6304 rows = 197
+  // workgroups on 256 CUs), 64-token tiles beyond (12608 rows = 197 workgroups; each streams the weight image once, so 64 tokens halve
+  // the L2 bytes per token).  Measured at 12608 rows: 394 x 32 tokens 45.6 us (two 512-thread workgroups of 208 registers per lane do not
+  // share a CU, so 138 CUs run two tiles one after the other), 197 x 64 tokens 34.0 us.  A token's arithmetic does not depend on the
+  // shape (token_tail_kernel): bit-identical results either way.
   int dev_ = 0, cus = 256;
   if (hipGetDevice(&dev_) == hipSuccess) {
     static int cu_cache[SAM6D_MAX_DEVICES];
@@ -1414,12 +1746,12 @@ extern "C" int sam6d_token_block(const float* hidden, const float* x, const void
       cus = cu_cache[dev_];
     }
   }
-  if ((M + 31) / 32 <= cus)
-    hipLaunchKernelGGL((token_block_kernel<0, 2, 2, TB_FD, 4, 2>), dim3((unsigned)((M + 31) / 32)), dim3(384), TB_LDS_BYTES2(2, 2),
-                       (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL((token_block_kernel<0, 4, 2, TB_FD, 4, 2>), dim3((unsigned)((M + 63) / 64)), dim3(512), TB_LDS_BYTES2(2, 2),
-                       (hipStream_t)stream, a);
+  const bool small = (M + 31) / 32 <= cus;
+  const dim3 grid((unsigned)(small ? (M + 31) / 32 : (M + 63) / 64));
+  const int ldsb = small ? TT_LDS_BYTES(2) : TT_LDS_BYTES(4);
+  auto kernel = small ? (a.half ? token_tail_kernel<2, TT_D2, true> : token_tail_kernel<2, TT_D2, false>)
+                      : (a.half ? token_tail_kernel<4, TT_D4, true> : token_tail_kernel<4, TT_D4, false>);
+  hipLaunchKernelGGL(kernel, grid, dim3(512), ldsb, (hipStream_t)stream, a);
   SAM6D_LAUNCH_CHECK("token_block");
 }
 

@@ -1,5 +1,6 @@
 #!/bin/bash
-# timing-only copies of the library with one ingredient of token_block_kernel's panel loop removed (results are garbage):
+# timing-only copies of the library with one ingredient of token_block_kernel's panel loop removed (results are garbage; the dense
+# layer only -- the 197-token layer tail runs token_tail_kernel, which has no panel loop):
 # scratch/abl/<noread|nodma|nobar|noreaddma>/libsam6d_hip.so
 set -e
 cd "$(dirname "$0")/.."

@@ -20,7 +20,7 @@ def find(prefix):
 
 sel = [("rpe_score_kernel", "rpe_score_kernel<2, true>", "one RPE layer over 64 clouds: indices + positions read, geometric score term written", 12608 * 197 * (16 + 4) + 12608 * (1024 + 128) * 4 + 12608 * 4 * 200 * 4),
        ("token_block_kernel<1> (sam6d_linattn_layer)", "token_block_kernel<1,", "one dense LinearTransformerLayer over 64 clouds x 2048 tokens: D read once + D' written once + kv / weight images", 273842176),
-       ("token_block_kernel<0> (sam6d_token_block, 12608 / 6304 rows)", "token_block_kernel<0,", "layer tail", None),
+       ("token_block_kernel<0> (sam6d_token_block, 12608 / 6304 rows; token_tail_kernel in later builds)", "token_block_kernel<0,", "layer tail", None),
        ("xattn_kernel<true> (sam6d_cross_attention_kv)", "xattn_kernel<true>", "cross attention incl. k / v projection", None),
        ("sattn_kernel (sam6d_rpe_self_attention)", "sattn_kernel", "q.k^T + G, softmax, P.v per (cloud, head): q | k | v rows and the score term read, hidden written", 12608 * (768 + 800 + 256) * 4),
        ("rpe_front_kernel", "rpe_front_kernel", "qkv + folds", None), ("rpe_listed_kernel", "rpe_listed_kernel", "listed pairs", None),
