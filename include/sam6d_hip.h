@@ -597,6 +597,40 @@ int sam6d_vit_attention(const float* qkv, float* out, int B, int n, void* stream
  * choose (B,N) i64 pixel indices -> out (B,N,256).  An index outside [0, 224*224) yields a NaN row. */
 int sam6d_vit_upsample_gather(const float* U, const long long* choose, float* out, int B, int N, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * ISM's proposal descriptors: CropResizePad and the DINOv2 ViT-L/14 (ISM/model/dinov2.py:115-326).  The residual stream is
+ * X (N*257, 1024) f32 row-major, row 0 of each image the cls token; the dense projections are sam6d_gemm_nt / _w16 (fc1 with act 2,
+ * LayerScale folded into the proj / fc2 weights by the caller).  (New entries only: no existing signature or buffer layout changed,
+ * so SAM6D_ABI_VERSION stays.)
+ * ---------------------------------------------------------------------------------------------------------- */
+
+/* process_rgb_proposals + process_masks_proposals (ISM/model/dinov2.py:160-173, :221-232) through CropResizePad(224)
+ * (ISM/utils/bbox_utils.py:89-126) for all N proposals in one launch: ToTensor + Normalize(mean 0.485/0.456/0.406, std
+ * 0.229/0.224/0.225) of image (H,W,3) u8, times masks[i] (N,H,W) f32, the crop boxes[i] = (x1, y1, x2, y2) i64 with exclusive ends,
+ * F.interpolate(scale_factor = 224 / max(box side), formed as torch does: fl32(1 / side) * 224) in nearest mode, zero padding to 224 x 224 (top / left get
+ * max((224 - side) // 2, 0)) and the second interpolate.  out_rgb (N,3,224,224) f32 and out_mask (N,224,224) f32 (the same gather
+ * of the mask); either may be NULL, and image too when out_rgb is.  Bit-exact: every source index is the one torch computes.  Boxes are expected inside the image
+ * (they are clipped to it; Python's negative-index wrap is not reproduced); a box whose resized crop is empty, which raises in the
+ * reference, gives an all-zero crop.  A square resized crop has side 223 or 224 for every box side, and the second interpolate of
+ * side 223 gives 224 pixels in torch too, so no box makes the output size differ from the reference's.  N <= 65535. */
+int sam6d_dino_crop_proposals(const unsigned char* image, const float* masks, const long long* boxes, int N, int H, int W,
+                              float* out_rgb, float* out_mask, void* stream);
+/* PatchEmbed + cls token of prepare_tokens_with_masks (ISM/model/vision_transformer.py:209-216): images (B,3,224,224) -> A (B*256, 608),
+ * row 16 py + px = the 14 x 14 patch in the Conv2d weight's (c, kh, kw) order (588 values) followed by 20 zeros (K padded to 19
+ * k-steps of 32; the packed weight's columns 588..607 are zero too), and the cls rows X[257 b] = cls_token + pos_embed[0]
+ * (1024 floats each; pos_embed already interpolated to the 16 x 16 grid). */
+int sam6d_dino_patch_rows(const float* img, const float* cls_token, const float* pos_embed, float* A, float* X, int B, void* stream);
+/* nn.LayerNorm(1024, eps) over `rows` rows of each of nimg images (ISM/model/layers/block.py:82-98 norm1 / norm2,
+ * vision_transformer.py:259-265 norm): row r of image b is x + b sx + r ldx -> y + b sy + r ldy (floats; strides multiples of 4,
+ * pointers 16-byte aligned), so the final norm writes x_norm_clstoken and x_norm_patchtokens straight into their own tensors. */
+int sam6d_dino_layernorm1024(const float* x, const float* gamma, const float* beta, float* y, int nimg, int rows, long ldx, long sx,
+                             long ldy, long sy, float eps, void* stream);
+/* Multi-head self-attention of a DINOv2 ViT-L block (ISM/model/layers/attention.py:49-62): qkv (B*n, 3072) = [q | k | v], head h at
+ * columns 64h .. 64h+63 of each part -> out (B*n, 1024) = softmax(q_h k_h^T / 8) v_h per head, 16 heads, in
+ * x.transpose(1,2).reshape(B,n,1024) order.  n <= 272 (the 257 tokens of a 224 x 224 image are not padded: the key tail is masked in
+ * the kernel).  fp16 x3 split MFMA products with power-of-two operand scales (fp32 softmax); the probabilities stay on chip. */
+int sam6d_dino_attention(const float* qkv, float* out, int B, int n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

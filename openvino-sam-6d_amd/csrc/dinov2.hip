@@ -1,0 +1,423 @@
+// ISM's proposal descriptors: CropResizePad and the DINOv2 ViT-L/14 around the library's GEMMs
+// (ISM/model/dinov2.py:115-326 CustomDINOv2, ISM/utils/bbox_utils.py:89-126 CropResizePad, ISM/model/vision_transformer.py:179-266,
+// ISM/model/layers/attention.py, layers/block.py, layers/layer_scale.py):
+//   crops       (H,W,3) u8 image + (N,H,W) masks + (N,4) boxes -> (N,3,224,224) normalised masked crops and (N,224,224) masks in one
+//               launch: ToTensor + Normalize, times the mask, crop, nearest resize by 224 / max(box side), zero padding, second resize.
+//               A pure gather; every source index is the one torch computes, so the result is bit-exact.
+//   patch rows  (N,3,224,224) -> A (N*256, 608): 588 = 3 x 14 x 14 values in the Conv2d weight's (c, kh, kw) order, then 20 zeros (K is
+//               padded to a multiple of 32 so that every GEMM route, the whole-tile one included, applies; the weight's columns 588..607
+//               are zero too), plus the cls rows cls_token + pos[0] of the residual stream X (N*257, 1024)
+//   LayerNorm   over 1024 channels, rows addressed per image as sam6d_vit_layernorm768 does (the final norm writes x_norm_clstoken and
+//               x_norm_patchtokens straight into their own tensors)
+//   attention   257 tokens, 16 heads of 64: one workgroup per (image, head); see dino_attention_kernel
+// The dense projections are sam6d_gemm_nt / _w16 (fc1 with the erf-GELU epilogue, proj / fc2 with the in-place residual; LayerScale is
+// folded into their weights at pack time).
+#include "common.h"
+#include "../../include/sam6d_hip.h"
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+typedef _Float16 half4 __attribute__((ext_vector_type(4)));
+
+#define DN_C 1024
+#define DN_IMG 224
+#define DN_PATCH 14
+#define DN_GRID 16
+#define DN_PATCHES 256
+#define DN_TOK 257
+#define DN_K 588    // 3 * 14 * 14
+#define DN_KPAD 608 // 19 k-steps of 32
+
+// ---- proposal crops -------------------------------------------------------------------------------------------------------------
+// F.interpolate(x, scale_factor = s) in the default nearest mode: output size floor(in * s) in double, source index
+// min((int) floorf(dst * (float)(1 / s)), in - 1) (ATen upsample_nearest with the scale it was given).
+__device__ __forceinline__ int dn_nearest(int dst, float scale, int in) {
+  const int s = (int)floorf((float)dst * scale);
+  return s < in - 1 ? s : in - 1;
+}
+
+__global__ __launch_bounds__(256) void dino_crop_kernel(const unsigned char* __restrict__ img, const float* __restrict__ masks,
+                                                        const long long* __restrict__ boxes, int H, int W,
+                                                        float* __restrict__ out_rgb, float* __restrict__ out_mask) {
+  const int i = blockIdx.y;
+  const int pix = blockIdx.x * 256 + threadIdx.x;
+  if (pix >= DN_IMG * DN_IMG) return;
+  const int Y = pix / DN_IMG, X = pix % DN_IMG;
+  const long long bx1 = boxes[4 * i], by1 = boxes[4 * i + 1], bx2 = boxes[4 * i + 2], by2 = boxes[4 * i + 3];
+  // scale_factor = 224 / max(box side) of the (unclamped) box sizes, bbox_utils.py:99-100: a Python number over a tensor, which torch
+  // evaluates as tensor.reciprocal() * 224 in fp32 -- two roundings, not one division (for side 3: 74.66667175, not 74.66666412)
+  const long long side = (bx2 - bx1) > (by2 - by1) ? (bx2 - bx1) : (by2 - by1);
+  const float sf = (1.0f / (float)side) * 224.0f;
+  // the slice image[:, y1:y2, x1:x2] (bbox_utils.py:104) ends at the image border
+  const int x1 = (int)(bx1 < 0 ? 0 : (bx1 > W ? W : bx1)), x2 = (int)(bx2 < 0 ? 0 : (bx2 > W ? W : bx2));
+  const int y1 = (int)(by1 < 0 ? 0 : (by1 > H ? H : by1)), y2 = (int)(by2 < 0 ? 0 : (by2 > H ? H : by2));
+  const int cw = x2 - x1, ch = y2 - y1;
+  int rw = 0, rh = 0;
+  if (side > 0 && cw > 0 && ch > 0) {
+    rw = (int)floor((double)cw * (double)sf);
+    rh = (int)floor((double)ch * (double)sf);
+  }
+  float r = 0.f, g = 0.f, b = 0.f, m = 0.f;
+  if (rw > 0 && rh > 0 && rw <= DN_IMG && rh <= DN_IMG) {  // (an empty resized crop raises in the reference: all padding here)
+    const float scale1 = (float)(1.0 / (double)sf);
+    int py = Y, px = X, pad_t = 0, pad_l = 0;
+    if (rw == rh) {
+      // square after the resize: no padding (bbox_utils.py:111); the second interpolate maps side rw -> 224.  rw is 223 or 224 for
+      // every box side (224 / side is good to 2 ulp), and torch sizes the second output as floor(223 * (224.0 / 223)) = 224, so the
+      // 224 pixels written here are the reference's (tests/test_dinov2_host.py checks both statements)
+      if (rw != DN_IMG) {
+        const float scale2 = (float)(1.0 / (224.0 / (double)rw));
+        py = dn_nearest(Y, scale2, rw);
+        px = dn_nearest(X, scale2, rw);
+      }
+    } else {
+      pad_t = (DN_IMG - rh) / 2;
+      pad_l = (DN_IMG - rw) / 2;
+    }
+    const int ry = py - pad_t, rx = px - pad_l;
+    if (ry >= 0 && ry < rh && rx >= 0 && rx < rw) {
+      const int sy = y1 + dn_nearest(ry, scale1, ch), sx = x1 + dn_nearest(rx, scale1, cw);
+      const size_t at = (size_t)sy * W + sx;
+      m = masks[(size_t)i * H * W + at];
+      if (out_rgb) {
+        const unsigned char* p = img + 3 * at;
+        // ToTensor (u8 / 255), Normalize ((x - mean) / std), times the mask: fp32, in torch's order (dinov2.py:144-149, 167-169)
+        r = (((float)p[0] / 255.0f) - 0.485f) / 0.229f * m;
+        g = (((float)p[1] / 255.0f) - 0.456f) / 0.224f * m;
+        b = (((float)p[2] / 255.0f) - 0.406f) / 0.225f * m;
+      }
+    }
+  }
+  if (out_rgb) {
+    float* o = out_rgb + (size_t)i * 3 * DN_IMG * DN_IMG + pix;
+    o[0] = r;
+    o[DN_IMG * DN_IMG] = g;
+    o[2 * DN_IMG * DN_IMG] = b;
+  }
+  if (out_mask) out_mask[(size_t)i * DN_IMG * DN_IMG + pix] = m;
+}
+
+extern "C" int sam6d_dino_crop_proposals(const unsigned char* image, const float* masks, const long long* boxes, int N, int H, int W,
+                                         float* out_rgb, float* out_mask, void* stream) {
+  SAM6D_REQUIRE(masks && boxes && (out_rgb || out_mask) && (image || !out_rgb), "dino_crop_proposals: null pointer");
+  SAM6D_REQUIRE(N >= 0 && N <= 65535, "dino_crop_proposals: N <= 65535 (got %d)", N);
+  SAM6D_REQUIRE(H > 0 && W > 0 && (long)H * W <= 2147483647L / 3, "dino_crop_proposals: bad image size %d x %d", H, W);
+  if (N == 0) return 0;
+  hipLaunchKernelGGL(dino_crop_kernel, dim3((DN_IMG * DN_IMG + 255) / 256, N), dim3(256), 0, (hipStream_t)stream, image, masks, boxes, H,
+                     W, out_rgb, out_mask);
+  SAM6D_LAUNCH_CHECK("dino_crop_proposals");
+}
+
+// ---- patch rows: workgroup (patch p, image b); p == 256 writes the image's cls row of X instead -----------------------------------
+__global__ __launch_bounds__(256) void dino_patch_rows_kernel(const float* __restrict__ img, const float* __restrict__ cls,
+                                                              const float* __restrict__ pos, float* __restrict__ A,
+                                                              float* __restrict__ X) {
+  const int p = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
+  if (p == DN_PATCHES) {
+    float* dst = X + (size_t)b * DN_TOK * DN_C;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) dst[t + 256 * u] = cls[t + 256 * u] + pos[t + 256 * u];
+    return;
+  }
+  const int py = p / DN_GRID, px = p % DN_GRID;
+  float* dst = A + ((size_t)b * DN_PATCHES + p) * DN_KPAD;
+  for (int col = t; col < DN_KPAD; col += 256) {
+    float v = 0.f;
+    if (col < DN_K) {
+      const int c = col / (DN_PATCH * DN_PATCH), k = col % (DN_PATCH * DN_PATCH), kh = k / DN_PATCH, kw = k % DN_PATCH;
+      v = img[(((size_t)b * 3 + c) * DN_IMG + py * DN_PATCH + kh) * DN_IMG + px * DN_PATCH + kw];
+    }
+    dst[col] = v;
+  }
+}
+
+extern "C" int sam6d_dino_patch_rows(const float* img, const float* cls_token, const float* pos_embed, float* A, float* X, int B,
+                                     void* stream) {
+  SAM6D_REQUIRE(img && cls_token && pos_embed && A && X && B >= 0, "dino_patch_rows: null pointer");
+  SAM6D_REQUIRE(B <= 65535, "dino_patch_rows: B <= 65535");
+  if (B == 0) return 0;
+  hipLaunchKernelGGL(dino_patch_rows_kernel, dim3(DN_PATCHES + 1, B), dim3(256), 0, (hipStream_t)stream, img, cls_token, pos_embed, A,
+                     X);
+  SAM6D_LAUNCH_CHECK("dino_patch_rows");
+}
+
+// ---- LayerNorm over 1024 channels: one wave per row, 16 floats per lane (four float4 at 4 lane + 256 u), two-pass mean / variance in
+// registers.  Row r of image b: x + b sx + r ldx -> y + b sy + r ldy, in floats (the row map of vit_layernorm768_kernel).
+__global__ __launch_bounds__(256) void dino_layernorm1024_kernel(const float* __restrict__ x, const float* __restrict__ g,
+                                                                 const float* __restrict__ be, float* __restrict__ y, long total,
+                                                                 int rows, long ldx, long sx, long ldy, long sy, float eps) {
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= total) return;
+  const int lane = threadIdx.x & 63;
+  const long b = row / rows, r = row % rows;
+  const float* src = x + b * sx + r * ldx;
+  float* dst = y + b * sy + r * ldy;
+  float4 v[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const float4*>(src + 4 * lane + 256 * u);
+  float s = 0.f;
+#pragma unroll
+  for (int u = 0; u < 4; ++u) s += (v[u].x + v[u].y) + (v[u].z + v[u].w);
+  const float mean = wave_sum_dpp(s) * (1.0f / DN_C);
+  float q = 0.f;
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    v[u].x -= mean; v[u].y -= mean; v[u].z -= mean; v[u].w -= mean;
+    q += (v[u].x * v[u].x + v[u].y * v[u].y) + (v[u].z * v[u].z + v[u].w * v[u].w);
+  }
+  const float rstd = 1.0f / sqrtf(wave_sum_dpp(q) * (1.0f / DN_C) + eps);
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int c = 4 * lane + 256 * u;
+    const float4 gg = *reinterpret_cast<const float4*>(g + c);
+    const float4 bb = *reinterpret_cast<const float4*>(be + c);
+    float4 o;
+    o.x = v[u].x * rstd * gg.x + bb.x;
+    o.y = v[u].y * rstd * gg.y + bb.y;
+    o.z = v[u].z * rstd * gg.z + bb.z;
+    o.w = v[u].w * rstd * gg.w + bb.w;
+    *reinterpret_cast<float4*>(dst + c) = o;
+  }
+}
+
+extern "C" int sam6d_dino_layernorm1024(const float* x, const float* gamma, const float* beta, float* y, int nimg, int rows, long ldx,
+                                        long sx, long ldy, long sy, float eps, void* stream) {
+  SAM6D_REQUIRE(x && gamma && beta && y, "dino_layernorm1024: null pointer");
+  SAM6D_REQUIRE(nimg >= 0 && rows >= 0 && ldx >= DN_C && ldy >= DN_C && sx >= 0 && sy >= 0, "dino_layernorm1024: bad sizes");
+  SAM6D_REQUIRE(((ldx | ldy | sx | sy) & 3) == 0 && ((((size_t)x) | ((size_t)y) | ((size_t)gamma) | ((size_t)beta)) & 15) == 0,
+                "dino_layernorm1024: strides must be multiples of 4 floats and pointers 16-byte aligned");
+  const long total = (long)nimg * rows;
+  if (total == 0) return 0;
+  SAM6D_REQUIRE((total + 3) / 4 < 2147483647L, "dino_layernorm1024: too many rows");
+  hipLaunchKernelGGL(dino_layernorm1024_kernel, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, gamma, beta,
+                     y, total, rows, ldx, sx, ldy, sy, eps);
+  SAM6D_LAUNCH_CHECK("dino_layernorm1024");
+}
+
+// ---- self-attention, up to 272 tokens, 16 heads of 64 ---------------------------------------------------------------------------
+// One workgroup (8 waves) per (image, head), the scheme of xattn.hip's sattn_kernel at 17 key tiles, as a kernel of its own: that
+// kernel's register plan (13 score tiles, 7 probability k-steps and the prefetched next group beside them) and its two-groups-per-wave
+// schedule are built around 208 keys; 272 keys need 17 tiles, 9 k-steps and up to three token groups per wave, and keeping one source
+// for both would have changed the code generated for the 197-token callers.  Here:
+//   k_h (272 x 64) and v_h^T (64 x 288) are cut ONCE into fp16 hi / lo images in LDS (power-of-two scale per image; rows / keys
+//   beyond n are zero), in plain row-major order with 16 bytes of padding per row (no swizzle);
+//   every 16-token group of a wave runs   S^T (keys x tok) = k_h . (q / 8)^T     17 tiles x 2 k-steps
+//                                         softmax over the lane's 68 values + 3 partner lanes, fp32, keys >= n masked to -inf
+//                                         out^T (64 x tok) = v_h^T . P^T         4 tiles x 9 k-steps
+//   on v_mfma_f32_16x16x32_f16 with three products per step (lo.hi, hi.lo, hi.hi).  The accumulator of S^T holds keys
+//   16 i + 4 g + r of the lane's own token, which is the B-operand layout of the second product when k-slot 8 g + e of step s stands
+//   for key 32 s + 16 (e >> 2) + 4 g + (e & 3): the probabilities never leave the registers.
+// The token count is not padded in HBM: 257 = 16 tiles + 1 key, the tail is masked here.
+#define DA_MAXN 272
+#define DA_NT 17
+#define DA_VS 9
+#define DA_WAVES 8
+#define DA_KROW 144                       // bytes per k row and plane: 64 fp16 + 16 bytes of padding
+#define DA_VROW 592                       // bytes per v^T row and plane: 288 fp16 + 16 bytes of padding
+#define DA_KPLANE (DA_MAXN * DA_KROW)     // 39 168
+#define DA_VPLANE (64 * DA_VROW)          // 37 888
+#define DA_LDS (2 * DA_KPLANE + 2 * DA_VPLANE + 64)  // 154 176 bytes of the 160 KiB
+
+__device__ __forceinline__ float da_pow2_scale(float amax) {
+  if (!(amax > 0.f) || !(amax < 3.0e38f)) return 1.0f;
+  int e;
+  (void)frexpf(amax, &e);
+  e = 14 - e;
+  e = e > 100 ? 100 : (e < -100 ? -100 : e);
+  return ldexpf(1.0f, e);
+}
+__device__ __forceinline__ float da_tok_max(float m) {
+  m = fmaxf(m, xor16_f32(m));
+  return fmaxf(m, xor32_f32(m));
+}
+__device__ __forceinline__ float da_tok_sum(float s) {
+  s += xor16_f32(s);
+  return s + xor32_f32(s);
+}
+__device__ __forceinline__ float da_amax4(float4 v) { return fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))); }
+
+__global__ __launch_bounds__(DA_WAVES * 64) void dino_attention_kernel(const float* __restrict__ qkv, float* __restrict__ out, int n) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+  unsigned char* kh = lds;
+  unsigned char* kl = lds + DA_KPLANE;
+  unsigned char* vh = lds + 2 * DA_KPLANE;
+  unsigned char* vl = vh + DA_VPLANE;
+  float* red = reinterpret_cast<float*>(vl + DA_VPLANE);  // 16 floats
+  const int h = blockIdx.x, b = blockIdx.y;
+  const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6), fr = lane & 15, fg = lane >> 4;
+  const int ngroups = (n + 15) >> 4;
+  const float* kb = qkv + (size_t)b * n * (3 * DN_C) + DN_C + 64 * h;
+  const float* vb = kb + DN_C;
+
+  // ---- the image scales: max |k|, max |v| of this (image, head)
+  float mk = 0.f, mv = 0.f;
+  for (int e = t; e < n * 16; e += DA_WAVES * 64) {
+    const int j = e >> 4, c4 = e & 15;
+    mk = fmaxf(mk, da_amax4(*reinterpret_cast<const float4*>(kb + (size_t)j * (3 * DN_C) + 4 * c4)));
+    mv = fmaxf(mv, da_amax4(*reinterpret_cast<const float4*>(vb + (size_t)j * (3 * DN_C) + 4 * c4)));
+  }
+  mk = wave_max_dpp(mk);
+  mv = wave_max_dpp(mv);
+  if (lane == 0) { red[wave] = mk; red[8 + wave] = mv; }
+  __syncthreads();
+  float sk = 0.f, sv = 0.f;
+#pragma unroll
+  for (int w = 0; w < DA_WAVES; ++w) { sk = fmaxf(sk, red[w]); sv = fmaxf(sv, red[8 + w]); }
+  sk = da_pow2_scale(sk);
+  sv = da_pow2_scale(sv);
+
+  // ---- k_h image: row = key, channel c at byte 2 c; every (key < 272, channel) slot is written (zeros beyond n)
+  for (int e = t; e < DA_MAXN * 16; e += DA_WAVES * 64) {
+    const int j = e >> 4, c4 = e & 15;
+    float4 kv = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (j < n) kv = *reinterpret_cast<const float4*>(kb + (size_t)j * (3 * DN_C) + 4 * c4);  // (second read: L2)
+    const float e4[4] = {kv.x * sk, kv.y * sk, kv.z * sk, kv.w * sk};
+    half4 hi4, lo4;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      _Float16 hi, lo;
+      sam6d_split_f16(e4[u], hi, lo);
+      hi4[u] = hi;
+      lo4[u] = lo;
+    }
+    *reinterpret_cast<half4*>(kh + (size_t)j * DA_KROW + 8 * c4) = hi4;
+    *reinterpret_cast<half4*>(kl + (size_t)j * DA_KROW + 8 * c4) = lo4;
+  }
+  // ---- v_h^T image: row = channel d, key j at byte 2 j; every (channel, key < 288) slot is written (zeros beyond n).  A wave reads
+  // 64 consecutive channels of one key.
+  for (int e = t; e < (DA_VS * 32 / 4) * 64; e += DA_WAVES * 64) {
+    const int d = e & 63, jq = e >> 6;
+    half4 hi4, lo4;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int j = 4 * jq + u;
+      const float x = (j < n) ? vb[(size_t)j * (3 * DN_C) + d] * sv : 0.f;
+      _Float16 hi, lo;
+      sam6d_split_f16(x, hi, lo);
+      hi4[u] = hi;
+      lo4[u] = lo;
+    }
+    *reinterpret_cast<half4*>(vh + (size_t)d * DA_VROW + 8 * jq) = hi4;
+    *reinterpret_cast<half4*>(vl + (size_t)d * DA_VROW + 8 * jq) = lo4;
+  }
+  __syncthreads();
+
+  const float inv_k = 1.0f / sk, inv_v = (1.0f / sv) * (1.0f / 16384.0f);
+  for (int grp = wave; grp < ngroups; grp += DA_WAVES) {  // (wave-uniform)
+    const int tok = min(grp * 16 + fr, n - 1);
+    // q / 8 (the softmax scale 1 / sqrt(64): a power of two) as split B fragments: k-slot 8 g + e of step ks = channel 32 ks + 8 g + e
+    const float* qsrc = qkv + ((size_t)b * n + tok) * (3 * DN_C) + 64 * h;
+    float4 qa[2], qb[2];
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      qa[ks] = *reinterpret_cast<const float4*>(qsrc + 32 * ks + 8 * fg);
+      qb[ks] = *reinterpret_cast<const float4*>(qsrc + 32 * ks + 8 * fg + 4);
+    }
+    float qm = fmaxf(fmaxf(da_amax4(qa[0]), da_amax4(qb[0])), fmaxf(da_amax4(qa[1]), da_amax4(qb[1])));
+    const float sq = da_pow2_scale(da_tok_max(qm * 0.125f));
+    half8 qh[2], ql[2];
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      const float e8[8] = {qa[ks].x, qa[ks].y, qa[ks].z, qa[ks].w, qb[ks].x, qb[ks].y, qb[ks].z, qb[ks].w};
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        _Float16 hi, lo;
+        sam6d_split_f16(e8[u] * 0.125f * sq, hi, lo);
+        qh[ks][u] = hi;
+        ql[ks][u] = lo;
+      }
+    }
+    // S^T tiles: rows = keys 16 i + fr (A operand from the k image), columns = the group's tokens
+    f32x4 s[DA_NT];
+#pragma unroll
+    for (int i = 0; i < DA_NT; ++i) {
+      f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        const size_t off = (size_t)(16 * i + fr) * DA_KROW + 64 * ks + 16 * fg;
+        const half8 ah = *reinterpret_cast<const half8*>(kh + off);
+        const half8 al = *reinterpret_cast<const half8*>(kl + off);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, qh[ks], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, ql[ks], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, qh[ks], acc, 0, 0, 0);
+      }
+      s[i] = acc;
+    }
+    // softmax over the keys (F.softmax: exp(x - max) / sum), the lane's 68 logits and its three partner lanes
+    const float inv = inv_k * (1.0f / sq);
+    float mx = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < DA_NT; ++i)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int key = 16 * i + 4 * fg + r;
+        s[i][r] = key < n ? s[i][r] * inv : -INFINITY;
+        mx = fmaxf(mx, s[i][r]);
+      }
+    mx = da_tok_max(mx);
+    float sum = 0.f;
+#pragma unroll
+    for (int i = 0; i < DA_NT; ++i)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        s[i][r] = __builtin_amdgcn_exp2f((s[i][r] - mx) * 1.4426950408889634f);
+        sum += s[i][r];
+      }
+    sum = da_tok_sum(sum);
+    const float pscale = 16384.0f / sum;  // probabilities times 2^14 (fp16-safe), the 2^-14 is in inv_v
+    half8 ph[DA_VS], pl[DA_VS];
+#pragma unroll
+    for (int i = 0; i < 2 * DA_VS; ++i)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float pv = i < DA_NT ? s[i < DA_NT ? i : 0][r] * pscale : 0.f;
+        _Float16 hi, lo;
+        sam6d_split_f16(pv, hi, lo);
+        ph[i >> 1][4 * (i & 1) + r] = hi;
+        pl[i >> 1][4 * (i & 1) + r] = lo;
+      }
+    // out^T tiles: rows = channels 16 i + fr (A operand from the v^T image: keys 32 s + 4 g .. + 3 and 32 s + 16 + 4 g .. + 3)
+    f32x4 o[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int st = 0; st < DA_VS; ++st) {
+        const size_t off = (size_t)(16 * i + fr) * DA_VROW + 2 * (32 * st + 4 * fg);
+        const half4 h0 = *reinterpret_cast<const half4*>(vh + off), h1 = *reinterpret_cast<const half4*>(vh + off + 32);
+        const half4 l0 = *reinterpret_cast<const half4*>(vl + off), l1 = *reinterpret_cast<const half4*>(vl + off + 32);
+        const half8 ah = half8{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
+        const half8 al = half8{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, ph[st], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, pl[st], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, ph[st], acc, 0, 0, 0);
+      }
+      o[i] = acc;
+    }
+    if (grp * 16 + fr < n) {
+      float* dst = out + ((size_t)b * n + tok) * DN_C + 64 * h;
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        *reinterpret_cast<float4*>(dst + 16 * i + 4 * fg) = make_float4(o[i][0] * inv_v, o[i][1] * inv_v, o[i][2] * inv_v, o[i][3] * inv_v);
+    }
+  }
+}
+
+extern "C" int sam6d_dino_attention(const float* qkv, float* out, int B, int n, void* stream) {
+  SAM6D_REQUIRE(qkv && out && B >= 0, "dino_attention: null pointer");
+  SAM6D_REQUIRE(n > 0 && n <= DA_MAXN, "dino_attention: needs 0 < n <= %d tokens per image (n = %d)", DA_MAXN, n);
+  SAM6D_REQUIRE(((((size_t)qkv) | ((size_t)out)) & 15) == 0, "dino_attention: pointers must be 16-byte aligned");
+  SAM6D_REQUIRE(B <= 65535, "dino_attention: B <= 65535");
+  if (B == 0) return 0;
+  static unsigned long long done = 0;
+  if (sam6d_first_use_on_device(&done)) {
+    hipError_t e = hipFuncSetAttribute((const void*)dino_attention_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, DA_LDS);
+    if (e != hipSuccess) {
+      sam6d_set_error("dino_attention: cannot reserve %d bytes of LDS: %s", DA_LDS, hipGetErrorString(e));
+      return (int)e;
+    }
+    sam6d_setup_done_on_device(&done);
+  }
+  hipLaunchKernelGGL(dino_attention_kernel, dim3(DN_C / 64, B), dim3(DA_WAVES * 64), DA_LDS, (hipStream_t)stream, qkv, out, n);
+  SAM6D_LAUNCH_CHECK("dino_attention");
+}

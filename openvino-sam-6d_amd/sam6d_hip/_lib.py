@@ -132,6 +132,10 @@ SIGNATURES = {
     "sam6d_vit_layernorm768": [c_p] * 4 + [c_i, c_i, c_l, c_l, c_l, c_l, c_f, c_p],
     "sam6d_vit_attention": [c_p, c_p, c_i, c_i, c_p],
     "sam6d_vit_upsample_gather": [c_p, c_p, c_p, c_i, c_i, c_p],
+    "sam6d_dino_crop_proposals": [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p],
+    "sam6d_dino_patch_rows": [c_p] * 5 + [c_i, c_p],
+    "sam6d_dino_layernorm1024": [c_p] * 4 + [c_i, c_i, c_l, c_l, c_l, c_l, c_f, c_p],
+    "sam6d_dino_attention": [c_p, c_p, c_i, c_i, c_p],
 }
 
 _lib = None
