@@ -631,6 +631,36 @@ int sam6d_dino_layernorm1024(const float* x, const float* gamma, const float* be
  * the kernel).  fp16 x3 split MFMA products with power-of-two operand scales (fp32 softmax); the probabilities stay on chip. */
 int sam6d_dino_attention(const float* qkv, float* out, int B, int n, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * SAM's automatic mask generator after the mask decoder (ISM/model/sam.py:52-148 CustomSamAutomaticMaskGenerator,
+ * ISM/segment_anything/automatic_mask_generator.py:266-321).  The network itself (image encoder, prompt encoder, mask decoder) is not
+ * part of the library.  (New entries only, so SAM6D_ABI_VERSION stays.)
+ * ---------------------------------------------------------------------------------------------------------- */
+
+/* Sam.postprocess_masks (ISM/segment_anything/modeling/sam.py:133-162), calculate_stability_score
+ * (ISM/segment_anything/utils/amg.py:156-176), the `> mask_threshold` of _process_batch (automatic_mask_generator.py:308) and
+ * batched_mask_to_box (amg.py:303-346) for one point batch, without the S x S or the full-resolution logits in memory:
+ * low (M, lh, lw) f32 low-resolution logits -> for every mask with live[m] != 0 (u8) and every pixel of the out_h x out_w crop the
+ * value of F.interpolate(F.interpolate(low, (S, S))[..., :in_h, :in_w], (out_h, out_w)) (bilinear, align_corners=False; the fp32
+ * recipe is written down in csrc/amg.hip and does not depend on the tiling), and from it
+ *   n_hi[m], n_lo[m] (i32) = pixels > mask_threshold + offset and > mask_threshold - offset (stability score = n_hi / n_lo),
+ *   area[m] (i32) and box[m] = (x0, y0, x1, y1) (i32, inclusive; [0, 0, 0, 0] for an empty mask) of the pixels > mask_threshold,
+ *   bits (M, out_h, ceil(out_w / 32)) u32: that binary mask, pixel x of a row in bit x % 32 of word x / 32 (unused bits 0),
+ *   logits_out (M, out_h, out_w) f32: the values themselves; NULL in the product path (a test measures the arithmetic with it).
+ * Rows with live[m] == 0 are left untouched in every output.  M <= 65535; in_h, in_w <= S.
+ * ws: sam6d_amg_mask_stats_workspace_bytes(M, lh, lw, S, in_h, out_h) bytes of device memory (per-band partial results; 0 = sizes
+ * the entry refuses). */
+size_t sam6d_amg_mask_stats_workspace_bytes(int M, int lh, int lw, int S, int in_h, int out_h);
+int sam6d_amg_mask_stats(const float* low, const unsigned char* live, int M, int lh, int lw, int S, int in_h, int in_w, int out_h,
+                         int out_w, float mask_threshold, float stability_score_offset, int* n_hi, int* n_lo, int* area, int* box,
+                         unsigned* bits, float* logits_out, void* ws, size_t ws_bytes, void* stream);
+/* replaces uncrop_masks + mask_to_rle_pytorch (ISM/segment_anything/utils/amg.py:255-264, :107-135) and the rle_to_mask loop with its
+ * torch.stack and upload (ISM/model/sam.py:146-148) for the masks that survived: out[k] (K, H, W), u8 or (as_f32 != 0) f32, 0 / 1, =
+ * row idx[k] (i64) of bits (n_src, out_h, ceil(out_w / 32)) placed at (x0, y0) of the H x W image, zero outside the crop.  An index
+ * outside [0, n_src) gives an all-zero mask.  K <= 65535. */
+int sam6d_amg_unpack_masks(const unsigned* bits, const long long* idx, long n_src, int K, int out_h, int out_w, int x0, int y0,
+                           int H, int W, int as_f32, void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

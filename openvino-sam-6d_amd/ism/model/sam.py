@@ -1,0 +1,231 @@
+"""Drop-in for ISM/model/sam.py: CustomSamAutomaticMaskGenerator with the reference's constructor and `generate_masks` contract, its
+tail after the mask decoder on sam6d_hip.amg (one fused launch per point batch instead of the 1024 x 1024 logits, the RLE round trip
+through the host and torchvision's NMS).
+
+The SAM network is not part of this project.  It is reached only through the `sam` object the caller passes in:
+    sam.image_encoder (.img_size; called on the preprocessed image), sam.prompt_encoder (called with points / boxes / masks keywords;
+    .get_dense_pe()), sam.mask_decoder (called with the reference's keywords, returns (low_res_masks, iou_predictions)),
+    sam.preprocess, sam.mask_threshold, sam.image_format, sam.device.
+The encoder's input resize (ResizeLongestSide.apply_image: PIL through torchvision) belongs to the network side: `set_image` goes
+through `encode_image(sam, image) -> (features, input_size)`; without one, segment_anything.SamPredictor is imported when the first
+image arrives.  Nothing here imports segment_anything, torchvision, cv2 or pycocotools at module import.
+"""
+import logging
+import os.path as osp
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from sam6d_hip import amg
+
+pretrained_weight_dict = {
+    "vit_l": "sam_vit_l_0b3195.pth",
+    "vit_b": "sam_vit_b_01ec64.pth",
+    "vit_h": "sam_vit_h_4b8939.pth",
+}
+
+
+def load_sam(model_type, checkpoint_dir):
+    try:
+        from segment_anything import sam_model_registry
+    except ImportError as e:
+        raise ImportError("load_sam needs the segment_anything package (the SAM network is not part of sam6d_hip): %s" % e)
+    logging.info("Loading SAM model from %s", checkpoint_dir)
+    return sam_model_registry[model_type](checkpoint=osp.join(checkpoint_dir, pretrained_weight_dict[model_type]))
+
+
+class Predictor:
+    """SamPredictor's part in the mask generator (ISM/segment_anything/predictor.py:34-90, 168-235): holds the model and the features of
+    the current crop, and runs prompt encoder + mask decoder for a batch of points up to `low_res_masks`."""
+
+    def __init__(self, sam_model, encode_image=None):
+        self.model = sam_model
+        self.encode_image = encode_image
+        self._sam_predictor = None
+        self.reset_image()
+
+    @property
+    def device(self):
+        return self.model.device
+
+    def reset_image(self):
+        self.is_image_set = False
+        self.features = None
+        self.original_size = None
+        self.input_size = None
+
+    @torch.no_grad()
+    def set_image(self, image, image_format="RGB"):
+        self.reset_image()
+        if self.encode_image is not None:
+            if image_format != self.model.image_format:
+                image = image[..., ::-1]
+            self.features, input_size = self.encode_image(self.model, image)
+            self.input_size = tuple(int(v) for v in input_size)
+        else:
+            if self._sam_predictor is None or self._sam_predictor.model is not self.model:
+                try:
+                    from segment_anything import SamPredictor
+                except ImportError as e:
+                    raise ImportError("CustomSamAutomaticMaskGenerator: encoding an image needs either an `encode_image(sam, image)` "
+                                      "callable or the segment_anything package (its SamPredictor.set_image resizes the image through "
+                                      "torchvision and PIL): %s" % e)
+                self._sam_predictor = SamPredictor(self.model)
+            self._sam_predictor.set_image(image, image_format)
+            self.features = self._sam_predictor.features
+            self.input_size = tuple(self._sam_predictor.input_size)
+            self._sam_predictor.reset_image()
+        self.original_size = tuple(image.shape[:2])
+        want = amg.preprocess_shape(self.original_size[0], self.original_size[1], self.model.image_encoder.img_size)
+        if self.input_size != want:
+            raise ValueError("set_image: the encoder's input is %s, a %s image resizes to %s" % (self.input_size, self.original_size, want))
+        self.is_image_set = True
+
+    @torch.no_grad()
+    def predict_low(self, points):
+        """points (B, 2) xy in the current crop -> (low_res_masks (B, 3, lh, lw), iou_predictions (B, 3)): apply_coords, one
+        foreground label per point, prompt encoder, mask decoder with multimask_output=True (automatic_mask_generator.py:276-284,
+        predictor.py:216-235)."""
+        if not self.is_image_set:
+            raise RuntimeError("An image must be set with .set_image(...) before mask prediction.")
+        coords = amg.apply_coords(points, self.original_size, self.model.image_encoder.img_size)
+        in_points = torch.as_tensor(coords, device=self.device)
+        in_labels = torch.ones(in_points.shape[0], dtype=torch.int, device=in_points.device)
+        sparse, dense = self.model.prompt_encoder(points=(in_points[:, None, :], in_labels[:, None]), boxes=None, masks=None)
+        return self.model.mask_decoder(image_embeddings=self.features, image_pe=self.model.prompt_encoder.get_dense_pe(),
+                                       sparse_prompt_embeddings=sparse, dense_prompt_embeddings=dense, multimask_output=True)
+
+
+class CustomSamAutomaticMaskGenerator:
+    def __init__(
+        self,
+        sam,
+        min_mask_region_area: int = 0,
+        points_per_batch: int = 64,
+        stability_score_thresh: float = 0.85,
+        box_nms_thresh: float = 0.7,
+        crop_overlap_ratio: float = 512 / 1500,
+        segmentor_width_size=None,
+        pred_iou_thresh: float = 0.88,
+        encode_image=None,
+    ):
+        # SamAutomaticMaskGenerator's own defaults for what the reference's subclass does not pass on
+        self.points_per_side = 32
+        self.stability_score_offset = 1.0
+        self.crop_n_layers = 0
+        self.crop_nms_thresh = 0.7
+        self.crop_n_points_downscale_factor = 1
+        self.output_mode = "binary_mask"
+        self.point_grids = amg.layer_point_grids(self.points_per_side, self.crop_n_layers, self.crop_n_points_downscale_factor)
+        self.predictor = Predictor(sam, encode_image)
+        self.points_per_batch = points_per_batch
+        self.pred_iou_thresh = pred_iou_thresh
+        self.stability_score_thresh = stability_score_thresh
+        self.box_nms_thresh = box_nms_thresh
+        self.crop_overlap_ratio = crop_overlap_ratio
+        self.min_mask_region_area = min_mask_region_area
+        self.segmentor_width_size = segmentor_width_size
+        logging.info("Init CustomSamAutomaticMaskGenerator done!")
+
+    def set_crop_layers(self, crop_n_layers, crop_n_points_downscale_factor=1):
+        """The reference fixes crop_n_layers = 0; more layers need their point grids rebuilt."""
+        self.crop_n_layers = crop_n_layers
+        self.crop_n_points_downscale_factor = crop_n_points_downscale_factor
+        self.point_grids = amg.layer_point_grids(self.points_per_side, crop_n_layers, crop_n_points_downscale_factor)
+
+    # ---- segmentor_width_size ---------------------------------------------------------------------------------------------------------
+    def _resized_shape(self, orig_size):
+        return int(self.segmentor_width_size * orig_size[0] / orig_size[1]), int(self.segmentor_width_size)
+
+    def preprocess_resize(self, image: np.ndarray):
+        orig_size = image.shape[:2]
+        height, width = self._resized_shape(orig_size)
+        if (height, width) == tuple(orig_size):
+            return image.copy()  # cv2.resize to the same size copies the pixels
+        import cv2
+        return cv2.resize(image.copy(), (width, height))
+
+    def postprocess_resize(self, detections, orig_size):
+        masks = detections["masks"].float()
+        if tuple(masks.shape[-2:]) != (orig_size[0], orig_size[1]):
+            masks = F.interpolate(masks.unsqueeze(1), size=(orig_size[0], orig_size[1]), mode="bilinear", align_corners=False)[:, 0, :, :]
+        detections["masks"] = masks  # same size: align_corners=False bilinear with scale 1 returns its input
+        scale = orig_size[1] / self.segmentor_width_size
+        detections["boxes"] = detections["boxes"].float() * scale
+        detections["boxes"][:, [0, 2]] = torch.clamp(detections["boxes"][:, [0, 2]], 0, orig_size[1] - 1)
+        detections["boxes"][:, [1, 3]] = torch.clamp(detections["boxes"][:, [1, 3]], 0, orig_size[0] - 1)
+        return detections
+
+    # ---- the generator -----------------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def generate_masks(self, image: np.ndarray):
+        orig_size = None
+        if self.segmentor_width_size is not None:
+            orig_size = image.shape[:2]
+            image = self.preprocess_resize(image)
+        # masks as float32 straight from the unpack launch when postprocess_resize would cast them anyway
+        as_float = orig_size is not None and self.min_mask_region_area <= 0
+        mask_data = self._generate_masks(image, torch.float32 if as_float else torch.bool)
+        if self.min_mask_region_area > 0:
+            mask_data = self.postprocess_small_regions(mask_data, self.min_mask_region_area, max(self.box_nms_thresh, self.crop_nms_thresh))
+        if orig_size is not None:
+            mask_data = self.postprocess_resize(mask_data, orig_size)
+        return mask_data
+
+    def _generate_masks(self, image: np.ndarray, mask_dtype=torch.bool):
+        orig_size = image.shape[:2]
+        boxes, layer_idxs = amg.crop_boxes(orig_size, self.crop_n_layers, self.crop_overlap_ratio)
+        results = [self._process_crop(image, box, layer, orig_size, mask_dtype) for box, layer in zip(boxes, layer_idxs)]
+        data = amg.merge_crops(results, boxes, self.crop_nms_thresh)
+        return {"masks": data["masks"], "boxes": data["boxes"]}
+
+    def _process_crop(self, image, crop_box, crop_layer_idx, orig_size, mask_dtype=torch.bool):
+        x0, y0, x1, y1 = crop_box
+        cropped = image[y0:y1, x0:x1, :]
+        cropped_size = cropped.shape[:2]
+        self.predictor.set_image(cropped)
+        points = self.point_grids[crop_layer_idx] * np.array(cropped_size)[None, ::-1]
+        state = amg.CropState(crop_box, orig_size, self.predictor.model.image_encoder.img_size, len(points), self.predictor.device,
+                              mask_threshold=self.predictor.model.mask_threshold, stability_score_offset=self.stability_score_offset,
+                              pred_iou_thresh=self.pred_iou_thresh, stability_score_thresh=self.stability_score_thresh)
+        points_dev = torch.as_tensor(points, dtype=torch.float64).to(self.predictor.device)  # one upload per crop
+        for b0 in range(0, len(points), self.points_per_batch):
+            low, iou_preds = self.predictor.predict_low(points[b0:b0 + self.points_per_batch])
+            amg.process_batch(low, iou_preds, state, points_dev[b0:b0 + self.points_per_batch])
+        self.predictor.reset_image()
+        return amg.finish_crop(state, crop_box, orig_size, self.box_nms_thresh, mask_dtype)
+
+    # ---- min_mask_region_area > 0: the reference's host route (needs cv2), not part of the HIP path ----------------------------------
+    @staticmethod
+    def postprocess_small_regions(mask_data, min_area, nms_thresh):
+        if len(mask_data["masks"]) == 0:
+            return mask_data
+        import cv2
+
+        def clean(mask, holes):
+            work = (holes ^ mask).astype(np.uint8)
+            n_labels, regions, stats, _ = cv2.connectedComponentsWithStats(work, 8)
+            sizes = stats[:, -1][1:]
+            small = [i + 1 for i, s in enumerate(sizes) if s < min_area]
+            if not small:
+                return mask, False
+            fill = [0] + small
+            if not holes:
+                fill = [i for i in range(n_labels) if i not in fill] or [int(np.argmax(sizes)) + 1]
+            return np.isin(regions, fill), True
+
+        dev = mask_data["masks"].device
+        new_masks, scores = [], []
+        for mask in mask_data["masks"].bool().cpu().numpy():
+            mask, c1 = clean(mask, True)
+            mask, c2 = clean(mask, False)
+            new_masks.append(torch.as_tensor(mask))
+            scores.append(float(not (c1 or c2)))
+        masks = torch.stack(new_masks).to(dev)
+        boxes = amg.mask_boxes(masks)
+        keep = amg.nms_torch(boxes.float(), torch.as_tensor(scores, device=dev), nms_thresh)
+        out_boxes = mask_data["boxes"].clone()
+        changed = torch.as_tensor(scores, device=dev) == 0.0
+        out_boxes[changed] = boxes[changed]
+        return {"masks": masks[keep].to(mask_data["masks"].dtype), "boxes": out_boxes[keep]}

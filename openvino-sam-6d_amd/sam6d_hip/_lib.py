@@ -136,6 +136,9 @@ SIGNATURES = {
     "sam6d_dino_patch_rows": [c_p] * 5 + [c_i, c_p],
     "sam6d_dino_layernorm1024": [c_p] * 4 + [c_i, c_i, c_l, c_l, c_l, c_l, c_f, c_p],
     "sam6d_dino_attention": [c_p, c_p, c_i, c_i, c_p],
+    "sam6d_amg_mask_stats_workspace_bytes": [c_i] * 6,
+    "sam6d_amg_mask_stats": [c_p, c_p] + [c_i] * 8 + [c_f, c_f] + [c_p] * 7 + [ctypes.c_size_t, c_p],
+    "sam6d_amg_unpack_masks": [c_p, c_p, c_l] + [c_i] * 8 + [c_p, c_p],
 }
 
 _lib = None

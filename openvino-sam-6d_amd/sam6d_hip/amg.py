@@ -1,0 +1,406 @@
+"""SAM's automatic mask generator after the mask decoder, on the library (ISM/model/sam.py:52-148 CustomSamAutomaticMaskGenerator,
+ISM/segment_anything/automatic_mask_generator.py:225-321, ISM/segment_anything/modeling/sam.py:133-162, ISM/segment_anything/utils/amg.py).
+
+Per point batch the decoder leaves `low` (B, 3, 256, 256) logits and `iou_preds` (B, 3).  The reference upsamples all of them to
+1024 x 1024 and on to the image size, thresholds that tensor three times, walks it for boxes, run-length encodes every kept mask through
+the host and decodes it again at the end.  Here one launch (sam6d_amg_mask_stats) leaves two counts, an area, a box and the bit-packed
+mask per live proposal; the keep decisions are small vector ops on the device; a crop ends with one compaction, sam6d_nms and one
+launch (sam6d_amg_unpack_masks) that writes the surviving masks in the image frame.  A crop costs two 4-byte read-backs (how many
+proposals the filters kept, how many NMS kept), whatever the number of batches and masks.
+
+`eager_tail` is the same tail in plain torch ops on any device: the CPU path, the SAM6D_HIP_AMG=0 path and the timing baseline.
+The geometry helpers (point grids, crop boxes, apply_coords) are the reference's arithmetic restated on the host.
+"""
+import math
+import os
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from . import _lib
+
+MASKS_PER_POINT = 3   # multimask_output=True
+EDGE_ATOL = 20.0      # is_box_near_crop_edge's default
+
+
+def hip_enabled(device):
+    """The library path is taken for HIP device tensors unless SAM6D_HIP_AMG=0."""
+    return torch.device(device).type == "cuda" and os.environ.get("SAM6D_HIP_AMG", "1") != "0"
+
+
+# ------------------------------------------------------------------------------------------------- geometry on the host
+def preprocess_shape(h, w, side):
+    """ResizeLongestSide.get_preprocess_shape (ISM/segment_anything/utils/transforms.py:91-102), in double."""
+    scale = side * 1.0 / max(h, w)
+    newh, neww = h * scale, w * scale
+    return int(newh + 0.5), int(neww + 0.5)
+
+
+def apply_coords(coords, original_size, side):
+    """ResizeLongestSide.apply_coords (transforms.py:33-45): (..., 2) xy points of an original_size = (H, W) image -> float64 points
+    of the resized input."""
+    old_h, old_w = original_size
+    new_h, new_w = preprocess_shape(old_h, old_w, side)
+    out = np.array(coords, dtype=np.float64, copy=True)
+    out[..., 0] = out[..., 0] * (new_w / old_w)
+    out[..., 1] = out[..., 1] * (new_h / old_h)
+    return out
+
+
+def point_grid(n_per_side):
+    """build_point_grid (amg.py:179-186): (n*n, 2) xy in [0, 1], x fastest."""
+    offset = 1 / (2 * n_per_side)
+    side = np.linspace(offset, 1 - offset, n_per_side)
+    xs = np.tile(side[None, :], (n_per_side, 1))
+    ys = np.tile(side[:, None], (1, n_per_side))
+    return np.stack([xs, ys], axis=-1).reshape(-1, 2)
+
+
+def layer_point_grids(n_per_side, n_layers, scale_per_layer):
+    """build_all_layer_point_grids (amg.py:189-197)."""
+    return [point_grid(int(n_per_side / (scale_per_layer ** i))) for i in range(n_layers + 1)]
+
+
+def crop_boxes(im_size, n_layers, overlap_ratio):
+    """generate_crop_boxes (amg.py:200-234): xyxy boxes (exclusive ends) and their layer, the whole image first."""
+    im_h, im_w = im_size
+    boxes, layers = [[0, 0, im_w, im_h]], [0]
+    short = min(im_h, im_w)
+    for i_layer in range(n_layers):
+        n = 2 ** (i_layer + 1)
+        overlap = int(overlap_ratio * short * (2 / n))
+        cw = int(math.ceil((overlap * (n - 1) + im_w) / n))
+        ch = int(math.ceil((overlap * (n - 1) + im_h) / n))
+        for x0 in [int((cw - overlap) * i) for i in range(n)]:
+            for y0 in [int((ch - overlap) * i) for i in range(n)]:
+                boxes.append([x0, y0, min(x0 + cw, im_w), min(y0 + ch, im_h)])
+                layers.append(i_layer + 1)
+    return boxes, layers
+
+
+# ------------------------------------------------------------------------------------------------- the two bindings
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _need_hip(t, who):
+    if not t.is_cuda:
+        raise RuntimeError("%s: needs HIP device tensors (eager_tail is the CPU path)" % who)
+
+
+def words(width):
+    return (width + 31) // 32
+
+
+def mask_stats(low, live, input_size, crop_size, img_size, thr, offset, out=None, logits=False):
+    """sam6d_amg_mask_stats.  low (M, lh, lw) float32, live (M) uint8 / bool, input_size = (in_h, in_w) of the encoder's unpadded
+    input, crop_size = (out_h, out_w), img_size = the encoder side S -> dict n_hi, n_lo, area (M) int32, box (M, 4) int32, bits
+    (M, out_h, ceil(out_w / 32)) int32 (the words of the packed mask), and `logits` (M, out_h, out_w) when asked for (a test's
+    measurement; the product path never is).  `out`: a dict of caller-owned tensors of those shapes to write into (rows with live == 0
+    stay as they are); without it fresh zero tensors are returned.  Asynchronous."""
+    _need_hip(low, "mask_stats")
+    if low.dim() != 3 or low.dtype != torch.float32:
+        raise ValueError("mask_stats: low must be (M, lh, lw) float32, got %s %s" % (tuple(low.shape), low.dtype))
+    low = low.contiguous()
+    M, lh, lw = low.shape
+    (in_h, in_w), (oh, ow) = input_size, crop_size
+    live8 = live.to(torch.uint8).contiguous()
+    if tuple(live8.shape) != (M,):
+        raise ValueError("mask_stats: live must be (%d,), got %s" % (M, tuple(live8.shape)))
+    dev = low.device
+    with torch.cuda.device(dev):
+        if out is None:
+            z = lambda *s: torch.zeros(s, dtype=torch.int32, device=dev)  # noqa: E731
+            out = dict(n_hi=z(M), n_lo=z(M), area=z(M), box=z(M, 4), bits=z(M, oh, words(ow)))
+        for k, shape in (("n_hi", (M,)), ("n_lo", (M,)), ("area", (M,)), ("box", (M, 4)), ("bits", (M, oh, words(ow)))):
+            t = out[k]
+            if tuple(t.shape) != shape or t.dtype != torch.int32 or not t.is_contiguous() or t.device != dev:
+                raise ValueError("mask_stats: out[%r] must be a contiguous int32 %s on %s" % (k, shape, dev))
+        lg = torch.empty((M, oh, ow), dtype=torch.float32, device=dev) if logits else None
+        nbytes = int(_lib.load().sam6d_amg_mask_stats_workspace_bytes(M, lh, lw, int(img_size), in_h, oh))
+        ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)
+        _lib.call("sam6d_amg_mask_stats", _ptr(low), _ptr(live8), M, lh, lw, int(img_size), in_h, in_w, oh, ow, float(thr), float(offset),
+                  _ptr(out["n_hi"]), _ptr(out["n_lo"]), _ptr(out["area"]), _ptr(out["box"]), _ptr(out["bits"]), _ptr(lg), _ptr(ws), nbytes,
+                  _stream())
+    if logits:
+        out = dict(out, logits=lg)
+    return out
+
+
+def unpack_masks(bits, idx, crop_size, crop_box, orig_size, dtype=torch.bool):
+    """sam6d_amg_unpack_masks.  bits (C, out_h, ceil(out_w / 32)) int32, idx (K) int64 rows of it -> (K, H, W) masks of the orig_size =
+    (H, W) image, the crop placed at crop_box's corner and zero around it (uncrop_masks); dtype bool / uint8 / float32."""
+    _need_hip(bits, "unpack_masks")
+    (oh, ow), (H, W) = crop_size, orig_size
+    x0, y0 = int(crop_box[0]), int(crop_box[1])
+    if tuple(bits.shape[1:]) != (oh, words(ow)) or bits.dtype != torch.int32 or not bits.is_contiguous():
+        raise ValueError("unpack_masks: bits must be a contiguous int32 (C, %d, %d), got %s %s" % (oh, words(ow), tuple(bits.shape), bits.dtype))
+    if dtype not in (torch.bool, torch.uint8, torch.float32):
+        raise ValueError("unpack_masks: dtype must be bool, uint8 or float32, got %s" % dtype)
+    idx = idx.to(device=bits.device, dtype=torch.int64).contiguous()
+    K = idx.shape[0]
+    f32 = dtype == torch.float32
+    with torch.cuda.device(bits.device):
+        out = torch.empty((K, H, W), dtype=torch.float32 if f32 else torch.uint8, device=bits.device)
+        for k0 in range(0, K, 65535):
+            k = min(65535, K - k0)
+            _lib.call("sam6d_amg_unpack_masks", _ptr(bits), idx.data_ptr() + 8 * k0, bits.shape[0], k, oh, ow, x0, y0, H, W, int(f32),
+                      out.data_ptr() + k0 * H * W * out.element_size(), _stream())
+    return out.view(torch.bool) if dtype == torch.bool else out
+
+
+# ------------------------------------------------------------------------------------------------- one crop
+class CropState:
+    """What one crop of the generator needs: its settings and, on a HIP device, the fixed-capacity device buffers that the point batches
+    fill (n_points * 3 proposals: packed masks, counts, boxes, scores, points, keep flags).  On any other device, or with
+    SAM6D_HIP_AMG=0, the batches are kept as eager results instead."""
+
+    def __init__(self, crop_box, orig_size, img_size, n_points, device, mask_threshold=0.0, stability_score_offset=1.0,
+                 pred_iou_thresh=0.88, stability_score_thresh=0.95, hip=None):
+        self.crop_box = [int(v) for v in crop_box]
+        self.orig_size = (int(orig_size[0]), int(orig_size[1]))
+        x0, y0, x1, y1 = self.crop_box
+        self.crop_size = (y1 - y0, x1 - x0)
+        self.img_size = int(img_size)
+        self.input_size = preprocess_shape(self.crop_size[0], self.crop_size[1], self.img_size)
+        self.mask_threshold = float(mask_threshold)
+        self.stability_score_offset = float(stability_score_offset)
+        self.pred_iou_thresh = float(pred_iou_thresh)
+        self.stability_score_thresh = float(stability_score_thresh)
+        self.device = torch.device(device)
+        self.hip = hip_enabled(self.device) if hip is None else bool(hip)
+        self.capacity = int(n_points) * MASKS_PER_POINT
+        self.filled = 0
+        self.parts = []  # the eager path's per-batch results
+        if self.hip:
+            dev, C = self.device, self.capacity
+            oh, ow = self.crop_size
+            z = lambda *s: torch.zeros(s, dtype=torch.int32, device=dev)  # noqa: E731
+            self.out = dict(n_hi=z(C), n_lo=z(C), area=z(C), box=z(C, 4), bits=torch.empty((C, oh, words(ow)), dtype=torch.int32, device=dev))
+            self.iou = torch.zeros(C, dtype=torch.float32, device=dev)
+            self.stability = torch.zeros(C, dtype=torch.float32, device=dev)
+            self.points = torch.zeros((C, 2), dtype=torch.float64, device=dev)
+            self.keep = torch.zeros(C, dtype=torch.uint8, device=dev)
+            self._crop = torch.tensor(self.crop_box, dtype=torch.float32, device=dev)
+            self._orig = torch.tensor([0, 0, self.orig_size[1], self.orig_size[0]], dtype=torch.float32, device=dev)
+            self._off = torch.tensor([x0, y0, x0, y0], dtype=torch.int32, device=dev)
+
+    def settings(self):
+        return dict(crop_box=self.crop_box, orig_size=self.orig_size, img_size=self.img_size, mask_threshold=self.mask_threshold,
+                    stability_score_offset=self.stability_score_offset, pred_iou_thresh=self.pred_iou_thresh,
+                    stability_score_thresh=self.stability_score_thresh)
+
+
+def _flat(low, iou_preds, points, device):
+    if low.dim() == 4:
+        low = low.flatten(0, 1)
+    iou = iou_preds.reshape(-1)
+    per = low.shape[0] // max(1, len(points))
+    if not torch.is_tensor(points):
+        points = torch.as_tensor(np.asarray(points, dtype=np.float64))
+    pts = points.to(device=device, dtype=torch.float64).repeat_interleave(per, dim=0)
+    return low, iou, pts
+
+
+def process_batch(low, iou_preds, state, points):
+    """_process_batch from the decoder's output onwards (automatic_mask_generator.py:286-321): low (B, 3, lh, lw) logits, iou_preds
+    (B, 3), points (B, 2) xy in the crop (a host array, or a tensor: one already on the device costs no upload).  On the library path everything lands in the crop's device buffers and
+    nothing is read back; otherwise the eager result of the batch is kept."""
+    low, iou, pts = _flat(low, iou_preds, points, low.device)
+    if not state.hip:
+        state.parts.append(eager_batch(low, iou, pts, **state.settings()))
+        return
+    M, a = low.shape[0], state.filled
+    if a + M > state.capacity:
+        raise ValueError("process_batch: %d proposals exceed the crop's capacity of %d" % (a + M, state.capacity))
+    b = a + M
+    live = iou > state.pred_iou_thresh if state.pred_iou_thresh > 0.0 else torch.ones_like(iou, dtype=torch.bool)
+    out = {k: v[a:b] for k, v in state.out.items()}
+    mask_stats(low.float(), live, state.input_size, state.crop_size, state.img_size, state.mask_threshold, state.stability_score_offset, out=out)
+    stab = out["n_hi"] / out["n_lo"]  # int32 / int32 true division, as calculate_stability_score returns it
+    keep = live
+    if state.stability_score_thresh > 0.0:
+        keep = keep & (stab >= state.stability_score_thresh)
+    boxes = (out["box"] + state._off).float()
+    near_crop = (boxes - state._crop).abs() <= EDGE_ATOL
+    near_image = (boxes - state._orig).abs() <= EDGE_ATOL
+    keep = keep & ~(near_crop & ~near_image).any(dim=1)
+    state.iou[a:b] = iou
+    state.stability[a:b] = stab
+    state.points[a:b] = pts
+    state.keep[a:b] = keep.to(torch.uint8)
+    state.filled = b
+
+
+def _empty_result(state, dev, mask_dtype):
+    H, W = state.orig_size
+    return dict(masks=torch.zeros((0, H, W), dtype=mask_dtype, device=dev), boxes=torch.zeros((0, 4), dtype=torch.int64, device=dev),
+                iou_preds=torch.zeros(0, dtype=torch.float32, device=dev), stability_score=torch.zeros(0, dtype=torch.float32, device=dev),
+                points=torch.zeros((0, 2), dtype=torch.float64, device=dev))
+
+
+def finish_crop(state, crop_box=None, orig_size=None, box_nms_thresh=0.7, mask_dtype=torch.bool):
+    """The end of _process_crop (automatic_mask_generator.py:250-264) and the masks of ISM/model/sam.py:146-148: NMS inside the crop,
+    boxes and points back in the image frame, masks (K, H, W) of the whole image.  -> {"masks", "boxes" (K, 4) int64 xyxy, "iou_preds",
+    "stability_score", "points"} on the device, in NMS order (score descending).  crop_box / orig_size, when given, must be the state's."""
+    if crop_box is not None and [int(v) for v in crop_box] != state.crop_box:
+        raise ValueError("finish_crop: crop_box %s is not the state's %s" % (list(crop_box), state.crop_box))
+    if orig_size is not None and (int(orig_size[0]), int(orig_size[1])) != state.orig_size:
+        raise ValueError("finish_crop: orig_size %s is not the state's %s" % (tuple(orig_size), state.orig_size))
+    if not state.hip:
+        return _eager_finish(state.parts, state, box_nms_thresh, mask_dtype)
+    from .ism import mask_to_indices, nms
+    n = state.filled
+    if n == 0:
+        return _empty_result(state, state.device, mask_dtype)
+    idx = mask_to_indices(state.keep[:n])                                        # read-back 1: proposals the filters kept
+    order = nms(state.out["box"][:n][idx].float(), state.iou[:n][idx], box_nms_thresh)  # read-back 2: proposals NMS kept
+    sel = idx[order]
+    x0, y0 = state.crop_box[:2]
+    masks = unpack_masks(state.out["bits"], sel, state.crop_size, state.crop_box, state.orig_size, mask_dtype)
+    boxes = state.out["box"][sel].long() + torch.tensor([x0, y0, x0, y0], device=state.device)
+    pts = state.points[sel] + torch.tensor([x0, y0], device=state.device)
+    return dict(masks=masks, boxes=boxes, iou_preds=state.iou[sel], stability_score=state.stability[sel], points=pts)
+
+
+def merge_crops(results, crop_box_list, crop_nms_thresh=0.7):
+    """ISM/model/sam.py:133-144 for crop_n_layers > 0: the crops' results concatenated, then NMS across crops that prefers the proposals
+    of smaller crops (score 1 / box_area(crop_box))."""
+    keys = ("masks", "boxes", "iou_preds", "stability_score", "points")
+    data = {k: torch.cat([r[k] for r in results], dim=0) for k in keys}
+    dev = data["boxes"].device
+    cb = torch.cat([torch.tensor([list(b)] * len(r["boxes"]), dtype=torch.int64).reshape(-1, 4) for r, b in zip(results, crop_box_list)])
+    data["crop_boxes"] = cb.to(dev)
+    if len(results) > 1:
+        scores = (1 / ((cb[:, 2] - cb[:, 0]) * (cb[:, 3] - cb[:, 1]))).to(dev)
+        if hip_enabled(dev):
+            from .ism import nms
+            keep = nms(data["boxes"].float(), scores, crop_nms_thresh)
+        else:
+            keep = nms_torch(data["boxes"].float(), scores, crop_nms_thresh)
+        data = {k: v[keep] for k, v in data.items()}
+    return data
+
+
+# ------------------------------------------------------------------------------------------------- the same tail in plain torch
+def postprocess_masks(low, input_size, crop_size, img_size):
+    """Sam.postprocess_masks (modeling/sam.py:133-162) for low (M, lh, lw): both interpolations as torch does them, in low's dtype."""
+    m = F.interpolate(low[:, None], (img_size, img_size), mode="bilinear", align_corners=False)
+    m = m[..., : input_size[0], : input_size[1]]
+    return F.interpolate(m, tuple(crop_size), mode="bilinear", align_corners=False)[:, 0]
+
+
+def mask_boxes(masks):
+    """batched_mask_to_box (amg.py:303-346) for (M, h, w) bool masks: (M, 4) int64 xyxy, [0, 0, 0, 0] for an empty mask."""
+    M, h, w = masks.shape
+    if masks.numel() == 0:
+        return torch.zeros((M, 4), dtype=torch.int64, device=masks.device)
+    in_h = masks.any(dim=2)
+    ys = torch.arange(h, device=masks.device)[None, :]
+    bottom = (in_h * ys).max(dim=1).values
+    top = (in_h * ys + h * (~in_h)).min(dim=1).values
+    in_w = masks.any(dim=1)
+    xs = torch.arange(w, device=masks.device)[None, :]
+    right = (in_w * xs).max(dim=1).values
+    left = (in_w * xs + w * (~in_w)).min(dim=1).values
+    empty = (right < left) | (bottom < top)
+    return torch.stack([left, top, right, bottom], dim=1) * (~empty)[:, None]
+
+
+def box_near_crop_edge(boxes, crop_box, orig_box, atol=EDGE_ATOL):
+    """is_box_near_crop_edge (amg.py:78-88); boxes in the crop's frame."""
+    dev = boxes.device
+    x0, y0 = crop_box[0], crop_box[1]
+    b = (boxes + torch.tensor([x0, y0, x0, y0], device=dev)).float()
+    near_crop = (b - torch.tensor(crop_box, dtype=torch.float32, device=dev)).abs() <= atol
+    near_image = (b - torch.tensor(orig_box, dtype=torch.float32, device=dev)).abs() <= atol
+    return (near_crop & ~near_image).any(dim=1)
+
+
+def stability_counts(logits, thr, offset):
+    """The two sums of calculate_stability_score (amg.py:156-176) as int32."""
+    hi = (logits > (thr + offset)).sum(-1, dtype=torch.int16).sum(-1, dtype=torch.int32)
+    lo = (logits > (thr - offset)).sum(-1, dtype=torch.int16).sum(-1, dtype=torch.int32)
+    return hi, lo
+
+
+def eager_batch(low, iou_preds, points, crop_box, orig_size, img_size, mask_threshold=0.0, stability_score_offset=1.0,
+                pred_iou_thresh=0.88, stability_score_thresh=0.95):
+    """One point batch as the reference works through it, filter by filter: low (M, lh, lw), iou_preds (M), points (M, 2) ->
+    {"masks" (k, H, W) bool in the image frame, "boxes" (k, 4) int64 in the crop's frame, "iou_preds", "stability_score", "points"}."""
+    x0, y0, x1, y1 = crop_box
+    H, W = orig_size
+    crop_size = (y1 - y0, x1 - x0)
+    input_size = preprocess_shape(crop_size[0], crop_size[1], img_size)
+    if pred_iou_thresh > 0.0:
+        k = iou_preds > pred_iou_thresh
+        low, iou_preds, points = low[k], iou_preds[k], points[k]
+    logits = postprocess_masks(low, input_size, crop_size, img_size)
+    hi, lo = stability_counts(logits, mask_threshold, stability_score_offset)
+    stab = hi / lo
+    if stability_score_thresh > 0.0:
+        k = stab >= stability_score_thresh
+        logits, iou_preds, points, stab = logits[k], iou_preds[k], points[k], stab[k]
+    masks = logits > mask_threshold
+    boxes = mask_boxes(masks)
+    k = ~box_near_crop_edge(boxes, crop_box, [0, 0, W, H])
+    masks, boxes, iou_preds, points, stab = masks[k], boxes[k], iou_preds[k], points[k], stab[k]
+    if not (x0 == 0 and y0 == 0 and x1 == W and y1 == H):
+        masks = F.pad(masks, (x0, W - x1, y0, H - y1), value=0)
+    return dict(masks=masks, boxes=boxes, iou_preds=iou_preds, stability_score=stab, points=points)
+
+
+def nms_torch(boxes, scores, thresh):
+    """torchvision.ops.nms restated: boxes (N, 4) float xyxy, scores (N) -> kept indices, score descending (stable).  The IoU matrix in
+    torch ops on the boxes' device, the greedy pass on the host."""
+    n = boxes.shape[0]
+    if n == 0:
+        return torch.zeros(0, dtype=torch.int64, device=boxes.device)
+    order = torch.sort(scores, descending=True, stable=True).indices
+    b = boxes[order]
+    area = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
+    w = (torch.minimum(b[:, None, 2], b[None, :, 2]) - torch.maximum(b[:, None, 0], b[None, :, 0])).clamp(min=0)
+    h = (torch.minimum(b[:, None, 3], b[None, :, 3]) - torch.maximum(b[:, None, 1], b[None, :, 1])).clamp(min=0)
+    inter = w * h
+    over = ((inter / (area[:, None] + area[None, :] - inter)) > thresh).cpu().numpy()
+    removed = np.zeros(n, dtype=bool)
+    kept = []
+    for i in range(n):
+        if not removed[i]:
+            kept.append(i)
+            removed[i + 1:] |= over[i, i + 1:]
+    return order[torch.as_tensor(kept, dtype=torch.int64, device=boxes.device)]
+
+
+def _eager_finish(parts, state, box_nms_thresh, mask_dtype):
+    dev = state.device
+    if not parts:
+        return _empty_result(state, dev, mask_dtype)
+    data = {k: torch.cat([p[k] for p in parts], dim=0) for k in parts[0]}
+    keep = nms_torch(data["boxes"].float(), data["iou_preds"], box_nms_thresh)
+    data = {k: v[keep] for k, v in data.items()}
+    x0, y0 = state.crop_box[:2]
+    data["boxes"] = data["boxes"] + torch.tensor([x0, y0, x0, y0], device=data["boxes"].device)
+    data["points"] = data["points"] + torch.tensor([x0, y0], device=data["points"].device)
+    data["masks"] = data["masks"].to(mask_dtype)
+    return data
+
+
+def eager_tail(batches, crop_box, orig_size, img_size, box_nms_thresh=0.7, mask_dtype=torch.bool, **settings):
+    """The whole tail of one crop in plain torch ops, on whatever device the inputs are on.  batches: an iterable of (low, iou_preds,
+    points) as process_batch takes them; settings: mask_threshold, stability_score_offset, pred_iou_thresh, stability_score_thresh.
+    -> the dict finish_crop returns."""
+    state = None
+    for low, iou_preds, points in batches:
+        if state is None:
+            state = CropState(crop_box, orig_size, img_size, 0, low.device, hip=False, **settings)
+        low, iou, pts = _flat(low, iou_preds, points, low.device)
+        state.parts.append(eager_batch(low, iou, pts, **state.settings()))
+    if state is None:
+        raise ValueError("eager_tail: no batches")
+    return _eager_finish(state.parts, state, box_nms_thresh, mask_dtype)

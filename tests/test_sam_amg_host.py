@@ -1,0 +1,185 @@
+"""SAM's mask-generator tail on the host: the float64 restatement (tests/sam_amg_ref.py) and sam6d_hip.amg.eager_tail against results
+captured from the reference (tests/gen_sam_amg_golden.py), the restated geometry helpers, the drop-in's constructor and imports, and the
+kernel's resources.  No GPU."""
+import importlib
+import inspect
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from tests import sam_amg_ref as R
+from tests._util import ROOT, golden
+
+
+def _cases():
+    z = golden("sam_amg")
+    for c, (H, W, x0, y0, x1, y1) in enumerate(z["cases"].tolist()):
+        low = R.build_logits(z["params"], z["c%d.seeds" % c])
+        yield z, c, (H, W), (x0, y0, x1, y1), low
+
+
+def _ref(z, c, key):
+    return z["c%d.%s" % (c, key)]
+
+
+def test_restatement_against_reference_results():
+    n = 0
+    for z, c, orig, box, low in _cases():
+        S, thr, off, eps = int(z["S"]), float(z["thr"]), float(z["offset"]), float(z["eps_gen"])
+        crop = (box[3] - box[1], box[2] - box[0])
+        inp = R.preprocess_shape(crop[0], crop[1], S)
+        assert inp == tuple(_ref(z, c, "input_size"))
+        lg = R.postprocess_masks(low, inp, crop, S)
+        st = int(z["stride"])
+        assert np.abs(lg[:, ::st, ::st] - _ref(z, c, "logits64_sample")).max() <= 1e-11
+        frac = R.check_cap(lg, (thr, thr + off, thr - off), eps)
+        print("\n[sam_amg] case %d: worst band fraction %.2e at eps %.1e, reference fp32 deviation %.2e" % (c, frac, eps, float(_ref(z, c, "fp32_deviation"))))
+        assert R.stability_decided(lg, thr, off, float(z["stability_thresh"]), eps).all()
+        # the reference's fp32 results under the comparison rule: its masks come back from its own RLE
+        H, W = orig
+        offs = _ref(z, c, "rle_offsets")
+        full = np.stack([R.rle_decode(_ref(z, c, "rle_counts")[offs[m]:offs[m + 1]].tolist(), H, W) for m in range(len(low))])
+        got = dict(n_hi=_ref(z, c, "n_hi"), n_lo=_ref(z, c, "n_lo"), area=_ref(z, c, "area"), box=_ref(z, c, "boxes"),
+                   masks=full[:, box[1]:box[3], box[0]:box[2]])
+        R.compare_stats(got, lg, thr, off, eps, "case %d" % c)
+        assert not full.sum() - got["masks"].sum(), "uncrop_masks pads with zeros"
+        # keep decisions
+        n_hi, n_lo, _, boxes, _ = R.stats(lg, thr, off)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            stab = n_hi / n_lo.astype(np.float64)
+        assert np.array_equal(stab >= float(z["stability_thresh"]), _ref(z, c, "keep_stability"))
+        assert np.array_equal(_ref(z, c, "iou_preds") > np.float32(z["pred_iou_thresh"]), _ref(z, c, "keep_iou"))
+        assert np.array_equal(~R.near_crop_edge(_ref(z, c, "boxes"), box, orig), _ref(z, c, "keep_edge"))
+        n += 1
+    assert n == 4
+
+
+def test_eager_tail_cpu_against_reference_results():
+    from sam6d_hip import amg
+    for z, c, orig, box, low in _cases():
+        S, thr, off = int(z["S"]), float(z["thr"]), float(z["offset"])
+        crop = (box[3] - box[1], box[2] - box[0])
+        t = torch.from_numpy(low)
+        lg = amg.postprocess_masks(t, tuple(_ref(z, c, "input_size")), crop, S)
+        hi, lo = amg.stability_counts(lg, thr, off)
+        assert np.array_equal(hi.numpy(), _ref(z, c, "n_hi")) and np.array_equal(lo.numpy(), _ref(z, c, "n_lo"))
+        assert np.array_equal(amg.mask_boxes(lg > thr).numpy(), _ref(z, c, "boxes"))
+        iou = torch.from_numpy(_ref(z, c, "iou_preds"))
+        pts = np.arange(2 * len(low), dtype=np.float64).reshape(-1, 2)
+        res = amg.eager_tail([(t, iou, pts)], box, orig, S, box_nms_thresh=2.0, mask_threshold=thr, stability_score_offset=off,
+                             pred_iou_thresh=float(z["pred_iou_thresh"]), stability_score_thresh=float(z["stability_thresh"]))
+        keep = _ref(z, c, "keep_iou") & _ref(z, c, "keep_stability") & _ref(z, c, "keep_edge")
+        want = np.flatnonzero(keep)
+        want = want[np.argsort(-_ref(z, c, "iou_preds")[want], kind="stable")]  # NMS order with nothing suppressed
+        assert np.array_equal(res["iou_preds"].numpy(), _ref(z, c, "iou_preds")[want])
+        assert np.array_equal(res["boxes"].numpy(), _ref(z, c, "boxes")[want] + np.array([box[0], box[1], box[0], box[1]]))
+        assert np.array_equal(res["points"].numpy(), pts[want] + np.array([box[0], box[1]]))
+        offs = _ref(z, c, "rle_offsets")
+        for k, m in enumerate(want):
+            assert R.rle_encode(res["masks"][k].numpy()) == _ref(z, c, "rle_counts")[offs[m]:offs[m + 1]].tolist()
+        assert res["masks"].dtype == torch.bool and tuple(res["masks"].shape[1:]) == orig
+
+
+def test_nms_torch_suppresses_in_score_order():
+    from sam6d_hip import amg
+    boxes = torch.tensor([[0, 0, 10, 10], [1, 1, 11, 11], [50, 50, 60, 60], [0, 0, 10, 10]], dtype=torch.float32)
+    scores = torch.tensor([0.5, 0.9, 0.1, 0.7])
+    assert amg.nms_torch(boxes, scores, 0.5).tolist() == [1, 2]
+    assert amg.nms_torch(boxes, scores, 0.7).tolist() == [1, 3, 2]
+    assert amg.nms_torch(boxes[:0], scores[:0], 0.5).numel() == 0
+
+
+def test_geometry_helpers_match_captured_values():
+    from sam6d_hip import amg
+    z = golden("sam_amg")
+    assert np.array_equal(amg.point_grid(4), z["grid4"]) and np.array_equal(amg.point_grid(32), z["grid32"])
+    assert np.array_equal(amg.layer_point_grids(32, 1, 2)[1], amg.point_grid(16))
+    for name, size, layers in (("crops_480x640_l1", (480, 640), 1), ("crops_480x640_l2", (480, 640), 2), ("crops_900x1200_l1", (900, 1200), 1)):
+        b, li = amg.crop_boxes(size, layers, 512 / 1500)
+        assert np.array_equal(np.array([bb + [l] for bb, l in zip(b, li)]), z[name]), name
+    assert amg.crop_boxes((480, 640), 0, None) == ([[0, 0, 640, 480]], [0])
+    for name, size in (("coords_480x640", (480, 640)), ("coords_270x360", (270, 360)), ("coords_900x1200", (900, 1200)), ("coords_333x517", (333, 517))):
+        assert np.array_equal(amg.apply_coords(z["coords_points"], size, 1024), z[name]), name
+        assert amg.preprocess_shape(size[0], size[1], 1024) == tuple(z[name + "_shape"]) == R.preprocess_shape(size[0], size[1], 1024)
+
+
+def test_dropin_signature_defaults_and_imports():
+    code = ("import sys; sys.path[:0] = %r\n"
+            "import importlib.abc\n"
+            "class Block(importlib.abc.MetaPathFinder):\n"
+            "    def find_spec(self, name, path, target=None):\n"
+            "        if name.split('.')[0] in ('segment_anything', 'torchvision', 'cv2', 'pycocotools'):\n"
+            "            raise ImportError('blocked: ' + name)\n"
+            "sys.meta_path.insert(0, Block())\n"
+            "from model.sam import CustomSamAutomaticMaskGenerator\n"
+            "import model.sam as m\n"
+            "assert m.__file__.replace('\\\\', '/').endswith('openvino-sam-6d_amd/ism/model/sam.py'), m.__file__\n"
+            "assert not any(k.split('.')[0] in ('segment_anything', 'torchvision', 'cv2', 'pycocotools') for k in sys.modules)\n"
+            "print('ok')\n") % ([os.path.join(ROOT, "openvino-sam-6d_amd", "ism"), os.path.join(ROOT, "openvino-sam-6d_amd")],)
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.strip() == "ok", r.stderr
+    mod = importlib.import_module("model.sam")
+    sig = inspect.signature(mod.CustomSamAutomaticMaskGenerator.__init__)
+    want = [("sam", inspect.Parameter.empty), ("min_mask_region_area", 0), ("points_per_batch", 64), ("stability_score_thresh", 0.85),
+            ("box_nms_thresh", 0.7), ("crop_overlap_ratio", 512 / 1500), ("segmentor_width_size", None), ("pred_iou_thresh", 0.88)]
+    got = [(k, p.default) for k, p in list(sig.parameters.items())[1:]]
+    assert got[:len(want)] == want, got
+    from tests.sam_amg_stub import StubSam, encode_image
+    g = mod.CustomSamAutomaticMaskGenerator(StubSam("cpu"), encode_image=encode_image)
+    assert (g.points_per_side, g.stability_score_offset, g.crop_n_layers, g.crop_nms_thresh, g.crop_n_points_downscale_factor) == (32, 1.0, 0, 0.7, 1)
+    assert len(g.point_grids) == 1 and g.point_grids[0].shape == (1024, 2) and g.predictor.model.device.type == "cpu"
+    g.predictor.encode_image = None
+    with pytest.raises(ImportError, match="segment_anything"):
+        g.predictor.set_image(np.zeros((48, 64, 3), dtype=np.uint8))
+
+
+def test_dropin_generate_masks_cpu_contract():
+    """The whole generator on the CPU (eager_tail) with the stub network: the {"masks", "boxes"} contract with and without
+    segmentor_width_size, survivors in descending predicted IoU, no duplicate of a bank mask left by NMS."""
+    mod = importlib.import_module("model.sam")
+    from tests.sam_amg_stub import StubSam, encode_image
+    image = np.zeros((480, 640, 3), dtype=np.uint8)
+    g = mod.CustomSamAutomaticMaskGenerator(StubSam("cpu"), encode_image=encode_image, points_per_batch=256)
+    g.point_grids = [g.point_grids[0][::4]]  # 256 points keep the CPU run short
+    out = g.generate_masks(image)
+    K = out["masks"].shape[0]
+    assert 3 <= K <= 12 and out["masks"].dtype == torch.bool and tuple(out["masks"].shape) == (K, 480, 640)
+    assert out["boxes"].dtype == torch.int64 and tuple(out["boxes"].shape) == (K, 4)
+    assert np.array_equal(out["boxes"].numpy(), np.array([R.mask_box(m) for m in out["masks"].numpy()]))
+    g.segmentor_width_size = 640
+    out2 = g.generate_masks(image)
+    assert out2["masks"].dtype == torch.float32 and torch.equal(out2["masks"], out["masks"].float())
+    assert out2["boxes"].dtype == torch.float32 and torch.equal(out2["boxes"], out["boxes"].float())
+
+
+def test_mask_stats_kernel_resources():
+    """the statistics kernel keeps within 64 VGPRs (eight waves per SIMD) and uses no scratch."""
+    from sam6d_hip import _lib
+    from tests.test_abi import _gfx950_code_objects
+    readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
+    if not os.path.exists(readelf):
+        pytest.skip("llvm-readelf not available")
+    found = None
+    for blob in _gfx950_code_objects(_lib.LIB_PATH):
+        if b"amg_stats_kernel" not in blob:
+            continue
+        p = os.path.join(os.environ.get("TMPDIR", "/tmp"), "amg_co_%d.elf" % os.getpid())
+        with open(p, "wb") as f:
+            f.write(blob)
+        try:
+            notes = subprocess.run([readelf, "--notes", p], capture_output=True, text=True, check=True).stdout
+        finally:
+            os.remove(p)
+        for entry in re.split(r"\n\s*- \.agpr_count", notes):
+            if re.search(r"\.name:\s+_Z16amg_stats_kernel", entry):
+                found = (int(re.search(r"\.vgpr_count:\s+(\d+)", entry).group(1)),
+                         int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", entry).group(1)),
+                         int(re.search(r"\.vgpr_spill_count:\s+(\d+)", entry).group(1)))
+    assert found is not None, "amg_stats_kernel not found in the library"
+    print("\n[sam_amg] statistics kernel: %d VGPRs, %d B scratch, %d spilled" % found)
+    assert found[0] <= 64 and found[1] == 0 and found[2] == 0, found
