@@ -437,7 +437,9 @@ int sam6d_fine_score(const float* pts1, const float* R, float* t, const float* m
 int sam6d_ism_cosine(const float* query, const float* ref, int Nq, int No, int Nt, int D, float* scores, void* stream);
 /* replaces the tail of compute_semantic_score + best_template_pose (ISM/model/detector.py:198-207, 265-296):
  * per query the aggregated score (mode 0 avg_5 / 1 mean / 2 max), arg-max object and its best template; `sel` = ascending
- * indices of the queries with score > thresh, *nsel their count (device int). */
+ * indices of the queries with score > thresh, *nsel their count (device int).  0 <= Nq <= 65535 (SAM's 32 x 32 point grid
+ * yields up to 3072 raw proposals), Nt <= 256; ties: the first maximal template, the first maximal object; avg_5 is the mean of the
+ * min(5, Nt) largest scores, equal values counted once each. */
 int sam6d_ism_semantic(const float* scores, int Nq, int No, int Nt, int mode, float thresh, float* sem, int* obj, int* best,
                        int* sel, int* nsel, void* stream);
 /* sam6d_ism_semantic with the survivors written out compacted as the tensors the reference's caller holds after its boolean-mask
@@ -479,8 +481,8 @@ int sam6d_ism_project2(const void* masks, int mask_bytes, const long long* mask_
 
 /* replaces depth_image_to_pointcloud_translate_torch(depth, scale, K) itself (ISM/utils/trimesh_utils.py:77-105) for a direct caller:
  * masked_depth (N,H,W) f32 = N already-masked depth maps (mm), K (3,3) f64 row-major, -> translate (N,3) f32 = the mean back-projected
- * point of each map over its pixels with Z > 0 (count + 1e-8 in the denominator); float64 per-pixel terms and sums like the reference's
- * real caller.  part_ws: N * 64 * 4 doubles of scratch.  One launch pair for all maps. */
+ * point of each map over its pixels with Z > 0; float64 per-pixel terms and sums like the reference's real caller, divided by the fp32
+ * count + 1e-8f (how torch evaluates the reference's int64 count + 1e-8; sam6d_ism_project / _project2 likewise).  part_ws: N * 64 * 4 doubles of scratch.  One launch pair for all maps. */
 int sam6d_ism_translate_maps(const float* masked_depth, const double* K, double depth_scale, int N, int H, int W, double* part_ws,
                              float* translate, void* stream);
 /* replaces compute_iou (ISM/utils/bbox_utils.py:197-222): boxes (Ns,4) int64; *all_positive = 0 when any pair has a

@@ -51,7 +51,7 @@ __global__ __launch_bounds__(256) void ism_cosine_kernel(const float* __restrict
 
 extern "C" int sam6d_ism_cosine(const float* query, const float* ref, int Nq, int No, int Nt, int D, float* scores,
                                 void* stream) {
-  SAM6D_REQUIRE(query && ref && scores, "ism_cosine: null pointer");
+  SAM6D_REQUIRE(ref && (Nq == 0 || (query && scores)), "ism_cosine: null pointer");  // (an empty tensor has no storage)
   SAM6D_REQUIRE(Nq >= 0 && No > 0 && Nt > 0 && D > 0 && (D & 3) == 0, "ism_cosine: bad sizes (D %% 4 == 0)");
   const long total = (long)Nq * No * Nt;
   if (total == 0) return 0;
@@ -122,23 +122,30 @@ __global__ __launch_bounds__(64) void ism_semantic_kernel(const float* __restric
   }
 }
 
-// ordered compaction of the queries whose score exceeds the confidence threshold (detector.py:284-287); Nq <= 1024.
+// ordered compaction of the queries whose score exceeds the confidence threshold (detector.py:284-287).  ONE workgroup walks the
+// queries 1024 at a time and carries the survivors' count from pass to pass, so the output order is the proposal order for any Nq
+// and nothing is handed from one workgroup to another (Nq <= 1024, the detector's usual size, is a single pass as before).
 __global__ __launch_bounds__(1024) void ism_select_kernel(const float* __restrict__ sem, int Nq, float thresh,
                                                           int* __restrict__ sel, int* __restrict__ nsel) {
   __shared__ int wcnt[16];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const bool keep = (t < Nq) && (sem[t] > thresh);
-  const unsigned long long m = __ballot(keep);
-  if (lane == 0) wcnt[wave] = __popcll(m);
-  __syncthreads();
-  int base = 0;
-  for (int w = 0; w < wave; ++w) base += wcnt[w];
-  if (keep) sel[base + __popcll(m & ((1ull << lane) - 1ull))] = t;
-  if (t == 0) {
-    int tot = 0;
-    for (int w = 0; w < 16; ++w) tot += wcnt[w];
-    *nsel = tot;
+  int done = 0;  // survivors of the passes before this one
+  for (int c0 = 0; c0 < Nq; c0 += 1024) {
+    const int i = c0 + t;
+    const bool keep = (i < Nq) && (sem[i] > thresh);
+    const unsigned long long m = __ballot(keep);
+    if (lane == 0) wcnt[wave] = __popcll(m);
+    __syncthreads();
+    int base = done, tot = 0;
+    for (int w = 0; w < 16; ++w) {
+      if (w < wave) base += wcnt[w];
+      tot += wcnt[w];
+    }
+    if (keep) sel[base + __popcll(m & ((1ull << lane) - 1ull))] = i;
+    done += tot;
+    __syncthreads();  // wcnt is rewritten by the next pass
   }
+  if (t == 0) *nsel = done;
 }
 
 // ism_select_kernel with the survivors' values written out compacted, as the int64 / float tensors the caller indexes with
@@ -150,33 +157,38 @@ __global__ __launch_bounds__(1024) void ism_select_compact_kernel(const float* _
                                                                   int* __restrict__ nsel) {
   __shared__ int wcnt[16];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const float v = t < Nq ? sem[t] : 0.f;
-  const bool keep = (t < Nq) && (v > thresh);
-  const unsigned long long m = __ballot(keep);
-  if (lane == 0) wcnt[wave] = __popcll(m);
-  __syncthreads();
-  int base = 0;
-  for (int w = 0; w < wave; ++w) base += wcnt[w];
-  if (keep) {
-    const int k = base + __popcll(m & ((1ull << lane) - 1ull));
-    sel[k] = t;
-    obj_sel[k] = obj[t];
-    sem_sel[k] = v;
-    best_sel[k] = best[t];
+  int done = 0;
+  for (int c0 = 0; c0 < Nq; c0 += 1024) {
+    const int i = c0 + t;
+    const float v = i < Nq ? sem[i] : 0.f;
+    const bool keep = (i < Nq) && (v > thresh);
+    const unsigned long long m = __ballot(keep);
+    if (lane == 0) wcnt[wave] = __popcll(m);
+    __syncthreads();
+    int base = done, tot = 0;
+    for (int w = 0; w < 16; ++w) {
+      if (w < wave) base += wcnt[w];
+      tot += wcnt[w];
+    }
+    if (keep) {
+      const int k = base + __popcll(m & ((1ull << lane) - 1ull));
+      sel[k] = i;
+      obj_sel[k] = obj[i];
+      sem_sel[k] = v;
+      best_sel[k] = best[i];
+    }
+    done += tot;
+    __syncthreads();
   }
-  if (t == 0) {
-    int tot = 0;
-    for (int w = 0; w < 16; ++w) tot += wcnt[w];
-    *nsel = tot;
-  }
+  if (t == 0) *nsel = done;
 }
 
 extern "C" int sam6d_ism_semantic_compact(const float* scores, int Nq, int No, int Nt, int mode, float thresh, float* sem_ws, int* obj_ws,
                                           int* best_ws, long long* sel, long long* obj_sel, float* sem_sel, long long* best_sel, int* nsel,
                                           void* stream) {
-  SAM6D_REQUIRE(scores && sem_ws && obj_ws && best_ws && sel && obj_sel && sem_sel && best_sel && nsel, "ism_semantic_compact: null pointer");
-  SAM6D_REQUIRE(Nq >= 0 && Nq <= 1024 && No > 0 && Nt > 0 && Nt <= 256 && mode >= 0 && mode <= 2,
-                "ism_semantic_compact: need Nq <= 1024, Nt <= 256, mode in {0 avg_5, 1 mean, 2 max}");
+  SAM6D_REQUIRE((scores || Nq == 0) && sem_ws && obj_ws && best_ws && sel && obj_sel && sem_sel && best_sel && nsel, "ism_semantic_compact: null pointer");
+  SAM6D_REQUIRE(Nq >= 0 && Nq <= 65535 && No > 0 && Nt > 0 && Nt <= 256 && mode >= 0 && mode <= 2,
+                "ism_semantic_compact: need Nq <= 65535, Nt <= 256, mode in {0 avg_5, 1 mean, 2 max}");
   hipStream_t s = (hipStream_t)stream;
   if (Nq > 0) hipLaunchKernelGGL(ism_semantic_kernel, dim3(Nq), dim3(64), 0, s, scores, No, Nt, mode, sem_ws, obj_ws, best_ws);
   hipLaunchKernelGGL(ism_select_compact_kernel, dim3(1), dim3(1024), 0, s, sem_ws, obj_ws, best_ws, Nq, thresh, sel, obj_sel, sem_sel,
@@ -186,9 +198,9 @@ extern "C" int sam6d_ism_semantic_compact(const float* scores, int Nq, int No, i
 
 extern "C" int sam6d_ism_semantic(const float* scores, int Nq, int No, int Nt, int mode, float thresh, float* sem, int* obj,
                                   int* best, int* sel, int* nsel, void* stream) {
-  SAM6D_REQUIRE(scores && sem && obj && best && sel && nsel, "ism_semantic: null pointer");
-  SAM6D_REQUIRE(Nq >= 0 && Nq <= 1024 && No > 0 && Nt > 0 && Nt <= 256 && mode >= 0 && mode <= 2,
-                "ism_semantic: need Nq <= 1024, Nt <= 256, mode in {0 avg_5, 1 mean, 2 max}");
+  SAM6D_REQUIRE((scores || Nq == 0) && sem && obj && best && sel && nsel, "ism_semantic: null pointer");
+  SAM6D_REQUIRE(Nq >= 0 && Nq <= 65535 && No > 0 && Nt > 0 && Nt <= 256 && mode >= 0 && mode <= 2,
+                "ism_semantic: need Nq <= 65535, Nt <= 256, mode in {0 avg_5, 1 mean, 2 max}");
   hipStream_t s = (hipStream_t)stream;
   if (Nq > 0) hipLaunchKernelGGL(ism_semantic_kernel, dim3(Nq), dim3(64), 0, s, scores, No, Nt, mode, sem, obj, best);
   hipLaunchKernelGGL(ism_select_kernel, dim3(1), dim3(1024), 0, s, sem, Nq, thresh, sel, nsel);
@@ -471,6 +483,9 @@ extern "C" int sam6d_ism_patch_fused_scores(const void* ws, int Ns, int P, float
 // The projection uses K cast to float32, as detector.py:225 does.
 // ---------------------------------------------------------------------------------------------------------------
 #define ISM_TCH 64  // pixel chunks per proposal
+// Denominator of the mean: the reference's `torch.count_nonzero(valid) + 1e-8` (trimesh_utils.py:98) is an int64 tensor plus a Python
+// float, which torch evaluates in float32 -- the fp32 count plus 1e-8f, equal to the count unless the mask is empty.
+__device__ __forceinline__ double ism_count_eps(double n) { return (double)((float)n + 1e-8f); }
 __global__ __launch_bounds__(256) void ism_translate_partial_kernel(const float* __restrict__ masks, const int* __restrict__ depth,
                                                                     const double* __restrict__ K, double scale, int H, int Wd,
                                                                     double* __restrict__ part) {
@@ -518,7 +533,7 @@ __global__ __launch_bounds__(256) void ism_project_kernel(const double* __restri
         s += part[((size_t)i * nch + c) * 4 + t];
         n += part[((size_t)i * nch + c) * 4 + 3];
       }
-      tr[t] = (float)(s / (n + 1e-8));
+      tr[t] = (float)(s / ism_count_eps(n));
     } else {
       // partials = (sum u md, sum v md, sum md, count) of the masked depth md (ism_translate_fast_kernel; exact: integers below 2^53):
       // sum_p (u - cx) Z / fx with Z = md zscale  =  (sum u md - cx sum md) zscale / fx
@@ -528,7 +543,7 @@ __global__ __launch_bounds__(256) void ism_project_kernel(const double* __restri
         su += q[0]; sv += q[1]; sm += q[2]; n += q[3];
       }
       const double v = t == 0 ? (su - Kd[2] * sm) * zscale / Kd[0] : t == 1 ? (sv - Kd[5] * sm) * zscale / Kd[4] : sm * zscale;
-      tr[t] = (float)(v / (n + 1e-8));
+      tr[t] = (float)(v / ism_count_eps(n));
     }
     translate[i * 3 + t] = tr[t];
   }
@@ -721,7 +736,7 @@ __global__ __launch_bounds__(64) void ism_translate_finish_kernel(const double* 
     s += part[((size_t)i * ISM_TCH + c) * 4 + t];
     n += part[((size_t)i * ISM_TCH + c) * 4 + 3];
   }
-  translate[e] = (float)(s / (n + 1e-8));
+  translate[e] = (float)(s / ism_count_eps(n));
 }
 
 extern "C" int sam6d_ism_translate_maps(const float* masked_depth, const double* K, double depth_scale, int N, int H, int W,
@@ -753,7 +768,7 @@ __global__ void ism_iou_kernel(const int* __restrict__ a, const long long* __res
 __global__ void set_int_kernel(int* p, int v) { *p = v; }
 
 extern "C" int sam6d_ism_iou(const int* xyxy, const long long* boxes, int Ns, float* iou, int* all_positive, void* stream) {
-  SAM6D_REQUIRE(xyxy && boxes && iou && all_positive && Ns >= 0, "ism_iou: bad arguments");
+  SAM6D_REQUIRE(all_positive && Ns >= 0 && (Ns == 0 || (xyxy && boxes && iou)), "ism_iou: bad arguments");  // (no pairs: the flag stays set)
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(set_int_kernel, dim3(1), dim3(1), 0, s, all_positive, 1);
   if (Ns > 0) hipLaunchKernelGGL(ism_iou_kernel, dim3(cdiv(Ns, 256)), dim3(256), 0, s, xyxy, boxes, Ns, iou, all_positive);
@@ -773,16 +788,16 @@ __global__ void ism_final_kernel(const float* __restrict__ sem, const float* __r
 
 extern "C" int sam6d_ism_final_score(const float* sem, const float* appe, const float* geo, const float* vis, const int* sel,
                                      int Ns, float* out, void* stream) {
-  SAM6D_REQUIRE(sem && appe && vis && out && Ns >= 0, "ism_final_score: bad arguments");
-  if (Ns == 0) return 0;
+  if (Ns == 0) return 0;  // (empty tensors have no storage)
+  SAM6D_REQUIRE(sem && appe && vis && out && Ns > 0, "ism_final_score: bad arguments");
   hipLaunchKernelGGL(ism_final_kernel, dim3(cdiv(Ns, 256)), dim3(256), 0, (hipStream_t)stream, sem, appe, geo, vis, sel, Ns, out, nullptr);
   SAM6D_LAUNCH_CHECK("ism_final_score");
 }
 
 extern "C" int sam6d_ism_final_score_flag(const float* sem, const float* appe, const float* geo, const float* vis, const int* all_positive,
                                           int Ns, float* out, void* stream) {
-  SAM6D_REQUIRE(sem && appe && geo && vis && all_positive && out && Ns >= 0, "ism_final_score_flag: bad arguments");
   if (Ns == 0) return 0;
+  SAM6D_REQUIRE(sem && appe && geo && vis && all_positive && out && Ns > 0, "ism_final_score_flag: bad arguments");
   hipLaunchKernelGGL(ism_final_kernel, dim3(cdiv(Ns, 256)), dim3(256), 0, (hipStream_t)stream, sem, appe, geo, vis, nullptr, Ns, out,
                      all_positive);
   SAM6D_LAUNCH_CHECK("ism_final_score_flag");

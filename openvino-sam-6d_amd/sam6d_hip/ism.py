@@ -22,7 +22,8 @@ def pairwise_similarity(query, reference):
 @on_tensor_device
 def semantic_select(scores, aggregation="avg_5", confidence_thresh=0.2):
     """ISM/model/detector.py:265-296 on precomputed scores (Nq,No,Nt).
-    Returns idx_selected (K,) i64, pred_idx_objects (K,) i64, semantic_score (K,), best_template (K,) i64.
+    Returns idx_selected (K,) i64, pred_idx_objects (K,) i64, semantic_score (K,), best_template (K,) i64, survivors in ascending
+    proposal order; any Nq from 0 to 65535 (SAM's 32 x 32 point grid yields up to 3072 raw proposals), Nt <= 256.
     (one host read-back of K, like the reference's boolean-mask indexing which also synchronises)"""
     if aggregation not in _MODES:
         raise NotImplementedError("aggregation_function %r (implemented: avg_5, mean, max)" % aggregation)
@@ -131,7 +132,8 @@ def project_template_to_image(best_pose, pred_obj, poses, pointcloud, masks, dep
     tr = torch.empty(Ns, 3, dtype=torch.float32, device=dev)
     fast = W % 16 == 0 and float(depth_scale) > 0.0
     if not fast:  # general shapes: float32 masks, gathered
-        masks = masks.to(torch.float32)
+        # (one-byte masks mean "non-zero = inside" on either path: 255 is a 1, not a factor of 255 on the depth)
+        masks = (masks != 0).to(torch.float32) if masks.dtype == torch.uint8 else masks.to(torch.float32)
         if mi is not None:
             masks = take_rows(masks, mi)
         part = torch.empty(max(Ns, 1) * 64 * 4, dtype=torch.float64, device=dev)
