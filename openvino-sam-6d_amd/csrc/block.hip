@@ -34,10 +34,8 @@
 #include <stdlib.h>
 #include <type_traits>
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned tb_u4 __attribute__((ext_vector_type(4)));
 typedef unsigned tb_u2 __attribute__((ext_vector_type(2)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 
 // tokens per workgroup = 16 x waves: 64 (4 waves, 2-slot panel ring, two independent workgroups per CU) or 128 (8 waves, 4-slot ring)
 // A panel = 32 weight rows x K (KS k-steps of 32): per row KS*32 hi halves | KS*32 lo halves, NO padding -- instead the 16-byte chunk
@@ -101,16 +99,6 @@ extern "C" int sam6d_pack_panels(const float* W, long ldw, int rows, int k0, int
   SAM6D_LAUNCH_CHECK("pack_panels");
 }
 
-__device__ __forceinline__ float pow2_scale_for(float amax) {
-  // power of two s with amax * s in [2^13, 2^14); 1 for zero / non-finite rows
-  if (!(amax > 0.f) || !(amax < 3.0e38f)) return 1.0f;
-  int e;
-  (void)frexpf(amax, &e);  // amax = m 2^e, m in [0.5, 1)
-  e = 14 - e;
-  e = e > 100 ? 100 : (e < -100 ? -100 : e);
-  return ldexpf(1.0f, e);
-}
-
 // per cloud: kv^T (4 heads x 64 d x 64 c) -> 8 panels of 32 d-rows x K = 64 (head h: panels 2h, 2h+1), every head scaled by its own
 // power of two (from the head's max |kv|); inv[4 b + h] = 1 / scale.
 __global__ __launch_bounds__(256) void tb_kv_pack_kernel(const float* __restrict__ kvT, unsigned char* __restrict__ dst,
@@ -130,7 +118,7 @@ __global__ __launch_bounds__(256) void tb_kv_pack_kernel(const float* __restrict
   __syncthreads();
   float scale[4];
 #pragma unroll
-  for (int hd = 0; hd < 4; ++hd) scale[hd] = pow2_scale_for(fmaxf(fmaxf(red[hd][0], red[hd][1]), fmaxf(red[hd][2], red[hd][3])));
+  for (int hd = 0; hd < 4; ++hd) scale[hd] = pow2_scale(fmaxf(fmaxf(red[hd][0], red[hd][1]), fmaxf(red[hd][2], red[hd][3])));
   if (t < 4) inv[(size_t)b * 4 + t] = 1.0f / (t == 0 ? scale[0] : t == 1 ? scale[1] : t == 2 ? scale[2] : scale[3]);
   unsigned char* out = dst + (size_t)b * (8 * TB_P64);
   for (int i = t; i < 16384; i += 256) {
@@ -259,7 +247,7 @@ __global__ __launch_bounds__(THREADS) void tb_kv_fused_kernel(const float* __res
   float mm = red[0];
 #pragma unroll
   for (int w = 1; w < NW; ++w) mm = fmaxf(mm, red[w]);
-  const float s2 = pow2_scale_for(mm);
+  const float s2 = pow2_scale(mm);
   if (t == 0) inv[(size_t)b * 4 + h] = 1.0f / s2;
   // image: head h, row d -> panel 2 h + (d >> 5), row m = d & 31; channel c sits in slot p = 32 (c >> 5) + 8 g + e of the 64-wide K
   // (tb_slot_channel inverted: g = (c >> 2) & 3, e = 4 ((c >> 4) & 1) + (c & 3))
@@ -380,16 +368,6 @@ __device__ __forceinline__ void tb_mma(f32x4& acc0, f32x4& acc1, unsigned panel,
   tb_mma_step<KS, 0, FD>(acc0, acc1, a, xh, xl, f, half);
 }
 
-// a token's channels live in the four lanes 16 apart (g = lane >> 4): reductions over the token
-__device__ __forceinline__ float tok_max(float m) {
-  m = fmaxf(m, xor16_f32(m));
-  return fmaxf(m, xor32_f32(m));
-}
-__device__ __forceinline__ float tok_sum(float s) {
-  s += xor16_f32(s);
-  return s + xor32_f32(s);
-}
-
 // makes a register value opaque to the optimiser (no instruction): without it the compiler keeps the fp32 images of y's hi / lo
 // halves, computed while splitting, alive across the whole FFN for the second residual (128 VGPRs -> scratch spills)
 __device__ __forceinline__ void tb_opaque(half8& x) {
@@ -406,7 +384,7 @@ __device__ __forceinline__ float tb_split_rows(const f32x4* v, half8* xh, half8*
   for (int t = 0; t < NT; ++t)
 #pragma unroll
     for (int r = 0; r < 4; ++r) m = fmaxf(m, fabsf(v[t][r]));
-  const float sc = pow2_scale_for(tok_max(m));
+  const float sc = pow2_scale(tok_max(m));
 #pragma unroll
   for (int t = 0; t < NT; ++t)
 #pragma unroll
@@ -644,7 +622,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void token_block_kernel(TbArgs a) { 
       m = fmaxf(m, fmaxf(fmaxf(fabsf(va[s].x), fabsf(va[s].y)), fmaxf(fabsf(va[s].z), fabsf(va[s].w))));
       m = fmaxf(m, fmaxf(fmaxf(fabsf(vb[s].x), fabsf(vb[s].y)), fmaxf(fabsf(vb[s].z), fabsf(vb[s].w))));
     }
-    sx = pow2_scale_for(tok_max(m));
+    sx = pow2_scale(tok_max(m));
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
       const float e[8] = {va[s].x, va[s].y, va[s].z, va[s].w, vb[s].x, vb[s].y, vb[s].z, vb[s].w};
@@ -1088,7 +1066,7 @@ __global__ __launch_bounds__(512) void token_tail_kernel(TbArgs a) {
   for (int i = 0; i < RPW; ++i) {
     const int tok = wave * RPW + i;
     const float m = wave_max_dpp(fmaxf(fmaxf(fabsf(xv[i].x), fabsf(xv[i].y)), fmaxf(fabsf(xv[i].z), fabsf(xv[i].w))));
-    const float sx = pow2_scale_for(m);
+    const float sx = pow2_scale(m);
     if (lane == 0) sxs[tok] = sx;
     unsigned h0, l0, h1, l1;
     sam6d_split2_f16(xv[i].x * sx, xv[i].y * sx, h0, l0);
@@ -1131,7 +1109,7 @@ __global__ __launch_bounds__(512) void token_tail_kernel(TbArgs a) {
     xmax(sy, 2);
 #pragma unroll
     for (int tt = 0; tt < TT; ++tt) {
-      const float sc = sy[tt] = pow2_scale_for(sy[tt]);
+      const float sc = sy[tt] = pow2_scale(sy[tt]);
       put(ybl, wave, tt, f32x4{y[0][tt][0] * sc, y[0][tt][1] * sc, y[0][tt][2] * sc, y[0][tt][3] * sc},
           f32x4{y[1][tt][0] * sc, y[1][tt][1] * sc, y[1][tt][2] * sc, y[1][tt][3] * sc});
     }
@@ -1300,7 +1278,7 @@ __global__ __launch_bounds__(512, 1) void rpe_front_kernel(RfArgs a) {
       m = fmaxf(m, fmaxf(fmaxf(fabsf(va[s].x), fabsf(va[s].y)), fmaxf(fabsf(va[s].z), fabsf(va[s].w))));
       m = fmaxf(m, fmaxf(fmaxf(fabsf(vb[s].x), fabsf(vb[s].y)), fmaxf(fabsf(vb[s].z), fabsf(vb[s].w))));
     }
-    sx = pow2_scale_for(tok_max(m));
+    sx = pow2_scale(tok_max(m));
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
       const float e[8] = {va[s].x, va[s].y, va[s].z, va[s].w, vb[s].x, vb[s].y, vb[s].z, vb[s].w};
@@ -1477,7 +1455,7 @@ __global__ __launch_bounds__(256, 2) void out_split_kernel(OsArgs a) {
     for (int s = 0; s < 8; ++s)
 #pragma unroll
       for (int r = 0; r < 4; ++r) m = fmaxf(m, fmaxf(fabsf(va[s][r]), fabsf(vb[s][r])));
-    sx = pow2_scale_for(tok_max(m));
+    sx = pow2_scale(tok_max(m));
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
       const float e[8] = {va[s][0], va[s][1], va[s][2], va[s][3], vb[s][0], vb[s][1], vb[s][2], vb[s][3]};
@@ -1626,7 +1604,7 @@ __global__ __launch_bounds__(512, 1) void rows_linear_kernel(RlArgs a) {
       m = fmaxf(m, fmaxf(fmaxf(fabsf(va[s].x), fabsf(va[s].y)), fmaxf(fabsf(va[s].z), fabsf(va[s].w))));
       m = fmaxf(m, fmaxf(fmaxf(fabsf(vb[s].x), fabsf(vb[s].y)), fmaxf(fabsf(vb[s].z), fabsf(vb[s].w))));
     }
-    sx = pow2_scale_for(tok_max(m));
+    sx = pow2_scale(tok_max(m));
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
       const float e[8] = {va[s].x, va[s].y, va[s].z, va[s].w, vb[s].x, vb[s].y, vb[s].z, vb[s].w};

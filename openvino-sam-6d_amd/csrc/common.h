@@ -44,6 +44,10 @@ void sam6d_set_error(const char* fmt, ...);
   } while (0)
 
 // ---- device helpers ---------------------------------------------------------------------------------------
+typedef float f32x4 __attribute__((ext_vector_type(4)));     // one MFMA accumulator tile per lane
+typedef _Float16 half8 __attribute__((ext_vector_type(8)));  // one fp16 MFMA operand (k = 32) per lane
+typedef _Float16 half4 __attribute__((ext_vector_type(4)));
+
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 __device__ __forceinline__ int wave_id() { return threadIdx.x >> 6; }
 
@@ -101,6 +105,16 @@ __device__ __forceinline__ float wave_max_dpp(float v) {
   v = fmaxf(v, xor16_f32(v));
   v = fmaxf(v, xor32_f32(v));
   return v;
+}
+
+// a token's channels live in the four lanes 16 apart (g = lane >> 4) of an MFMA tile: reductions over the token
+__device__ __forceinline__ float tok_max(float m) {
+  m = fmaxf(m, xor16_f32(m));
+  return fmaxf(m, xor32_f32(m));
+}
+__device__ __forceinline__ float tok_sum(float s) {
+  s += xor16_f32(s);
+  return s + xor32_f32(s);
 }
 
 __device__ __forceinline__ float row16_min_dpp(float v) {
@@ -184,6 +198,18 @@ __device__ __forceinline__ void sam6d_split_f16(float x, _Float16& hi, _Float16&
   asm("" : "+v"(x));
   hi = (_Float16)x;
   lo = (_Float16)(x - (float)hi);
+}
+
+// The range of every split-precision operand: its values are multiplied by pow2_scale(their max |.|) before the split and the product
+// by the inverse afterwards (exact, both are powers of two), so no hi half overflows fp16 and no lo half falls into subnormals.
+__device__ __forceinline__ float pow2_scale(float amax) {
+  // power of two s with amax * s in [2^13, 2^14); 1 for zero / non-finite input
+  if (!(amax > 0.f) || !(amax < 3.0e38f)) return 1.0f;
+  int e;
+  (void)frexpf(amax, &e);  // amax = m 2^e, m in [0.5, 1)
+  e = 14 - e;
+  e = e > 100 ? 100 : (e < -100 ? -100 : e);
+  return ldexpf(1.0f, e);
 }
 
 // The same split for a pair, as four instructions: v_cvt_pk_f16_f32 (hi pair, round to nearest even), two v_fma_mix_f32 (x - hi, exact: the

@@ -4,29 +4,16 @@
 //   crops       (H,W,3) u8 image + (N,H,W) masks + (N,4) boxes -> (N,3,224,224) normalised masked crops and (N,224,224) masks in one
 //               launch: ToTensor + Normalize, times the mask, crop, nearest resize by 224 / max(box side), zero padding, second resize.
 //               A pure gather; every source index is the one torch computes, so the result is bit-exact.
-//   patch rows  (N,3,224,224) -> A (N*256, 608): 588 = 3 x 14 x 14 values in the Conv2d weight's (c, kh, kw) order, then 20 zeros (K is
-//               padded to a multiple of 32 so that every GEMM route, the whole-tile one included, applies; the weight's columns 588..607
-//               are zero too), plus the cls rows cls_token + pos[0] of the residual stream X (N*257, 1024)
-//   LayerNorm   over 1024 channels, rows addressed per image as sam6d_vit_layernorm768 does (the final norm writes x_norm_clstoken and
-//               x_norm_patchtokens straight into their own tensors)
+//   patch rows, LayerNorm: patch_rows_kernel<1024, 14, 608> and rows_layernorm_kernel<1024> of vit.hip (the row kernels of the ViT
+//               encoders), behind sam6d_dino_patch_rows / sam6d_dino_layernorm1024 there
 //   attention   257 tokens, 16 heads of 64: one workgroup per (image, head); see dino_attention_kernel
 // The dense projections are sam6d_gemm_nt / _w16 (fc1 with the erf-GELU epilogue, proj / fc2 with the in-place residual; LayerScale is
 // folded into their weights at pack time).
 #include "common.h"
 #include "../../include/sam6d_hip.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-
 #define DN_C 1024
 #define DN_IMG 224
-#define DN_PATCH 14
-#define DN_GRID 16
-#define DN_PATCHES 256
-#define DN_TOK 257
-#define DN_K 588    // 3 * 14 * 14
-#define DN_KPAD 608 // 19 k-steps of 32
 
 // ---- proposal crops -------------------------------------------------------------------------------------------------------------
 // F.interpolate(x, scale_factor = s) in the default nearest mode: output size floor(in * s) in double, source index
@@ -108,92 +95,6 @@ extern "C" int sam6d_dino_crop_proposals(const unsigned char* image, const float
   SAM6D_LAUNCH_CHECK("dino_crop_proposals");
 }
 
-// ---- patch rows: workgroup (patch p, image b); p == 256 writes the image's cls row of X instead -----------------------------------
-__global__ __launch_bounds__(256) void dino_patch_rows_kernel(const float* __restrict__ img, const float* __restrict__ cls,
-                                                              const float* __restrict__ pos, float* __restrict__ A,
-                                                              float* __restrict__ X) {
-  const int p = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
-  if (p == DN_PATCHES) {
-    float* dst = X + (size_t)b * DN_TOK * DN_C;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) dst[t + 256 * u] = cls[t + 256 * u] + pos[t + 256 * u];
-    return;
-  }
-  const int py = p / DN_GRID, px = p % DN_GRID;
-  float* dst = A + ((size_t)b * DN_PATCHES + p) * DN_KPAD;
-  for (int col = t; col < DN_KPAD; col += 256) {
-    float v = 0.f;
-    if (col < DN_K) {
-      const int c = col / (DN_PATCH * DN_PATCH), k = col % (DN_PATCH * DN_PATCH), kh = k / DN_PATCH, kw = k % DN_PATCH;
-      v = img[(((size_t)b * 3 + c) * DN_IMG + py * DN_PATCH + kh) * DN_IMG + px * DN_PATCH + kw];
-    }
-    dst[col] = v;
-  }
-}
-
-extern "C" int sam6d_dino_patch_rows(const float* img, const float* cls_token, const float* pos_embed, float* A, float* X, int B,
-                                     void* stream) {
-  SAM6D_REQUIRE(img && cls_token && pos_embed && A && X && B >= 0, "dino_patch_rows: null pointer");
-  SAM6D_REQUIRE(B <= 65535, "dino_patch_rows: B <= 65535");
-  if (B == 0) return 0;
-  hipLaunchKernelGGL(dino_patch_rows_kernel, dim3(DN_PATCHES + 1, B), dim3(256), 0, (hipStream_t)stream, img, cls_token, pos_embed, A,
-                     X);
-  SAM6D_LAUNCH_CHECK("dino_patch_rows");
-}
-
-// ---- LayerNorm over 1024 channels: one wave per row, 16 floats per lane (four float4 at 4 lane + 256 u), two-pass mean / variance in
-// registers.  Row r of image b: x + b sx + r ldx -> y + b sy + r ldy, in floats (the row map of vit_layernorm768_kernel).
-__global__ __launch_bounds__(256) void dino_layernorm1024_kernel(const float* __restrict__ x, const float* __restrict__ g,
-                                                                 const float* __restrict__ be, float* __restrict__ y, long total,
-                                                                 int rows, long ldx, long sx, long ldy, long sy, float eps) {
-  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= total) return;
-  const int lane = threadIdx.x & 63;
-  const long b = row / rows, r = row % rows;
-  const float* src = x + b * sx + r * ldx;
-  float* dst = y + b * sy + r * ldy;
-  float4 v[4];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const float4*>(src + 4 * lane + 256 * u);
-  float s = 0.f;
-#pragma unroll
-  for (int u = 0; u < 4; ++u) s += (v[u].x + v[u].y) + (v[u].z + v[u].w);
-  const float mean = wave_sum_dpp(s) * (1.0f / DN_C);
-  float q = 0.f;
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    v[u].x -= mean; v[u].y -= mean; v[u].z -= mean; v[u].w -= mean;
-    q += (v[u].x * v[u].x + v[u].y * v[u].y) + (v[u].z * v[u].z + v[u].w * v[u].w);
-  }
-  const float rstd = 1.0f / sqrtf(wave_sum_dpp(q) * (1.0f / DN_C) + eps);
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const int c = 4 * lane + 256 * u;
-    const float4 gg = *reinterpret_cast<const float4*>(g + c);
-    const float4 bb = *reinterpret_cast<const float4*>(be + c);
-    float4 o;
-    o.x = v[u].x * rstd * gg.x + bb.x;
-    o.y = v[u].y * rstd * gg.y + bb.y;
-    o.z = v[u].z * rstd * gg.z + bb.z;
-    o.w = v[u].w * rstd * gg.w + bb.w;
-    *reinterpret_cast<float4*>(dst + c) = o;
-  }
-}
-
-extern "C" int sam6d_dino_layernorm1024(const float* x, const float* gamma, const float* beta, float* y, int nimg, int rows, long ldx,
-                                        long sx, long ldy, long sy, float eps, void* stream) {
-  SAM6D_REQUIRE(x && gamma && beta && y, "dino_layernorm1024: null pointer");
-  SAM6D_REQUIRE(nimg >= 0 && rows >= 0 && ldx >= DN_C && ldy >= DN_C && sx >= 0 && sy >= 0, "dino_layernorm1024: bad sizes");
-  SAM6D_REQUIRE(((ldx | ldy | sx | sy) & 3) == 0 && ((((size_t)x) | ((size_t)y) | ((size_t)gamma) | ((size_t)beta)) & 15) == 0,
-                "dino_layernorm1024: strides must be multiples of 4 floats and pointers 16-byte aligned");
-  const long total = (long)nimg * rows;
-  if (total == 0) return 0;
-  SAM6D_REQUIRE((total + 3) / 4 < 2147483647L, "dino_layernorm1024: too many rows");
-  hipLaunchKernelGGL(dino_layernorm1024_kernel, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, gamma, beta,
-                     y, total, rows, ldx, sx, ldy, sy, eps);
-  SAM6D_LAUNCH_CHECK("dino_layernorm1024");
-}
-
 // ---- self-attention, up to 272 tokens, 16 heads of 64 ---------------------------------------------------------------------------
 // One workgroup (8 waves) per (image, head), the scheme of xattn.hip's sattn_kernel at 17 key tiles, as a kernel of its own: that
 // kernel's register plan (13 score tiles, 7 probability k-steps and the prefetched next group beside them) and its two-groups-per-wave
@@ -218,22 +119,6 @@ extern "C" int sam6d_dino_layernorm1024(const float* x, const float* gamma, cons
 #define DA_VPLANE (64 * DA_VROW)          // 37 888
 #define DA_LDS (2 * DA_KPLANE + 2 * DA_VPLANE + 64)  // 154 176 bytes of the 160 KiB
 
-__device__ __forceinline__ float da_pow2_scale(float amax) {
-  if (!(amax > 0.f) || !(amax < 3.0e38f)) return 1.0f;
-  int e;
-  (void)frexpf(amax, &e);
-  e = 14 - e;
-  e = e > 100 ? 100 : (e < -100 ? -100 : e);
-  return ldexpf(1.0f, e);
-}
-__device__ __forceinline__ float da_tok_max(float m) {
-  m = fmaxf(m, xor16_f32(m));
-  return fmaxf(m, xor32_f32(m));
-}
-__device__ __forceinline__ float da_tok_sum(float s) {
-  s += xor16_f32(s);
-  return s + xor32_f32(s);
-}
 __device__ __forceinline__ float da_amax4(float4 v) { return fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))); }
 
 __global__ __launch_bounds__(DA_WAVES * 64) void dino_attention_kernel(const float* __restrict__ qkv, float* __restrict__ out, int n) {
@@ -263,8 +148,8 @@ __global__ __launch_bounds__(DA_WAVES * 64) void dino_attention_kernel(const flo
   float sk = 0.f, sv = 0.f;
 #pragma unroll
   for (int w = 0; w < DA_WAVES; ++w) { sk = fmaxf(sk, red[w]); sv = fmaxf(sv, red[8 + w]); }
-  sk = da_pow2_scale(sk);
-  sv = da_pow2_scale(sv);
+  sk = pow2_scale(sk);
+  sv = pow2_scale(sv);
 
   // ---- k_h image: row = key, channel c at byte 2 c; every (key < 272, channel) slot is written (zeros beyond n)
   for (int e = t; e < DA_MAXN * 16; e += DA_WAVES * 64) {
@@ -314,7 +199,7 @@ __global__ __launch_bounds__(DA_WAVES * 64) void dino_attention_kernel(const flo
       qb[ks] = *reinterpret_cast<const float4*>(qsrc + 32 * ks + 8 * fg + 4);
     }
     float qm = fmaxf(fmaxf(da_amax4(qa[0]), da_amax4(qb[0])), fmaxf(da_amax4(qa[1]), da_amax4(qb[1])));
-    const float sq = da_pow2_scale(da_tok_max(qm * 0.125f));
+    const float sq = pow2_scale(tok_max(qm * 0.125f));
     half8 qh[2], ql[2];
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
@@ -354,7 +239,7 @@ __global__ __launch_bounds__(DA_WAVES * 64) void dino_attention_kernel(const flo
         s[i][r] = key < n ? s[i][r] * inv : -INFINITY;
         mx = fmaxf(mx, s[i][r]);
       }
-    mx = da_tok_max(mx);
+    mx = tok_max(mx);
     float sum = 0.f;
 #pragma unroll
     for (int i = 0; i < DA_NT; ++i)
@@ -363,7 +248,7 @@ __global__ __launch_bounds__(DA_WAVES * 64) void dino_attention_kernel(const flo
         s[i][r] = __builtin_amdgcn_exp2f((s[i][r] - mx) * 1.4426950408889634f);
         sum += s[i][r];
       }
-    sum = da_tok_sum(sum);
+    sum = tok_sum(sum);
     const float pscale = 16384.0f / sum;  // probabilities times 2^14 (fp16-safe), the 2^-14 is in inv_v
     half8 ph[DA_VS], pl[DA_VS];
 #pragma unroll

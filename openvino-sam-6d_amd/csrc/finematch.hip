@@ -22,8 +22,6 @@
 #include "../../include/sam6d_hip.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 typedef float fm_f4 __attribute__((ext_vector_type(4)));
 
 #define FM_C 256          // channels

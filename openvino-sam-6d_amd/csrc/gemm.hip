@@ -212,8 +212,6 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const float* __restrict__ 
 // LDS rows are 40 halves (80 B): 16 consecutive rows land on 16 different 16-byte slots of the 256-B bank row, so
 // the ds_read_b128 fragment reads are conflict-free.
 // ---------------------------------------------------------------------------------------------------------------
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 #define H_BK 32
 #define H_LD 40
 

@@ -223,7 +223,6 @@ __global__ __launch_bounds__(256, 2) void geo_embed_kernel(const float4* __restr
 // four row groups, so the max over the 3 angular rows and the final add stay in registers.  proj_d / proj_a arrive
 // pre-split and pre-tiled: Wp[kc][mat][col][40 halves] = 16 hi | 16 lo | 8 pad halves of (W * 1024)[col][16 kc .. +16]
 // (sam6d_split_f16 + a host-side re-tiling at weight-load time); 2^-10 is undone in the epilogue (exact).
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 #define GH_P 64
 #define GH_BK 16
 #define GH_LD 24                        // halves per A row in LDS (48 B)

@@ -140,8 +140,6 @@ __global__ __launch_bounds__(PM_WAVES * 64) void pe_mlp_max_kernel(
 // Persistent waves (3 workgroups of 4 waves per CU) stride over the points; the neighbour indices are loaded two
 // tiles ahead and the gathered coordinates one tile ahead, so the idx -> xyz dependent loads hide behind a tile's MFMAs.
 // ===============================================================================================================
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define PH_WAVES 4
 #define PH_L2 40   // halves per row of the K=32 images (80 B)
 #define PH_L3 72   // halves per row of the K=64 images (144 B = 9 x 16 B: 16 consecutive rows hit 16 different slots)
@@ -152,16 +150,6 @@ __device__ __forceinline__ int pe_swap23(int k) { return (k & ~12) | ((k & 4) <<
 // BN(eval) + ReLU + fp16 hi/lo split of the 8 accumulator registers [8*half, 8*half + 8) of one transposed tile; the
 // channels of those registers are base + 8*g + 4*fk + e (g = 2*half + (j>>2), e = j&3): two 16-byte constant reads each.
 // PRE: the accumulators are first multiplied by `pre` (layer 1: the inverse of this lane's feature scale times the inverse W1 scale).
-__device__ __forceinline__ float pe_pow2_scale(float amax) {
-  // power of two s with amax * s in [2^13, 2^14); 1 for zero / non-finite input
-  if (!(amax > 0.f) || !(amax < 3.0e38f)) return 1.0f;
-  int e;
-  (void)frexpf(amax, &e);
-  e = 14 - e;
-  e = e > 100 ? 100 : (e < -100 ? -100 : e);
-  return ldexpf(1.0f, e);
-}
-
 template <bool PRE = false>
 __device__ __forceinline__ void pe_split8(const f32x16& acc, int half, const float* __restrict__ sc, const float* __restrict__ sh,
                                           int fk, half8& hi, half8& lo, float pre = 1.0f) {
@@ -216,7 +204,7 @@ __global__ __launch_bounds__(PH_WAVES * 64) __attribute__((amdgpu_waves_per_eu(3
     w1max = m;
   }
   __syncthreads();
-  const float w1scale = pe_pow2_scale(w1max), w1inv = 1.0f / w1scale;
+  const float w1scale = pow2_scale(w1max), w1inv = 1.0f / w1scale;
   for (int e = t; e < 32 * 6; e += PH_WAVES * 64) w1s[(e / 6) * 7 + (e % 6)] = W1[e] * w1scale;
   for (int e = t; e < 64 * 32; e += PH_WAVES * 64) {
     const float v = W2[e];

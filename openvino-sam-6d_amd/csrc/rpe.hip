@@ -19,7 +19,6 @@
 #include "common.h"
 #include "../../include/sam6d_hip.h"
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f2 __attribute__((ext_vector_type(2)));
 typedef unsigned u2 __attribute__((ext_vector_type(2)));
@@ -29,7 +28,6 @@ typedef unsigned u2 __attribute__((ext_vector_type(2)));
 #define RP_MAXM 256
 #define RP_K 32
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 template <int CTRL>
 __device__ __forceinline__ float dpp_mov(float x) {

@@ -1,85 +1,110 @@
-// The ViT-B/16 image encoder of PEM's feature extraction (PEM/model/feature_extraction.py:21-35 ViT.forward, :98-118 ViT_AE.forward,
-// :141-142 get_img_feats, PEM/utils/model_utils.py:86-98 get_chosen_pixel_feats) around the library's GEMMs and attention:
-//   patch rows  (B,3,224,224) -> A (B*196, 768) in the Conv2d weight's (c, kh, kw) order, plus the cls rows cls_token + pos_embed[0]
-//               of the residual stream X (B*197, 768); the patch GEMM (sam6d_gemm_nt_w16) adds the conv bias and pos_embed[1:]
-//   LayerNorm   over 768 channels (eps as given: 1e-6 for the ViT), rows addressed per image, so the same kernel writes the four
-//               pyramid taps straight into the (B*196, 3072) concat buffer at column 768 j (the cls rows are skipped)
+// The row kernels of the ViT encoders: what PEM's ViT-B/16 (PEM/model/feature_extraction.py:21-35 ViT.forward, :98-118 ViT_AE.forward,
+// :141-142 get_img_feats, PEM/utils/model_utils.py:86-98 get_chosen_pixel_feats) and ISM's DINOv2 ViT-L/14 (dinov2.hip) run around the
+// library's GEMMs and attention.  One template each, instantiated per encoder:
+//   patch rows  (B,3,224,224) -> A (B*NP, KPAD): the 3 P P values of a patch in the Conv2d weight's (c, kh, kw) order, zeros from there
+//               to KPAD (K padded to a multiple of the GEMM's 32-wide k-step: ViT-B 768 = 768, DINOv2 588 -> 608, the packed weight's
+//               columns 588..607 are zero too), plus the cls rows cls_token + pos_embed[0] of the residual stream X (B*(NP+1), C); the
+//               patch GEMM (sam6d_gemm_nt_w16) adds the conv bias and pos_embed[1:]
+//   LayerNorm   over C = 768 or 1024 channels (eps as given: 1e-6 for both), rows addressed per image, so the same kernel writes the
+//               four pyramid taps straight into the (B*196, 3072) concat buffer at column 768 j (the cls rows are skipped), and
+//               DINOv2's x_norm_clstoken / x_norm_patchtokens into their own tensors
+// and, for ViT-B alone:
 //   gather      output_upscaling output U (B*196, 4096) -> bilinear 56 -> 224 -> chosen pixels (B, N, 256): only the four taps of
 //               each chosen pixel are read; the (B, 256, 224, 224) map is never formed
 // The attention (sam6d_vit_attention) is the RPE self-attention kernel of xattn.hip in the ViT layout; the GELU of fc1 is the GEMM's
 // act = 2 epilogue (gemm.hip).
 //
-// All three kernels here are memory-bound data movement (no MFMA).  Resource use (-Rpass-analysis=kernel-resource-usage, gfx950):
-//   vit_patch_rows_kernel         11 VGPRs, 0 spill, 0 B LDS, occupancy 8 waves / SIMD      (B = 32: 12 us)
-//   vit_layernorm768_kernel       54 VGPRs, 0 spill, 0 B LDS, occupancy 8 waves / SIMD      (B = 32: 8 us per launch, ~20 MB moved)
-//   vit_upsample_gather_kernel    30 VGPRs, 0 spill, 0 B LDS, occupancy 8 waves / SIMD      (B = 32, N = 2048: 42 us)
+// All kernels here are memory-bound data movement (no MFMA).  Resource use (-Rpass-analysis=kernel-resource-usage, gfx950):
+//   patch_rows_kernel<768, 16, 768>     8 VGPRs, 0 spill, 0 B LDS, occupancy 8 waves / SIMD      (B = 32: 12 us)
+//   patch_rows_kernel<1024, 14, 608>   14 VGPRs, 0 spill, 0 B LDS, occupancy 8 waves / SIMD
+//   rows_layernorm_kernel<768>        54 VGPRs, 0 spill, 0 B LDS, occupancy 8 waves / SIMD      (B = 32: 8 us per launch, ~20 MB moved)
+//   rows_layernorm_kernel<1024>       60 VGPRs, 0 spill, 0 B LDS, occupancy 8 waves / SIMD
+//   vit_upsample_gather_kernel        30 VGPRs, 0 spill, 0 B LDS, occupancy 8 waves / SIMD      (B = 32, N = 2048: 42 us)
 //   sattn_kernel<true> (xattn.hip) 153 VGPRs, 0 spill, 118 848 B dynamic LDS, 1 workgroup / CU (B = 32: 384 workgroups, 40 us)
 #include "common.h"
 #include "../../include/sam6d_hip.h"
 
-#define VIT_C 768
 #define VIT_IMG 224
 #define VIT_GRID 14
 #define VIT_PATCHES 196
-#define VIT_TOK 197
 
-// ---- patch rows: workgroup (patch p, image b); p == 196 writes the image's cls row of X instead -------------------------------
-__global__ __launch_bounds__(256) void vit_patch_rows_kernel(const float* __restrict__ img, const float* __restrict__ cls,
-                                                             const float* __restrict__ pos, float* __restrict__ A,
-                                                             float* __restrict__ X) {
+// ---- patch rows of an encoder of width C with P x P patches: workgroup (patch p, image b); p == NP writes the image's cls row of X
+// instead ---------------------------------------------------------------------------------------------------------------------------
+template <int C, int P, int KPAD>
+__global__ __launch_bounds__(256) void patch_rows_kernel(const float* __restrict__ img, const float* __restrict__ cls,
+                                                         const float* __restrict__ pos, float* __restrict__ A, float* __restrict__ X) {
+  constexpr int GRID = VIT_IMG / P, NP = GRID * GRID, K = 3 * P * P;
+  static_assert(C % 256 == 0 && VIT_IMG % P == 0 && KPAD >= K, "patch_rows_kernel: bad instantiation");
   const int p = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
-  if (p == VIT_PATCHES) {
-    float* dst = X + (size_t)b * VIT_TOK * VIT_C;
+  if (p == NP) {
+    float* dst = X + (size_t)b * (NP + 1) * C;
 #pragma unroll
-    for (int u = 0; u < 3; ++u) dst[t + 256 * u] = cls[t + 256 * u] + pos[t + 256 * u];
+    for (int u = 0; u < C / 256; ++u) dst[t + 256 * u] = cls[t + 256 * u] + pos[t + 256 * u];
     return;
   }
-  const int py = p / VIT_GRID, px = p % VIT_GRID;
-  float* dst = A + ((size_t)b * VIT_PATCHES + p) * VIT_C;
-#pragma unroll
-  for (int u = 0; u < 3; ++u) {
-    const int col = t + 256 * u, c = col >> 8, kh = (col >> 4) & 15, kw = col & 15;  // column = c * 256 + kh * 16 + kw
-    dst[col] = img[(((size_t)b * 3 + c) * VIT_IMG + py * 16 + kh) * VIT_IMG + px * 16 + kw];
+  const int py = p / GRID, px = p % GRID;
+  float* dst = A + ((size_t)b * NP + p) * KPAD;
+  for (int col = t; col < KPAD; col += 256) {  // column = (c P + kh) P + kw
+    float v = 0.f;
+    if (col < K) {
+      const int c = col / (P * P), k = col % (P * P), kh = k / P, kw = k % P;
+      v = img[(((size_t)b * 3 + c) * VIT_IMG + py * P + kh) * VIT_IMG + px * P + kw];
+    }
+    dst[col] = v;
   }
+}
+
+template <int C, int P, int KPAD>
+static int patch_rows(const char* name, const float* img, const float* cls_token, const float* pos_embed, float* A, float* X, int B,
+                      void* stream) {
+  SAM6D_REQUIRE(img && cls_token && pos_embed && A && X && B >= 0, "%s: null pointer", name);
+  SAM6D_REQUIRE(B <= 65535, "%s: B <= 65535", name);
+  if (B == 0) return 0;
+  constexpr int NP = (VIT_IMG / P) * (VIT_IMG / P);
+  hipLaunchKernelGGL((patch_rows_kernel<C, P, KPAD>), dim3(NP + 1, B), dim3(256), 0, (hipStream_t)stream, img, cls_token, pos_embed, A,
+                     X);
+  SAM6D_LAUNCH_CHECK(name);
 }
 
 extern "C" int sam6d_vit_patch_rows(const float* img, const float* cls_token, const float* pos_embed, float* A, float* X, int B,
                                     void* stream) {
-  SAM6D_REQUIRE(img && cls_token && pos_embed && A && X && B >= 0, "vit_patch_rows: null pointer");
-  SAM6D_REQUIRE(B <= 65535, "vit_patch_rows: B <= 65535");
-  if (B == 0) return 0;
-  hipLaunchKernelGGL(vit_patch_rows_kernel, dim3(VIT_PATCHES + 1, B), dim3(256), 0, (hipStream_t)stream, img, cls_token, pos_embed, A,
-                     X);
-  SAM6D_LAUNCH_CHECK("vit_patch_rows");
+  return patch_rows<768, 16, 768>("vit_patch_rows", img, cls_token, pos_embed, A, X, B, stream);
+}
+extern "C" int sam6d_dino_patch_rows(const float* img, const float* cls_token, const float* pos_embed, float* A, float* X, int B,
+                                     void* stream) {
+  return patch_rows<1024, 14, 608>("dino_patch_rows", img, cls_token, pos_embed, A, X, B, stream);
 }
 
-// ---- LayerNorm over 768 channels: one wave per row, 12 floats per lane (three float4 at 4 lane + 256 u), two-pass mean / variance
-// in registers.  Row r of image b: x + (b sx + r) ldx -> y + (b sy + r) ldy.
-__global__ __launch_bounds__(256) void vit_layernorm768_kernel(const float* __restrict__ x, const float* __restrict__ g,
-                                                               const float* __restrict__ be, float* __restrict__ y, long total,
-                                                               int rows, long ldx, long sx, long ldy, long sy, float eps) {
+// ---- LayerNorm over C channels: one wave per row, C / 64 floats per lane (C / 256 float4 at 4 lane + 256 u), two-pass mean / variance
+// in registers.  Row r of image b: x + b sx + r ldx -> y + b sy + r ldy, in floats.
+template <int C>
+__global__ __launch_bounds__(256) void rows_layernorm_kernel(const float* __restrict__ x, const float* __restrict__ g,
+                                                             const float* __restrict__ be, float* __restrict__ y, long total, int rows,
+                                                             long ldx, long sx, long ldy, long sy, float eps) {
+  constexpr int U = C / 256;
+  static_assert(C % 256 == 0, "rows_layernorm_kernel: C must be a multiple of 256");
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= total) return;
   const int lane = threadIdx.x & 63;
   const long b = row / rows, r = row % rows;
   const float* src = x + b * sx + r * ldx;
   float* dst = y + b * sy + r * ldy;
-  float4 v[3];
+  float4 v[U];
 #pragma unroll
-  for (int u = 0; u < 3; ++u) v[u] = *reinterpret_cast<const float4*>(src + 4 * lane + 256 * u);
+  for (int u = 0; u < U; ++u) v[u] = *reinterpret_cast<const float4*>(src + 4 * lane + 256 * u);
   float s = 0.f;
 #pragma unroll
-  for (int u = 0; u < 3; ++u) s += (v[u].x + v[u].y) + (v[u].z + v[u].w);
-  const float mean = wave_sum_dpp(s) * (1.0f / VIT_C);
+  for (int u = 0; u < U; ++u) s += (v[u].x + v[u].y) + (v[u].z + v[u].w);
+  const float mean = wave_sum_dpp(s) * (1.0f / C);
   float q = 0.f;
 #pragma unroll
-  for (int u = 0; u < 3; ++u) {
+  for (int u = 0; u < U; ++u) {
     v[u].x -= mean; v[u].y -= mean; v[u].z -= mean; v[u].w -= mean;
     q += (v[u].x * v[u].x + v[u].y * v[u].y) + (v[u].z * v[u].z + v[u].w * v[u].w);
   }
-  const float rstd = 1.0f / sqrtf(wave_sum_dpp(q) * (1.0f / VIT_C) + eps);
+  const float rstd = 1.0f / sqrtf(wave_sum_dpp(q) * (1.0f / C) + eps);
 #pragma unroll
-  for (int u = 0; u < 3; ++u) {
+  for (int u = 0; u < U; ++u) {
     const int c = 4 * lane + 256 * u;
     const float4 gg = *reinterpret_cast<const float4*>(g + c);
     const float4 bb = *reinterpret_cast<const float4*>(be + c);
@@ -92,18 +117,28 @@ __global__ __launch_bounds__(256) void vit_layernorm768_kernel(const float* __re
   }
 }
 
-extern "C" int sam6d_vit_layernorm768(const float* x, const float* gamma, const float* beta, float* y, int nimg, int rows, long ldx,
-                                      long sx, long ldy, long sy, float eps, void* stream) {
-  SAM6D_REQUIRE(x && gamma && beta && y, "vit_layernorm768: null pointer");
-  SAM6D_REQUIRE(nimg >= 0 && rows >= 0 && ldx >= VIT_C && ldy >= VIT_C && sx >= 0 && sy >= 0, "vit_layernorm768: bad sizes");
+template <int C>
+static int rows_layernorm(const char* name, const float* x, const float* gamma, const float* beta, float* y, int nimg, int rows, long ldx,
+                          long sx, long ldy, long sy, float eps, void* stream) {
+  SAM6D_REQUIRE(x && gamma && beta && y, "%s: null pointer", name);
+  SAM6D_REQUIRE(nimg >= 0 && rows >= 0 && ldx >= C && ldy >= C && sx >= 0 && sy >= 0, "%s: bad sizes", name);
   SAM6D_REQUIRE(((ldx | ldy | sx | sy) & 3) == 0 && ((((size_t)x) | ((size_t)y) | ((size_t)gamma) | ((size_t)beta)) & 15) == 0,
-                "vit_layernorm768: strides must be multiples of 4 floats and pointers 16-byte aligned");
+                "%s: strides must be multiples of 4 floats and pointers 16-byte aligned", name);
   const long total = (long)nimg * rows;
   if (total == 0) return 0;
-  SAM6D_REQUIRE((total + 3) / 4 < 2147483647L, "vit_layernorm768: too many rows");
-  hipLaunchKernelGGL(vit_layernorm768_kernel, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, y,
+  SAM6D_REQUIRE((total + 3) / 4 < 2147483647L, "%s: too many rows", name);
+  hipLaunchKernelGGL(rows_layernorm_kernel<C>, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, y,
                      total, rows, ldx, sx, ldy, sy, eps);
-  SAM6D_LAUNCH_CHECK("vit_layernorm768");
+  SAM6D_LAUNCH_CHECK(name);
+}
+
+extern "C" int sam6d_vit_layernorm768(const float* x, const float* gamma, const float* beta, float* y, int nimg, int rows, long ldx,
+                                      long sx, long ldy, long sy, float eps, void* stream) {
+  return rows_layernorm<768>("vit_layernorm768", x, gamma, beta, y, nimg, rows, ldx, sx, ldy, sy, eps, stream);
+}
+extern "C" int sam6d_dino_layernorm1024(const float* x, const float* gamma, const float* beta, float* y, int nimg, int rows, long ldx,
+                                        long sx, long ldy, long sy, float eps, void* stream) {
+  return rows_layernorm<1024>("dino_layernorm1024", x, gamma, beta, y, nimg, rows, ldx, sx, ldy, sy, eps, stream);
 }
 
 // ---- output_upscaling -> bilinear (56 -> 224, align_corners = False) -> chosen pixels.

@@ -20,8 +20,6 @@
 #include <type_traits>
 #include "../../include/sam6d_hip.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 
 #define XA_MAXKEY 208     // 13 key tiles of 16
 #define XA_NT 13
@@ -33,23 +31,6 @@ typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 
 // slot p (0..31) of a 32-wide k-step <-> channel (see block.hip): channel = 16 (e >> 2) + 4 g + (e & 3), p = 8 g + e
 __device__ __forceinline__ int xa_channel_slot(int c) { return 8 * ((c >> 2) & 3) + 4 * (c >> 4) + (c & 3); }
-
-__device__ __forceinline__ float xa_pow2_scale(float amax) {
-  if (!(amax > 0.f) || !(amax < 3.0e38f)) return 1.0f;
-  int e;
-  (void)frexpf(amax, &e);
-  e = 14 - e;
-  e = e > 100 ? 100 : (e < -100 ? -100 : e);
-  return ldexpf(1.0f, e);
-}
-__device__ __forceinline__ float xa_tok_max(float m) {
-  m = fmaxf(m, xor16_f32(m));
-  return fmaxf(m, xor32_f32(m));
-}
-__device__ __forceinline__ float xa_tok_sum(float s) {
-  s += xor16_f32(s);
-  return s + xor32_f32(s);
-}
 
 // acc (16 out rows x 16 tokens) += W[rows r0 .. r0+16) . X over KS k-steps.  Image rows are ROWB bytes: hi plane then lo plane (LOCH
 // 16-byte chunks further), chunk c stored at (c & ~15) | ((c ^ row) & 15).
@@ -130,7 +111,7 @@ __device__ __forceinline__ float xa_load_rows(const float* __restrict__ base, in
     mx = fmaxf(mx, fmaxf(fmaxf(fabsf(va[s].x), fabsf(va[s].y)), fmaxf(fabsf(va[s].z), fabsf(va[s].w))));
     mx = fmaxf(mx, fmaxf(fmaxf(fabsf(vb4[s].x), fabsf(vb4[s].y)), fmaxf(fabsf(vb4[s].z), fabsf(vb4[s].w))));
   }
-  const float sx = xa_pow2_scale(xa_tok_max(mx));
+  const float sx = pow2_scale(tok_max(mx));
 #pragma unroll
   for (int s = 0; s < 8; ++s) {
     const float e8[8] = {va[s].x, va[s].y, va[s].z, va[s].w, vb4[s].x, vb4[s].y, vb4[s].z, vb4[s].w};
@@ -223,8 +204,8 @@ __global__ __launch_bounds__(XA_WAVES * 64) void xattn_kernel(XaArgs a) {
     dma64(a.wq + (size_t)h * XA_WQ_BYTES, regA);
 #pragma unroll
     for (int w = 0; w < XA_WAVES; ++w) { sk = fmaxf(sk, red[w]); sv = fmaxf(sv, red[8 + w]); }
-    sk = xa_pow2_scale(sk);
-    sv = xa_pow2_scale(sv);
+    sk = pow2_scale(sk);
+    sv = pow2_scale(sv);
     // k_h image rows of this wave's tokens, over the Wv image (rows >= m are never read unmasked)
 #pragma unroll
     for (int gi = 0; gi < 2; ++gi) {
@@ -271,8 +252,8 @@ __global__ __launch_bounds__(XA_WAVES * 64) void xattn_kernel(XaArgs a) {
     __syncthreads();
 #pragma unroll
     for (int w = 0; w < XA_WAVES; ++w) { sk = fmaxf(sk, red[w]); sv = fmaxf(sv, red[8 + w]); }
-    sk = xa_pow2_scale(sk);
-    sv = xa_pow2_scale(sv);
+    sk = pow2_scale(sk);
+    sv = pow2_scale(sv);
     // k_h image: every (key < 208, channel) slot is written (zeros beyond m), so no separate clearing pass
 #pragma unroll
     for (int i = 0; i < XA_EPT; ++i) {
@@ -317,7 +298,7 @@ __global__ __launch_bounds__(XA_WAVES * 64) void xattn_kernel(XaArgs a) {
           mx = fmaxf(mx, fmaxf(fmaxf(fabsf(va[s].x), fabsf(va[s].y)), fmaxf(fabsf(va[s].z), fabsf(va[s].w))));
           mx = fmaxf(mx, fmaxf(fmaxf(fabsf(vb4[s].x), fabsf(vb4[s].y)), fmaxf(fabsf(vb4[s].z), fabsf(vb4[s].w))));
         }
-        const float sx = xa_pow2_scale(xa_tok_max(mx));
+        const float sx = pow2_scale(tok_max(mx));
 #pragma unroll
         for (int s = 0; s < 8; ++s) {
           const float e8[8] = {va[s].x, va[s].y, va[s].z, va[s].w, vb4[s].x, vb4[s].y, vb4[s].z, vb4[s].w};
@@ -347,7 +328,7 @@ __global__ __launch_bounds__(XA_WAVES * 64) void xattn_kernel(XaArgs a) {
           acc[i][3] = acc[i][3] * inv + bb.w * 0.125f;
           qm = fmaxf(qm, fmaxf(fmaxf(fabsf(acc[i][0]), fabsf(acc[i][1])), fmaxf(fabsf(acc[i][2]), fabsf(acc[i][3]))));
         }
-        sq[gi] = xa_pow2_scale(xa_tok_max(qm));
+        sq[gi] = pow2_scale(tok_max(qm));
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -424,7 +405,7 @@ __global__ __launch_bounds__(XA_WAVES * 64) void xattn_kernel(XaArgs a) {
           s[i][r] = key < m ? s[i][r] * inv : -INFINITY;
           mx = fmaxf(mx, s[i][r]);
         }
-      mx = xa_tok_max(mx);
+      mx = tok_max(mx);
       float sum = 0.f;
 #pragma unroll
       for (int i = 0; i < XA_NT; ++i)
@@ -433,7 +414,7 @@ __global__ __launch_bounds__(XA_WAVES * 64) void xattn_kernel(XaArgs a) {
           s[i][r] = __builtin_amdgcn_exp2f((s[i][r] - mx) * 1.4426950408889634f);
           sum += s[i][r];
         }
-      sum = xa_tok_sum(sum);
+      sum = tok_sum(sum);
       const float pscale = 16384.0f / sum;  // probabilities times 2^14 (<= 2^14: fp16-safe), the 2^-14 is in inv_v
       half8 ph[7], pl[7];
 #pragma unroll
@@ -674,8 +655,8 @@ __global__ __launch_bounds__(XA_WAVES * 64) void sattn_kernel(SaArgs a) {
   float sk = 0.f, sv = 0.f;
 #pragma unroll
   for (int w = 0; w < XA_WAVES; ++w) { sk = fmaxf(sk, red[w]); sv = fmaxf(sv, red[8 + w]); }
-  sk = xa_pow2_scale(sk);
-  sv = xa_pow2_scale(sv);
+  sk = pow2_scale(sk);
+  sv = pow2_scale(sv);
   typedef unsigned sa_u2 __attribute__((ext_vector_type(2)));
   // k_h image: channels 4 c .. 4 c + 3 of key j are four consecutive slots (8 bytes) of its row; every (key < 208, channel) slot is
   // written (zeros beyond m)
@@ -727,7 +708,7 @@ __global__ __launch_bounds__(XA_WAVES * 64) void sattn_kernel(SaArgs a) {
         qm = fmaxf(qm, fmaxf(fmaxf(fabsf(u.x), fabsf(u.y)), fmaxf(fabsf(u.z), fabsf(u.w))));
         qm = fmaxf(qm, fmaxf(fmaxf(fabsf(w.x), fabsf(w.y)), fmaxf(fabsf(w.z), fabsf(w.w))));
       }
-      const float sq = xa_pow2_scale(xa_tok_max(qm * 0.125f));
+      const float sq = pow2_scale(tok_max(qm * 0.125f));
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {
         const float e8[8] = {qa[gi][s2].x, qa[gi][s2].y, qa[gi][s2].z, qa[gi][s2].w, qb[gi][s2].x, qb[gi][s2].y, qb[gi][s2].z, qb[gi][s2].w};
@@ -761,7 +742,7 @@ __global__ __launch_bounds__(XA_WAVES * 64) void sattn_kernel(SaArgs a) {
           mx = fmaxf(mx, s[i][r]);
         }
       }
-      mx = xa_tok_max(mx);
+      mx = tok_max(mx);
       float sum = 0.f;
 #pragma unroll
       for (int i = 0; i < XA_NT; ++i)
@@ -770,7 +751,7 @@ __global__ __launch_bounds__(XA_WAVES * 64) void sattn_kernel(SaArgs a) {
           s[i][r] = __builtin_amdgcn_exp2f((s[i][r] - mx) * 1.4426950408889634f);
           sum += s[i][r];
         }
-      sum = xa_tok_sum(sum);
+      sum = tok_sum(sum);
       const float pscale = 16384.0f / sum;  // probabilities times 2^14 (fp16-safe), the 2^-14 is in inv_v
       half8 ph[7], pl[7];
 #pragma unroll

@@ -2,8 +2,8 @@
 (ISM/model/dinov2.py:115-326 CustomDINOv2, ISM/utils/bbox_utils.py:89-126, ISM/model/vision_transformer.py:179-266, ISM/model/layers).
 torch provides device buffers only (and, once at pack time on the host, the bicubic interpolation of the position embedding).
 
-Layout: the residual stream is X (N*257, 1024) fp32, row 0 of each image the cls token.  Per block:
-    LN1 -> qkv GEMM -> attention -> proj GEMM (+ X, in place) -> LN2 -> fc1 GEMM (GELU) -> fc2 GEMM (+ X, in place)
+The encoder itself (patch embedding, blocks, LayerNorm launches) is encoder.py's, described by ENC below: the residual stream is
+X (N*257, 1024) fp32, row 0 of each image the cls token.
 LayerScale (ls1.gamma, ls2.gamma) is folded into the rows of proj / fc2 and their biases at pack time: gamma * (W y + b) =
 (gamma W) y + gamma b, so the GEMMs with the in-place residual are the ones the ViT-B encoder uses.  The patch GEMM reads K = 608
 columns: the 588 = 3 x 14 x 14 values of a patch and 20 zeros in both operands, so that K is a multiple of the 32-wide k-step and every
@@ -18,8 +18,8 @@ import math
 import torch
 import torch.nn.functional as F
 
-from . import _lib
-from .pem import Linear, _empty, _flags, _getter, _p, _s, gemm, on_tensor_device
+from . import _lib, encoder
+from .pem import Linear, _empty, _getter, _p, _s, on_tensor_device
 
 D = 1024       # embed_dim of vit_large
 HEADS = 16
@@ -35,6 +35,8 @@ KPAD = 608              # ... padded to 19 k-steps of 32
 EPS = 1e-6              # partial(nn.LayerNorm, eps=1e-6)
 SLICE = 64              # images per pass of the encoder (see the module docstring)
 MAXN = 272              # sam6d_dino_attention's token limit
+ENC = encoder.Encoder("sam6d_hip.dinov2", "descriptor model", D, HID, DEPTH, NP, NT, KPAD, EPS, "sam6d_dino_patch_rows",
+                      "sam6d_dino_layernorm1024", "sam6d_dino_attention")
 
 
 def interpolate_pos_embed(pos_embed, grid=GRID, offset=0.1):
@@ -97,7 +99,7 @@ def check_state_dict(sd):
         raise NotImplementedError("sam6d_hip.dinov2: pos_embed must hold a square patch grid, got %d positions" % n)
 
 
-class DinoWeights:
+class DinoWeights(encoder.Weights):
     """A dinov2_vitl14 state dict (with or without a `model.` prefix) packed once: the patch conv as a (1024, 608) matrix in
     (c, kh, kw) column order with zero columns 588..607, qkv / proj / fc1 / fc2 of the 24 blocks as Linear objects (fp32 + the pre-split
     fp16 halves of the w16 GEMM route) with LayerScale folded into proj and fc2, the norms, cls_token and the position embedding
@@ -112,44 +114,21 @@ class DinoWeights:
         self.options = options
         g = _getter(sd, dev)
         g64 = lambda k: sd[k].detach().to(device="cpu", dtype=torch.float64)  # noqa: E731
-        with torch.cuda.device(dev) if dev.type == "cuda" else _nullctx():
+        f32 = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()  # noqa: E731
+
+        def fold(lin, ls):  # in float64, rounded to fp32 once
+            return map(f32, fold_layerscale(g64(lin + ".weight"), g64(lin + ".bias"), g64(ls + ".gamma")))
+
+        with encoder.device_of(dev):
             pw = torch.zeros((D, KPAD), dtype=torch.float32, device=dev)
             pw[:, :KP] = g("patch_embed.proj.weight").reshape(D, KP)
             self.patch = Linear(pw, g("patch_embed.proj.bias"))
             self.cls = g("cls_token").reshape(D)
             self.pos_full = interpolate_pos_embed(sd["pos_embed"].detach().to("cpu"))  # (1, 257, 1024), host
             self.pos = self.pos_full.to(device=dev, dtype=torch.float32).reshape(NT * D).contiguous()
-            self.blocks = []
-            for i in range(DEPTH):
-                b = "blocks.%d." % i
-                # the fold in float64, rounded to fp32 once
-                pw_, pb_ = fold_layerscale(g64(b + "attn.proj.weight"), g64(b + "attn.proj.bias"), g64(b + "ls1.gamma"))
-                fw_, fb_ = fold_layerscale(g64(b + "mlp.fc2.weight"), g64(b + "mlp.fc2.bias"), g64(b + "ls2.gamma"))
-                f32 = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()  # noqa: E731
-                self.blocks.append(dict(
-                    n1=(g(b + "norm1.weight"), g(b + "norm1.bias")),
-                    qkv=Linear(g(b + "attn.qkv.weight"), g(b + "attn.qkv.bias")),
-                    proj=Linear(f32(pw_), f32(pb_)),
-                    n2=(g(b + "norm2.weight"), g(b + "norm2.bias")),
-                    fc1=Linear(g(b + "mlp.fc1.weight"), g(b + "mlp.fc1.bias")),
-                    fc2=Linear(f32(fw_), f32(fb_))))
+            self.blocks = [encoder.pack_block(g, "blocks.%d." % i, fold) for i in range(ENC.depth)]
             self.norm = (g("norm.weight"), g("norm.bias"))
-            if dev.type == "cuda":
-                for lin in self.linears():
-                    lin.w16()  # the fp16 halves, cut once here
-
-    def linears(self):
-        yield self.patch
-        for b in self.blocks:
-            yield from (b["qkv"], b["proj"], b["fc1"], b["fc2"])
-
-
-class _nullctx:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
+            self.cut_w16()
 
 
 def check_images(images):
@@ -159,37 +138,6 @@ def check_images(images):
         raise NotImplementedError("sam6d_hip.dinov2: only 224 x 224 images are implemented, got %d x %d" % tuple(images.shape[2:]))
     if images.dtype != torch.float32:
         raise ValueError("sam6d_hip.dinov2: images must be float32, got %s" % images.dtype)
-
-
-def _require_mode():
-    if _flags().mode == 2:
-        raise NotImplementedError("sam6d_hip.dinov2: matmul mode 2 is not implemented for the descriptor model (modes 0 and 1 are)")
-
-
-# ------------------------------------------------------------------------------------------------- launches
-def _ln(x, gb, y, nimg, rows, ldx, sx, ldy, sy, x_off=0, y_off=0):
-    _lib.call("sam6d_dino_layernorm1024", _p(x, x_off), _p(gb[0]), _p(gb[1]), _p(y, y_off), nimg, rows, ldx, sx, ldy, sy, EPS, _s())
-
-
-def _embed(images, W, X, A):
-    """X (B*257, 1024) = [cls_token; patch_embed(images)] + pos; A (>= B*256*608 floats) is the patch-row workspace."""
-    B = images.shape[0]
-    _lib.call("sam6d_dino_patch_rows", _p(images), _p(W.cls), _p(W.pos), _p(A), _p(X), B, _s())
-    # one problem per image: rows land one below the image's cls row, pos[1:] is the residual (batch stride 0)
-    gemm(A, W.patch.w, W.patch.b, X, NP, D, KPAD, KPAD, KPAD, D, c_off=D, residual=W.pos, r_off=D, ldr=D, batch=B, sA=NP * KPAD,
-         sW=0, sC=NT * D, sR=0, w16=W.patch.w16())
-
-
-def _block(X, blk, B, Y, T, n=NT):
-    """One block on X (B*n, 1024) in place; Y (B*n, 1024) and T (>= B*n*4096 floats) are workspaces."""
-    M = B * n
-    _ln(X, blk["n1"], Y, 1, M, D, 0, D, 0)
-    gemm(Y, blk["qkv"].w, blk["qkv"].b, T, M, 3 * D, D, D, D, 3 * D, w16=blk["qkv"].w16())
-    _lib.call("sam6d_dino_attention", _p(T), _p(Y), B, n, _s())
-    gemm(Y, blk["proj"].w, blk["proj"].b, X, M, D, D, D, D, D, residual=X, ldr=D, w16=blk["proj"].w16())
-    _ln(X, blk["n2"], Y, 1, M, D, 0, D, 0)
-    gemm(Y, blk["fc1"].w, blk["fc1"].b, T, M, HID, D, D, D, HID, act=2, w16=blk["fc1"].w16())
-    gemm(T, blk["fc2"].w, blk["fc2"].b, X, M, D, HID, HID, HID, D, residual=X, ldr=D, w16=blk["fc2"].w16())
 
 
 # ------------------------------------------------------------------------------------------------- crops in plain torch
@@ -300,7 +248,7 @@ def crop_proposals(image_u8, masks, boxes, rgb=True, mask=True, options=None):
 @on_tensor_device
 def encode(images, W, options=None):
     """images (N, 3, 224, 224) -> (x_norm_clstoken (N, 1024), x_norm_patchtokens (N, 256, 1024)), in slices of SLICE images."""
-    _require_mode()
+    ENC.require_mode()
     check_images(images)
     images = images.contiguous()
     N = images.shape[0]
@@ -315,11 +263,11 @@ def encode(images, W, options=None):
     A = _empty((S * NP, KPAD), images)
     for i0 in range(0, N, S):
         B = min(S, N - i0)
-        _embed(images[i0:i0 + B], W, X, A)
+        ENC.embed(images[i0:i0 + B], W, X, A)
         for blk in W.blocks:
-            _block(X, blk, B, Y, T)
-        _ln(X, W.norm, cls, B, 1, D, NT * D, D, D, y_off=i0 * D)
-        _ln(X, W.norm, tok, B, NP, D, NT * D, D, NP * D, x_off=D, y_off=i0 * NP * D)
+            ENC.block(X, blk, B, Y, T)
+        ENC.ln(X, W.norm, cls, B, 1, D, NT * D, D, D, y_off=i0 * D)
+        ENC.ln(X, W.norm, tok, B, NP, D, NT * D, D, NP * D, x_off=D, y_off=i0 * NP * D)
     return cls, tok
 
 
@@ -334,41 +282,5 @@ def descriptors(images, masks224, W, patch_size=PATCH, validpatch_thresh=0.5, op
     return cls, masked_patch_features(tok, masks224, patch_size, validpatch_thresh)
 
 
-# ------------------------------------------------------------------------------------------------- pieces (tests)
-@on_tensor_device
-def embed(images, W, options=None):
-    """images (B, 3, 224, 224) -> X (B, 257, 1024) = cat(cls_token, patch_embed(images)) + interpolated pos_embed."""
-    check_images(images)
-    images = images.contiguous()
-    B = images.shape[0]
-    X = _empty((B * NT, D), images)
-    _embed(images, W, X, _empty((B * NP, KPAD), images))
-    return X.view(B, NT, D)
-
-
-@on_tensor_device
-def layernorm(x, gamma, beta, options=None):
-    """x (..., 1024) -> nn.LayerNorm(1024, eps=1e-6)(x) (sam6d_dino_layernorm1024)."""
-    x2 = x.reshape(-1, D).contiguous()
-    y = torch.empty_like(x2)
-    _ln(x2, (gamma.contiguous(), beta.contiguous()), y, 1, x2.shape[0], D, 0, D, 0)
-    return y.view(x.shape)
-
-
-@on_tensor_device
-def attention(qkv, B, options=None):
-    """qkv (B*n, 3072) -> (B*n, 1024): the block's multi-head attention alone (sam6d_dino_attention), n <= 272."""
-    qkv = qkv.contiguous()
-    out = _empty((qkv.shape[0], D), qkv)
-    _lib.call("sam6d_dino_attention", _p(qkv), _p(out), B, qkv.shape[0] // B, _s())
-    return out
-
-
-@on_tensor_device
-def block(x, W, i, options=None):
-    """x (B, n, 1024), n <= 272 -> block i of the encoder applied to a copy."""
-    _require_mode()
-    B, n = x.shape[:2]
-    X = x.reshape(B * n, D).contiguous().clone()
-    _block(X, W.blocks[i], B, _empty((B * n, D), X), _empty((B * n, HID), X), n=n)
-    return X.view(B, n, D)
+# embed(images, W), layernorm(x, gamma, beta), attention(qkv, B), block(x, W, i) with n <= MAXN tokens: single stages, for the tests
+embed, layernorm, attention, block = encoder.pieces(ENC, check_images)
