@@ -1,20 +1,20 @@
-// Fused transformer-block kernels for 256-channel token rows: a tile of 128 tokens stays on chip from the block's input to
-// its second LayerNorm.
+// Fused transformer-block kernels for 256-channel token rows: a tile of tokens stays on chip from the block's input to its second
+// LayerNorm.
 //
-//   mode 0 -- the tail every attention layer of PEM/model/transformer.py ends with (AttentionLayer.forward :152-160 /
+//   the layer tail -- what every attention layer of PEM/model/transformer.py ends with (AttentionLayer.forward :152-160 /
 //             RPEAttentionLayer.forward :436-444 after the attention itself, then AttentionOutput :184-199):
 //                 y   = LayerNorm(hidden . Wlin^T + b + x)
 //                 out = LayerNorm(relu(y . Wexp^T + b) . Wsq^T + b + y)
-//   mode 1 -- the whole dense LinearTransformerLayer of the sparse-to-dense lift (:532-622) on the 2048 dense tokens of a cloud:
+//             on its own for the 197-token layers: token_tail_kernel (sam6d_token_block), which has a data flow of its own.
+//   the dense layer -- the whole LinearTransformerLayer of the sparse-to-dense lift (:532-622) on the 2048 dense tokens of a cloud:
 //                 q = D . Wq^T + b;  phi(q) (focused ReLU kernel);  z_h = 1 / (phi(q)_h . ksum_h + 1e-6);
-//                 hidden_h = (phi(q)_h . kv_h) z_h;  then mode 0 with x = D.
-//             (k / v side: the 196 sparse tokens, reduced to kv^T and key sums by linattn.hip)
+//                 hidden_h = (phi(q)_h . kv_h) z_h;  then the layer tail with x = D: token_block_kernel (sam6d_linattn_layer).
+//             (k / v side: the 196 sparse tokens, reduced to kv^T and key sums by tb_kv_fused_kernel)
 //
 // Before: 8 GEMM launches + 2 LayerNorm + focus passes per dense layer = twelve passes over 134 MB tensors (~3.2 GB of HBM traffic
 // per layer); now D is read once and D' written once (268 MB).
 //
-// (The layer tail of the 197-token layers -- mode 0 as launched by sam6d_token_block -- has a data flow of its own, see
-// token_tail_kernel; what follows describes token_block_kernel, the dense layer.)
+// What follows describes token_block_kernel and the kernels that share its panel machinery (rpe_front, out_split, rows_linear).
 // Layout: one workgroup = 4 waves, one wave = 16 tokens, and every product is computed TRANSPOSED:
 //     Y^T (out-channel x token) = W (out-channel x k) . X^T (k x token)          v_mfma_f32_16x16x32_f16
 // so the weights are the A operand (streamed through LDS by LDS-DMA, shared by the waves of a workgroup) and a wave's activations are the B
@@ -32,12 +32,7 @@
 #include "common.h"
 #include "../../include/sam6d_hip.h"
 #include <stdlib.h>
-#include <type_traits>
 
-typedef unsigned tb_u4 __attribute__((ext_vector_type(4)));
-typedef unsigned tb_u2 __attribute__((ext_vector_type(2)));
-
-// tokens per workgroup = 16 x waves: 64 (4 waves, 2-slot panel ring, two independent workgroups per CU) or 128 (8 waves, 4-slot ring)
 // A panel = 32 weight rows x K (KS k-steps of 32): per row KS*32 hi halves | KS*32 lo halves, NO padding -- instead the 16-byte chunk
 // c of row r is stored at chunk c ^ (r & 15), which makes the ds_read_b128 fragment reads (16 rows x 2 adjacent chunks per lane
 // group) conflict-free.  The global image is stored swizzled, so a linear LDS-DMA copy reproduces it.
@@ -296,16 +291,15 @@ extern "C" long sam6d_linattn_kv_image_bytes(void) { return 8 * TB_P64; }
 // of step s are issued (the eight waves run in lock-step between the panel barriers, so nothing else hides the LDS latency).  The
 // reads and their counted waits are inline assembly: left to the compiler, the machine scheduler sinks every read to just before its
 // use and waits with lgkmcnt(0) (measured: 2.7x the MFMA time per panel).
-typedef unsigned tb_u32x4 __attribute__((ext_vector_type(4)));
 template <int OFF>
-__device__ __forceinline__ tb_u32x4 tb_lds128(unsigned addr) {
-  tb_u32x4 r;
+__device__ __forceinline__ u32x4 tb_lds128(unsigned addr) {
+  u32x4 r;
   asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
   return r;
 }
 // wait until at most N LDS operations are outstanding; the fragments are in/out operands so that their uses stay behind the wait
 template <int N>
-__device__ __forceinline__ void tb_wait(tb_u32x4& a, tb_u32x4& b, tb_u32x4& c, tb_u32x4& d) {
+__device__ __forceinline__ void tb_wait(u32x4& a, u32x4& b, u32x4& c, u32x4& d) {
   asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(N));
 }
 // chunk (16 B) index of (plane P, step S, lane group g) in a row: P * KS * 4 + 4 S + g; its low four bits are XORed with the row:
@@ -317,7 +311,7 @@ struct TbChunk {
   static constexpr int off = (c & ~15) * 16;
 };
 template <int KS, int S>
-__device__ __forceinline__ void tb_load_step(const unsigned (&a)[4], tb_u32x4* f) {
+__device__ __forceinline__ void tb_load_step(const unsigned (&a)[4], u32x4* f) {
   constexpr int R1 = 16 * TB_ROWB(KS);
   typedef TbChunk<KS, 0, S> H;
   typedef TbChunk<KS, 1, S> L;
@@ -335,7 +329,7 @@ __device__ __forceinline__ void tb_load_step(const unsigned (&a)[4], tb_u32x4* f
 #define TB_FD 1
 template <int KS, int S, int FD_>
 __device__ __forceinline__ void tb_mma_step(f32x4& acc0, f32x4& acc1, const unsigned (&a)[4], const half8* __restrict__ xh,
-                                            const half8* __restrict__ xl, tb_u32x4 (&f)[FD_ + 1][4], bool half) {
+                                            const half8* __restrict__ xl, u32x4 (&f)[FD_ + 1][4], bool half) {
   constexpr int cur = S % (FD_ + 1);
 #ifndef TB_ABL_NOREAD  // (scratch/abl_build.sh: timing-only builds without the fragment reads / the panel DMA / the panel barrier)
   if constexpr (S + FD_ < KS) tb_load_step<KS, S + FD_>(a, f[(S + FD_) % (FD_ + 1)]);
@@ -361,7 +355,7 @@ __device__ __forceinline__ void tb_mma(f32x4& acc0, f32x4& acc1, unsigned panel,
   const unsigned rowbase = panel + fr * TB_ROWB(KS);
   const unsigned a[4] = {rowbase + (((0 + fg) ^ fr) << 4), rowbase + (((4 + fg) ^ fr) << 4), rowbase + (((8 + fg) ^ fr) << 4),
                          rowbase + (((12 + fg) ^ fr) << 4)};
-  tb_u32x4 f[FD + 1][4];
+  u32x4 f[FD + 1][4];
   tb_load_step<KS, 0>(a, f[0]);
   if constexpr (FD >= 2 && KS >= 2) tb_load_step<KS, 1>(a, f[1]);
   if constexpr (FD >= 3 && KS >= 3) tb_load_step<KS, 2>(a, f[2]);
@@ -371,7 +365,7 @@ __device__ __forceinline__ void tb_mma(f32x4& acc0, f32x4& acc1, unsigned panel,
 // makes a register value opaque to the optimiser (no instruction): without it the compiler keeps the fp32 images of y's hi / lo
 // halves, computed while splitting, alive across the whole FFN for the second residual (128 VGPRs -> scratch spills)
 __device__ __forceinline__ void tb_opaque(half8& x) {
-  tb_u32x4 t = __builtin_bit_cast(tb_u32x4, x);
+  u32x4 t = __builtin_bit_cast(u32x4, x);
   asm volatile("" : "+v"(t));
   x = __builtin_bit_cast(half8, t);
 }
@@ -388,16 +382,7 @@ __device__ __forceinline__ float tb_split_rows(const f32x4* v, half8* xh, half8*
 #pragma unroll
   for (int t = 0; t < NT; ++t)
 #pragma unroll
-    for (int r = 0; r < 4; r += 2) {
-      unsigned hi, lo;
-      sam6d_split2_f16(v[t][r] * sc, v[t][r + 1] * sc, hi, lo);
-      const _Float16 __attribute__((ext_vector_type(2))) h2 = __builtin_bit_cast(_Float16 __attribute__((ext_vector_type(2))), hi);
-      const _Float16 __attribute__((ext_vector_type(2))) l2 = __builtin_bit_cast(_Float16 __attribute__((ext_vector_type(2))), lo);
-      xh[t >> 1][4 * (t & 1) + r] = h2[0];
-      xh[t >> 1][4 * (t & 1) + r + 1] = h2[1];
-      xl[t >> 1][4 * (t & 1) + r] = l2[0];
-      xl[t >> 1][4 * (t & 1) + r + 1] = l2[1];
-    }
+    for (int r = 0; r < 4; r += 2) sam6d_split2_f16(v[t][r] * sc, v[t][r + 1] * sc, xh[t >> 1], xl[t >> 1], 4 * (t & 1) + r);
   return sc;
 }
 
@@ -428,58 +413,35 @@ __device__ __forceinline__ void tb_layernorm(f32x4* v, const float* __restrict__
 }
 
 struct TbArgs {
-  const float* in;        // mode 0: hidden (M,256); mode 1: D (B, I, 256)
-  const float* resid;     // mode 0: x (M,256);      mode 1: unused (the residual is D)
-  float* out;             // mode 0: (M,256);        mode 1: D' (B, I, 256)
+  const float* in;        // tail: hidden (M,256);   dense layer: D (B, I, 256)
+  const float* resid;     // tail: x (M,256);        dense layer: unused (the residual is D)
+  float* out;             // tail: (M,256);          dense layer: D' (B, I, 256)
   const unsigned char* wimg;
   const float* consts;
-  const unsigned char* kvimg;  // mode 1: (B, 8 panels)
-  const float* kvinv;          // mode 1: (B, 4) one inverse image scale per head
-  const float* ksum;           // mode 1: (B, 256)
-  long M;                 // mode 0: rows
-  int I, row0, tiles_per_b;  // mode 1: rows per cloud, first row handled, tiles per cloud
+  const unsigned char* kvimg;  // dense layer: (B, 8 panels)
+  const float* kvinv;          // dense layer: (B, 4) one inverse image scale per head
+  const float* ksum;           // dense layer: (B, 256)
+  long M;                 // tail: rows
+  int I, row0, tiles_per_b;  // dense layer: rows per cloud, first row handled, tiles per cloud
   float eps;
   int half;               // 1: fp16 single product (matmul mode 2)
 };
 
-// compile-time loop: f(std::integral_constant<int, I>) for I = B .. E-1
-template <int B, int E, class F>
-__device__ __forceinline__ void tb_static_for(F&& f) {
-  if constexpr (B < E) {
-    f(std::integral_constant<int, B>{});
-    tb_static_for<B + 1, E>(f);
-  }
-}
-
-// The panel sequence of a launch (MODE 1: proj_q x8, kv x8, then the common part; common: linear x8, 4 x {expand x4, squeeze x8}) and
-// the number of 1 KiB DMA pieces EACH WAVE copies for panel i (8 waves): 4 (K = 256), 2 (K = 128), 1 (K = 64), 0 past the end.
-template <int MODE, int WAVES>
+// The dense layer's panel sequence: proj_q x8 (K = 256), kv x8 (K = 64, the cloud's own image), linear x8 (K = 256), then per 128-wide FFN
+// chunk expand x4 (K = 256) and squeeze x8 (K = 128).
 struct TbSched {
-  static constexpr int NPAN = (MODE ? 16 : 0) + 8 + 4 * 12;
-  static constexpr int per_wave(int i) {
-    if (i < 0 || i >= NPAN) return 0;
-    if (MODE) {
-      if (i < 8) return (32 + WAVES - 1) / WAVES;
-      if (i < 16) return (8 + WAVES - 1) / WAVES;
-      i -= 16;
-    }
-    if (i < 8) return (32 + WAVES - 1) / WAVES;
-    return ((((i - 8) % 12) < 4 ? 32 : 16) + WAVES - 1) / WAVES;
+  static constexpr int NPAN = 16 + 8 + 4 * 12;
+  static constexpr int P0 = 16;  // first panel of the layer tail
+  static constexpr bool kv(int i) { return i >= 8 && i < 16; }
+  static constexpr int pieces(int i) {  // 1 KiB DMA pieces of panel i
+    return kv(i) ? 8 : (i >= P0 + 8 && ((i - P0 - 8) % 12) >= 4) ? 16 : 32;
   }
-  static constexpr int per_issuer(int i, int nw) {  // pieces of panel i each of nw issuing waves copies
-    return (i < 0 || i >= NPAN) ? 0 : (pieces(i) + nw - 1) / nw;
-  }
-  static constexpr int pieces(int i) {  // 1 KiB pieces of panel i
-    if (MODE && i >= 8 && i < 16) return 8;
-    const int k = MODE ? i - 16 : i;
-    return (k >= 8 && ((k - 8) % 12) >= 4) ? 16 : 32;
-  }
-  // pieces of the panels I+1 .. I+NBUF-2 (in flight while panel I is awaited)
-  template <int NBUF>
-  static constexpr int in_flight(int i) {
-    int n = 0;
-    for (int k = 1; k <= NBUF - 2; ++k) n += per_wave(i + k);
-    return n;
+  static constexpr size_t offset(int i) {  // of panel i in the weight image (kv panels: in the cloud's kv image)
+    if (i < 8) return TB_Q_OFF + (size_t)i * TB_P256;
+    if (i < P0) return (size_t)(i - 8) * TB_P64;
+    if (i < P0 + 8) return (size_t)(i - P0) * TB_P256;
+    const int c = (i - P0 - 8) / 12, u = (i - P0 - 8) % 12;
+    return 8 * (size_t)TB_P256 + c * (size_t)TB_CHUNK_BYTES + (u < 4 ? u * (size_t)TB_P256 : 4 * (size_t)TB_P256 + (u - 4) * (size_t)TB_P128);
   }
 };
 
@@ -490,168 +452,85 @@ extern "C" int sam6d_tb_debug_stamps(void* dst) {
   return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(tb_stamps), sizeof(unsigned long long) * 512 * 8 * TB_NSTAMP);
 }
 // (stamps go to LDS and are flushed at the end: a global store before a panel's s_waitcnt vmcnt would itself be waited for)
-#define TB_ST(i) do { if (lane == 0 && wave < WAVES && (i) < TB_NSTAMP) st_lds[wave][(i)] = __builtin_amdgcn_s_memtime(); } while (0)
+#define TB_ST(i) do { if (lane == 0 && wave < TB_WAVES && (i) < TB_NSTAMP) st_lds[wave][(i)] = __builtin_amdgcn_s_memtime(); } while (0)
 #else
 #define TB_ST(i)
 #endif
 
-// (Until the layer tail of the 197-token layers got a kernel of its own, token_tail_kernel below, this kernel also ran it, with extra
-// loader waves that did nothing but the panel DMA and ring slots of two panels; only the dense layer, MODE 1, is instantiated now.)
-template <int MODE, int WAVES, int NBUF, int FD = TB_FD>
-__global__ __launch_bounds__(WAVES * 64, 2) void token_block_kernel(TbArgs a) {  // (2 waves per SIMD: <= 256 VGPR + AGPR)
-  // Only the dense layer is launched.  The MODE == 0 branches below are the layer tail on its own as this kernel ran it before
-  // token_tail_kernel; they are kept because the tail INSIDE the dense layer shares every line with them, not as a route.
-  static_assert(MODE == 1, "token_block_kernel is the dense layer; the layer tail on its own is token_tail_kernel");
-  constexpr int TB_TOK = 16 * WAVES, TB_NBUF = NBUF;
-  constexpr int NTHREADS = WAVES * 64;
-  constexpr int SLOT_BYTES = TB_PANEL_BYTES;
+// The dense layer: a workgroup = TB_WAVES waves x 16 tokens, the weight panels pass through a ring of TB_NBUF LDS slots; every wave
+// issues its share of each panel's DMA.  (77 KB of LDS: two workgroups per CU, which run out of step, so one's row epilogues overlap
+// the other's MFMAs.)
+#define TB_WAVES 4
+#define TB_NBUF 2
+#define TB_LDS_BYTES (TB_NBUF * TB_PANEL_BYTES + (TC_N + 256) * 4)
+static_assert(8 % TB_WAVES == 0, "every panel (8, 16 or 32 pieces) is dealt evenly to the waves");
+__global__ __launch_bounds__(TB_WAVES * 64, 2) void token_block_kernel(TbArgs a) {  // (2 waves per SIMD: <= 256 VGPR + AGPR)
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   unsigned char* pan = lds;                                                   // TB_NBUF panel slots
-  float* cst = reinterpret_cast<float*>(lds + TB_NBUF * SLOT_BYTES);          // TC_N floats
-  float* ksm = cst + TC_N;                                                    // 256 floats (mode 1)
+  float* cst = reinterpret_cast<float*>(lds + TB_NBUF * TB_PANEL_BYTES);      // TC_N floats
+  float* ksm = cst + TC_N;                                                    // 256 floats
   const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6), fr = lane & 15, fg = lane >> 4;
-  typedef TbSched<MODE, WAVES> SCH;
   const bool half = a.half != 0;
 #ifdef TB_STAMP
-  __shared__ unsigned long long st_lds[WAVES][TB_NSTAMP];
+  __shared__ unsigned long long st_lds[TB_WAVES][TB_NSTAMP];
   unsigned long long* st_base = tb_stamps + ((size_t)(blockIdx.x < 512 ? blockIdx.x : 0) * 8 + wave) * TB_NSTAMP;
 #endif
   TB_ST(0);
   const unsigned pan_lds = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)pan;
 
-  // ---- which rows
-  long row;       // global row of this lane's token
-  bool valid;
-  int b = 0;
-  if (MODE == 0) {
-    const long r0 = (long)blockIdx.x * TB_TOK + wave * 16 + fr;
-    valid = r0 < a.M;
-    row = valid ? r0 : a.M - 1;
-  } else {
-    b = blockIdx.x / a.tiles_per_b;
-    const int tk = (blockIdx.x % a.tiles_per_b) * TB_TOK + wave * 16 + fr + a.row0;
-    valid = tk < a.I;
-    row = (long)b * a.I + (valid ? tk : a.I - 1);
-  }
+  // ---- which rows: this lane's token of its cloud (rows past the cloud's end recompute its last row and are not stored)
+  const int b = blockIdx.x / a.tiles_per_b;
+  const int tk = (blockIdx.x % a.tiles_per_b) * (16 * TB_WAVES) + wave * 16 + fr + a.row0;
+  const bool valid = tk < a.I;
+  const long row = (long)b * a.I + (valid ? tk : a.I - 1);
 
-  const unsigned char* kvp = MODE ? a.kvimg + (size_t)b * (8 * TB_P64) : nullptr;
-  constexpr int NW = WAVES;   // every wave issues its share of the DMA
-  const int lw = wave;
-  // LDS-DMA of panel I into its ring slot: SCH::per_issuer(I, NW) pieces of 1 KiB per issuing wave (the global image IS the LDS image)
+  const unsigned char* kvp = a.kvimg + (size_t)b * (8 * TB_P64);
+  // LDS-DMA of panel I into its ring slot, dealt to the waves (the global image IS the LDS image)
   auto dma = [&](auto IC) {
     constexpr int I = decltype(IC)::value;
-    constexpr int NP = SCH::per_issuer(I, NW);
-    if constexpr (NP > 0) {
-      constexpr int K = MODE ? I - 16 : I;   // index in the common part (negative: proj_q / kv panels)
-      const unsigned char* src;
-      if constexpr (MODE && I < 8) src = a.wimg + TB_Q_OFF + (size_t)I * TB_P256;
-      else if constexpr (MODE && I < 16) src = kvp + (size_t)(I - 8) * TB_P64;
-      else if constexpr (K < 8) src = a.wimg + (size_t)K * TB_P256;
-      else {
-        constexpr int c = (K - 8) / 12, u = (K - 8) % 12;
-        constexpr size_t base = 8 * (size_t)TB_P256 + c * (size_t)TB_CHUNK_BYTES;
-        src = a.wimg + (u < 4 ? base + u * (size_t)TB_P256 : base + 4 * (size_t)TB_P256 + (u - 4) * (size_t)TB_P128);
-      }
-      unsigned char* dst = pan + (I % TB_NBUF) * SLOT_BYTES;
-#pragma unroll
-      for (int k = 0; k < NP; ++k) {
-        const int pc = lw + NW * k;
-        __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)(src + (size_t)pc * 1024 + lane * 16),
-                                         (void __attribute__((address_space(3)))*)(dst + pc * 1024), 16, 0, 0);
-      }
-    }
+    if constexpr (I < TbSched::NPAN)
+      dma_pieces<TbSched::pieces(I) / TB_WAVES>((TbSched::kv(I) ? kvp : a.wimg) + TbSched::offset(I), pan + (I % TB_NBUF) * TB_PANEL_BYTES, wave,
+                                                TB_WAVES, lane);
   };
-  // Start of panel I: this wave's pieces of panel I have landed once at most the pieces of the panels issued after it (I+1 ..
-  // I+NBUF-2; the vector-memory counter retires in order) are outstanding; the barrier then publishes the panel to the other waves
-  // and at the same time retires panel I-1 in every wave, whose ring slot the DMA of panel I+NBUF-1 overwrites.
-  // pieces per issuing wave of the steps T+1 .. T+NBUF-2 (in flight while step T is awaited)
-  auto step_in_flight = [](int T) constexpr {
-    int n = 0;
-    for (int k = 1; k <= NBUF - 2; ++k) n += SCH::per_issuer(T + k, NW);
-    return n;
-  };
-  auto dma_step = [&](auto TC) { dma(TC); };  // a step = one panel
-  auto step_sync = [&](auto TC) {  // start of step T: its panels have landed and are published; the slot of step T-1 is free
-    constexpr int T = decltype(TC)::value;
-    static_assert(NBUF == 2 || (32 % NW) == 0, "counted waits need the same number of pieces in every wave");
-    constexpr int N = step_in_flight(T);
-    TB_ST(4 + 3 * T);
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-    TB_ST(5 + 3 * T);
+  // Start of panel I: with two slots, panel I is the only DMA in flight (panel I + 1 goes out below, after the barrier), so
+  // vmcnt(0) is exactly "this wave's pieces of panel I have landed".  The barrier then publishes the panel to the other waves and at the
+  // same time retires panel I - 1 in every wave, whose ring slot the DMA of panel I + 1 overwrites.
+  static_assert(TB_NBUF == 2, "a deeper ring needs counted waits");
+  auto next_panel = [&](auto IC) -> unsigned {
+    constexpr int I = decltype(IC)::value;
+    TB_ST(4 + 3 * I);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    TB_ST(5 + 3 * I);
 #ifndef TB_ABL_NOBAR
     __syncthreads();
 #endif
-    TB_ST(6 + 3 * T);
+    TB_ST(6 + 3 * I);
 #ifndef TB_ABL_NODMA
-    dma_step(std::integral_constant<int, T + NBUF - 1>{});
+    dma(std::integral_constant<int, I + 1>{});
 #endif
-  };
-  auto next_panel = [&](auto IC) -> unsigned {
-    constexpr int I = decltype(IC)::value;
-    step_sync(IC);
-    return pan_lds + (I % TB_NBUF) * SLOT_BYTES;
+    return pan_lds + (I % TB_NBUF) * TB_PANEL_BYTES;
   };
 
-  tb_static_for<0, NBUF - 1>([&](auto TC) { dma_step(TC); });
-  for (int i = t; i < TC_N; i += NTHREADS) cst[i] = a.consts[i];
-  if (MODE && t < 256) ksm[t] = a.ksum[(size_t)b * 256 + t];
+  dma(std::integral_constant<int, 0>{});
+  for (int i = t; i < TC_N; i += TB_WAVES * 64) cst[i] = a.consts[i];
+  if (t < 256) ksm[t] = a.ksum[(size_t)b * 256 + t];
 
-  // ---- X: the input rows, split (mode 0: hidden; mode 1: D)
+  // ---- X: the input rows D, split
+  // the dense layer streams 134 MB of tokens in and out once: non-temporal, so that they do not evict the weight / kv images that
+  // 2048 workgroups re-read from the L2 (FETCH_SIZE: 237 MB for 140 MB of compulsory reads with ordinary loads)
   half8 xh[8], xl[8];
-  float sx;
-  {
-    const float* src = a.in + (size_t)row * 256;
-    float4 va[8], vb[8];
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-      if constexpr (MODE != 0) {
-        // the dense layer streams 134 MB of tokens in and out once: non-temporal, so that they do not evict the weight / kv images that
-        // 2048 workgroups re-read from the L2 (FETCH_SIZE: 237 MB for 140 MB of compulsory reads with ordinary loads)
-        const f32x4 x0 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src + 32 * s + 4 * fg));
-        const f32x4 x1 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src + 32 * s + 16 + 4 * fg));
-        va[s] = make_float4(x0[0], x0[1], x0[2], x0[3]);
-        vb[s] = make_float4(x1[0], x1[1], x1[2], x1[3]);
-      } else {
-        va[s] = *reinterpret_cast<const float4*>(src + 32 * s + 4 * fg);
-        vb[s] = *reinterpret_cast<const float4*>(src + 32 * s + 16 + 4 * fg);
-      }
-    }
-    float m = 0.f;
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-      m = fmaxf(m, fmaxf(fmaxf(fabsf(va[s].x), fabsf(va[s].y)), fmaxf(fabsf(va[s].z), fabsf(va[s].w))));
-      m = fmaxf(m, fmaxf(fmaxf(fabsf(vb[s].x), fabsf(vb[s].y)), fmaxf(fabsf(vb[s].z), fabsf(vb[s].w))));
-    }
-    sx = pow2_scale(tok_max(m));
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-      const float e[8] = {va[s].x, va[s].y, va[s].z, va[s].w, vb[s].x, vb[s].y, vb[s].z, vb[s].w};
-#pragma unroll
-      for (int u = 0; u < 8; u += 2) {
-        unsigned hi, lo;
-        sam6d_split2_f16(e[u] * sx, e[u + 1] * sx, hi, lo);
-        const _Float16 __attribute__((ext_vector_type(2))) h2 = __builtin_bit_cast(_Float16 __attribute__((ext_vector_type(2))), hi);
-        const _Float16 __attribute__((ext_vector_type(2))) l2 = __builtin_bit_cast(_Float16 __attribute__((ext_vector_type(2))), lo);
-        xh[s][u] = h2[0];
-        xh[s][u + 1] = h2[1];
-        xl[s][u] = l2[0];
-        xl[s][u + 1] = l2[1];
-      }
-    }
-  }
+  float sx = split_row256<true>(a.in + (size_t)row * 256, fg, xh, xl);
 
-  // mode 1: the split input rows D stay in registers for the residual add three products later (re-reading them cost a second
+  // the split input rows D stay in registers for the residual add three products later (re-reading them cost a second
   // 134 MB pass over D per layer: 1.7x the layer's algorithmic traffic, rocprof FETCH_SIZE)
-  half8 dh[MODE ? 8 : 1], dl[MODE ? 8 : 1];
+  half8 dh[8], dl[8];
   const float sd = sx;
-  if constexpr (MODE != 0) {
 #pragma unroll
-    for (int s = 0; s < 8; ++s) {
-      dh[s] = xh[s];
-      dl[s] = xl[s];
-      tb_opaque(dh[s]);
-      tb_opaque(dl[s]);
-    }
+  for (int s = 0; s < 8; ++s) {
+    dh[s] = xh[s];
+    dl[s] = xl[s];
+    tb_opaque(dh[s]);
+    tb_opaque(dl[s]);
   }
 
   TB_ST(1);
@@ -660,94 +539,87 @@ __global__ __launch_bounds__(WAVES * 64, 2) void token_block_kernel(TbArgs a) { 
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
   };
-  constexpr int P0 = MODE ? 16 : 0;  // first panel of the common part
-  if constexpr (MODE != 0) {
-    // ---- q = D Wq^T + b, focus, z
-    zero_acc();
-    tb_static_for<0, 8>([&](auto J) {
-      constexpr int j = decltype(J)::value;
-      const unsigned p = next_panel(std::integral_constant<int, j>{});
-      tb_mma<8, FD>(acc[2 * j], acc[2 * j + 1], p, xh, xl, fr, fg, half);
-    });
-    {
-      const float inv = cst[TC_SC + 0] * (1.0f / sx);
-      float n1 = 0.f, n3 = 0.f;
+  constexpr int P0 = TbSched::P0;
+  // ---- q = D Wq^T + b, focus, z
+  zero_acc();
+  static_for<0, 8>([&](auto J) {
+    constexpr int j = decltype(J)::value;
+    const unsigned p = next_panel(std::integral_constant<int, j>{});
+    tb_mma<8>(acc[2 * j], acc[2 * j + 1], p, xh, xl, fr, fg, half);
+  });
+  {
+    const float inv = cst[TC_SC + 0] * (1.0f / sx);
+    float n1 = 0.f, n3 = 0.f;
 #pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const float4 bq = *reinterpret_cast<const float4*>(cst + TC_BQ + 16 * i + 4 * fg);
-        const float4 is = *reinterpret_cast<const float4*>(cst + TC_ISP + 16 * i + 4 * fg);
-        const float bb[4] = {bq.x, bq.y, bq.z, bq.w}, ii[4] = {is.x, is.y, is.z, is.w};
+    for (int i = 0; i < 16; ++i) {
+      const float4 bq = *reinterpret_cast<const float4*>(cst + TC_BQ + 16 * i + 4 * fg);
+      const float4 is = *reinterpret_cast<const float4*>(cst + TC_ISP + 16 * i + 4 * fg);
+      const float bb[4] = {bq.x, bq.y, bq.z, bq.w}, ii[4] = {is.x, is.y, is.z, is.w};
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          float v = acc[i][u] * inv + bb[u];
-          v = ((v > 0.f ? v : 0.f) + 1e-6f) * ii[u];
-          n1 += v * v;
-          const float c3 = (v * v) * v;
-          n3 += c3 * c3;
-          acc[i][u] = c3;
-        }
+      for (int u = 0; u < 4; ++u) {
+        float v = acc[i][u] * inv + bb[u];
+        v = ((v > 0.f ? v : 0.f) + 1e-6f) * ii[u];
+        n1 += v * v;
+        const float c3 = (v * v) * v;
+        n3 += c3 * c3;
+        acc[i][u] = c3;
       }
-      const float f = sqrtf(tok_sum(n1)) / sqrtf(tok_sum(n3));  // phi = c3 / |c3| * |v|
-#pragma unroll
-      for (int hd = 0; hd < 4; ++hd) {
-        float dot = 0.f;
-#pragma unroll
-        for (int ii = 0; ii < 4; ++ii) {
-          const int i = 4 * hd + ii;
-          const float4 ks = *reinterpret_cast<const float4*>(ksm + 16 * i + 4 * fg);
-          acc[i][0] *= f; acc[i][1] *= f; acc[i][2] *= f; acc[i][3] *= f;
-          dot += (acc[i][0] * ks.x + acc[i][1] * ks.y) + (acc[i][2] * ks.z + acc[i][3] * ks.w);
-        }
-        const float z = 1.0f / (tok_sum(dot) + 1e-6f);
-#pragma unroll
-        for (int ii = 0; ii < 4; ++ii) {
-          acc[4 * hd + ii][0] *= z; acc[4 * hd + ii][1] *= z; acc[4 * hd + ii][2] *= z; acc[4 * hd + ii][3] *= z;
-        }
-      }
-      sx = tb_split_rows<16>(acc, xh, xl);
     }
-    // ---- hidden_h = phi(q)_h kv_h  (K = 64 per head: k-steps 2h, 2h+1)
-    zero_acc();
-    tb_static_for<0, 8>([&](auto J) {
-      constexpr int j = decltype(J)::value;
-      const unsigned p = next_panel(std::integral_constant<int, 8 + j>{});
-      tb_mma<2, FD>(acc[2 * j], acc[2 * j + 1], p, xh + 2 * (j >> 1), xl + 2 * (j >> 1), fr, fg, half);
-    });
-    {
-      const float4 kvi = *reinterpret_cast<const float4*>(a.kvinv + (size_t)b * 4);  // the four heads' image scales
-      const float isx = 1.0f / sx;
-      const float invh[4] = {kvi.x * isx, kvi.y * isx, kvi.z * isx, kvi.w * isx};
+    const float f = sqrtf(tok_sum(n1)) / sqrtf(tok_sum(n3));  // phi = c3 / |c3| * |v|
 #pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const float inv = invh[i >> 2];  // accumulator tiles 4 h .. 4 h + 3 hold head h's 64 channels
-        acc[i][0] *= inv; acc[i][1] *= inv; acc[i][2] *= inv; acc[i][3] *= inv;
+    for (int hd = 0; hd < 4; ++hd) {
+      float dot = 0.f;
+#pragma unroll
+      for (int ii = 0; ii < 4; ++ii) {
+        const int i = 4 * hd + ii;
+        const float4 ks = *reinterpret_cast<const float4*>(ksm + 16 * i + 4 * fg);
+        acc[i][0] *= f; acc[i][1] *= f; acc[i][2] *= f; acc[i][3] *= f;
+        dot += (acc[i][0] * ks.x + acc[i][1] * ks.y) + (acc[i][2] * ks.z + acc[i][3] * ks.w);
       }
-      sx = tb_split_rows<16>(acc, xh, xl);
+      const float z = 1.0f / (tok_sum(dot) + 1e-6f);
+#pragma unroll
+      for (int ii = 0; ii < 4; ++ii) {
+        acc[4 * hd + ii][0] *= z; acc[4 * hd + ii][1] *= z; acc[4 * hd + ii][2] *= z; acc[4 * hd + ii][3] *= z;
+      }
     }
+    sx = tb_split_rows<16>(acc, xh, xl);
+  }
+  // ---- hidden_h = phi(q)_h kv_h  (K = 64 per head: k-steps 2h, 2h+1)
+  zero_acc();
+  static_for<0, 8>([&](auto J) {
+    constexpr int j = decltype(J)::value;
+    const unsigned p = next_panel(std::integral_constant<int, 8 + j>{});
+    tb_mma<2>(acc[2 * j], acc[2 * j + 1], p, xh + 2 * (j >> 1), xl + 2 * (j >> 1), fr, fg, half);
+  });
+  {
+    const float4 kvi = *reinterpret_cast<const float4*>(a.kvinv + (size_t)b * 4);  // the four heads' image scales
+    const float isx = 1.0f / sx;
+    const float invh[4] = {kvi.x * isx, kvi.y * isx, kvi.z * isx, kvi.w * isx};
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const float inv = invh[i >> 2];  // accumulator tiles 4 h .. 4 h + 3 hold head h's 64 channels
+      acc[i][0] *= inv; acc[i][1] *= inv; acc[i][2] *= inv; acc[i][3] *= inv;
+    }
+    sx = tb_split_rows<16>(acc, xh, xl);
   }
 
   // ---- y = LayerNorm(hidden Wlin^T + b + residual)
   zero_acc();
-  tb_static_for<0, 8>([&](auto J) {
+  static_for<0, 8>([&](auto J) {
     constexpr int j = decltype(J)::value;
     const unsigned p = next_panel(std::integral_constant<int, P0 + j>{});
-    tb_mma<8, FD>(acc[2 * j], acc[2 * j + 1], p, xh, xl, fr, fg, half);
+    tb_mma<8>(acc[2 * j], acc[2 * j + 1], p, xh, xl, fr, fg, half);
   });
   {
     const float inv = cst[TC_SC + 1] * (1.0f / sx);
-    const float* rs = a.resid + (size_t)row * 256;
     const float isd = 1.0f / sd;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      float4 rv;
-      if constexpr (MODE != 0) {  // D = (hi + lo) / scale: 22 significand bits of the fp32 input
-        rv.x = ((float)dh[i >> 1][4 * (i & 1) + 0] + (float)dl[i >> 1][4 * (i & 1) + 0]) * isd;
-        rv.y = ((float)dh[i >> 1][4 * (i & 1) + 1] + (float)dl[i >> 1][4 * (i & 1) + 1]) * isd;
-        rv.z = ((float)dh[i >> 1][4 * (i & 1) + 2] + (float)dl[i >> 1][4 * (i & 1) + 2]) * isd;
-        rv.w = ((float)dh[i >> 1][4 * (i & 1) + 3] + (float)dl[i >> 1][4 * (i & 1) + 3]) * isd;
-      } else {
-        rv = *reinterpret_cast<const float4*>(rs + 16 * i + 4 * fg);
-      }
+      float4 rv;  // D = (hi + lo) / scale: 22 significand bits of the fp32 input
+      rv.x = ((float)dh[i >> 1][4 * (i & 1) + 0] + (float)dl[i >> 1][4 * (i & 1) + 0]) * isd;
+      rv.y = ((float)dh[i >> 1][4 * (i & 1) + 1] + (float)dl[i >> 1][4 * (i & 1) + 1]) * isd;
+      rv.z = ((float)dh[i >> 1][4 * (i & 1) + 2] + (float)dl[i >> 1][4 * (i & 1) + 2]) * isd;
+      rv.w = ((float)dh[i >> 1][4 * (i & 1) + 3] + (float)dl[i >> 1][4 * (i & 1) + 3]) * isd;
       const float4 bl = *reinterpret_cast<const float4*>(cst + TC_BLIN + 16 * i + 4 * fg);
       acc[i][0] = (acc[i][0] * inv + bl.x) + rv.x;
       acc[i][1] = (acc[i][1] * inv + bl.y) + rv.y;
@@ -768,14 +640,14 @@ __global__ __launch_bounds__(WAVES * 64, 2) void token_block_kernel(TbArgs a) { 
   zero_acc();
   {
     const float inv_e = cst[TC_SC + 2] * (1.0f / sy), sh = cst[TC_SC + 4];
-    tb_static_for<0, 4>([&](auto CC) {
+    static_for<0, 4>([&](auto CC) {
       constexpr int c = decltype(CC)::value;
       half8 hh[4], hl[4];
-      tb_static_for<0, 4>([&](auto U) {
+      static_for<0, 4>([&](auto U) {
         constexpr int u = decltype(U)::value;
         const unsigned p = next_panel(std::integral_constant<int, P0 + 8 + 12 * c + u>{});
         f32x4 ha[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-        tb_mma<8, FD>(ha[0], ha[1], p, xh, xl, fr, fg, half);
+        tb_mma<8>(ha[0], ha[1], p, xh, xl, fr, fg, half);
 #pragma unroll
         for (int w = 0; w < 2; ++w) {
           const float4 be = *reinterpret_cast<const float4*>(cst + TC_BEXP + 128 * c + 32 * u + 16 * w + 4 * fg);
@@ -785,21 +657,14 @@ __global__ __launch_bounds__(WAVES * 64, 2) void token_block_kernel(TbArgs a) { 
             float v0 = ha[w][r] * inv_e + bb[r], v1 = ha[w][r + 1] * inv_e + bb[r + 1];
             v0 = (v0 > 0.f ? v0 : 0.f) * sh;
             v1 = (v1 > 0.f ? v1 : 0.f) * sh;
-            unsigned hi, lo;
-            sam6d_split2_f16(v0, v1, hi, lo);
-            const _Float16 __attribute__((ext_vector_type(2))) h2 = __builtin_bit_cast(_Float16 __attribute__((ext_vector_type(2))), hi);
-            const _Float16 __attribute__((ext_vector_type(2))) l2 = __builtin_bit_cast(_Float16 __attribute__((ext_vector_type(2))), lo);
-            hh[u][4 * w + r] = h2[0];
-            hh[u][4 * w + r + 1] = h2[1];
-            hl[u][4 * w + r] = l2[0];
-            hl[u][4 * w + r + 1] = l2[1];
+            sam6d_split2_f16(v0, v1, hh[u], hl[u], 4 * w + r);
           }
         }
       });
-      tb_static_for<0, 8>([&](auto J) {
+      static_for<0, 8>([&](auto J) {
         constexpr int j = decltype(J)::value;
         const unsigned p = next_panel(std::integral_constant<int, P0 + 8 + 12 * c + 4 + j>{});
-        tb_mma<4, FD>(acc[2 * j], acc[2 * j + 1], p, hh, hl, fr, fg, half);
+        tb_mma<4>(acc[2 * j], acc[2 * j + 1], p, hh, hl, fr, fg, half);
       });
     });
   }
@@ -821,10 +686,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void token_block_kernel(TbArgs a) { 
   if (valid) {
     float* o = a.out + (size_t)row * 256;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      if constexpr (MODE != 0) __builtin_nontemporal_store(acc[i], reinterpret_cast<f32x4*>(o + 16 * i + 4 * fg));
-      else *reinterpret_cast<float4*>(o + 16 * i + 4 * fg) = make_float4(acc[i][0], acc[i][1], acc[i][2], acc[i][3]);
-    }
+    for (int i = 0; i < 16; ++i) __builtin_nontemporal_store(acc[i], reinterpret_cast<f32x4*>(o + 16 * i + 4 * fg));
   }
   TB_ST(3);
 #ifdef TB_STAMP
@@ -885,7 +747,7 @@ __global__ __launch_bounds__(512) void token_tail_kernel(TbArgs a) {
   typedef __attribute__((address_space(3))) unsigned char lds_u8;
   typedef __attribute__((address_space(3))) float lds_f32;
   typedef __attribute__((address_space(3))) half8 lds_h8;
-  typedef __attribute__((address_space(3))) tb_u32x4 lds_u4;
+  typedef __attribute__((address_space(3))) u32x4 lds_u4;
   lds_u8* ybl = (lds_u8*)yb + lane * 16;
   lds_u8* hbl = (lds_u8*)hb + lane * 16;
   lds_f32* redl = (lds_f32*)red + fr;
@@ -921,7 +783,7 @@ __global__ __launch_bounds__(512) void token_tail_kernel(TbArgs a) {
     o8[q] = fr * TB_ROWB(8) + (((4 * q + fg) ^ fr) << 4);
     o4[q] = fr * TB_ROWB(4) + (((4 * q + fg) ^ fr) << 4);
   }
-  tb_u32x4 ar[D + 1][4];
+  u32x4 ar[D + 1][4];
   auto wload = [&](auto GC) {
     constexpr int G = decltype(GC)::value;
     if constexpr (G < TT_NSTEP) {
@@ -930,14 +792,14 @@ __global__ __launch_bounds__(512) void token_tail_kernel(TbArgs a) {
       typedef TbChunk<ST::KS, 1, ST::S> L;
       constexpr int R1 = 16 * TB_ROWB(ST::KS);
       const unsigned o = ST::KS == 8 ? o8[H::q] : o4[H::q];
-      tb_u32x4* f = ar[G % (D + 1)];
+      u32x4* f = ar[G % (D + 1)];
       f[0] = __builtin_amdgcn_raw_buffer_load_b128(wr, o + H::off, wp[ST::P], 0);
       f[1] = __builtin_amdgcn_raw_buffer_load_b128(wr, o + L::off, wp[ST::P], 0);
       f[2] = __builtin_amdgcn_raw_buffer_load_b128(wr, o + H::off, wp[ST::P] + R1, 0);
       f[3] = __builtin_amdgcn_raw_buffer_load_b128(wr, o + L::off, wp[ST::P] + R1, 0);
     }
   };
-  tb_static_for<0, D>([&](auto GC) { wload(GC); });
+  static_for<0, D>([&](auto GC) { wload(GC); });
 
   // NS k-steps starting at stream step G0: acc[rt][tt] += W(rows 16 rt ..) . B(token tile tt); B fragments one step ahead
   auto product = [&](auto G0C, auto NSC, f32x4 (&acc)[2][TT], const lds_u8* bbase) {
@@ -951,12 +813,12 @@ __global__ __launch_bounds__(512) void token_tail_kernel(TbArgs a) {
       }
     };
     bload(0, bq[0]);
-    tb_static_for<0, NS>([&](auto SC) {
+    static_for<0, NS>([&](auto SC) {
       constexpr int S = decltype(SC)::value, G = G0 + S;
       wload(std::integral_constant<int, G + D>{});
       if constexpr (S + 1 < NS) bload(S + 1, bq[(S + 1) & 1]);
       __builtin_amdgcn_sched_barrier(0);
-      const tb_u32x4* f = ar[G % (D + 1)];
+      const u32x4* f = ar[G % (D + 1)];
       const half8 ah[2] = {__builtin_bit_cast(half8, f[0]), __builtin_bit_cast(half8, f[2])};
       const half8 al[2] = {__builtin_bit_cast(half8, f[1]), __builtin_bit_cast(half8, f[3])};
       const half8(&b)[TT][2] = bq[S & 1];
@@ -1057,8 +919,8 @@ __global__ __launch_bounds__(512) void token_tail_kernel(TbArgs a) {
     sam6d_split2_f16(v0[2], v0[3], h1, l1);
     sam6d_split2_f16(v1[0], v1[1], h2, l2);
     sam6d_split2_f16(v1[2], v1[3], h3, l3);
-    *reinterpret_cast<lds_u4*>(buf + ((ks * 2 + 0) * TT + tt) * 1024) = tb_u32x4{h0, h1, h2, h3};
-    *reinterpret_cast<lds_u4*>(buf + ((ks * 2 + 1) * TT + tt) * 1024) = tb_u32x4{l0, l1, l2, l3};
+    *reinterpret_cast<lds_u4*>(buf + ((ks * 2 + 0) * TT + tt) * 1024) = u32x4{h0, h1, h2, h3};
+    *reinterpret_cast<lds_u4*>(buf + ((ks * 2 + 1) * TT + tt) * 1024) = u32x4{l0, l1, l2, l3};
   };
 
   // ---- the input rows, split: lane l holds channels 4 l .. 4 l + 3 = k-step l >> 3, lane group l & 3, slots 4 ((l >> 2) & 1) ..
@@ -1072,8 +934,8 @@ __global__ __launch_bounds__(512) void token_tail_kernel(TbArgs a) {
     sam6d_split2_f16(xv[i].x * sx, xv[i].y * sx, h0, l0);
     sam6d_split2_f16(xv[i].z * sx, xv[i].w * sx, h1, l1);
     unsigned char* dst = hb + (size_t)(tok >> 4) * 1024 + ((lane & 3) * 16 + (tok & 15)) * 16 + 8 * ((lane >> 2) & 1);
-    *reinterpret_cast<tb_u2*>(dst + ((lane >> 3) * 2 + 0) * TT * 1024) = tb_u2{h0, h1};
-    *reinterpret_cast<tb_u2*>(dst + ((lane >> 3) * 2 + 1) * TT * 1024) = tb_u2{l0, l1};
+    *reinterpret_cast<u32x2*>(dst + ((lane >> 3) * 2 + 0) * TT * 1024) = u32x2{h0, h1};
+    *reinterpret_cast<u32x2*>(dst + ((lane >> 3) * 2 + 1) * TT * 1024) = u32x2{l0, l1};
   }
   __syncthreads();
 
@@ -1119,7 +981,7 @@ __global__ __launch_bounds__(512) void token_tail_kernel(TbArgs a) {
   // ---- out = LayerNorm(relu(y Wexp^T + b) Wsq^T + b + y), the hidden row in two halves of 256 channels
   f32x4 acc[2][TT];
   zero(acc);
-  tb_static_for<0, 2>([&](auto HC) {
+  static_for<0, 2>([&](auto HC) {
     constexpr int hf = decltype(HC)::value;
     f32x4 ha[2][TT];
     zero(ha);
@@ -1235,15 +1097,7 @@ __global__ __launch_bounds__(512, 1) void rpe_front_kernel(RfArgs a) {
       constexpr size_t off = I < 24 ? (size_t)I * TB_P256
                                     : (((I - 24) % 3) == 2 ? 24 * (size_t)TB_P256 + 32 * (size_t)TB_P64
                                                            : 24 * (size_t)TB_P256 + (size_t)(((I - 24) / 3) * 8 + ((I - 24) % 3) * 4) * TB_P64);
-      constexpr int NP = 32 / 4;
-      const unsigned char* src = a.wimg + off;
-      unsigned char* dst = pan + (I & 1) * TB_PANEL_BYTES;
-#pragma unroll
-      for (int k = 0; k < NP; ++k) {
-        const int pc = (wave - 4) + 4 * k;
-        __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)(src + (size_t)pc * 1024 + lane * 16),
-                                         (void __attribute__((address_space(3)))*)(dst + pc * 1024), 16, 0, 0);
-      }
+      dma_pieces<32 / 4>(a.wimg + off, pan + (I & 1) * TB_PANEL_BYTES, wave - 4, 4, lane);
     }
   };
   // the computing waves' side of the loader waves' barrier of unit I
@@ -1254,7 +1108,7 @@ __global__ __launch_bounds__(512, 1) void rpe_front_kernel(RfArgs a) {
   };
   if (wave >= 4) {  // a loader wave: unit I + 1 goes out once unit I has landed and every wave has left unit I - 1
     dma(std::integral_constant<int, 0>{});
-    tb_static_for<0, NPAN>([&](auto IC) {
+    static_for<0, NPAN>([&](auto IC) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
       dma(std::integral_constant<int, decltype(IC)::value + 1>{});
@@ -1263,43 +1117,12 @@ __global__ __launch_bounds__(512, 1) void rpe_front_kernel(RfArgs a) {
   }
 
   half8 xh[8], xl[8];
-  float sx;
-  {
-    const float* src = a.x + (size_t)row * 256;
-    float4 va[8], vb[8];
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-      va[s] = *reinterpret_cast<const float4*>(src + 32 * s + 4 * fg);
-      vb[s] = *reinterpret_cast<const float4*>(src + 32 * s + 16 + 4 * fg);
-    }
-    float m = 0.f;
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-      m = fmaxf(m, fmaxf(fmaxf(fabsf(va[s].x), fabsf(va[s].y)), fmaxf(fabsf(va[s].z), fabsf(va[s].w))));
-      m = fmaxf(m, fmaxf(fmaxf(fabsf(vb[s].x), fabsf(vb[s].y)), fmaxf(fabsf(vb[s].z), fabsf(vb[s].w))));
-    }
-    sx = pow2_scale(tok_max(m));
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-      const float e[8] = {va[s].x, va[s].y, va[s].z, va[s].w, vb[s].x, vb[s].y, vb[s].z, vb[s].w};
-#pragma unroll
-      for (int u = 0; u < 8; u += 2) {
-        unsigned hi, lo;
-        sam6d_split2_f16(e[u] * sx, e[u + 1] * sx, hi, lo);
-        const _Float16 __attribute__((ext_vector_type(2))) h2 = __builtin_bit_cast(_Float16 __attribute__((ext_vector_type(2))), hi);
-        const _Float16 __attribute__((ext_vector_type(2))) l2 = __builtin_bit_cast(_Float16 __attribute__((ext_vector_type(2))), lo);
-        xh[s][u] = h2[0];
-        xh[s][u + 1] = h2[1];
-        xl[s][u] = l2[0];
-        xl[s][u + 1] = l2[1];
-      }
-    }
-  }
+  const float sx = split_row256<false>(a.x + (size_t)row * 256, fg, xh, xl);
   // ---- qkv: 24 panels; the q tiles (first 8 panels) are kept for the folds
   f32x4 qa[16];
   const float inv0 = a.inv_qkv * (1.0f / sx);
   float* orow = a.qkv + (size_t)row * 768;
-  tb_static_for<0, 24>([&](auto J) {
+  static_for<0, 24>([&](auto J) {
     constexpr int j = decltype(J)::value;
     const unsigned p = next_panel(std::integral_constant<int, j>{});
     f32x4 c0 = f32x4{0.f, 0.f, 0.f, 0.f}, c1 = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -1331,13 +1154,13 @@ __global__ __launch_bounds__(512, 1) void rpe_front_kernel(RfArgs a) {
   const float sq = tb_split_rows<16>(qa, qh, ql);
   // ---- per head: qp_h = Wp_h^T q_h (8 panels, K = 64 = k-steps 2h, 2h+1 of q), then qd_h = D_c^T qp_h (1 panel, K = 256)
   const float inv1 = a.inv_wp * (1.0f / sq);
-  tb_static_for<0, 4>([&](auto HH) {
+  static_for<0, 4>([&](auto HH) {
     constexpr int h = decltype(HH)::value;
     f32x4 pa[16];
-    tb_static_for<0, 2>([&](auto GG) {
+    static_for<0, 2>([&](auto GG) {
       constexpr int gq = decltype(GG)::value;
       const unsigned p4 = next_panel(std::integral_constant<int, 24 + 3 * h + gq>{});
-      tb_static_for<0, 4>([&](auto U) {
+      static_for<0, 4>([&](auto U) {
         constexpr int j = 4 * gq + decltype(U)::value;
         f32x4 c0 = f32x4{0.f, 0.f, 0.f, 0.f}, c1 = f32x4{0.f, 0.f, 0.f, 0.f};
         tb_mma<2>(c0, c1, p4 + decltype(U)::value * TB_P64, qh + 2 * h, ql + 2 * h, fr, fg, false);
@@ -1384,15 +1207,9 @@ static int rpe_front_launch(const float* x, const void* wimage, const float* bia
                 "rpe_front: pointers must be 16-byte aligned");
   if (M == 0) return 0;
   static unsigned long long done = 0;
-  if (sam6d_first_use_on_device(&done)) {
-    hipError_t e = hipFuncSetAttribute((const void*)rpe_front_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * TB_PANEL_BYTES);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)rpe_front_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * TB_PANEL_BYTES);
-    if (e != hipSuccess) {
-      sam6d_set_error("rpe_front: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return (int)e;
-    }
-    sam6d_setup_done_on_device(&done);
-  }
+  if (int rc = sam6d_reserve_lds(&done, "rpe_front", {{(const void*)rpe_front_kernel<false>, 2 * TB_PANEL_BYTES},
+                                                      {(const void*)rpe_front_kernel<true>, 2 * TB_PANEL_BYTES}}))
+    return rc;
   RfArgs a{x, (const unsigned char*)wimage, bias_qkv, qkv, qp, qd, M, inv_qkv, inv_wp, inv_dc, vT, n, ldp};
   const dim3 g((unsigned)((M + 63) / 64));
   if (vT)
@@ -1427,56 +1244,19 @@ __global__ __launch_bounds__(256, 2) void out_split_kernel(OsArgs a) {
   const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6), fr = lane & 15, fg = lane >> 4;
   const unsigned pan_lds = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)lds;
   auto dma_step = [&](int T) {  // panel T into slot T & 1, dealt to the four waves
-    const unsigned char* src = a.wimg + (size_t)T * TB_PANEL_BYTES;
-    unsigned char* dst = lds + (T & 1) * TB_PANEL_BYTES;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int pc = wave + 4 * k;
-      __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)(src + (size_t)pc * 1024 + lane * 16),
-                                       (void __attribute__((address_space(3)))*)(dst + pc * 1024), 16, 0, 0);
-    }
+    dma_pieces<8>(a.wimg + (size_t)T * TB_PANEL_BYTES, lds + (T & 1) * TB_PANEL_BYTES, wave, 4, lane);
   };
   dma_step(0);
   const long r0 = (long)blockIdx.x * 64 + wave * 16 + fr;
   const bool valid = r0 < a.M;
   const long row = valid ? r0 : a.M - 1;
   half8 xh[8], xl[8];
-  float sx;
-  {
-    const float* src = a.x + (size_t)row * 256;
-    f32x4 va[8], vb[8];
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-      va[s] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src + 32 * s + 4 * fg));
-      vb[s] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src + 32 * s + 16 + 4 * fg));
-    }
-    float m = 0.f;
-#pragma unroll
-    for (int s = 0; s < 8; ++s)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) m = fmaxf(m, fmaxf(fabsf(va[s][r]), fabsf(vb[s][r])));
-    sx = pow2_scale(tok_max(m));
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-      const float e[8] = {va[s][0], va[s][1], va[s][2], va[s][3], vb[s][0], vb[s][1], vb[s][2], vb[s][3]};
-#pragma unroll
-      for (int u = 0; u < 8; u += 2) {
-        unsigned hi, lo;
-        sam6d_split2_f16(e[u] * sx, e[u + 1] * sx, hi, lo);
-        const _Float16 __attribute__((ext_vector_type(2))) h2 = __builtin_bit_cast(_Float16 __attribute__((ext_vector_type(2))), hi);
-        const _Float16 __attribute__((ext_vector_type(2))) l2 = __builtin_bit_cast(_Float16 __attribute__((ext_vector_type(2))), lo);
-        xh[s][u] = h2[0];
-        xh[s][u + 1] = h2[1];
-        xl[s][u] = l2[0];
-        xl[s][u + 1] = l2[1];
-      }
-    }
-  }
+  const float sx = split_row256<true>(a.x + (size_t)row * 256, fg, xh, xl);
   f32x4 acc[16];
 #pragma unroll
   for (int i = 0; i < 16; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
   const bool half = a.half != 0;
-  tb_static_for<0, 8>([&](auto J) {
+  static_for<0, 8>([&](auto J) {
     constexpr int j = decltype(J)::value;
     // panel j has landed and is published; the slot of panel j - 1 is free
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1505,8 +1285,8 @@ __global__ __launch_bounds__(256, 2) void out_split_kernel(OsArgs a) {
       unsigned h01, l01, h23, l23;
       sam6d_split2_f16((acc[i][0] / d) * 1024.0f, (acc[i][1] / d) * 1024.0f, h01, l01);
       sam6d_split2_f16((acc[i][2] / d) * 1024.0f, (acc[i][3] / d) * 1024.0f, h23, l23);
-      *reinterpret_cast<tb_u2*>(oh + 16 * i) = tb_u2{h01, h23};
-      *reinterpret_cast<tb_u2*>(ol + 16 * i) = tb_u2{l01, l23};
+      *reinterpret_cast<u32x2*>(oh + 16 * i) = u32x2{h01, h23};
+      *reinterpret_cast<u32x2*>(ol + 16 * i) = u32x2{l01, l23};
     }
   }
 }
@@ -1526,14 +1306,7 @@ extern "C" int sam6d_linear_norm_split(const float* x, const void* wimage, const
                 "linear_norm_split: pointers must be 16-byte aligned");
   if (M == 0) return 0;
   static unsigned long long done = 0;
-  if (sam6d_first_use_on_device(&done)) {
-    hipError_t e = hipFuncSetAttribute((const void*)out_split_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * TB_PANEL_BYTES);
-    if (e != hipSuccess) {
-      sam6d_set_error("linear_norm_split: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return (int)e;
-    }
-    sam6d_setup_done_on_device(&done);
-  }
+  if (int rc = sam6d_reserve_lds(&done, "linear_norm_split", {{(const void*)out_split_kernel, 2 * TB_PANEL_BYTES}})) return rc;
   OsArgs a{x, (const unsigned char*)wimage, bias, (_Float16*)fh, (_Float16*)fl, M, inv_w_scale, sam6d_half_for(1)};
   hipLaunchKernelGGL(out_split_kernel, dim3((unsigned)((M + 63) / 64)), dim3(256), 2 * TB_PANEL_BYTES, (hipStream_t)stream, a);
   SAM6D_LAUNCH_CHECK("linear_norm_split");
@@ -1566,14 +1339,7 @@ __global__ __launch_bounds__(512, 1) void rows_linear_kernel(RlArgs a) {
   static_assert(NP % 2 == 0, "two panels per step");
   if (wave >= 4) {  // loader waves
     auto dma_step = [&](int T) {
-      const unsigned char* src = a.wimg + (size_t)T * SLOT;
-      unsigned char* dst = lds + (T & 1) * SLOT;
-#pragma unroll
-      for (int k = 0; k < 16; ++k) {
-        const int pc = (wave - 4) + 4 * k;
-        __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)(src + (size_t)pc * 1024 + lane * 16),
-                                         (void __attribute__((address_space(3)))*)(dst + pc * 1024), 16, 0, 0);
-      }
+      dma_pieces<16>(a.wimg + (size_t)T * SLOT, lds + (T & 1) * SLOT, wave - 4, 4, lane);
     };
     dma_step(0);
 #pragma unroll
@@ -1589,42 +1355,11 @@ __global__ __launch_bounds__(512, 1) void rows_linear_kernel(RlArgs a) {
   const long R = valid ? r0 : a.M - 1;
   const long cb = R / a.rpb, cr = R - cb * a.rpb;
   half8 xh[8], xl[8];
-  float sx;
-  {
-    const float* src = a.x + (size_t)(cb * a.x_bs + a.x_r0 + cr) * 256;
-    float4 va[8], vb[8];
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-      va[s] = *reinterpret_cast<const float4*>(src + 32 * s + 4 * fg);
-      vb[s] = *reinterpret_cast<const float4*>(src + 32 * s + 16 + 4 * fg);
-    }
-    float m = 0.f;
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-      m = fmaxf(m, fmaxf(fmaxf(fabsf(va[s].x), fabsf(va[s].y)), fmaxf(fabsf(va[s].z), fabsf(va[s].w))));
-      m = fmaxf(m, fmaxf(fmaxf(fabsf(vb[s].x), fabsf(vb[s].y)), fmaxf(fabsf(vb[s].z), fabsf(vb[s].w))));
-    }
-    sx = pow2_scale(tok_max(m));
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-      const float e[8] = {va[s].x, va[s].y, va[s].z, va[s].w, vb[s].x, vb[s].y, vb[s].z, vb[s].w};
-#pragma unroll
-      for (int u = 0; u < 8; u += 2) {
-        unsigned hi, lo;
-        sam6d_split2_f16(e[u] * sx, e[u + 1] * sx, hi, lo);
-        const _Float16 __attribute__((ext_vector_type(2))) h2 = __builtin_bit_cast(_Float16 __attribute__((ext_vector_type(2))), hi);
-        const _Float16 __attribute__((ext_vector_type(2))) l2 = __builtin_bit_cast(_Float16 __attribute__((ext_vector_type(2))), lo);
-        xh[s][u] = h2[0];
-        xh[s][u + 1] = h2[1];
-        xl[s][u] = l2[0];
-        xl[s][u + 1] = l2[1];
-      }
-    }
-  }
+  const float sx = split_row256<false>(a.x + (size_t)(cb * a.x_bs + a.x_r0 + cr) * 256, fg, xh, xl);
   const bool half = a.half != 0;
   const float inv = a.inv_w * (1.0f / sx);
   float* orow = a.out + (size_t)(cb * a.o_bs + a.o_r0 + cr) * (32 * NP);
-  tb_static_for<0, NP>([&](auto J) {
+  static_for<0, NP>([&](auto J) {
     constexpr int j = decltype(J)::value;
     if constexpr ((j & 1) == 0) __syncthreads();  // step j / 2 has landed (loader waves) and is published
     const unsigned p = pan_lds + ((j >> 1) & 1) * SLOT + (j & 1) * TB_PANEL_BYTES;
@@ -1652,16 +1387,9 @@ extern "C" int sam6d_rows_linear(const float* x, const void* wimage, int npanels
   SAM6D_REQUIRE(((((size_t)x) | ((size_t)wimage) | ((size_t)bias) | ((size_t)out)) & 15) == 0, "rows_linear: pointers must be 16-byte aligned");
   if (M == 0) return 0;
   static unsigned long long done = 0;
-  if (sam6d_first_use_on_device(&done)) {
-    hipError_t e = hipFuncSetAttribute((const void*)rows_linear_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TB_PANEL_BYTES);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void*)rows_linear_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TB_PANEL_BYTES);
-    if (e != hipSuccess) {
-      sam6d_set_error("rows_linear: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return (int)e;
-    }
-    sam6d_setup_done_on_device(&done);
-  }
+  if (int rc = sam6d_reserve_lds(&done, "rows_linear", {{(const void*)rows_linear_kernel<8>, 4 * TB_PANEL_BYTES},
+                                                        {(const void*)rows_linear_kernel<16>, 4 * TB_PANEL_BYTES}}))
+    return rc;
   RlArgs a{x, (const unsigned char*)wimage, bias, out, M, rows_per_cloud, x_cloud_rows, x_row0, out_cloud_rows, out_row0, inv_w_scale,
            sam6d_half_for(1)};
   const dim3 g((unsigned)((M + 63) / 64));
@@ -1672,34 +1400,15 @@ extern "C" int sam6d_rows_linear(const float* x, const void* wimage, int npanels
   SAM6D_LAUNCH_CHECK("rows_linear");
 }
 
-#define TB_LDS_BYTES(NBUF) ((NBUF) * TB_PANEL_BYTES + (TC_N + 256) * 4)
-
-// The launched shapes: the dense layer (sam6d_linattn_layer) runs 4 waves x 16 tokens with a 2-slot panel ring (77 KB of LDS: two
-// workgroups per CU, which run out of step, so one's row epilogues overlap the other's MFMAs); the 197-token layers (sam6d_token_block)
-// run token_tail_kernel: eight waves per 32- or 64-token tile, output channels dealt to the waves.
-
-template <class K>
-static int tb_attr(K kernel, int bytes) {
-  hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e != hipSuccess) {
-    sam6d_set_error("token_block: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-    return (int)e;
-  }
-  return 0;
-}
-
-static int tb_set_attr() {
-  static unsigned long long done0 = 0;
-  if (sam6d_first_use_on_device(&done0)) {
-    int rc = tb_attr(token_block_kernel<1, 4, 2>, TB_LDS_BYTES(2));
-    if (!rc) rc = tb_attr(token_tail_kernel<2, TT_D2, false>, TT_LDS_BYTES(2));
-    if (!rc) rc = tb_attr(token_tail_kernel<4, TT_D4, false>, TT_LDS_BYTES(4));
-    if (!rc) rc = tb_attr(token_tail_kernel<2, TT_D2, true>, TT_LDS_BYTES(2));
-    if (!rc) rc = tb_attr(token_tail_kernel<4, TT_D4, true>, TT_LDS_BYTES(4));
-    if (rc) return rc;
-    sam6d_setup_done_on_device(&done0);
-  }
-  return 0;
+// The launched shapes: the dense layer (sam6d_linattn_layer) runs token_block_kernel, 64 tokens per workgroup; the 197-token layers
+// (sam6d_token_block) run token_tail_kernel: eight waves per 32- or 64-token tile, output channels dealt to the waves.
+static int tb_reserve_lds(const char* name) {
+  static unsigned long long done = 0;
+  return sam6d_reserve_lds(&done, name, {{(const void*)token_block_kernel, TB_LDS_BYTES},
+                                         {(const void*)token_tail_kernel<2, TT_D2, false>, TT_LDS_BYTES(2)},
+                                         {(const void*)token_tail_kernel<4, TT_D4, false>, TT_LDS_BYTES(4)},
+                                         {(const void*)token_tail_kernel<2, TT_D2, true>, TT_LDS_BYTES(2)},
+                                         {(const void*)token_tail_kernel<4, TT_D4, true>, TT_LDS_BYTES(4)}});
 }
 
 extern "C" int sam6d_token_block(const float* hidden, const float* x, const void* wimage, const float* consts, float* out, long M,
@@ -1707,8 +1416,7 @@ extern "C" int sam6d_token_block(const float* hidden, const float* x, const void
   SAM6D_REQUIRE(hidden && x && wimage && consts && out && M >= 0, "token_block: bad arguments");
   SAM6D_REQUIRE(((((size_t)hidden) | ((size_t)x) | ((size_t)out) | ((size_t)wimage)) & 15) == 0, "token_block: pointers must be 16-byte aligned");
   if (M == 0) return 0;
-  int rc = tb_set_attr();
-  if (rc) return rc;
+  if (int rc = tb_reserve_lds("token_block")) return rc;
   TbArgs a{hidden, x, out, (const unsigned char*)wimage, consts, nullptr, nullptr, nullptr, M, 0, 0, 0, eps,
            sam6d_half_for(1)};
   // The tile shape is a function of M and the CU count only: 32-token tiles while they all fit the chip in one round (6304 rows = 197
@@ -1716,14 +1424,8 @@ extern "C" int sam6d_token_block(const float* hidden, const float* x, const void
   // the L2 bytes per token).  Measured at 12608 rows: 394 x 32 tokens 45.6 us (two 512-thread workgroups of 208 registers per lane do not
   // share a CU, so 138 CUs run two tiles one after the other), 197 x 64 tokens 34.0 us.  A token's arithmetic does not depend on the
   // shape (token_tail_kernel): bit-identical results either way.
-  int dev_ = 0, cus = 256;
-  if (hipGetDevice(&dev_) == hipSuccess) {
-    static int cu_cache[SAM6D_MAX_DEVICES];
-    if (dev_ >= 0 && dev_ < SAM6D_MAX_DEVICES) {
-      if (!cu_cache[dev_] && hipDeviceGetAttribute(&cu_cache[dev_], hipDeviceAttributeMultiprocessorCount, dev_) != hipSuccess) cu_cache[dev_] = 256;
-      cus = cu_cache[dev_];
-    }
-  }
+  int cus = sam6d_cu_count();
+  if (cus <= 0) cus = 256;  // (an unknown device: the MI355X's count)
   const bool small = (M + 31) / 32 <= cus;
   const dim3 grid((unsigned)(small ? (M + 31) / 32 : (M + 63) / 64));
   const int ldsb = small ? TT_LDS_BYTES(2) : TT_LDS_BYTES(4);
@@ -1739,12 +1441,11 @@ extern "C" int sam6d_linattn_layer(const float* D, const void* wimage, const flo
                 "linattn_layer: bad arguments");
   SAM6D_REQUIRE(((((size_t)D) | ((size_t)Dout) | ((size_t)wimage) | ((size_t)kvimage)) & 15) == 0, "linattn_layer: pointers must be 16-byte aligned");
   if (B == 0) return 0;
-  int rc = tb_set_attr();
-  if (rc) return rc;
-  const int tiles = (I - row0 + 63) / 64;  // 64-token workgroups
+  if (int rc = tb_reserve_lds("linattn_layer")) return rc;
+  const int tiles = (I - row0 + 16 * TB_WAVES - 1) / (16 * TB_WAVES);  // 64-token workgroups
   SAM6D_REQUIRE((long)B * tiles < 2147483647L, "linattn_layer: too many tiles");
   TbArgs a{D, nullptr, Dout, (const unsigned char*)wimage, consts, (const unsigned char*)kvimage, kvinv, ksum, 0, I, row0, tiles, eps,
            sam6d_half_for(1)};
-  hipLaunchKernelGGL((token_block_kernel<1, 4, 2>), dim3((unsigned)(B * tiles)), dim3(256), TB_LDS_BYTES(2), (hipStream_t)stream, a);
+  hipLaunchKernelGGL(token_block_kernel, dim3((unsigned)(B * tiles)), dim3(TB_WAVES * 64), TB_LDS_BYTES, (hipStream_t)stream, a);
   SAM6D_LAUNCH_CHECK("linattn_layer");
 }

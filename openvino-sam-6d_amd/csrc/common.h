@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <initializer_list>
+#include <type_traits>
 
 #define SAM6D_WAVE 64
 
@@ -47,6 +49,8 @@ void sam6d_set_error(const char* fmt, ...);
 typedef float f32x4 __attribute__((ext_vector_type(4)));     // one MFMA accumulator tile per lane
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));  // one fp16 MFMA operand (k = 32) per lane
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));  // 16 bytes of packed halves: one LDS / buffer fragment read
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 __device__ __forceinline__ int wave_id() { return threadIdx.x >> 6; }
@@ -224,6 +228,70 @@ __device__ __forceinline__ void sam6d_split2_f16(float a, float b, unsigned& hi2
   asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(lo2) : "v"(la), "v"(lb));
 }
 
+// ---- shared steps of the split-precision panel kernels (block.hip, xattn.hip) ------------------------------------
+// compile-time loop: f(std::integral_constant<int, I>) for I = B .. E-1
+template <int B, int E, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+  if constexpr (B < E) {
+    f(std::integral_constant<int, B>{});
+    static_for<B + 1, E>(f);
+  }
+}
+
+// split the pair (a, b) into slots i, i + 1 of an MFMA operand pair: hi halves to xh, lo halves to xl
+__device__ __forceinline__ void sam6d_split2_f16(float a, float b, half8& xh, half8& xl, int i) {
+  typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+  unsigned hi, lo;
+  sam6d_split2_f16(a, b, hi, lo);
+  const f16x2 h2 = __builtin_bit_cast(f16x2, hi), l2 = __builtin_bit_cast(f16x2, lo);
+  xh[i] = h2[0];
+  xh[i + 1] = h2[1];
+  xl[i] = l2[0];
+  xl[i + 1] = l2[1];
+}
+
+// One 256-channel fp32 row as the B operand of a transposed product (block.hip, header comment): lane group fg = lane >> 4 of the
+// token's four lanes takes channels 32 s + 4 fg .. + 3 and 32 s + 16 + 4 fg .. + 3 of every k-step s = 0 .. 7.  The row is scaled by
+// pow2_scale of its max |.| and split into xh[8] / xl[8]; returns the scale.  NT: non-temporal loads, for rows that are read exactly
+// once and must not evict the weight images that every workgroup re-reads from the L2.
+template <bool NT>
+__device__ __forceinline__ float split_row256(const float* __restrict__ src, int fg, half8* xh, half8* xl) {
+  f32x4 va[8], vb[8];
+#pragma unroll
+  for (int s = 0; s < 8; ++s) {
+    const f32x4* pa = reinterpret_cast<const f32x4*>(src + 32 * s + 4 * fg);
+    const f32x4* pb = reinterpret_cast<const f32x4*>(src + 32 * s + 16 + 4 * fg);
+    va[s] = NT ? __builtin_nontemporal_load(pa) : *pa;
+    vb[s] = NT ? __builtin_nontemporal_load(pb) : *pb;
+  }
+  float m = 0.f;
+#pragma unroll
+  for (int s = 0; s < 8; ++s) {
+    m = fmaxf(m, fmaxf(fmaxf(fabsf(va[s][0]), fabsf(va[s][1])), fmaxf(fabsf(va[s][2]), fabsf(va[s][3]))));
+    m = fmaxf(m, fmaxf(fmaxf(fabsf(vb[s][0]), fabsf(vb[s][1])), fmaxf(fabsf(vb[s][2]), fabsf(vb[s][3]))));
+  }
+  const float sx = pow2_scale(tok_max(m));
+#pragma unroll
+  for (int s = 0; s < 8; ++s) {
+    const float e[8] = {va[s][0], va[s][1], va[s][2], va[s][3], vb[s][0], vb[s][1], vb[s][2], vb[s][3]};
+#pragma unroll
+    for (int u = 0; u < 8; u += 2) sam6d_split2_f16(e[u] * sx, e[u + 1] * sx, xh[s], xl[s], u);
+  }
+  return sx;
+}
+
+// LDS-DMA of NP pieces of 1 KiB (64 lanes x 16 B) from a global image to the same offsets of its LDS copy: pieces first, first + stride, ...
+// (the waves that share a copy pass their index and their number).  Unrolled at compile time, not a loop: in a loop the compiler hoists
+// src + lane * 16 as loop-invariant, and every piece then needs a 64-bit vector address instead of scalar base + 32-bit lane offset.
+template <int NP>
+__device__ __forceinline__ void dma_pieces(const unsigned char* src, unsigned char* dst, int first, int stride, int lane) {
+  static_for<0, NP>([&](auto K) {
+    const int pc = first + stride * decltype(K)::value;
+    __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)(src + (size_t)pc * 1024 + lane * 16),
+                                     (void __attribute__((address_space(3)))*)(dst + pc * 1024), 16, 0, 0);
+  });
+}
+
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // One-time per-DEVICE setup (hipFuncSetAttribute, CU count ...): `done` is a bit mask over device ordinals owned by the call site.
@@ -247,6 +315,39 @@ static inline void sam6d_setup_done_on_device(unsigned long long* done) {
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= SAM6D_MAX_DEVICES) return;
   (void)__atomic_fetch_or(done, 1ull << dev, __ATOMIC_RELEASE);
+}
+
+// Reserves dynamic LDS beyond the 64 KB default, once per device: hipFuncSetAttribute for every (kernel, bytes) pair; the device's
+// bit in the call site's `done` mask is set only after all of them succeeded (see above: a failure is retried by the next call).
+struct Sam6dLdsUse {
+  const void* kernel;
+  int bytes;
+};
+static inline int sam6d_reserve_lds(unsigned long long* done, const char* name, std::initializer_list<Sam6dLdsUse> uses) {
+  if (!sam6d_first_use_on_device(done)) return 0;
+  for (const Sam6dLdsUse& u : uses) {
+    const hipError_t e = hipFuncSetAttribute(u.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, u.bytes);
+    if (e != hipSuccess) {
+      sam6d_set_error("%s: cannot reserve %d bytes of LDS: %s", name, u.bytes, hipGetErrorString(e));
+      return (int)e;
+    }
+  }
+  sam6d_setup_done_on_device(done);
+  return 0;
+}
+
+// Compute units of the calling thread's current device, asked once per device (and source file); 0 if the query fails or the ordinal
+// is >= SAM6D_MAX_DEVICES -- what a caller does then is its own policy.
+static inline int sam6d_cu_count() {
+  static int cache[SAM6D_MAX_DEVICES];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= SAM6D_MAX_DEVICES) return 0;
+  int cu = __atomic_load_n(&cache[dev], __ATOMIC_RELAXED);
+  if (cu <= 0) {
+    if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cu <= 0) return 0;
+    __atomic_store_n(&cache[dev], cu, __ATOMIC_RELAXED);
+  }
+  return cu;
 }
 
 // matmul mode 2 (fp16 single product) per kernel family: bit 0 generic GEMM, 1 block kernels, 2 cross attention, 3 fine similarity.

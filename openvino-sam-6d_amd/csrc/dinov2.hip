@@ -295,14 +295,7 @@ extern "C" int sam6d_dino_attention(const float* qkv, float* out, int B, int n, 
   SAM6D_REQUIRE(B <= 65535, "dino_attention: B <= 65535");
   if (B == 0) return 0;
   static unsigned long long done = 0;
-  if (sam6d_first_use_on_device(&done)) {
-    hipError_t e = hipFuncSetAttribute((const void*)dino_attention_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, DA_LDS);
-    if (e != hipSuccess) {
-      sam6d_set_error("dino_attention: cannot reserve %d bytes of LDS: %s", DA_LDS, hipGetErrorString(e));
-      return (int)e;
-    }
-    sam6d_setup_done_on_device(&done);
-  }
+  if (int rc = sam6d_reserve_lds(&done, "dino_attention", {{(const void*)dino_attention_kernel, DA_LDS}})) return rc;
   hipLaunchKernelGGL(dino_attention_kernel, dim3(DN_C / 64, B), dim3(DA_WAVES * 64), DA_LDS, (hipStream_t)stream, qkv, out, n);
   SAM6D_LAUNCH_CHECK("dino_attention");
 }

@@ -215,7 +215,6 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const float* __restrict__ 
 #define H_BK 32
 #define H_LD 40
 
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void split4(const float4 v, half4& hi, half4& lo) {
   unsigned h0, h1, l0, l1;
   sam6d_split2_f16(v.x, v.y, h0, l0);

@@ -368,16 +368,7 @@ extern "C" int sam6d_split_f16(const float* x, long n, float scale, void* hi, vo
 
 static int h3_reserve_lds() {
   static unsigned long long attr_done = 0;
-  if (sam6d_first_use_on_device(&attr_done)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(geo_embed_h3_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, GH_LDS_BYTES);
-    if (e != hipSuccess) {
-      sam6d_set_error("geo_embed_h3: cannot reserve %d bytes of LDS: %s", GH_LDS_BYTES, hipGetErrorString(e));
-      return (int)e;
-    }
-    sam6d_setup_done_on_device(&attr_done);
-  }
-  return 0;
+  return sam6d_reserve_lds(&attr_done, "geo_embed_h3", {{(const void*)geo_embed_h3_kernel, GH_LDS_BYTES}});
 }
 
 extern "C" int sam6d_geo_embed_h3(const float* idx_ws, long pairs, const float* div_term, const void* w_packed, const float* bd,
@@ -593,24 +584,10 @@ extern "C" int sam6d_geo_embed_cheb(const float* idx_ws, long pairs, const void*
                 "geo_embed_cheb: idx_ws/weights must be 16-byte aligned");
   if (pairs == 0) return 0;
   if (int rc = h3_reserve_lds()) return rc;
-  static int n_cu_dev[SAM6D_MAX_DEVICES];
   static unsigned long long cheb_done = 0;
-  int dev = 0;
-  if (sam6d_first_use_on_device(&cheb_done, &dev)) {
-    SAM6D_REQUIRE(dev >= 0, "geo_embed_cheb: device ordinal beyond SAM6D_MAX_DEVICES");
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(geo_cheb_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, GC_LDS_BYTES);
-    int cu = 0;
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e != hipSuccess || cu <= 0) {
-      sam6d_set_error("geo_embed_cheb: cannot reserve %d bytes of LDS / query the device: %s", GC_LDS_BYTES,
-                      hipGetErrorString(e));
-      return e != hipSuccess ? (int)e : SAM6D_EINVAL;
-    }
-    n_cu_dev[dev] = cu;
-    sam6d_setup_done_on_device(&cheb_done);
-  }
-  const int n_cu = n_cu_dev[dev];
+  if (int rc = sam6d_reserve_lds(&cheb_done, "geo_embed_cheb", {{(const void*)geo_cheb_kernel, GC_LDS_BYTES}})) return rc;
+  const int n_cu = sam6d_cu_count();  // the persistent grid's size
+  SAM6D_REQUIRE(n_cu > 0, "geo_embed_cheb: cannot query the device's CU count (or device ordinal beyond SAM6D_MAX_DEVICES)");
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(geo_list_reset_kernel, dim3(1), dim3(1), 0, s, list_ws);
   hipLaunchKernelGGL(geo_classify_kernel, dim3((unsigned)((pairs + GCL_PER - 1) / GCL_PER)), dim3(256), 0, s,

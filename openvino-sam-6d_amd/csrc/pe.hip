@@ -406,15 +406,7 @@ static int pe_mlp_max_impl(const float* pts, const int* idx, int B, int N, int S
     SAM6D_REQUIRE(total < (1l << 31) / 64, "pe_mlp_max: B*N too large for 32-bit point ids (%ld)", total);
     const size_t lds = (size_t)PH_WBYTES;
     static unsigned long long attr_h3 = 0;
-    if (sam6d_first_use_on_device(&attr_h3)) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pe_mlp_max_h3_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) {
-        sam6d_set_error("pe_mlp_max: cannot reserve %zu bytes of LDS: %s", lds, hipGetErrorString(e));
-        return (int)e;
-      }
-      sam6d_setup_done_on_device(&attr_h3);
-    }
+    if (int rc = sam6d_reserve_lds(&attr_h3, "pe_mlp_max", {{(const void*)pe_mlp_max_h3_kernel, (int)lds}})) return rc;
     // persistent waves: 3 workgroups of 4 waves fit one CU's LDS (3 x 48.6 KB) -> 768 workgroups fill the 256 CUs once
     const long want = (total + PH_WAVES - 1) / PH_WAVES;
     const long cap = (max_wg > 0 && max_wg < 768) ? max_wg : 768;
@@ -426,15 +418,7 @@ static int pe_mlp_max_impl(const float* pts, const int* idx, int B, int N, int S
   } else {
     const size_t lds = (size_t)(PM_WFLOATS + PM_WAVES * PM_HFLOATS) * 4;
     static unsigned long long attr_set = 0;
-    if (sam6d_first_use_on_device(&attr_set)) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pe_mlp_max_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) {
-        sam6d_set_error("pe_mlp_max: cannot reserve %zu bytes of LDS: %s", lds, hipGetErrorString(e));
-        return (int)e;
-      }
-      sam6d_setup_done_on_device(&attr_set);
-    }
+    if (int rc = sam6d_reserve_lds(&attr_set, "pe_mlp_max", {{(const void*)pe_mlp_max_kernel, (int)lds}})) return rc;
     hipLaunchKernelGGL(pe_mlp_max_kernel, grid, dim3(PM_WAVES * 64), lds, (hipStream_t)stream, pts, idx, N, S, total, W1, sc1,
                        sh1, W2, sc2, sh2, W3, sc3, sh3, out, ldo, off);
   }

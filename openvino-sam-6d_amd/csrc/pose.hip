@@ -378,15 +378,7 @@ extern "C" int sam6d_coarse_soft_assign(const float* att, int B, int R, int C, f
                 "coarse_soft_assign: the %d x %d matrix does not fit the 160 KB of LDS (use sam6d_soft_assign + sam6d_coarse_weights)", R, C);
   if (B == 0) return 0;
   static unsigned long long cas_done = 0;
-  if (sam6d_first_use_on_device(&cas_done)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(coarse_assign_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       160 * 1024);
-    if (e != hipSuccess) {
-      sam6d_set_error("coarse_soft_assign: cannot reserve LDS: %s", hipGetErrorString(e));
-      return (int)e;
-    }
-    sam6d_setup_done_on_device(&cas_done);
-  }
+  if (int rc = sam6d_reserve_lds(&cas_done, "coarse_soft_assign", {{(const void*)coarse_assign_kernel, 160 * 1024}})) return rc;
   hipLaunchKernelGGL(coarse_assign_kernel, dim3(B), dim3(1024), CAS_LDS_BYTES(R, C), (hipStream_t)stream, att, R, C, rmax, rsum, cmax,
                      csum, label1, label2, weights, w1);
   SAM6D_LAUNCH_CHECK("coarse_soft_assign");
@@ -1149,15 +1141,7 @@ extern "C" int sam6d_score_select_hypotheses_ws(const int* sel, const float* Rs,
   const long tiles = ((long)k * N1 + 31) / 32;
   const int wgs = (int)((tiles + SM_WAVES * SM_CT - 1) / (SM_WAVES * SM_CT));
   static unsigned long long shm_done = 0;  // P = 4096 needs 80 KB of dynamic LDS: above the default 64 KB limit
-  if (sam6d_first_use_on_device(&shm_done)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(score_hyp_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       4096 * 20);
-    if (e != hipSuccess) {
-      sam6d_set_error("score_select_hypotheses_ws: cannot reserve LDS: %s", hipGetErrorString(e));
-      return (int)e;
-    }
-    sam6d_setup_done_on_device(&shm_done);
-  }
+  if (int rc = sam6d_reserve_lds(&shm_done, "score_select_hypotheses_ws", {{(const void*)score_hyp_mfma_kernel, 4096 * 20}})) return rc;
   hipLaunchKernelGGL(score_hyp_mfma_kernel, dim3(wgs, B), dim3(SM_WAVES * 64), (size_t)Ppad * 20, s, sel, Rs, ts, pts1, w1, model, radius, N1,
                      P, Ppad, nh, k, ws);
   SAM6D_LAUNCH_CHECK_CONT("score_select_hypotheses_ws(score)");
@@ -1528,15 +1512,8 @@ extern "C" int sam6d_fine_score(const float* pts1, const float* R, float* t, con
   SAM6D_REQUIRE(B >= 0 && N > 0 && P > 0 && P <= 8192 && B <= 65535, "fine_score: bad sizes (P <= 8192)");
   if (B == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
-  static unsigned long long fn_done = 0;
-  if (sam6d_first_use_on_device(&fn_done)) {  // P = 8192 CAD points are 128 KB of dynamic LDS (the default limit is 64 KB)
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fine_near_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 8192 * 16);
-    if (e != hipSuccess) {
-      sam6d_set_error("fine_score: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return (int)e;
-    }
-    sam6d_setup_done_on_device(&fn_done);
-  }
+  static unsigned long long fn_done = 0;  // P = 8192 CAD points are 128 KB of dynamic LDS (the default limit is 64 KB)
+  if (int rc = sam6d_reserve_lds(&fn_done, "fine_score", {{(const void*)fine_near_kernel, 8192 * 16}})) return rc;
   hipLaunchKernelGGL(zero_kernel, dim3(cdiv(2 * B, 256)), dim3(256), 0, s, cnt_ws, 2 * B);
   // the matrix-core kernel while its Ppad * 20 bytes of CAD points fit the default 64 KB of LDS (P <= 3264); the vector-ALU kernel beyond
   const int Ppad = (P + 31) & ~31;

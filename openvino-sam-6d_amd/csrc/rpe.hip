@@ -69,7 +69,6 @@ __device__ __forceinline__ void swap16(float& a, float& b) {
 #define RP_QF_BYTES 4096                       // folded query as stage-2 B fragments: [G 8][kg 4][head 4][8 halves], hi plane | lo plane
 #define RP_QW_FLOATS (RP_QF_BYTES / 4 + 128)   // + qd [head][32]
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 #ifndef RP_PRIO
 #define RP_PRIO 1
 #endif
@@ -523,29 +522,14 @@ static int rpe_scores_impl(const float* idx_ws, const int* pos_ws, const int* li
                 "rpe_scores: idx_ws / wa_cheb / qp / qd / rows must be 16-byte aligned");
   if (Q == 0) return 0;
   const int lds_max = 160 * 1024 - 64;  // dynamic part: the kernel has one static word (its query counter)
-  static int n_cu_dev[SAM6D_MAX_DEVICES];
   static unsigned long long rpe_done = 0;
-  int dev = 0;
-  if (sam6d_first_use_on_device(&rpe_done, &dev)) {
-    SAM6D_REQUIRE(dev >= 0, "rpe_scores: device ordinal beyond SAM6D_MAX_DEVICES");
-    int cu = 0;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(rpe_score_kernel<3>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(rpe_score_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(rpe_score_kernel<3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(rpe_score_kernel<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e != hipSuccess || cu <= 0) {
-      sam6d_set_error("rpe_scores: cannot reserve %d bytes of LDS / query the device: %s", lds_max, hipGetErrorString(e));
-      return e != hipSuccess ? (int)e : SAM6D_EINVAL;
-    }
-    n_cu_dev[dev] = cu;
-    sam6d_setup_done_on_device(&rpe_done);
-  }
-  const int n_cu = n_cu_dev[dev];
+  if (int rc = sam6d_reserve_lds(&rpe_done, "rpe_scores", {{(const void*)rpe_score_kernel<3>, lds_max},
+                                                           {(const void*)rpe_score_kernel<2>, lds_max},
+                                                           {(const void*)rpe_score_kernel<3, true>, lds_max},
+                                                           {(const void*)rpe_score_kernel<2, true>, lds_max}}))
+    return rc;
+  const int n_cu = sam6d_cu_count();  // the persistent grid's size
+  SAM6D_REQUIRE(n_cu > 0, "rpe_scores: cannot query the device's CU count (or device ordinal beyond SAM6D_MAX_DEVICES)");
   const float scale = 0.125f;  // 1/sqrt(64): d_model 256, 4 heads (coarse_point_matching.py:24, fine_point_matching.py:31)
   const int mpad = ((n + 15) / 16) * 16;
   const int per_wave = (RP_QW_FLOATS + 4 * mpad) * 4;

@@ -17,7 +17,6 @@
 // fp16 x3 split products with power-of-two operand scales (per token row for x, q, P; per image for Wq, k, v): range-safe, ~1e-6.
 #include "common.h"
 #include <stdlib.h>
-#include <type_traits>
 #include "../../include/sam6d_hip.h"
 
 
@@ -37,20 +36,19 @@ __device__ __forceinline__ int xa_channel_slot(int c) { return 8 * ((c >> 2) & 3
 // The fragment reads run XA_FD steps ahead of the MFMAs, as inline assembly with counted waits (block.hip tb_mma does the same): left
 // to the compiler every ds_read_b128 sinks to just before its use behind an lgkmcnt(0), and with three MFMAs (48 cycles) per step the
 // LDS latency (~150 cycles) was exposed on every one of a wave's ~300 steps -- half of the kernel (SQ_WAIT_ANY 52 % of the wave cycles).
-typedef unsigned xa_u32x4 __attribute__((ext_vector_type(4)));
 #define XA_FD 4
-__device__ __forceinline__ xa_u32x4 xa_lds128(unsigned addr) {
-  xa_u32x4 r;
+__device__ __forceinline__ u32x4 xa_lds128(unsigned addr) {
+  u32x4 r;
   asm volatile("ds_read_b128 %0, %1" : "=v"(r) : "v"(addr));
   return r;
 }
 template <int N>
-__device__ __forceinline__ void xa_wait(xa_u32x4& a, xa_u32x4& b) {
+__device__ __forceinline__ void xa_wait(u32x4& a, u32x4& b) {
   asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N));
 }
 template <int ROWB, int LOCH, int KS, int S>
 __device__ __forceinline__ void xa_mma_step(f32x4& acc, unsigned rb, int row, int fg, const half8* __restrict__ xh,
-                                            const half8* __restrict__ xl, xa_u32x4 (&fh)[XA_FD + 1], xa_u32x4 (&fl)[XA_FD + 1], bool half) {
+                                            const half8* __restrict__ xl, u32x4 (&fh)[XA_FD + 1], u32x4 (&fl)[XA_FD + 1], bool half) {
   if constexpr (S + XA_FD < KS) {
     const int ch = 4 * (S + XA_FD) + fg, cl = LOCH + 4 * (S + XA_FD) + fg;
     fh[(S + XA_FD) % (XA_FD + 1)] = xa_lds128(rb + (((ch & ~15) | ((ch ^ row) & 15)) << 4));
@@ -72,7 +70,7 @@ __device__ __forceinline__ void xa_mma(f32x4& acc, const unsigned char* __restri
                                        const half8* __restrict__ xl, int fr, int fg, bool half) {
   const int row = r0 + fr;
   const unsigned rb = (unsigned)(size_t)(__attribute__((address_space(3))) const unsigned char*)img + (unsigned)row * ROWB;
-  xa_u32x4 fh[XA_FD + 1], fl[XA_FD + 1];
+  u32x4 fh[XA_FD + 1], fl[XA_FD + 1];
 #pragma unroll
   for (int s = 0; s < XA_FD && s < KS; ++s) {
     const int ch = 4 * s + fg, cl = LOCH + 4 * s + fg;
@@ -96,40 +94,6 @@ struct XaArgs {
   float inv_wkv;             // KVP: 1 / pack scale of [Wk; Wv]
 };
 
-// the 16-token group `grp` of rows (b, tok, 256 channels) as split B fragments: returns the row scale
-__device__ __forceinline__ float xa_load_rows(const float* __restrict__ base, int tok, half8* xh, half8* xl, int fg) {
-  const float* src = base + (size_t)tok * 256;
-  float4 va[8], vb4[8];
-#pragma unroll
-  for (int s = 0; s < 8; ++s) {
-    va[s] = *reinterpret_cast<const float4*>(src + 32 * s + 4 * fg);
-    vb4[s] = *reinterpret_cast<const float4*>(src + 32 * s + 16 + 4 * fg);
-  }
-  float mx = 0.f;
-#pragma unroll
-  for (int s = 0; s < 8; ++s) {
-    mx = fmaxf(mx, fmaxf(fmaxf(fabsf(va[s].x), fabsf(va[s].y)), fmaxf(fabsf(va[s].z), fabsf(va[s].w))));
-    mx = fmaxf(mx, fmaxf(fmaxf(fabsf(vb4[s].x), fabsf(vb4[s].y)), fmaxf(fabsf(vb4[s].z), fabsf(vb4[s].w))));
-  }
-  const float sx = pow2_scale(tok_max(mx));
-#pragma unroll
-  for (int s = 0; s < 8; ++s) {
-    const float e8[8] = {va[s].x, va[s].y, va[s].z, va[s].w, vb4[s].x, vb4[s].y, vb4[s].z, vb4[s].w};
-#pragma unroll
-    for (int u = 0; u < 8; u += 2) {
-      unsigned hi, lo;
-      sam6d_split2_f16(e8[u] * sx, e8[u + 1] * sx, hi, lo);
-      const _Float16 __attribute__((ext_vector_type(2))) h2 = __builtin_bit_cast(_Float16 __attribute__((ext_vector_type(2))), hi);
-      const _Float16 __attribute__((ext_vector_type(2))) l2 = __builtin_bit_cast(_Float16 __attribute__((ext_vector_type(2))), lo);
-      xh[s][u] = h2[0];
-      xh[s][u + 1] = h2[1];
-      xl[s][u] = l2[0];
-      xl[s][u + 1] = l2[1];
-    }
-  }
-  return sx;
-}
-
 template <bool KVP>
 __global__ __launch_bounds__(XA_WAVES * 64) void xattn_kernel(XaArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -142,14 +106,7 @@ __global__ __launch_bounds__(XA_WAVES * 64) void xattn_kernel(XaArgs a) {
   const bool half = a.half != 0;
 
   // 64 KiB image -> regA by LDS-DMA (64 pieces of 1 KiB)
-  auto dma64 = [&](const unsigned char* src, unsigned char* dst) {
-#pragma unroll
-    for (int k = 0; k < 64 / XA_WAVES; ++k) {
-      const int pc = wave + XA_WAVES * k;
-      __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)(src + (size_t)pc * 1024 + lane * 16),
-                                       (void __attribute__((address_space(3)))*)(dst + pc * 1024), 16, 0, 0);
-    }
-  };
+  auto dma64 = [&](const unsigned char* src, unsigned char* dst) { dma_pieces<64 / XA_WAVES>(src, dst, wave, XA_WAVES, lane); };
   constexpr int XA_EPT = (XA_MAXKEY * 64) / (XA_WAVES * 64);  // 26
   float kreg[KVP ? 1 : XA_EPT], vreg[KVP ? 1 : XA_EPT];
   f32x4 vacc[KVP ? 2 : 1][4];
@@ -171,14 +128,14 @@ __global__ __launch_bounds__(XA_WAVES * 64) void xattn_kernel(XaArgs a) {
     float mk = 0.f, mv = 0.f;
     half8 xh[8], xl[8];
     float sx = 1.0f;
-    if (wave < mgroups) sx = xa_load_rows(mb, min(wave * 16 + fr, m - 1), xh, xl, fg);
+    if (wave < mgroups) sx = split_row256<false>(mb + (size_t)min(wave * 16 + fr, m - 1) * 256, fg, xh, xl);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 #pragma unroll
     for (int gi = 0; gi < 2; ++gi) {
       const int grp = wave + XA_WAVES * gi;
       if (grp < mgroups) {  // (wave-uniform)
-        if (gi == 1) sx = xa_load_rows(mb, min(grp * 16 + fr, m - 1), xh, xl, fg);
+        if (gi == 1) sx = split_row256<false>(mb + (size_t)min(grp * 16 + fr, m - 1) * 256, fg, xh, xl);
         const float inv = a.inv_wkv * (1.0f / sx);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -214,15 +171,14 @@ __global__ __launch_bounds__(XA_WAVES * 64) void xattn_kernel(XaArgs a) {
         // channels 16 i + 4 g + r (r = 0..3) of a key are the slots 32 (i >> 1) + 8 g + 4 (i & 1) + r of its row: four consecutive halves,
         // one 8-byte write per plane (was eight 2-byte writes)
         unsigned char* row = kimg + (size_t)j * 256;
-        typedef unsigned xa_u2 __attribute__((ext_vector_type(2)));
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           unsigned h01, l01, h23, l23;
           sam6d_split2_f16(kacc[gi][i][0] * sk, kacc[gi][i][1] * sk, h01, l01);
           sam6d_split2_f16(kacc[gi][i][2] * sk, kacc[gi][i][3] * sk, h23, l23);
           const int ch = 4 * (i >> 1) + fg, cl = 8 + ch, off = 8 * (i & 1);
-          *reinterpret_cast<xa_u2*>(row + ((ch ^ (j & 15)) << 4) + off) = xa_u2{h01, h23};
-          *reinterpret_cast<xa_u2*>(row + ((cl ^ (j & 15)) << 4) + off) = xa_u2{l01, l23};
+          *reinterpret_cast<u32x2*>(row + ((ch ^ (j & 15)) << 4) + off) = u32x2{h01, h23};
+          *reinterpret_cast<u32x2*>(row + ((cl ^ (j & 15)) << 4) + off) = u32x2{l01, l23};
         }
       }
     }
@@ -444,31 +400,15 @@ __global__ __launch_bounds__(XA_WAVES * 64) void xattn_kernel(XaArgs a) {
   }
 }
 
-static int xa_cu_count[SAM6D_MAX_DEVICES];
-// query split of a launch: two workgroups per (cloud, head) while they all fit the chip at once (the results do not depend on it)
+// query split of a launch: two workgroups per (cloud, head) while they all fit the chip at once (the results do not depend on it;
+// an unknown CU count: one workgroup)
 static int xa_qsplit(int B, int n) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= SAM6D_MAX_DEVICES) return 1;
-  const int cu = xa_cu_count[dev];
+  const int cu = sam6d_cu_count();
   return (cu > 0 && 8 * B <= cu && n > 16) ? 2 : 1;
 }
-static int xa_reserve() {
+static int xa_reserve(const char* name) {
   static unsigned long long done = 0;
-  int dev_ = 0;
-  if (sam6d_first_use_on_device(&done, &dev_)) {
-    if (dev_ >= 0 && dev_ < SAM6D_MAX_DEVICES) {
-      int cu = 0;
-      if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev_) == hipSuccess) xa_cu_count[dev_] = cu;
-    }
-    hipError_t e = hipFuncSetAttribute((const void*)xattn_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, XA_LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)xattn_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, XA_LDS_KV);
-    if (e != hipSuccess) {
-      sam6d_set_error("cross_attention: cannot reserve %d bytes of LDS: %s", XA_LDS, hipGetErrorString(e));
-      return (int)e;
-    }
-    sam6d_setup_done_on_device(&done);
-  }
-  return 0;
+  return sam6d_reserve_lds(&done, name, {{(const void*)xattn_kernel<false>, XA_LDS}, {(const void*)xattn_kernel<true>, XA_LDS_KV}});
 }
 
 extern "C" int sam6d_cross_attention(const float* x, const float* kv, const void* wq_image, const float* bq, float inv_wq_scale,
@@ -480,7 +420,7 @@ extern "C" int sam6d_cross_attention(const float* x, const float* kv, const void
                 "cross_attention: pointers must be 16-byte aligned");
   SAM6D_REQUIRE(B <= 65535 && inv_wq_scale > 0.f, "cross_attention: bad arguments");
   if (B == 0) return 0;
-  if (int rc = xa_reserve()) return rc;
+  if (int rc = xa_reserve("cross_attention")) return rc;
   XaArgs a{x, kv, (const unsigned char*)wq_image, bq, out, n, m, inv_wq_scale, sam6d_half_for(2), nullptr, nullptr, 1.0f};
   hipLaunchKernelGGL(xattn_kernel<false>, dim3(4, B, xa_qsplit(B, n)), dim3(XA_WAVES * 64), XA_LDS, (hipStream_t)stream, a);
   SAM6D_LAUNCH_CHECK("cross_attention");
@@ -498,7 +438,7 @@ extern "C" int sam6d_cross_attention_kv(const float* x, const float* mem, const 
                 "cross_attention_kv: pointers must be 16-byte aligned");
   SAM6D_REQUIRE(B <= 65535 && inv_wq_scale > 0.f && inv_wkv_scale > 0.f, "cross_attention_kv: bad arguments");
   if (B == 0) return 0;
-  if (int rc = xa_reserve()) return rc;
+  if (int rc = xa_reserve("cross_attention_kv")) return rc;
   XaArgs a{x, mem, (const unsigned char*)wq_image, bq, out, n, m, inv_wq_scale, sam6d_half_for(2), (const unsigned char*)wkv_image, bkv,
            inv_wkv_scale};
   hipLaunchKernelGGL(xattn_kernel<true>, dim3(4, B, xa_qsplit(B, n)), dim3(XA_WAVES * 64), XA_LDS_KV, (hipStream_t)stream, a);
@@ -537,7 +477,7 @@ struct SaArgs {
 #define XA_FDR 4  // ring depth of the score-tile stream
 template <int NT, int S>
 __device__ __forceinline__ void xa_rows_step(f32x4* acc, unsigned kb, int fr, int fg, const half8* __restrict__ xh,
-                                             const half8* __restrict__ xl, xa_u32x4 (&fh)[XA_FDR + 1], xa_u32x4 (&fl)[XA_FDR + 1], bool half) {
+                                             const half8* __restrict__ xl, u32x4 (&fh)[XA_FDR + 1], u32x4 (&fl)[XA_FDR + 1], bool half) {
   auto issue = [&](int st) {
     const int row = 16 * (st >> 1) + fr, ks = st & 1;
     const int ch = 4 * ks + fg, cl = 8 + 4 * ks + fg;
@@ -657,7 +597,6 @@ __global__ __launch_bounds__(XA_WAVES * 64) void sattn_kernel(SaArgs a) {
   for (int w = 0; w < XA_WAVES; ++w) { sk = fmaxf(sk, red[w]); sv = fmaxf(sv, red[8 + w]); }
   sk = pow2_scale(sk);
   sv = pow2_scale(sv);
-  typedef unsigned sa_u2 __attribute__((ext_vector_type(2)));
   // k_h image: channels 4 c .. 4 c + 3 of key j are four consecutive slots (8 bytes) of its row; every (key < 208, channel) slot is
   // written (zeros beyond m)
 #pragma unroll
@@ -669,8 +608,8 @@ __global__ __launch_bounds__(XA_WAVES * 64) void sattn_kernel(SaArgs a) {
       sam6d_split2_f16(kreg[i].z * sk, kreg[i].w * sk, h23, l23);
       const int ch = 4 * (c4 >> 3) + (c4 & 3), cl = 8 + ch, off = ((c4 >> 2) & 1) * 8;  // slot 32 (d >> 5) + 8 ((d >> 2) & 3) + 4 ((d >> 4) & 1) + (d & 3)
       unsigned char* row = kimg + (size_t)j * 256;
-      *reinterpret_cast<sa_u2*>(row + ((ch ^ (j & 15)) << 4) + off) = sa_u2{h01, h23};
-      *reinterpret_cast<sa_u2*>(row + ((cl ^ (j & 15)) << 4) + off) = sa_u2{l01, l23};
+      *reinterpret_cast<u32x2*>(row + ((ch ^ (j & 15)) << 4) + off) = u32x2{h01, h23};
+      *reinterpret_cast<u32x2*>(row + ((cl ^ (j & 15)) << 4) + off) = u32x2{l01, l23};
     }
   }
   // v_h^T image: row d, K = key; keys 4 q .. 4 q + 3 are four consecutive slots
@@ -684,8 +623,8 @@ __global__ __launch_bounds__(XA_WAVES * 64) void sattn_kernel(SaArgs a) {
       const int j0 = 4 * jq, p = 32 * (j0 >> 5) + xa_channel_slot(j0 & 31);
       const int ch = p >> 3, cl = 32 + (p >> 3), off = (p & 7) * 2;
       unsigned char* row = regA + (size_t)d * 1024;
-      *reinterpret_cast<sa_u2*>(row + ((((ch & ~15) | ((ch ^ d) & 15))) << 4) + off) = sa_u2{h01, h23};
-      *reinterpret_cast<sa_u2*>(row + ((((cl & ~15) | ((cl ^ d) & 15))) << 4) + off) = sa_u2{l01, l23};
+      *reinterpret_cast<u32x2*>(row + ((((ch & ~15) | ((ch ^ d) & 15))) << 4) + off) = u32x2{h01, h23};
+      *reinterpret_cast<u32x2*>(row + ((((cl & ~15) | ((cl ^ d) & 15))) << 4) + off) = u32x2{l01, l23};
     }
   }
   SA_ST(3);
@@ -725,7 +664,7 @@ __global__ __launch_bounds__(XA_WAVES * 64) void sattn_kernel(SaArgs a) {
       for (int i = 0; i < XA_NT; ++i) s[i] = f32x4{0.f, 0.f, 0.f, 0.f};
       SA_ST(5 + 5 * gi);
       {
-        xa_u32x4 fh[XA_FDR + 1], fl[XA_FDR + 1];
+        u32x4 fh[XA_FDR + 1], fl[XA_FDR + 1];
         xa_rows_step<XA_NT, 0>(s, kimg_lds, fr, fg, qh, ql, fh, fl, half);
       }
       SA_ST(6 + 5 * gi);
@@ -785,8 +724,7 @@ __global__ __launch_bounds__(XA_WAVES * 64) void sattn_kernel(SaArgs a) {
       SA_ST(9 + 5 * gi);
     }
   };
-  group(std::integral_constant<int, 0>{});
-  group(std::integral_constant<int, 1>{});
+  static_for<0, 2>(group);
 #ifdef SA_STAMP
   st[15] = __builtin_amdgcn_s_memtime();
   if (lane == 0 && blockIdx.y * 4 + blockIdx.x < 256)
@@ -802,14 +740,7 @@ extern "C" int sam6d_rpe_self_attention(const float* qkv, const float* G, float*
   SAM6D_REQUIRE(B <= 65535, "rpe_self_attention: B <= 65535");
   if (B == 0) return 0;
   static unsigned long long done = 0;
-  if (sam6d_first_use_on_device(&done)) {
-    hipError_t e = hipFuncSetAttribute((const void*)sattn_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, XA_LDS);
-    if (e != hipSuccess) {
-      sam6d_set_error("rpe_self_attention: cannot reserve %d bytes of LDS: %s", XA_LDS, hipGetErrorString(e));
-      return (int)e;
-    }
-    sam6d_setup_done_on_device(&done);
-  }
+  if (int rc = sam6d_reserve_lds(&done, "rpe_self_attention", {{(const void*)sattn_kernel<false>, XA_LDS}})) return rc;
   SaArgs a{qkv, G, hidden, n, ldp, sam6d_half_for(2)};
   hipLaunchKernelGGL(sattn_kernel<false>, dim3(4, B), dim3(XA_WAVES * 64), XA_LDS, (hipStream_t)stream, a);
   SAM6D_LAUNCH_CHECK("rpe_self_attention");
@@ -824,14 +755,7 @@ extern "C" int sam6d_vit_attention(const float* qkv, float* out, int B, int n, v
   SAM6D_REQUIRE(B <= 65535, "vit_attention: B <= 65535");
   if (B == 0) return 0;
   static unsigned long long done = 0;
-  if (sam6d_first_use_on_device(&done)) {
-    hipError_t e = hipFuncSetAttribute((const void*)sattn_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, XA_LDS);
-    if (e != hipSuccess) {
-      sam6d_set_error("vit_attention: cannot reserve %d bytes of LDS: %s", XA_LDS, hipGetErrorString(e));
-      return (int)e;
-    }
-    sam6d_setup_done_on_device(&done);
-  }
+  if (int rc = sam6d_reserve_lds(&done, "vit_attention", {{(const void*)sattn_kernel<true>, XA_LDS}})) return rc;
   SaArgs a{qkv, nullptr, out, n, 0, sam6d_half_for(2)};
   hipLaunchKernelGGL(sattn_kernel<true>, dim3(12, B), dim3(XA_WAVES * 64), XA_LDS, (hipStream_t)stream, a);
   SAM6D_LAUNCH_CHECK("vit_attention");
