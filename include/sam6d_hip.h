@@ -353,8 +353,11 @@ int sam6d_l2norm256(const float* x, float* y, long rows, long ldx, long ldy, voi
 int sam6d_soft_assign(const float* att, int B, int R, int C, float* rmax, float* rsum, float* cmax, float* csum,
                       int* label1, int* label2, float* ws, long ws_floats, void* stream);
 /* sam6d_soft_assign + sam6d_coarse_weights in one launch for matrices that fit the 160 KB of LDS of a CU (R * C + 3 R + 3 C floats:
- * the 197 x 197 coarse attention), one workgroup per proposal; every output has the bits of the two-call form (same per-element
- * arithmetic, same summation orders: PEM/utils/model_utils.py:229-240).  rc < 0 for larger matrices. */
+ * the 197 x 197 coarse attention; 199 x 199 is the largest square), one workgroup per proposal; for R <= 256 every output has the
+ * bits of the two-call form (same per-element arithmetic, same summation orders: PEM/utils/model_utils.py:229-240).  A taller matrix
+ * that still fits (R > 256, C small) keeps this arithmetic -- expf and one sequential column sum, the reference's -- while
+ * sam6d_soft_assign switches to 16 row slices and the hardware exponential there, so the two agree to rounding only.  rc < 0 for
+ * larger matrices. */
 int sam6d_coarse_soft_assign(const float* att, int B, int R, int C, float* rmax, float* rsum, float* cmax, float* csum, int* label1,
                              int* label2, float* weights, float* w1, void* stream);
 /* replaces pairwise_distance(x, y) (PEM/utils/model_utils.py:101-128; normalized = False, channel-last): x (B,N,3), y (B,M,3) ->
@@ -375,7 +378,8 @@ int sam6d_coarse_hypotheses(const int* idx, const float* pts1, const float* pts2
                             float* Rs, float* ts, float* dis, void* stream);
 /* torch.topk(k, largest=False) indices, ascending (PEM/utils/model_utils.py:258). */
 int sam6d_select_smallest(const float* dis, int B, int n, int k, int* sel, void* stream);
-/* Hypothesis scoring + argmax (PEM/utils/model_utils.py:261-270); model (B,P,3) raw, radius (B). */
+/* Hypothesis scoring + argmax (PEM/utils/model_utils.py:261-270); model (B,P,3) raw, radius (B).  P <= 8192 (16 bytes of LDS a CAD
+ * point, reserved on first use). */
 int sam6d_score_select_hypotheses(const int* sel, const float* Rs, const float* ts, const float* pts1, const float* w1,
                                   const float* model, const float* radius, int B, int N1, int P, int nh, int k,
                                   float* scores, float* R, float* t, int* best, void* stream);

@@ -909,7 +909,11 @@ extern "C" int sam6d_select_smallest(const float* dis, int B, int n, int k, int*
 // distances in the pairwise_distance bit recipe, model = model_raw / (radius + 1e-6) (coarse_point_matching.py:60).
 // One workgroup scores SH_G hypotheses: SH_G * N1 (hypothesis, point) items are dealt to the 256 threads (98 % lane
 // utilisation at N1 = 196 instead of 77 % with one hypothesis per workgroup) and the LDS copy of the CAD points is
-// shared by the group.  Reductions are in a fixed order (wave butterfly, then waves 0..3): scores are reproducible.
+// shared by the group.  Thread t serves slot g = t % SH_G of the group and the points t / SH_G, t / SH_G + 64, ...: a
+// hypothesis's points meet the same lanes (up to the shift by g, which the xor butterfly does not see: the other
+// slots' lanes hold exact zeros) in the same order whatever slot it sits in, so two identical hypotheses get identical
+// score bits and the arg-max keeps the first, as the reference's does (dealing item = g * N1 + i linearly gave each
+// slot a summation order of its own).  Reductions are in a fixed order (wave butterfly, then waves 0..3).
 #define SH_G 4
 __global__ __launch_bounds__(256) void score_hyp_kernel(const int* __restrict__ sel, const float* __restrict__ Rs,
                                                         const float* __restrict__ ts, const float* __restrict__ pts1,
@@ -933,11 +937,9 @@ __global__ __launch_bounds__(256) void score_hyp_kernel(const int* __restrict__ 
     sRt[g][e] = (e < 9) ? Rs[((size_t)b * nh + h) * 9 + e] : ts[((size_t)b * nh + h) * 3 + (e - 9)];
   }
   __syncthreads();
-  float sw[SH_G], sdw[SH_G];
-#pragma unroll
-  for (int g = 0; g < SH_G; ++g) sw[g] = sdw[g] = 0.f;
-  for (int item = t; item < SH_G * N1; item += 256) {
-    const int g = item / N1, i = item - g * N1;
+  const int g = t % SH_G;
+  float sw_t = 0.f, sdw_t = 0.f;
+  for (int i = t / SH_G; i < N1; i += 256 / SH_G) {
     const float* R = sRt[g];
     const float* p = pts1 + ((size_t)b * N1 + i) * 3;
     const float d0 = p[0] - R[9], d1 = p[1] - R[10], d2 = p[2] - R[11];
@@ -970,19 +972,15 @@ __global__ __launch_bounds__(256) void score_hyp_kernel(const int* __restrict__ 
     float mn = fminf(fminf(mn0, mn1), fminf(mn2, mn3));
     mn = mn < 0.0f ? 0.0f : mn;
     const float wv = w1[(size_t)b * N1 + i];
-#pragma unroll
-    for (int gg = 0; gg < SH_G; ++gg)
-      if (gg == g) {
-        sw[gg] += wv;
-        sdw[gg] += sqrtf(mn) * wv;
-      }
+    sw_t += wv;
+    sdw_t += sqrtf(mn) * wv;
   }
 #pragma unroll
-  for (int g = 0; g < SH_G; ++g) {
-    const float a = wave_sum(sw[g]), c = wave_sum(sdw[g]);
+  for (int gg = 0; gg < SH_G; ++gg) {
+    const float a = wave_sum(gg == g ? sw_t : 0.f), c = wave_sum(gg == g ? sdw_t : 0.f);
     if ((t & 63) == 0) {
-      red[0][g][t >> 6] = a;
-      red[1][g][t >> 6] = c;
+      red[0][gg][t >> 6] = a;
+      red[1][gg][t >> 6] = c;
     }
   }
   __syncthreads();
@@ -1158,6 +1156,8 @@ extern "C" int sam6d_score_select_hypotheses(const int* sel, const float* Rs, co
   SAM6D_REQUIRE(B >= 0 && N1 > 0 && P > 0 && P <= 8192 && k > 0 && B <= 65535, "score_select_hypotheses: bad sizes (P <= 8192)");
   if (B == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
+  static unsigned long long sh_done = 0;  // P = 8192 CAD points are 128 KB of dynamic LDS (the default limit is 64 KB)
+  if (int rc = sam6d_reserve_lds(&sh_done, "score_select_hypotheses", {{(const void*)score_hyp_kernel, 8192 * 16}})) return rc;
   hipLaunchKernelGGL(score_hyp_kernel, dim3(cdiv(k, SH_G), B), dim3(256), (size_t)P * 16, s, sel, Rs, ts, pts1, w1, model, radius, N1, P, nh, k,
                      scores);
   hipLaunchKernelGGL(pick_best_kernel, dim3(B), dim3(64), 0, s, scores, sel, Rs, ts, nh, k, R, t, best);

@@ -1094,10 +1094,14 @@ def test_template_cloud_fps_210k(dev):
     assert torch.equal(sf.cpu(), torch.gather(feats, 1, want.long().unsqueeze(2).expand(1, 2048, 8)))
 
 
-@pytest.mark.parametrize("B,R,C,peaky", [(3, 197, 197, False), (2, 197, 197, True), (2, 50, 120, False), (1, 2, 2, False)])
+@pytest.mark.parametrize("B,R,C,peaky", [(3, 197, 197, False), (2, 197, 197, True), (2, 50, 120, False), (1, 2, 2, False),
+                                         (3, 199, 199, False), (2, 50, 770, False), (2, 256, 155, False), (2, 200, 40, False)])
 def test_coarse_soft_assign_one_launch_is_bit_identical(dev, B, R, C, peaky):
     """sam6d_coarse_soft_assign (matrix in LDS, one workgroup per proposal) against sam6d_soft_assign + sam6d_coarse_weights: every
-    statistic, label and weight bit for bit (the sampled hypothesis indices downstream depend on the exact weights)."""
+    statistic, label and weight bit for bit (the sampled hypothesis indices downstream depend on the exact weights).  At the 160 KB
+    bound of (R * C + 3 R + 3 C) * 4 bytes: 199 x 199 is the largest square, 50 x 770 sits exactly on the bound, 256 x 155 is the
+    tallest matrix whose two-call form still sums a column in one slice; 200 x 40 has fewer columns than a wave has lanes
+    (tests/test_pose_shapes_host.py checks the arithmetic, tests/test_pose_shapes_gpu.py the first shape over the bound)."""
     from sam6d_hip import _lib, pem
     gen = torch.Generator().manual_seed(B * 1000 + R + C + int(peaky))
     att = torch.randn(B, R, C, generator=gen) * (0.2 if not peaky else 1.0)
