@@ -29,8 +29,9 @@ const char* sam6d_last_error(void);
  * mismatch (sam6d_hip/_lib.py and tests/cabi/cabi_check.c do).
  *   1  rounds 1-3
  *   2  sam6d_set_thread_matmul_mode added; round 3's layout change made visible: sam6d_linattn_kv_pack / sam6d_linattn_kv_image write 4*B floats to `inv` (one image
- *      scale per head), sam6d_linattn_layer reads kvinv as (B,4) -- a version-1 consumer allocated B floats */
-#define SAM6D_ABI_VERSION 3
+ *      scale per head), sam6d_linattn_layer reads kvinv as (B,4) -- a version-1 consumer allocated B floats
+ *   4  sam6d_gemm_ln256 removed (nothing selected it since its switch SAM6D_FUSED_LN was retired) */
+#define SAM6D_ABI_VERSION 4
 int sam6d_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -156,11 +157,6 @@ int sam6d_get_thread_matmul_mode(void);
 /* nn.LayerNorm(256) over `rows` rows (PEM/model/transformer.py:158,189,436,597).  eps as in torch (1e-5). */
 int sam6d_layernorm256(const float* x, const float* gamma, const float* beta, float* y, long rows, long ldx, long ldy,
                        float eps, void* stream);
-/* attention.linear / output.squeeze + residual + LayerNorm of a transformer block in one launch
- * (PEM/model/transformer.py:152-158, 184-199, 436-441, 597-603): Y (M,256) = LayerNorm(A (M,K) . W (256,K)^T + bias + residual)
- * * gamma + beta, eps as nn.LayerNorm.  Split-precision mode only (rc < 0 in mode 0: use sam6d_gemm_nt + sam6d_layernorm256). */
-int sam6d_gemm_ln256(const float* A, const float* W, const float* bias, const float* residual, const float* gamma,
-                     const float* beta, float* Y, int M, int K, long lda, long ldw, long ldr, long ldy, float eps, void* stream);
 
 /* Fused transformer-block kernels (csrc/block.hip): a tile of 128 token rows (256 channels) stays on chip from the block's input to
  * its second LayerNorm; split-precision (fp16 x3) MFMA arithmetic with power-of-two operand scaling (range-safe for any finite fp32

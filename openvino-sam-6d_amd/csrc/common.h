@@ -292,6 +292,99 @@ __device__ __forceinline__ void dma_pieces(const unsigned char* src, unsigned ch
   });
 }
 
+// ---- shared steps of the 32x32x16 split-product tile kernels (gemm.hip, ism.hip, finematch.hip) ------------------
+// Four waves in a 2 x 2 grid over a BM x BN workgroup tile, each wave TM x TN tiles of v_mfma_f32_32x32x16_f16.  The operands lie in
+// LDS as four fp16 planes (A hi, A lo, B hi, B lo) of one 32-wide k chunk; a . b is evaluated as a_lo.b_hi + a_hi.b_lo + a_hi.b_hi.
+typedef float f32x16 __attribute__((ext_vector_type(16)));  // one 32 x 32 MFMA accumulator tile per lane
+
+// k chunk of a plane and its LDS row in halves.  Rows of 40 halves (80 B): 16 consecutive rows land on 16 different 16-byte slots of
+// the 256-B bank row, so the ds_read_b128 fragment reads are conflict-free.
+#define SP_BK 32
+#define SP_LD 40
+
+// C/D map of the 32 x 32 tile: register r of lane (fr = lane & 31, fk = lane >> 5) is column fr of row (r & 3) + 8 (r >> 2) + 4 fk.
+// row0: the tile's first row, in the caller's index type (the terms are added to it one by one, as the kernels wrote it out).
+template <class T>
+__device__ __forceinline__ T sp_row(T row0, int r, int fk) {
+  return row0 + (r & 3) + 8 * (r >> 2) + 4 * fk;
+}
+
+template <int TM, int TN>
+__device__ __forceinline__ void sp_zero(f32x16 (&acc)[TM][TN]) {
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+}
+
+// The four planes of a BM x BN tile in one staging buffer of SpLayout<BM, BN>::HALVES halves: offsets of A hi, A lo, B hi, B lo
+template <int BM, int BN>
+struct SpLayout {
+  static constexpr int AH = 0, AL = BM * SP_LD, BH = 2 * BM * SP_LD, BL = (2 * BM + BN) * SP_LD, HALVES = 2 * (BM + BN) * SP_LD;
+};
+struct SpPlanes {
+  _Float16 *Ah, *Al, *Bh, *Bl;
+};
+
+__device__ __forceinline__ void split4(const float4 v, half4& hi, half4& lo) {
+  unsigned h0, h1, l0, l1;
+  sam6d_split2_f16(v.x, v.y, h0, l0);
+  sam6d_split2_f16(v.z, v.w, h1, l1);
+  hi = __builtin_bit_cast(half4, u32x2{h0, h1});
+  lo = __builtin_bit_cast(half4, u32x2{l0, l1});
+}
+
+// The products of one staged chunk into the wave's TM x TN accumulators, per accumulator al . bh, then ah . bl, then ah . bh.  The
+// wave's tile starts at row wm of the A planes and row wn of the B planes; lane = (fr = lane & 31, fk = lane >> 5).
+// single (launch-uniform): matmul mode 2 keeps the hi . hi product only.
+template <int TM, int TN>
+__device__ __forceinline__ void sp_chunk(f32x16 (&acc)[TM][TN], const SpPlanes& p, int wm, int wn, int fr, int fk, bool single) {
+#pragma unroll
+  for (int ks = 0; ks < SP_BK; ks += 16) {
+    half8 ah[TM], al[TM], bh[TN], bl[TN];
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+      ah[i] = *reinterpret_cast<const half8*>(&p.Ah[(wm + 32 * i + fr) * SP_LD + ks + 8 * fk]);
+      al[i] = *reinterpret_cast<const half8*>(&p.Al[(wm + 32 * i + fr) * SP_LD + ks + 8 * fk]);
+    }
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+      bh[j] = *reinterpret_cast<const half8*>(&p.Bh[(wn + 32 * j + fr) * SP_LD + ks + 8 * fk]);
+      bl[j] = *reinterpret_cast<const half8*>(&p.Bl[(wn + 32 * j + fr) * SP_LD + ks + 8 * fk]);
+    }
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j) {
+        if (!single) {
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[j], acc[i][j], 0, 0, 0);
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);
+        }
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
+      }
+  }
+}
+
+// Wave-private transposing slab: a wave puts EJ accumulator tiles (32 rows x WC = 32 EJ columns) through LDS so that a lane owns 4
+// consecutive columns of one row and its global accesses are 16 bytes wide.  Rows of SLD floats; LPR lanes per row, RPP rows per pass,
+// NP passes: pass `it` gives the lane row it * RPP + lane / LPR, columns (lane % LPR) * 4 .. + 3.  The caller reads the slab and
+// puts a wave barrier behind its reads before the next write.
+template <int EJ>
+struct SpSlab {
+  static constexpr int WC = EJ * 32, SLD = WC + 4, LPR = WC / 4, RPP = 64 / LPR, NP = 32 / RPP;
+  static __device__ __forceinline__ void write(float* slab, const f32x16* tiles, int fr, int fk) {
+    float* dst = &slab[sp_row(0, 0, fk) * SLD + fr];
+#pragma unroll
+    for (int j = 0; j < EJ; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) dst[sp_row(0, r, 0) * SLD + j * 32] = tiles[j][r];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
+};
+
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // One-time per-DEVICE setup (hipFuncSetAttribute, CU count ...): `done` is a bit mask over device ordinals owned by the call site.

@@ -21,9 +21,6 @@
 #include "common.h"
 #include "../../include/sam6d_hip.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float fm_f4 __attribute__((ext_vector_type(4)));
-
 #define FM_C 256          // channels
 #define FM_COL0 3         // physical column of logical column 0
 #define FM_CHUNK 2048     // columns one label / assignment workgroup covers (32 per lane); np = 2048 (config 2) or 4096 (config 5)
@@ -67,16 +64,12 @@ __global__ __launch_bounds__(256) void fm_prep_kernel(const float* __restrict__ 
 // (Measured and removed, round 4: 256 x 128 tiles -- eight waves in a 4 x 2 grid, 70 KB of dynamic LDS, a quarter less operand traffic from
 // the L2 per output.  At 128 registers (two workgroups per CU) the kernel spills 9 VGPRs, at 151 only one
 // workgroup of eight waves fits a CU; bit-identical results, the fine-match pipeline 0.592 ms against 0.537 ms with the 128 x 128 tile.)
-#define FM_BK 32
-#define FM_LD 40  // halves per LDS row (80 B): the ds_read_b128 fragment reads of 16 consecutive rows are conflict-free
 __global__ __launch_bounds__(256) void fm_sim_kernel(const _Float16* __restrict__ fh, const _Float16* __restrict__ fl, int B,
                                                      float k1, float k2, float* __restrict__ E, float* __restrict__ rowpart,
                                                      float* __restrict__ colpart, int half, int np) {
-  __shared__ __attribute__((aligned(16))) _Float16 smem[4 * 128 * FM_LD];  // 40 KB; reused by the epilogue's transpose slabs
-  _Float16* Ah = smem;
-  _Float16* Al = Ah + 128 * FM_LD;
-  _Float16* Bh = Al + 128 * FM_LD;
-  _Float16* Bl = Bh + 128 * FM_LD;
+  __shared__ __attribute__((aligned(16))) _Float16 smem[SpLayout<128, 128>::HALVES];  // 40 KB; reused by the epilogue's transpose slabs
+  using L = SpLayout<128, 128>;
+  const SpPlanes pl{smem + L::AH, smem + L::AL, smem + L::BH, smem + L::BL};
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   // proposal z's tiles get the workgroup ids congruent to z mod 8: one XCD (one L2) reads that proposal's operands
   const int nt = np / 128, per = nt * nt;
@@ -93,12 +86,7 @@ __global__ __launch_bounds__(256) void fm_sim_kernel(const _Float16* __restrict_
   const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
 
   f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  sp_zero(acc);
 
   // staging: thread t copies rows (t >> 2) and (t >> 2) + 64, halves (t & 3) * 8 .. +8 of the chunk, for each of the 4 planes
   const int sr = t >> 2, sk = (t & 3) * 8;
@@ -115,39 +103,19 @@ __global__ __launch_bounds__(256) void fm_sim_kernel(const _Float16* __restrict_
   };
   const int fr = lane & 31, fk = lane >> 5;
   fetch(0);
-  for (int k0 = 0; k0 < FM_C; k0 += FM_BK) {
+  for (int k0 = 0; k0 < FM_C; k0 += SP_BK) {
     __syncthreads();
-    *reinterpret_cast<half8*>(&Ah[sr * FM_LD + sk]) = v[0];
-    *reinterpret_cast<half8*>(&Ah[(sr + 64) * FM_LD + sk]) = v[1];
-    *reinterpret_cast<half8*>(&Al[sr * FM_LD + sk]) = v[2];
-    *reinterpret_cast<half8*>(&Al[(sr + 64) * FM_LD + sk]) = v[3];
-    *reinterpret_cast<half8*>(&Bh[sr * FM_LD + sk]) = v[4];
-    *reinterpret_cast<half8*>(&Bh[(sr + 64) * FM_LD + sk]) = v[5];
-    *reinterpret_cast<half8*>(&Bl[sr * FM_LD + sk]) = v[6];
-    *reinterpret_cast<half8*>(&Bl[(sr + 64) * FM_LD + sk]) = v[7];
+    *reinterpret_cast<half8*>(&pl.Ah[sr * SP_LD + sk]) = v[0];
+    *reinterpret_cast<half8*>(&pl.Ah[(sr + 64) * SP_LD + sk]) = v[1];
+    *reinterpret_cast<half8*>(&pl.Al[sr * SP_LD + sk]) = v[2];
+    *reinterpret_cast<half8*>(&pl.Al[(sr + 64) * SP_LD + sk]) = v[3];
+    *reinterpret_cast<half8*>(&pl.Bh[sr * SP_LD + sk]) = v[4];
+    *reinterpret_cast<half8*>(&pl.Bh[(sr + 64) * SP_LD + sk]) = v[5];
+    *reinterpret_cast<half8*>(&pl.Bl[sr * SP_LD + sk]) = v[6];
+    *reinterpret_cast<half8*>(&pl.Bl[(sr + 64) * SP_LD + sk]) = v[7];
     __syncthreads();
-    if (k0 + FM_BK < FM_C) fetch(k0 + FM_BK);
-#pragma unroll
-    for (int ks = 0; ks < FM_BK; ks += 16) {
-      half8 ah[2], al[2], bh[2], bl[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        ah[i] = *reinterpret_cast<const half8*>(&Ah[(wm + 32 * i + fr) * FM_LD + ks + 8 * fk]);
-        al[i] = *reinterpret_cast<const half8*>(&Al[(wm + 32 * i + fr) * FM_LD + ks + 8 * fk]);
-        bh[i] = *reinterpret_cast<const half8*>(&Bh[(wn + 32 * i + fr) * FM_LD + ks + 8 * fk]);
-        bl[i] = *reinterpret_cast<const half8*>(&Bl[(wn + 32 * i + fr) * FM_LD + ks + 8 * fk]);
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          if (!half) {  // (launch-uniform) matmul mode 2 keeps the hi . hi product only
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[j], acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-          }
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-        }
-    }
+    if (k0 + SP_BK < FM_C) fetch(k0 + SP_BK);
+    sp_chunk(acc, pl, wm, wn, fr, fk, half);  // (launch-uniform) matmul mode 2 keeps the hi . hi product only
   }
   // ---- E = exp(att - c), in the accumulator registers
 #pragma unroll
@@ -156,7 +124,7 @@ __global__ __launch_bounds__(256) void fm_sim_kernel(const _Float16* __restrict_
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = __builtin_amdgcn_exp2f(fmaf(acc[i][j][r], k1, -k2));
-  // ---- column partial sums of this wave's 64 rows: lane (fr, fk) holds rows (r&3) + 8(r>>2) + 4 fk of column fr
+  // ---- column partial sums of this wave's 64 rows: lane (fr, fk) holds rows sp_row(0, r, fk) of column fr
   const int nrow0 = 128 * tm, mcol0 = 128 * tn;  // point indices (n - 1, m - 1) of the tile origin
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
@@ -176,29 +144,25 @@ __global__ __launch_bounds__(256) void fm_sim_kernel(const _Float16* __restrict_
       float s = acc[i][0][r] + acc[i][1][r];
       s = row16_sum_dpp(s);
       s += xor16_f32(s);
-      if (fr == 0) rowpart[((size_t)b * np + nrow0 + wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * fk) * slots + 2 * tn + (wave & 1)] = s;
+      if (fr == 0) rowpart[sp_row((size_t)b * np + nrow0 + wm + 32 * i, r, fk) * slots + 2 * tn + (wave & 1)] = s;
     }
   // ---- E store: each wave transposes its 32 x 64 slabs through LDS so that a lane owns 4 consecutive columns (16-byte stores)
-  constexpr int WC = 64, SLD = WC + 4, LPR = WC / 4, RPP = 64 / LPR, NP = 32 / RPP;
+  using Slab = SpSlab<2>;
+  constexpr int SLD = Slab::SLD, LPR = Slab::LPR, RPP = Slab::RPP, NP = Slab::NP;
   __syncthreads();
   float* slab = reinterpret_cast<float*>(smem) + wave * (32 * SLD);
   const int rr0 = lane / LPR, c4 = (lane % LPR) * 4;
   float* Eb = E + (size_t)b * (np + 1) * lde + FM_COL0;
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) slab[((r & 3) + 8 * (r >> 2) + 4 * fk) * SLD + j * 32 + fr] = acc[i][j][r];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    Slab::write(slab, acc[i], fr, fk);
 #pragma unroll
     for (int it = 0; it < NP; ++it) {
       const int rr = it * RPP + rr0;
       const int nn = 1 + nrow0 + wm + 32 * i + rr, mm = 1 + mcol0 + wn + c4;
       // non-temporal: E (537 MB per step) is read back only by the label / assignment passes, long after it has left the L2 -- kept out
       // of the cache it stops evicting the GEMM operands (4 MB per proposal = one XCD's L2) the neighbouring tiles are about to re-read
-      __builtin_nontemporal_store(*reinterpret_cast<const fm_f4*>(&slab[rr * SLD + c4]), reinterpret_cast<fm_f4*>(Eb + (size_t)nn * lde + mm));
+      __builtin_nontemporal_store(*reinterpret_cast<const f32x4*>(&slab[rr * SLD + c4]), reinterpret_cast<f32x4*>(Eb + (size_t)nn * lde + mm));
     }
     __builtin_amdgcn_wave_barrier();
   }
@@ -315,7 +279,7 @@ __global__ __launch_bounds__(256) void fm_labels_kernel(const float* __restrict_
     float4 e[8];
 #pragma unroll
     for (int g = 0; g < 8; ++g) {
-      const fm_f4 x = __builtin_nontemporal_load(reinterpret_cast<const fm_f4*>(er + 1 + 4 * (lane + 64 * g)));  // streamed once
+      const f32x4 x = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(er + 1 + 4 * (lane + 64 * g)));  // streamed once
       e[g] = make_float4(x[0], x[1], x[2], x[3]);
     }
     float bv = -INFINITY;
@@ -451,7 +415,7 @@ __global__ __launch_bounds__(256) void fm_assign_kernel(const float* __restrict_
       float4 e[8];
 #pragma unroll
       for (int g = 0; g < 8; ++g) {
-      const fm_f4 x = __builtin_nontemporal_load(reinterpret_cast<const fm_f4*>(er + 1 + 4 * (lane + 64 * g)));  // streamed once
+      const f32x4 x = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(er + 1 + 4 * (lane + 64 * g)));  // streamed once
       e[g] = make_float4(x[0], x[1], x[2], x[3]);
     }
 #pragma unroll

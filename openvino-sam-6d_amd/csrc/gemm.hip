@@ -11,8 +11,6 @@
 #include "common.h"
 #include "../../include/sam6d_hip.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 // act = 2: exact (erf) GELU, x * 0.5 * (1 + erf(x / sqrt 2)) as nn.GELU() / F.gelu compute it (the ViT MLP's fc1,
 // PEM/model/feature_extraction.py:21-35 through timm's Mlp)
 __device__ __forceinline__ float gelu_erf(float x) { return x * 0.5f * (1.0f + erff(x * 0.70710678118654752f)); }
@@ -64,6 +62,38 @@ __device__ __forceinline__ bool gemm_tile(int M, int N, const Batch2& b2, int& z
   return true;
 }
 
+// The batch element's operands: z = b1 * n2 + b2 addresses base + b1 * s + b2 * s2.  Returns the offset of W (the pre-split weight
+// halves share its layout).
+__device__ __forceinline__ size_t gemm_batch_offset(int z, const Batch2& b2, long sA, long sW, long sC, long sR,
+                                                    const float* __restrict__& A, const float* __restrict__& W,
+                                                    float* __restrict__& C, const float* __restrict__& residual) {
+  const int bz = z / b2.n2, bi = z % b2.n2;
+  const size_t ow = (size_t)bz * sW + (size_t)bi * b2.sW2;
+  A += (size_t)bz * sA + (size_t)bi * b2.sA2;
+  W += ow;
+  C += (size_t)bz * sC + (size_t)bi * b2.sC2;
+  if (residual) residual += (size_t)bz * sR + (size_t)bi * b2.sR2;
+  return ow;
+}
+
+// Four floats at k0 of each of a thread's R staged rows (p[u] points at column sk of its row): 16-byte loads when the rows are
+// aligned and the chunk lies inside K (whole), else element by element with zeros past K.
+template <int R>
+__device__ __forceinline__ void gemm_fetch_rows(float4 (&v)[R], const float* const (&p)[R], int k0, int sk, int K, bool whole) {
+  if (whole) {
+#pragma unroll
+    for (int u = 0; u < R; ++u) v[u] = *reinterpret_cast<const float4*>(p[u] + k0);
+  } else {
+    float tmp[4];
+#pragma unroll
+    for (int u = 0; u < R; ++u) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) tmp[e] = (k0 + sk + e) < K ? p[u][k0 + e] : 0.f;
+      v[u] = make_float4(tmp[0], tmp[1], tmp[2], tmp[3]);
+    }
+  }
+}
+
 // Exact fp32 main loop of one BM x BN tile (v_mfma_f32_32x32x2_f32: a k-ordered fmaf chain).  Shared by gemm_nt_kernel and by the
 // split-precision kernel's out-of-range fallback.  As / Bs: BM x GM_LD and BN x GM_LD floats of LDS.
 template <int BM, int BN>
@@ -74,46 +104,19 @@ __device__ __forceinline__ void gemm_exact_mainloop(f32x16 (&acc)[BM / 64][BN / 
   constexpr int RA = BM / 64, RB = BN / 64;  // float4 staging loads per thread
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int wm = (wave >> 1) * (BM / 2), wn = (wave & 1) * (BN / 2);
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  sp_zero(acc);
 
   // staging map: rows (t>>2) + 64*u, k4 = (t&3)*4
   const int sr = t >> 2, sk = (t & 3) * 4;
-  const float* ap[RA];
-  const float* bp[RB];
+  const float* rp[RA + RB];  // this thread's rows of A, then of W
 #pragma unroll
-  for (int u = 0; u < RA; ++u) ap[u] = A + (size_t)min(m0 + sr + 64 * u, M - 1) * lda + sk;
+  for (int u = 0; u < RA; ++u) rp[u] = A + (size_t)min(m0 + sr + 64 * u, M - 1) * lda + sk;
 #pragma unroll
-  for (int u = 0; u < RB; ++u) bp[u] = W + (size_t)min(n0 + sr + 64 * u, N - 1) * ldw + sk;
+  for (int u = 0; u < RB; ++u) rp[RA + u] = W + (size_t)min(n0 + sr + 64 * u, N - 1) * ldw + sk;
   const bool vec = ((lda & 3) == 0) && ((ldw & 3) == 0) && ((((size_t)A | (size_t)W) & 15) == 0);
 
-  float4 va[RA], vb[RB];
-  auto fetch = [&](int k0) {
-    if (vec && k0 + GM_BK <= K) {
-#pragma unroll
-      for (int u = 0; u < RA; ++u) va[u] = *reinterpret_cast<const float4*>(ap[u] + k0);
-#pragma unroll
-      for (int u = 0; u < RB; ++u) vb[u] = *reinterpret_cast<const float4*>(bp[u] + k0);
-    } else {
-      float tmp[4];
-#pragma unroll
-      for (int u = 0; u < RA; ++u) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) tmp[e] = (k0 + sk + e) < K ? ap[u][k0 + e] : 0.f;
-        va[u] = make_float4(tmp[0], tmp[1], tmp[2], tmp[3]);
-      }
-#pragma unroll
-      for (int u = 0; u < RB; ++u) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) tmp[e] = (k0 + sk + e) < K ? bp[u][k0 + e] : 0.f;
-        vb[u] = make_float4(tmp[0], tmp[1], tmp[2], tmp[3]);
-      }
-    }
-  };
+  float4 v[RA + RB];
+  auto fetch = [&](int k0) { gemm_fetch_rows(v, rp, k0, sk, K, vec && k0 + GM_BK <= K); };
 
   const int fr = lane & 31, fk = lane >> 5;
   fetch(0);
@@ -122,12 +125,12 @@ __device__ __forceinline__ void gemm_exact_mainloop(f32x16 (&acc)[BM / 64][BN / 
 #pragma unroll
     for (int u = 0; u < RA; ++u) {
       float* d = As + (sr + 64 * u) * GM_LD + sk;
-      d[0] = va[u].x; d[1] = va[u].y; d[2] = va[u].z; d[3] = va[u].w;
+      d[0] = v[u].x; d[1] = v[u].y; d[2] = v[u].z; d[3] = v[u].w;
     }
 #pragma unroll
     for (int u = 0; u < RB; ++u) {
       float* d = Bs + (sr + 64 * u) * GM_LD + sk;
-      d[0] = vb[u].x; d[1] = vb[u].y; d[2] = vb[u].z; d[3] = vb[u].w;
+      d[0] = v[RA + u].x; d[1] = v[RA + u].y; d[2] = v[RA + u].z; d[3] = v[RA + u].w;
     }
     __syncthreads();
     if (k0 + GM_BK < K) fetch(k0 + GM_BK);  // in flight during the MFMAs below
@@ -158,18 +161,15 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const float* __restrict__ 
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   int zz, tm_, tn_;
   if (!gemm_tile<BM, BN>(M, N, b2, zz, tm_, tn_)) return;  // padding workgroup (uniform)
-  const int bz = zz / b2.n2, bi = zz % b2.n2;
-  A += (size_t)bz * sA + (size_t)bi * b2.sA2;
-  W += (size_t)bz * sW + (size_t)bi * b2.sW2;
-  C += (size_t)bz * sC + (size_t)bi * b2.sC2;
-  if (residual) residual += (size_t)bz * sR + (size_t)bi * b2.sR2;
+  gemm_batch_offset(zz, b2, sA, sW, sC, sR, A, W, C, residual);
   const int m0 = tm_ * BM, n0 = tn_ * BN;
   const int wm = (wave >> 1) * (BM / 2), wn = (wave & 1) * (BN / 2);
 
   f32x16 acc[TM][TN];
   gemm_exact_mainloop<BM, BN>(acc, A, W, M, N, K, lda, ldw, m0, n0, As, Bs);
   const int fr = lane & 31, fk = lane >> 5;
-  // epilogue: C/D map of the 32x32 tile: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
+  // epilogue: C/D map of the 32x32 tile (sp_row), col = lane & 31.  (gemm_nt_h3_kernel ends with the same loop: as one shared function
+  // it changed this kernel's register count at 128 x 128, so each kernel keeps its copy.)
 #pragma unroll
   for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -183,12 +183,12 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const float* __restrict__ 
       float rv[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = m0 + wm + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fk;
+        const int row = sp_row(m0 + wm + i * 32, r, fk);
         rv[r] = (residual && row < M) ? residual[(size_t)row * ldr + col] : 0.f;
       }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = m0 + wm + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fk;
+        const int row = sp_row(m0 + wm + i * 32, r, fk);
         if (row < M) {
           float v = acc[i][j][r];
           if (divisor != 1.0f) v = v / divisor;
@@ -208,20 +208,9 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const float* __restrict__ 
 // (22 significand bits together) and a.b is evaluated as a_lo.b_hi + a_hi.b_lo + a_hi.b_hi on
 // v_mfma_f32_32x32x16_f16: fp16 products are exact in the fp32 accumulator, the dropped a_lo.b_lo term is 2^-22
 // relative.  Three MFMAs at 16x the fp32-MFMA rate = 5.3x the exact kernel's ceiling at ~1e-6 relative error
-// (tests compare both modes with the same golden vectors).  The split happens while staging the tile into LDS.
-// LDS rows are 40 halves (80 B): 16 consecutive rows land on 16 different 16-byte slots of the 256-B bank row, so
-// the ds_read_b128 fragment reads are conflict-free.
+// (tests compare both modes with the same golden vectors).  The split happens while staging the tile into LDS
+// (planes, k chunk and product step: common.h, "shared steps of the 32x32x16 split-product tile kernels").
 // ---------------------------------------------------------------------------------------------------------------
-#define H_BK 32
-#define H_LD 40
-
-__device__ __forceinline__ void split4(const float4 v, half4& hi, half4& lo) {
-  unsigned h0, h1, l0, l1;
-  sam6d_split2_f16(v.x, v.y, h0, l0);
-  sam6d_split2_f16(v.z, v.w, h1, l1);
-  hi = __builtin_bit_cast(half4, u32x2{h0, h1});
-  lo = __builtin_bit_cast(half4, u32x2{l0, l1});
-}
 
 // WS: the weight operand arrives pre-split -- Wh / Wl = fp16 hi / lo of W * 2^e, same (N, K) layout and strides as W, cut once at
 // weight-load time (sam6d_split_f16) -- so staging it is a copy: the per-k-step VALU split of the weight tile (half of the
@@ -238,36 +227,25 @@ __global__ __launch_bounds__(256, FAST ? 3 : 2) void gemm_nt_h3_kernel(const flo
                                                          float w_unscale) {
   constexpr int TM = BM / 64, TN = BN / 64;
   constexpr int RA = BM / 32, RB = BN / 32;  // float4 staging loads per thread (32 rows x 8 float4 per pass)
-  __shared__ __attribute__((aligned(16))) _Float16 smem[2 * (BM + BN) * H_LD];  // also the epilogue's transpose slabs
-  _Float16* Ah = smem;
-  _Float16* Al = Ah + BM * H_LD;
-  _Float16* Bh = Al + BM * H_LD;
-  _Float16* Bl = Bh + BN * H_LD;
+  using L = SpLayout<BM, BN>;
+  __shared__ __attribute__((aligned(16))) _Float16 smem[L::HALVES];  // also the epilogue's transpose slabs
+  const SpPlanes pl{smem + L::AH, smem + L::AL, smem + L::BH, smem + L::BL};
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int wide = FAST ? 1 : wide_, half = FAST ? 0 : half_, act = FAST ? 0 : act_;
   const float divisor = FAST ? 1.0f : divisor_;
   if (FAST) colscale = nullptr;
   int zz, tm_, tn_;
   if (!gemm_tile<BM, BN>(M, N, b2, zz, tm_, tn_)) return;  // padding workgroup (uniform)
-  const int bz = zz / b2.n2, bi = zz % b2.n2;
-  A += (size_t)bz * sA + (size_t)bi * b2.sA2;
-  W += (size_t)bz * sW + (size_t)bi * b2.sW2;
+  const size_t ow = gemm_batch_offset(zz, b2, sA, sW, sC, sR, A, W, C, residual);
   if (WS) {
-    Wh += (size_t)bz * sW + (size_t)bi * b2.sW2;
-    Wl += (size_t)bz * sW + (size_t)bi * b2.sW2;
+    Wh += ow;
+    Wl += ow;
   }
-  C += (size_t)bz * sC + (size_t)bi * b2.sC2;
-  if (residual) residual += (size_t)bz * sR + (size_t)bi * b2.sR2;
   const int m0 = tm_ * BM, n0 = tn_ * BN;
   const int wm = (wave >> 1) * (BM / 2), wn = (wave & 1) * (BN / 2);
 
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  sp_zero(acc);
 
   const int sr = t >> 3, sk = (t & 7) * 4;
   const float* ap[RA];
@@ -292,7 +270,7 @@ __global__ __launch_bounds__(256, FAST ? 3 : 2) void gemm_nt_h3_kernel(const flo
 #pragma unroll
     for (int u = 0; u < RB; ++u) {
       const size_t o = (size_t)(FAST ? n0 + sr + 32 * u : min(n0 + sr + 32 * u, N - 1)) * ldw + sk + k0;
-      if (wvec && (FAST || k0 + H_BK <= K)) {
+      if (wvec && (FAST || k0 + SP_BK <= K)) {
         wbh[u] = *reinterpret_cast<const half4*>(Wh + o);
         wbl[u] = *reinterpret_cast<const half4*>(Wl + o);
       } else {
@@ -305,35 +283,10 @@ __global__ __launch_bounds__(256, FAST ? 3 : 2) void gemm_nt_h3_kernel(const flo
       }
     }
   };
-  auto fetch_a = [&](float4 (&fa)[RA], int k0) {
-    if (vec && (FAST || k0 + H_BK <= K)) {
-#pragma unroll
-      for (int u = 0; u < RA; ++u) fa[u] = *reinterpret_cast<const float4*>(ap[u] + k0);
-    } else {
-      float tmp[4];
-#pragma unroll
-      for (int u = 0; u < RA; ++u) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) tmp[e] = (k0 + sk + e) < K ? ap[u][k0 + e] : 0.f;
-        fa[u] = make_float4(tmp[0], tmp[1], tmp[2], tmp[3]);
-      }
-    }
-  };
+  auto fetch_a = [&](float4 (&fa)[RA], int k0) { gemm_fetch_rows(fa, ap, k0, sk, K, vec && (FAST || k0 + SP_BK <= K)); };
   auto fetch_w = [&](int k0) {
-    if (WS) {
-      fetch_w16(k0);
-    } else if (vec && (FAST || k0 + H_BK <= K)) {
-#pragma unroll
-      for (int u = 0; u < RB; ++u) vb[u] = *reinterpret_cast<const float4*>(bp[u] + k0);
-    } else {
-      float tmp[4];
-#pragma unroll
-      for (int u = 0; u < RB; ++u) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) tmp[e] = (k0 + sk + e) < K ? bp[u][k0 + e] : 0.f;
-        vb[u] = make_float4(tmp[0], tmp[1], tmp[2], tmp[3]);
-      }
-    }
+    if (WS) fetch_w16(k0);
+    else gemm_fetch_rows(vb, bp, k0, sk, K, vec && (FAST || k0 + SP_BK <= K));
   };
 
   const int fr = lane & 31, fk = lane >> 5;
@@ -341,11 +294,11 @@ __global__ __launch_bounds__(256, FAST ? 3 : 2) void gemm_nt_h3_kernel(const flo
   fetch_w(0);
 #pragma unroll
   for (int st = 0; st < NS - 1; ++st)
-    if (st * H_BK < K) fetch_a(va[st], st * H_BK);
-  for (int kb = 0; kb < K; kb += NS * H_BK) {
+    if (st * SP_BK < K) fetch_a(va[st], st * SP_BK);
+  for (int kb = 0; kb < K; kb += NS * SP_BK) {
 #pragma unroll
     for (int st = 0; st < NS; ++st) {
-      const int k0 = kb + st * H_BK;
+      const int k0 = kb + st * SP_BK;
       if (k0 < K) {  // (uniform)
         __syncthreads();
 #pragma unroll
@@ -354,8 +307,8 @@ __global__ __launch_bounds__(256, FAST ? 3 : 2) void gemm_nt_h3_kernel(const flo
           ma = fmaxf(fmaxf(ma, fabsf(v.x)), fmaxf(fabsf(v.y), fmaxf(fabsf(v.z), fabsf(v.w))));
           half4 hi, lo;
           split4(v, hi, lo);
-          *reinterpret_cast<half4*>(&Ah[(sr + 32 * u) * H_LD + sk]) = hi;
-          if (!half) *reinterpret_cast<half4*>(&Al[(sr + 32 * u) * H_LD + sk]) = lo;
+          *reinterpret_cast<half4*>(&pl.Ah[(sr + 32 * u) * SP_LD + sk]) = hi;
+          if (!half) *reinterpret_cast<half4*>(&pl.Al[(sr + 32 * u) * SP_LD + sk]) = lo;
         }
 #pragma unroll
         for (int u = 0; u < RB; ++u) {
@@ -367,20 +320,22 @@ __global__ __launch_bounds__(256, FAST ? 3 : 2) void gemm_nt_h3_kernel(const flo
             mw = fmaxf(fmaxf(mw, fabsf(vb[u].x)), fmaxf(fabsf(vb[u].y), fmaxf(fabsf(vb[u].z), fabsf(vb[u].w))));
             split4(vb[u], hi, lo);
           }
-          *reinterpret_cast<half4*>(&Bh[(sr + 32 * u) * H_LD + sk]) = hi;
-          if (!half) *reinterpret_cast<half4*>(&Bl[(sr + 32 * u) * H_LD + sk]) = lo;
+          *reinterpret_cast<half4*>(&pl.Bh[(sr + 32 * u) * SP_LD + sk]) = hi;
+          if (!half) *reinterpret_cast<half4*>(&pl.Bl[(sr + 32 * u) * SP_LD + sk]) = lo;
         }
         __syncthreads();
-        if (k0 + H_BK < K) fetch_w(k0 + H_BK);
-        if (k0 + (NS - 1) * H_BK < K) fetch_a(va[(st + NS - 1) % NS], k0 + (NS - 1) * H_BK);
+        if (k0 + SP_BK < K) fetch_w(k0 + SP_BK);
+        if (k0 + (NS - 1) * SP_BK < K) fetch_a(va[(st + NS - 1) % NS], k0 + (NS - 1) * SP_BK);
+        // (Not sp_chunk: its per-accumulator test of the flag gives this kernel one copy of the MFMAs instead of two, and a shared
+        // two-path form lowered the register count of three instantiations -- the disassembly rule of the tile helpers keeps this pair.)
         if (half) {  // single product: hi halves only (workgroup-uniform branch)
 #pragma unroll
-          for (int ks = 0; ks < H_BK; ks += 16) {
+          for (int ks = 0; ks < SP_BK; ks += 16) {
             half8 ah[TM], bh[TN];
 #pragma unroll
-            for (int i = 0; i < TM; ++i) ah[i] = *reinterpret_cast<const half8*>(&Ah[(wm + 32 * i + fr) * H_LD + ks + 8 * fk]);
+            for (int i = 0; i < TM; ++i) ah[i] = *reinterpret_cast<const half8*>(&pl.Ah[(wm + 32 * i + fr) * SP_LD + ks + 8 * fk]);
 #pragma unroll
-            for (int j = 0; j < TN; ++j) bh[j] = *reinterpret_cast<const half8*>(&Bh[(wn + 32 * j + fr) * H_LD + ks + 8 * fk]);
+            for (int j = 0; j < TN; ++j) bh[j] = *reinterpret_cast<const half8*>(&pl.Bh[(wn + 32 * j + fr) * SP_LD + ks + 8 * fk]);
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -388,17 +343,17 @@ __global__ __launch_bounds__(256, FAST ? 3 : 2) void gemm_nt_h3_kernel(const flo
           }
         } else {
 #pragma unroll
-          for (int ks = 0; ks < H_BK; ks += 16) {
+          for (int ks = 0; ks < SP_BK; ks += 16) {
             half8 ah[TM], al[TM], bh[TN], bl[TN];
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
-              ah[i] = *reinterpret_cast<const half8*>(&Ah[(wm + 32 * i + fr) * H_LD + ks + 8 * fk]);
-              al[i] = *reinterpret_cast<const half8*>(&Al[(wm + 32 * i + fr) * H_LD + ks + 8 * fk]);
+              ah[i] = *reinterpret_cast<const half8*>(&pl.Ah[(wm + 32 * i + fr) * SP_LD + ks + 8 * fk]);
+              al[i] = *reinterpret_cast<const half8*>(&pl.Al[(wm + 32 * i + fr) * SP_LD + ks + 8 * fk]);
             }
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
-              bh[j] = *reinterpret_cast<const half8*>(&Bh[(wn + 32 * j + fr) * H_LD + ks + 8 * fk]);
-              bl[j] = *reinterpret_cast<const half8*>(&Bl[(wn + 32 * j + fr) * H_LD + ks + 8 * fk]);
+              bh[j] = *reinterpret_cast<const half8*>(&pl.Bh[(wn + 32 * j + fr) * SP_LD + ks + 8 * fk]);
+              bl[j] = *reinterpret_cast<const half8*>(&pl.Bl[(wn + 32 * j + fr) * SP_LD + ks + 8 * fk]);
             }
 #pragma unroll
             for (int i = 0; i < TM; ++i)
@@ -445,7 +400,9 @@ __global__ __launch_bounds__(256, FAST ? 3 : 2) void gemm_nt_h3_kernel(const flo
     // consecutive columns of one row: residual loads and C stores become 16-byte accesses of full 128/256-byte row
     // segments (the accumulator layout itself gives 4-byte accesses, 4x the instructions and half-used lines).
     // (at most two 32-column tiles per pass: a 64 x 256 workgroup tile goes through the slab in two passes per row tile)
-    constexpr int EJ = TN > 2 ? 2 : TN, WC = EJ * 32, SLD = WC + 4, LPR = WC / 4, RPP = 64 / LPR, NP = 32 / RPP;
+    constexpr int EJ = TN > 2 ? 2 : TN;
+    using Slab = SpSlab<EJ>;
+    constexpr int WC = Slab::WC, SLD = Slab::SLD, LPR = Slab::LPR, RPP = Slab::RPP, NP = Slab::NP;
     __syncthreads();  // every wave is done reading operand fragments: the staging buffers can be reused
     float* slab = reinterpret_cast<float*>(smem) + wave * (32 * SLD);
     const int rr0 = lane / LPR, c4 = (lane % LPR) * 4;
@@ -459,12 +416,7 @@ __global__ __launch_bounds__(256, FAST ? 3 : 2) void gemm_nt_h3_kernel(const flo
         if (bias) bv4 = *reinterpret_cast<const float4*>(bias + col);
         if (colscale) cs4 = *reinterpret_cast<const float4*>(colscale + col);
       }
-#pragma unroll
-      for (int j = 0; j < EJ; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) slab[((r & 3) + 8 * (r >> 2) + 4 * fk) * SLD + j * 32 + fr] = acc[i][jp * EJ + j][r];
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
+      Slab::write(slab, &acc[i][jp * EJ], fr, fk);
       float4 rv[NP];
 #pragma unroll
       for (int it = 0; it < NP; ++it) {
@@ -510,12 +462,12 @@ __global__ __launch_bounds__(256, FAST ? 3 : 2) void gemm_nt_h3_kernel(const flo
       float rv[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = m0 + wm + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fk;
+        const int row = sp_row(m0 + wm + i * 32, r, fk);
         rv[r] = (residual && row < M) ? residual[(size_t)row * ldr + col] : 0.f;
       }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = m0 + wm + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fk;
+        const int row = sp_row(m0 + wm + i * 32, r, fk);
         if (row < M) {
           float v = acc[i][j][r];
           if (divisor != 1.0f) v = v / divisor;
@@ -679,176 +631,6 @@ extern "C" int sam6d_gemm_nt_b2(const float* A, const float* W, float* C, int M,
                                 int batch, long sA, long sW, long sC, int batch2, long sA2, long sW2, long sC2, void* stream) {
   return gemm_launch(A, W, nullptr, nullptr, nullptr, C, M, N, K, lda, ldw, ldc, 0, batch, sA, sW, sC, 0,
                      Batch2{batch2, sA2, sW2, sC2, 0, 0}, 1.0f, 0, stream);
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// GEMM + bias + residual + LayerNorm in one kernel for the 256-wide projections that every transformer block ends with
-// (attention.linear -> +x -> norm, output.squeeze -> +y -> norm: PEM/model/transformer.py:152-199, 436-479, 597-622):
-//     Y[m, :] = LayerNorm(A[m, :] . W^T + bias + R[m, :]) * gamma + beta          N = 256 fixed
-// One workgroup owns 64 full rows (BN = 256: wave w has columns [64 w, 64 w + 64)), so the row statistics never leave the
-// chip: per-lane partial sums -> DPP / permlane reduction over the 32 column lanes -> 4 wave partials through LDS -> mean, then
-// the same for the centred squares (two-pass variance like layernorm256_kernel).  A is read once (the 128 x 128 tiling reads it
-// once per column tile) and the separate LayerNorm launch with its 2 x M x 1 KiB of traffic disappears.
-// Split-precision (fp16 x3) arithmetic as gemm_nt_h3_kernel; staging identical.
-// ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void gemm_ln_h3_kernel(const float* __restrict__ A, const float* __restrict__ W,
-                                                         const float* __restrict__ bias, const float* __restrict__ residual,
-                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                         float* __restrict__ Y, int M, int K, long lda, long ldw, long ldr,
-                                                         long ldy, float eps) {
-  constexpr int BM = 64, BN = 256, RA = 2, RB = 8;
-  __shared__ __attribute__((aligned(16))) _Float16 smem[2 * (BM + BN) * H_LD];
-  __shared__ float red[4][BM];
-  __shared__ float stat[BM];
-  _Float16* Ah = smem;
-  _Float16* Al = Ah + BM * H_LD;
-  _Float16* Bh = Al + BM * H_LD;
-  _Float16* Bl = Bh + BN * H_LD;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int m0 = blockIdx.x * BM, wn = wave * 64;
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-  const int sr = t >> 3, sk = (t & 7) * 4;
-  const float* ap[RA];
-  const float* bp[RB];
-#pragma unroll
-  for (int u = 0; u < RA; ++u) ap[u] = A + (size_t)min(m0 + sr + 32 * u, M - 1) * lda + sk;
-#pragma unroll
-  for (int u = 0; u < RB; ++u) bp[u] = W + (size_t)(sr + 32 * u) * ldw + sk;
-  float4 va[RA], vb[RB];
-  auto fetch = [&](int k0) {
-#pragma unroll
-    for (int u = 0; u < RA; ++u) va[u] = *reinterpret_cast<const float4*>(ap[u] + k0);
-#pragma unroll
-    for (int u = 0; u < RB; ++u) vb[u] = *reinterpret_cast<const float4*>(bp[u] + k0);
-  };
-  const int fr = lane & 31, fk = lane >> 5;
-  fetch(0);
-  for (int k0 = 0; k0 < K; k0 += H_BK) {
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < RA; ++u) {
-      half4 hi, lo;
-      split4(va[u], hi, lo);
-      *reinterpret_cast<half4*>(&Ah[(sr + 32 * u) * H_LD + sk]) = hi;
-      *reinterpret_cast<half4*>(&Al[(sr + 32 * u) * H_LD + sk]) = lo;
-    }
-#pragma unroll
-    for (int u = 0; u < RB; ++u) {
-      half4 hi, lo;
-      split4(vb[u], hi, lo);
-      *reinterpret_cast<half4*>(&Bh[(sr + 32 * u) * H_LD + sk]) = hi;
-      *reinterpret_cast<half4*>(&Bl[(sr + 32 * u) * H_LD + sk]) = lo;
-    }
-    __syncthreads();
-    if (k0 + H_BK < K) fetch(k0 + H_BK);
-#pragma unroll
-    for (int ks = 0; ks < H_BK; ks += 16) {
-      half8 ah[2], al[2], bh[2], bl[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        ah[i] = *reinterpret_cast<const half8*>(&Ah[(32 * i + fr) * H_LD + ks + 8 * fk]);
-        al[i] = *reinterpret_cast<const half8*>(&Al[(32 * i + fr) * H_LD + ks + 8 * fk]);
-      }
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        bh[j] = *reinterpret_cast<const half8*>(&Bh[(wn + 32 * j + fr) * H_LD + ks + 8 * fk]);
-        bl[j] = *reinterpret_cast<const half8*>(&Bl[(wn + 32 * j + fr) * H_LD + ks + 8 * fk]);
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-        }
-    }
-  }
-  // ---- epilogue: x = acc + bias + residual (kept in the accumulator registers)
-  float bv[2], gv[2], tv[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int col = wn + 32 * j + fr;
-    bv[j] = bias ? bias[col] : 0.f;
-    gv[j] = gamma[col];
-    tv[j] = beta[col];
-  }
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    float rv[2][16];
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = m0 + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * fk;
-        rv[j][r] = (residual && row < M) ? residual[(size_t)row * ldr + wn + 32 * j + fr] : 0.f;
-      }
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = (acc[i][j][r] + bv[j]) + rv[j][r];
-  }
-  // row sums over this wave's 64 columns: 2 per lane, then the 32 lanes that share fk (row16 all-reduce + the lane 16 away)
-  auto wave_rows = [&](auto f) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        float p = f(i, r);
-        p = row16_sum_dpp(p);
-        p += xor16_f32(p);
-        if (fr == 0) red[wave][32 * i + (r & 3) + 8 * (r >> 2) + 4 * fk] = p;
-      }
-  };
-  wave_rows([&](int i, int r) { return acc[i][0][r] + acc[i][1][r]; });
-  __syncthreads();
-  if (t < BM) stat[t] = ((red[0][t] + red[1][t]) + (red[2][t] + red[3][t])) * (1.0f / 256.0f);
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float mean = stat[32 * i + (r & 3) + 8 * (r >> 2) + 4 * fk];
-      acc[i][0][r] -= mean;
-      acc[i][1][r] -= mean;
-    }
-  __syncthreads();  // every lane has read `stat` before it is rewritten with the variances
-  wave_rows([&](int i, int r) { return acc[i][0][r] * acc[i][0][r] + acc[i][1][r] * acc[i][1][r]; });
-  __syncthreads();
-  if (t < BM) stat[t] = 1.0f / sqrtf(((red[0][t] + red[1][t]) + (red[2][t] + red[3][t])) * (1.0f / 256.0f) + eps);
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int rl = 32 * i + (r & 3) + 8 * (r >> 2) + 4 * fk;
-      const int row = m0 + rl;
-      if (row < M) {
-        const float rstd = stat[rl];
-#pragma unroll
-        for (int j = 0; j < 2; ++j) Y[(size_t)row * ldy + wn + 32 * j + fr] = acc[i][j][r] * rstd * gv[j] + tv[j];
-      }
-    }
-}
-
-extern "C" int sam6d_gemm_ln256(const float* A, const float* W, const float* bias, const float* residual, const float* gamma,
-                                const float* beta, float* Y, int M, int K, long lda, long ldw, long ldr, long ldy, float eps,
-                                void* stream) {
-  SAM6D_REQUIRE(A && W && gamma && beta && Y, "gemm_ln256: null pointer");
-  SAM6D_REQUIRE(M >= 0 && K >= 32 && (K % 32) == 0, "gemm_ln256: K must be a positive multiple of 32 (got %d)", K);
-  SAM6D_REQUIRE(lda >= K && ldw >= K && ldy >= 256 && (!residual || ldr >= 256), "gemm_ln256: leading dimension too small");
-  SAM6D_REQUIRE(((lda | ldw) & 3) == 0 && ((((size_t)A) | ((size_t)W)) & 15) == 0, "gemm_ln256: A and W rows must be 16-byte aligned");
-  SAM6D_REQUIRE(sam6d_get_matmul_mode() >= 1, "gemm_ln256: split-precision mode only (use sam6d_gemm_nt + sam6d_layernorm256 in mode 0)");
-  if (M == 0) return 0;
-  hipLaunchKernelGGL(gemm_ln_h3_kernel, dim3((unsigned)cdiv(M, 64)), dim3(256), 0, (hipStream_t)stream, A, W, bias, residual, gamma,
-                     beta, Y, M, K, lda, ldw, ldr, ldy, eps);
-  SAM6D_LAUNCH_CHECK("gemm_ln256");
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -13,7 +13,6 @@
 #include "common.h"
 #include "../../include/sam6d_hip.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // ---------------------------------------------------------------------------------------------------- 1. kNN
 // one wave per (b,i); n <= 256 (4 candidates per lane).  4 rounds of wave arg-min on (bits(dist), index).

@@ -283,19 +283,9 @@ extern "C" int sam6d_ism_patch_scores(const float* sim, const float* q_appe, int
 // the summation order of ism_patch_scores_kernel, so both paths return the same bits given the same products.
 // (N, 256, 256) floats = 39 MB written + read and 2 x 157 MB of gathered descriptors per pass disappear.
 // ---------------------------------------------------------------------------------------------------------------
-typedef float ip_f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 ip_half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 ip_half4 __attribute__((ext_vector_type(4)));
-typedef unsigned ip_u2 __attribute__((ext_vector_type(2)));
-#define IP_BK 32
-#define IP_LD 40
 #define IP_SCALE 1024.0f
-__device__ __forceinline__ void ip_split4(const float4 v, ip_half4& hi, ip_half4& lo) {
-  unsigned h0, h1, l0, l1;
-  sam6d_split2_f16(v.x * IP_SCALE, v.y * IP_SCALE, h0, l0);
-  sam6d_split2_f16(v.z * IP_SCALE, v.w * IP_SCALE, h1, l1);
-  hi = __builtin_bit_cast(ip_half4, ip_u2{h0, h1});
-  lo = __builtin_bit_cast(ip_half4, ip_u2{l0, l1});
+__device__ __forceinline__ void ip_split4(const float4 v, half4& hi, half4& lo) {
+  split4(make_float4(v.x * IP_SCALE, v.y * IP_SCALE, v.z * IP_SCALE, v.w * IP_SCALE), hi, lo);
 }
 
 __global__ __launch_bounds__(256) void ism_patch_fused_kernel(const float* __restrict__ q, const long long* __restrict__ qsel,
@@ -303,23 +293,16 @@ __global__ __launch_bounds__(256) void ism_patch_fused_kernel(const float* __res
                                                               const long long* __restrict__ best, int Nt, int P, int D,
                                                               float* __restrict__ rowpart, float* __restrict__ colpart,
                                                               float* __restrict__ nzflag) {
-  __shared__ __attribute__((aligned(16))) _Float16 smem[4 * 128 * IP_LD];
-  _Float16* Ah = smem;
-  _Float16* Al = Ah + 128 * IP_LD;
-  _Float16* Bh = Al + 128 * IP_LD;
-  _Float16* Bl = Bh + 128 * IP_LD;
+  __shared__ __attribute__((aligned(16))) _Float16 smem[SpLayout<128, 128>::HALVES];
+  using L = SpLayout<128, 128>;
+  const SpPlanes pl{smem + L::AH, smem + L::AL, smem + L::BH, smem + L::BL};
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int p = blockIdx.y, nt = P / 128, tm = blockIdx.x % nt, tn = blockIdx.x / nt, slots = 2 * nt;
   const float* A = q + ((size_t)(qsel ? qsel[p] : p) * P + 128 * tm) * D;
   const float* W = ref + (((size_t)obj[p] * Nt + (size_t)best[p]) * P + 128 * tn) * D;
   const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
-  ip_f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  f32x16 acc[2][2];
+  sp_zero(acc);
   const int sr = t >> 3, sk = (t & 7) * 4;
   float4 va[4], vb[4];
   float rs[4] = {0.f, 0.f, 0.f, 0.f};
@@ -332,43 +315,25 @@ __global__ __launch_bounds__(256) void ism_patch_fused_kernel(const float* __res
   };
   const int fr = lane & 31, fk = lane >> 5;
   fetch(0);
-  for (int k0 = 0; k0 < D; k0 += IP_BK) {
+  for (int k0 = 0; k0 < D; k0 += SP_BK) {
     __syncthreads();
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      ip_half4 hi, lo;
+      half4 hi, lo;
       ip_split4(va[u], hi, lo);
-      *reinterpret_cast<ip_half4*>(&Ah[(sr + 32 * u) * IP_LD + sk]) = hi;
-      *reinterpret_cast<ip_half4*>(&Al[(sr + 32 * u) * IP_LD + sk]) = lo;
+      *reinterpret_cast<half4*>(&pl.Ah[(sr + 32 * u) * SP_LD + sk]) = hi;
+      *reinterpret_cast<half4*>(&pl.Al[(sr + 32 * u) * SP_LD + sk]) = lo;
       rs[u] += (va[u].x + va[u].y) + (va[u].z + va[u].w);
       ip_split4(vb[u], hi, lo);
-      *reinterpret_cast<ip_half4*>(&Bh[(sr + 32 * u) * IP_LD + sk]) = hi;
-      *reinterpret_cast<ip_half4*>(&Bl[(sr + 32 * u) * IP_LD + sk]) = lo;
+      *reinterpret_cast<half4*>(&pl.Bh[(sr + 32 * u) * SP_LD + sk]) = hi;
+      *reinterpret_cast<half4*>(&pl.Bl[(sr + 32 * u) * SP_LD + sk]) = lo;
     }
     __syncthreads();
-    if (k0 + IP_BK < D) fetch(k0 + IP_BK);
-#pragma unroll
-    for (int ks = 0; ks < IP_BK; ks += 16) {
-      ip_half8 ah[2], al[2], bh[2], bl[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        ah[i] = *reinterpret_cast<const ip_half8*>(&Ah[(wm + 32 * i + fr) * IP_LD + ks + 8 * fk]);
-        al[i] = *reinterpret_cast<const ip_half8*>(&Al[(wm + 32 * i + fr) * IP_LD + ks + 8 * fk]);
-        bh[i] = *reinterpret_cast<const ip_half8*>(&Bh[(wn + 32 * i + fr) * IP_LD + ks + 8 * fk]);
-        bl[i] = *reinterpret_cast<const ip_half8*>(&Bl[(wn + 32 * i + fr) * IP_LD + ks + 8 * fk]);
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-        }
-    }
+    if (k0 + SP_BK < D) fetch(k0 + SP_BK);
+    sp_chunk(acc, pl, wm, wn, fr, fk, false);
   }
   const float un = 1.0f / (IP_SCALE * IP_SCALE);
-  // lane (fr, fk) holds rows (r & 3) + 8 (r >> 2) + 4 fk of column fr of each 32 x 32 tile
+  // lane (fr, fk) holds rows sp_row(0, r, fk) of column fr of each 32 x 32 tile
   // ---- column maxima over this wave's 64 rows
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
@@ -388,7 +353,7 @@ __global__ __launch_bounds__(256) void ism_patch_fused_kernel(const float* __res
       float m = fmaxf(acc[i][0][r], acc[i][1][r]);
       m = row16_max_dpp(m);
       m = fmaxf(m, xor16_f32(m));
-      if (fr == 0) rowpart[((size_t)p * P + 128 * tm + wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * fk) * slots + 2 * tn + (wave & 1)] = m * un;
+      if (fr == 0) rowpart[sp_row((size_t)p * P + 128 * tm + wm + 32 * i, r, fk) * slots + 2 * tn + (wave & 1)] = m * un;
     }
   // ---- occupancy of the query patches (count_nonzero(query.sum(-1)), loss.py:58): the workgroups of the first column tile
   if (tn == 0) {
@@ -450,7 +415,7 @@ extern "C" size_t sam6d_ism_patch_fused_workspace_bytes(int Ns, int P) { return 
 extern "C" int sam6d_ism_patch_fused(const float* q, const long long* qsel, const float* ref, const long long* obj, const long long* best,
                                      int Ns, int Nt, int P, int D, void* ws, size_t ws_bytes, void* stream) {
   SAM6D_REQUIRE(q && ref && obj && best && ws && Ns >= 0 && Nt > 0, "ism_patch_fused: bad arguments");
-  SAM6D_REQUIRE(P > 0 && (P % 128) == 0 && D > 0 && (D % IP_BK) == 0, "ism_patch_fused: P must be a multiple of 128, D of 32");
+  SAM6D_REQUIRE(P > 0 && (P % 128) == 0 && D > 0 && (D % SP_BK) == 0, "ism_patch_fused: P must be a multiple of 128, D of 32");
   SAM6D_REQUIRE(((((size_t)q) | ((size_t)ref) | ((size_t)ws)) & 15) == 0 && ws_bytes >= sam6d_ism_patch_fused_workspace_bytes(Ns, P),
                 "ism_patch_fused: 16-byte alignment / workspace size (sam6d_ism_patch_fused_workspace_bytes)");
   if (Ns == 0) return 0;

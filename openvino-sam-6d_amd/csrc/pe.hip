@@ -14,7 +14,6 @@
 // B = 32).  Weights + BN constants of the scale live in LDS (44 KB), 8 waves per workgroup.
 // Layer-1 features are formed in registers: {p_idx - (p_j + 1e-8), p_idx}  (new_xyz = pts + 1e-8, :117).
 // ===============================================================================================================
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define PM_WAVES 8
 #define PM_PPW 8
 #define PM_WFLOATS (32 * 7 + 64 * 33 + 128 * 65 + 448)

@@ -1021,7 +1021,6 @@ __global__ __launch_bounds__(64) void pick_best_kernel(const float* __restrict__
 // loads once per row tile for all its column tiles.  Items are (rank s of the hypothesis, scene point i) in one linear order per
 // proposal, so no lane idles at N1 = 196; the weighted distances go to a workspace and are summed per hypothesis in a fixed order by
 // score_sum_kernel; pick_best_kernel takes the arg-max (first maximum, model_utils.py:268).
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define SM_CT 8
 #define SM_WAVES 4
 __global__ __launch_bounds__(SM_WAVES * 64) void score_hyp_mfma_kernel(const int* __restrict__ sel, const float* __restrict__ Rs,

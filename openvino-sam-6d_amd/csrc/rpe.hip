@@ -19,7 +19,6 @@
 #include "common.h"
 #include "../../include/sam6d_hip.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f2 __attribute__((ext_vector_type(2)));
 typedef unsigned u2 __attribute__((ext_vector_type(2)));
 
@@ -73,26 +72,6 @@ __device__ __forceinline__ void swap16(float& a, float& b) {
 #define RP_PRIO 1
 #endif
 
-__device__ __forceinline__ unsigned rp_cvt_pk(float a, float b) {
-  unsigned r;
-  asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-// f - (float)half, exact: v_fma_mix_f32 reads the low (HI = 0) or high half of h2 as its first operand
-template <int HI>
-__device__ __forceinline__ float rp_sub_half(float f, unsigned h2) {
-  float r;
-  if (HI)
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h2), "v"(f));
-  else
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h2), "v"(f));
-  return r;
-}
-// (a, b) -> packed fp16 hi pair and lo pair, hi + lo = value to 22 bits (same roundings as sam6d_split_f16)
-__device__ __forceinline__ void rp_split2(float a, float b, unsigned& hi, unsigned& lo) {
-  hi = rp_cvt_pk(a, b);
-  lo = rp_cvt_pk(rp_sub_half<0>(a, hi), rp_sub_half<1>(b, hi));
-}
 __device__ __forceinline__ half8 rp_h8(unsigned a, unsigned b, unsigned c, unsigned d) {
   return __builtin_bit_cast(half8, u32x4{a, b, c, d});
 }
@@ -207,10 +186,10 @@ __global__ __launch_bounds__(768) void rpe_score_kernel(const float4* __restrict
       for (int u = 0; u < 2; ++u) {
         const int e = lane + 64 * u;
         unsigned h0, h1, h2, h3, l0, l1, l2, l3;
-        rp_split2(a[u].x * beta, a[u].y * beta, h0, l0);
-        rp_split2(a[u].z * beta, a[u].w * beta, h1, l1);
-        rp_split2(b[u].x * beta, b[u].y * beta, h2, l2);
-        rp_split2(b[u].z * beta, b[u].w * beta, h3, l3);
+        sam6d_split2_f16(a[u].x * beta, a[u].y * beta, h0, l0);
+        sam6d_split2_f16(a[u].z * beta, a[u].w * beta, h1, l1);
+        sam6d_split2_f16(b[u].x * beta, b[u].y * beta, h2, l2);
+        sam6d_split2_f16(b[u].z * beta, b[u].w * beta, h3, l3);
         *reinterpret_cast<u32x4*>(qf + e * 16) = u32x4{h0, h1, h2, h3};
         *reinterpret_cast<u32x4*>(qf + 2048 + e * 16) = u32x4{l0, l1, l2, l3};
       }
@@ -299,7 +278,7 @@ __global__ __launch_bounds__(768) void rpe_score_kernel(const float4* __restrict
       for (int k = 0; k < 3; ++k) {
         unsigned h[4], l[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) rp_split2(R[k + 1][2 * j], R[k + 1][2 * j + 1], h[j], l[j]);
+        for (int j = 0; j < 4; ++j) sam6d_split2_f16(R[k + 1][2 * j], R[k + 1][2 * j + 1], h[j], l[j]);
         ah[k] = rp_h8(h[0], h[1], h[2], h[3]);
         if (NP == 2) {
 #pragma unroll
@@ -339,7 +318,7 @@ __global__ __launch_bounds__(768) void rpe_score_kernel(const float4* __restrict
       };
       auto split_half = [&](int cb, int half) {  // two of the four maxima of block cb
         const int G = cb >> 1, o = 2 * (cb & 1) + half;
-        rp_split2(g[cb & 1][2 * half], g[cb & 1][2 * half + 1], gh[G & 1][o], gl[G & 1][o]);
+        sam6d_split2_f16(g[cb & 1][2 * half], g[cb & 1][2 * half + 1], gh[G & 1][o], gl[G & 1][o]);
       };
       half8 qh, ql;
       auto load_q = [&](int G) {

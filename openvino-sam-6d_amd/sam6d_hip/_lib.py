@@ -11,7 +11,7 @@ LIB_PATH = os.environ.get("SAM6D_LIB") or os.path.join(os.path.dirname(_HERE), "
 
 c_f = ctypes.c_float
 c_i = ctypes.c_int
-ABI_VERSION = 3  # include/sam6d_hip.h SAM6D_ABI_VERSION (tests/test_abi.py keeps the two equal)
+ABI_VERSION = 4  # include/sam6d_hip.h SAM6D_ABI_VERSION (tests/test_abi.py keeps the two equal)
 c_l = ctypes.c_long
 c_p = ctypes.c_void_p
 
@@ -33,7 +33,6 @@ SIGNATURES = {
     "sam6d_set_matmul_mode": [c_i],
     "sam6d_set_thread_matmul_mode": [c_i],
     "sam6d_layernorm256": [c_p, c_p, c_p, c_p, c_l, c_l, c_l, c_f, c_p],
-    "sam6d_gemm_ln256": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_l, c_l, c_l, c_l, c_f, c_p],
     "sam6d_geo_embedding": [c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_i, c_i, c_p, c_p, c_p, c_p],
     "sam6d_geo_indices": [c_p, c_i, c_i, c_f, c_f, c_i, c_p, c_p, c_p],
     "sam6d_geo_embed": [c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_p],

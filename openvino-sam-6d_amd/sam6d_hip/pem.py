@@ -497,16 +497,6 @@ def _fused_block():
     return _flags().fused_block
 
 
-def gemm_ln(x, lin, residual, norm, eps=1e-5):
-    """LayerNorm(x @ lin.w^T + lin.b + residual) for 256 output channels (sam6d_gemm_ln256).  Not on the path: the two launches of
-    _post_attention measured 1 % faster."""
-    M, K = x.shape
-    out = _empty((M, C), x)
-    _lib.call("sam6d_gemm_ln256", _p(x), _p(lin.w), _p(lin.b), _p(residual), _p(norm[0]), _p(norm[1]), _p(out), M, K, K, K, C, C,
-              float(eps), _s())
-    return out
-
-
 # optional profiling hook: bench.py sets PROFILE = {} and reads back lists of (start, end) torch.cuda.Event pairs per
 # kernel name.  Events are recorded on the launch stream and cost nothing when PROFILE is None.  An event pair is not free on
 # the GPU (each record is a barrier packet: ~150 pairs per step cost 1.6 ms of a 9.4 ms step), so PROFILE_NAMES limits the
