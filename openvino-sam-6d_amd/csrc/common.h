@@ -146,6 +146,27 @@ __device__ __forceinline__ void wave_argmax_first(float& best, int& bi) {
   best = m;
   bi = nk < -1.0e30f ? 0x7fffffff : (int)(-nk);
 }
+// The first-maximum scan itself: take() the candidates in ascending index order (strict >, so the first maximum stays), wave_merge()
+// where a wave shares the scan, label() maps "no element seen" (nothing but -inf / NaN) to 0.
+struct FirstMax {
+  int bi = 0x7fffffff;
+  float best = -INFINITY;
+  __device__ __forceinline__ void take(float v, int i) {
+    if (v > best) {
+      best = v;
+      bi = i;
+    }
+  }
+  // a candidate that is itself a (value, index) pair in memory: the index is read only where the value wins
+  __device__ __forceinline__ void take(float v, const int* i) {
+    if (v > best) {
+      best = v;
+      bi = *i;
+    }
+  }
+  __device__ __forceinline__ void wave_merge() { wave_argmax_first(best, bi); }
+  __device__ __forceinline__ int label() const { return bi == 0x7fffffff ? 0 : bi; }
+};
 
 __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
 #pragma unroll

@@ -282,12 +282,11 @@ __global__ __launch_bounds__(256) void fm_labels_kernel(const float* __restrict_
       const f32x4 x = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(er + 1 + 4 * (lane + 64 * g)));  // streamed once
       e[g] = make_float4(x[0], x[1], x[2], x[3]);
     }
-    float bv = -INFINITY;
-    int bi = 0x7fffffff;
+    FirstMax row;
     if (lane == 0 && chunk == 0) {  // the bg column: a candidate of the row arg-max only
       const float e0 = er[0];
-      bv = (e0 * irs) * (e0 * ics0);
-      bi = 0;
+      row.best = (e0 * irs) * (e0 * ics0);
+      row.bi = 0;
     }
 #pragma unroll
     for (int g = 0; g < 8; ++g) {
@@ -295,27 +294,27 @@ __global__ __launch_bounds__(256) void fm_labels_kernel(const float* __restrict_
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const float v = (ev[j] * irs) * (ev[j] * ics[4 * g + j]);
-        if (v > bv) { bv = v; bi = c0 + 1 + 4 * (lane + 64 * g) + j; }
+        row.take(v, c0 + 1 + 4 * (lane + 64 * g) + j);
         if (v > cb[4 * g + j]) { cb[4 * g + j] = v; ci[4 * g + j] = nn; }
       }
     }
     if (want_row_label) {
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        fm_better(bv, bi, ov, oi);
+        const float ov = __shfl_xor(row.best, o, 64);
+        const int oi = __shfl_xor(row.bi, o, 64);
+        fm_better(row.best, row.bi, ov, oi);
       }
       if (lane == 0) {
-        if (gridDim.z == 1) label1[(size_t)b * np + nn - 1] = bi;
+        if (gridDim.z == 1) label1[(size_t)b * np + nn - 1] = row.bi;
         else {
-          rowbest[((size_t)chunk * gridDim.y + b) * np + nn - 1] = bv;
-          rowidx[((size_t)chunk * gridDim.y + b) * np + nn - 1] = bi;
+          rowbest[((size_t)chunk * gridDim.y + b) * np + nn - 1] = row.best;
+          rowidx[((size_t)chunk * gridDim.y + b) * np + nn - 1] = row.bi;
         }
       }
     }
   };
-  // (a lane visits its columns in ascending order, g-major, so `v > bv` keeps its first maximum; across lanes fm_better prefers the
+  // (a lane visits its columns in ascending order, g-major, so take() keeps its first maximum; across lanes fm_better prefers the
   // lower column on ties)
   if (slab == 0 && wave == 0) do_row(0, false);
   for (int k = 0; k < 16; ++k) do_row(1 + 64 * slab + wave + 4 * k, true);
@@ -348,13 +347,10 @@ __global__ __launch_bounds__(256) void fm_merge_labels_kernel(const float* __res
   const int b = blockIdx.y, m = blockIdx.x * 256 + threadIdx.x;
   if (m >= np) return;
   const int slabs = FM_SLABS(np);
-  float bv = -INFINITY;
-  int bi = 0x7fffffff;
-  for (int s = 0; s < slabs; ++s) {  // slabs in ascending row order: strict > keeps the first maximum
-    const float v = pbest[((size_t)b * slabs + s) * np + m];
-    if (v > bv) { bv = v; bi = pidx[((size_t)b * slabs + s) * np + m]; }
-  }
-  label2[(size_t)b * np + m] = (bi == 0x7fffffff) ? 0 : bi;
+  FirstMax fm;
+  for (int s = 0; s < slabs; ++s)  // slabs in ascending row order: strict > keeps the first maximum
+    fm.take(pbest[((size_t)b * slabs + s) * np + m], &pidx[((size_t)b * slabs + s) * np + m]);
+  label2[(size_t)b * np + m] = fm.label();
 }
 
 // np > 2048: row arg-max over the column chunks (ascending column order: strict > keeps the first maximum)
@@ -362,13 +358,9 @@ __global__ __launch_bounds__(256) void fm_merge_rows_kernel(const float* __restr
                                                             int np, int chunks, int* __restrict__ label1) {
   const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
   if (i >= np) return;
-  float bv = -INFINITY;
-  int bi = 0x7fffffff;
-  for (int c = 0; c < chunks; ++c) {
-    const float v = rowbest[((size_t)c * B + b) * np + i];
-    if (v > bv) { bv = v; bi = rowidx[((size_t)c * B + b) * np + i]; }
-  }
-  label1[(size_t)b * np + i] = (bi == 0x7fffffff) ? 0 : bi;
+  FirstMax fm;
+  for (int c = 0; c < chunks; ++c) fm.take(rowbest[((size_t)c * B + b) * np + i], &rowidx[((size_t)c * B + b) * np + i]);
+  label1[(size_t)b * np + i] = fm.label();
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -3,7 +3,9 @@
 //   compute_coarse_Rt      PEM/utils/model_utils.py:204-275  (+ weighted_sampling_onnx_compatible :277-305)
 //   compute_fine_Rt        PEM/utils/model_utils.py:308-341
 //   weighted_procrustes    PEM/utils/model_utils.py:343-436  (torch.svd / torch.det :469-481, 513-526)
-// HBM/latency-bound vector work: coalesced row passes, wave butterflies, LDS-staged point sets; no MFMA.
+// HBM/latency-bound vector work: coalesced row passes, wave butterflies, LDS-staged point sets.  The nearest-CAD-point searches of the
+// two scoring paths run their K = 3 contraction on the fp32 matrix cores (v_mfma_f32_32x32x2_f32) while the CAD points fit its LDS
+// layout, on the vector ALU beyond.
 #include "common.h"
 #include "../../include/sam6d_hip.h"
 
@@ -14,6 +16,176 @@
 // The sampled indices of tests/golden/coarse_rt.npz stay bit-exact; on config 2 every index remains a first-(cum >= u) index of the
 // oracle's cumulative weights within 1e-6 (test_config2_full_batch_vs_oracle).
 __device__ __forceinline__ float sa_pow15(float v) { return v * sqrtf(v); }
+
+// =========================================================================================================
+// Shared steps of this file's kernels (each kernel keeps its own schedule and reduction order; FirstMax is in common.h):
+//   soft assignment   sa_row_stats: sa_row_stats_kernel (long rows), coarse_assign_kernel.   sa_col_stats: sa_col_stats_part_kernel,
+//                     coarse_assign_kernel.   sa_mask / sa_weight: coarse_weights_kernel, coarse_assign_kernel, fine_assign_kernel.
+//                     FirstMax: the sa_*_labels kernels, coarse_assign_kernel, pick_best_kernel.   sa_launch: the FAST kernels' host side.
+//   nearest CAD point pose_apply: all four kernels.   cad_stage_aos + cad_min_vec: score_hyp_kernel, fine_near_kernel (vector ALU).
+//                     cad_stage_planes + Mc*: score_hyp_mfma_kernel, fine_near_mfma_kernel (matrix cores).
+//   fp64 3-vectors    dot3 / cross3 / orthogonal_part: rotation_from_H, frame3, frame_from_dir, rotation_3pt, the two solver kernels.
+// =========================================================================================================
+// ---- soft assignment
+// max and sum exp(. - max) of row[0 .. C) by one wave: lane-strided partial results, wave reductions (the order every row pass keeps)
+__device__ __forceinline__ void sa_row_stats(const float* row, int C, int lane, float& mx, float& s) {
+  mx = -INFINITY;
+  s = 0.f;
+  for (int c = lane; c < C; c += 64) mx = fmaxf(mx, row[c]);
+  mx = wave_max(mx);
+  for (int c = lane; c < C; c += 64) s += expf(row[c] - mx);
+  s = wave_sum(s);
+}
+// the same pair for rows [r0, r1) of one column (col: its element in row 0, ld: the row stride) by ONE thread, sequential in row order:
+// the plain fp32 sum that the reference's softmax(dim=1) computes.  UM / US: loads in flight in the max / the sum loop; the sum itself
+// stays sequential.
+template <int UM, int US>
+__device__ __forceinline__ void sa_col_stats(const float* col, size_t ld, int r0, int r1, float& mx, float& s) {
+  mx = -INFINITY;
+#pragma unroll UM
+  for (int r = r0; r < r1; ++r) mx = fmaxf(mx, col[(size_t)r * ld]);
+  s = 0.f;
+#pragma unroll US
+  for (int r = r0; r < r1; ++r) s += expf(col[(size_t)r * ld] - mx);
+}
+// A = S [label1 > 0] [label2 > 0] (model_utils.py:233, 324) and the sampling weight A ^ 1.5 (:238); f1, f2 = sa_flag(label)
+__device__ __forceinline__ float sa_flag(int label) { return label > 0 ? 1.f : 0.f; }
+__device__ __forceinline__ float sa_mask(float v, float f1, float f2) { return (v * f1) * f2; }
+__device__ __forceinline__ float sa_weight(float v, float f1, float f2) { return sa_pow15(sa_mask(v, f1, f2)); }
+// launch of a <bool FAST> kernel (256 threads, no dynamic LDS): the hardware exp / rcp instantiation for the fine-stage sizes (see sa_val)
+template <class... P, class... A>
+static inline void sa_launch(bool fast, void (*k_fast)(P...), void (*k_exact)(P...), dim3 grid, hipStream_t s, A... args) {
+  hipLaunchKernelGGL(fast ? k_fast : k_exact, grid, dim3(256), 0, s, args...);
+}
+
+// ---- nearest CAD point
+// x = (p - t) R and |x|^2 in the fixed fma order of the bit recipe (model_utils.py:267, 333)
+struct Posed {
+  float x0, x1, x2, sx;
+};
+__device__ __forceinline__ Posed pose_apply(const float* p, const float* R, const float* t) {
+  const float d0 = p[0] - t[0], d1 = p[1] - t[1], d2 = p[2] - t[2];
+  Posed x;
+  x.x0 = fmaf(d2, R[6], fmaf(d1, R[3], d0 * R[0]));
+  x.x1 = fmaf(d2, R[7], fmaf(d1, R[4], d0 * R[1]));
+  x.x2 = fmaf(d2, R[8], fmaf(d1, R[5], d0 * R[2]));
+  x.sx = sqnorm3(x.x0, x.x1, x.x2);
+  return x;
+}
+// CAD points of proposal b, model / (radius + 1e-6), into LDS by nt threads.  Vector-ALU layout: [P][4] = x, y, z, |y|^2
+__device__ __forceinline__ void cad_stage_aos(float* sm, const float* model, const float* radius, int b, int P, int tid, int nt) {
+  const float den = radius[b] + 1e-6f;
+  const float* mb = model + (size_t)b * P * 3;
+  for (int i = tid; i < P; i += nt) {
+    const float x = mb[i * 3] / den, y = mb[i * 3 + 1] / den, z = mb[i * 3 + 2] / den;
+    sm[i * 4] = x; sm[i * 4 + 1] = y; sm[i * 4 + 2] = z; sm[i * 4 + 3] = sqnorm3(x, y, z);
+  }
+}
+// matrix-core layout: [4][Ppad] = -2 y0 | -2 y1 | -2 y2 | 1, then [Ppad] = |y|^2; rows P .. Ppad are zeros with |y|^2 = +inf
+__device__ __forceinline__ void cad_stage_planes(float* sm, const float* model, const float* radius, int b, int P, int Ppad, int tid,
+                                                 int nt) {
+  const float den = radius[b] + 1e-6f;
+  const float* mb = model + (size_t)b * P * 3;
+  for (int i = tid; i < Ppad; i += nt) {
+    float x = 0.f, y = 0.f, z = 0.f, sq = INFINITY;
+    if (i < P) {
+      x = mb[i * 3] / den; y = mb[i * 3 + 1] / den; z = mb[i * 3 + 2] / den;
+      sq = sqnorm3(x, y, z);
+    }
+    sm[i] = -2.0f * x; sm[Ppad + i] = -2.0f * y; sm[2 * Ppad + i] = -2.0f * z; sm[3 * Ppad + i] = 1.0f;
+    sm[4 * Ppad + i] = sq;
+  }
+}
+// min over the CAD points [m0, m1) of the AoS layout of pdist3(x, y_m), six VALU instructions per pair instead of eight, same bits:
+// 2*xy is exact, so sx - 2*xy = fma(-2, xy, sx); and min_m max(d_m, 0) = max(min_m d_m, 0), so the clamp moves out of the loop (and
+// out of a minimum over several ranges).  W points per step, each with a running minimum of its own (W = 4 or 2: the registers the
+// kernel has for loads in flight); an empty range gives +inf.
+template <int W>
+__device__ __forceinline__ float cad_min_vec(const float* sm, int m0, int m1, const Posed& x) {
+  auto raw = [&](const float4& q) {
+    const float xy = fmaf(x.x2, q.z, fmaf(x.x1, q.y, x.x0 * q.x));
+    return fmaf(-2.0f, xy, x.sx) + q.w;
+  };
+  float mn[W];
+  static_for<0, W>([&](auto U) { mn[U] = INFINITY; });
+  int m = m0;
+  for (; m + W <= m1; m += W) {
+    float4 q[W];
+    static_for<0, W>([&](auto U) { q[U] = *reinterpret_cast<const float4*>(&sm[m * 4 + 4 * U]); });
+    static_for<0, W>([&](auto U) { mn[U] = fminf(mn[U], raw(q[U])); });
+  }
+  for (; m < m1; ++m) mn[0] = fminf(mn[0], raw(*reinterpret_cast<const float4*>(&sm[m * 4])));
+  static_for<1, W>([&](auto U) { mn[0] = fminf(mn[0], mn[U]); });
+  return mn[0] < 0.0f ? 0.0f : mn[0];
+}
+// The matrix-core step (arithmetic: see score_hyp_mfma_kernel).  Lane (j = lane & 31, kk = lane >> 5) holds column j (an item) of the
+// B operands and row j of a 32-row CAD tile of the A operands, k half kk.
+struct McItem {  // B operands of one item: (x0, x1 | x2, |x|^2)
+  float b1, b2;
+  __device__ __forceinline__ McItem(const Posed& x, int kk) : b1(kk ? x.x1 : x.x0), b2(kk ? x.sx : x.x2) {}
+  McItem() = default;
+};
+struct McTile {  // A operands and the 16 norms of this lane's accumulator rows, of the CAD rows r .. r + 31
+  float a1, a2;
+  float4 s0, s1, s2, s3;
+};
+struct McPlanes {  // this lane's three LDS pointers into the planes of cad_stage_planes
+  const float *a1p, *a2p, *syp;
+  __device__ __forceinline__ McPlanes(const float* sm, int Ppad, int j, int kk)
+      : a1p(sm + kk * Ppad + j), a2p(sm + (2 + kk) * Ppad + j), syp(sm + 4 * Ppad + kk * 4) {}
+  __device__ __forceinline__ McTile load(int r) const {
+    McTile t;
+    t.a1 = a1p[r];
+    t.a2 = a2p[r];
+    t.s0 = *reinterpret_cast<const float4*>(syp + r);
+    t.s1 = *reinterpret_cast<const float4*>(syp + r + 8);
+    t.s2 = *reinterpret_cast<const float4*>(syp + r + 16);
+    t.s3 = *reinterpret_cast<const float4*>(syp + r + 24);
+    return t;
+  }
+};
+__device__ __forceinline__ f32x16 mc_zero() {
+  f32x16 zero;
+#pragma unroll
+  for (int v = 0; v < 16; ++v) zero[v] = 0.f;
+  return zero;
+}
+// rn(|x|^2 - 2 x . y) of 32 CAD rows x 32 items: two instructions on a zero accumulator
+__device__ __forceinline__ f32x16 mc_pair(const McTile& t, const McItem& it, const f32x16& zero) {
+  const f32x16 acc = __builtin_amdgcn_mfma_f32_32x32x2f32(t.a1, it.b1, zero, 0, 0, 0);
+  return __builtin_amdgcn_mfma_f32_32x32x2f32(t.a2, it.b2, acc, 0, 0, 0);
+}
+// + |y|^2 and the running minimum; accumulator register v of this lane: CAD row r + 8 (v >> 2) + 4 kk + (v & 3), column j
+__device__ __forceinline__ float mc_fold(float mn, const f32x16& acc, const McTile& t) {
+  const float m0 = fminf(fminf(acc[0] + t.s0.x, acc[1] + t.s0.y), fminf(acc[2] + t.s0.z, acc[3] + t.s0.w));
+  const float m1 = fminf(fminf(acc[4] + t.s1.x, acc[5] + t.s1.y), fminf(acc[6] + t.s1.z, acc[7] + t.s1.w));
+  const float m2 = fminf(fminf(acc[8] + t.s2.x, acc[9] + t.s2.y), fminf(acc[10] + t.s2.z, acc[11] + t.s2.w));
+  const float m3 = fminf(fminf(acc[12] + t.s3.x, acc[13] + t.s3.y), fminf(acc[14] + t.s3.z, acc[15] + t.s3.w));
+  return fminf(fminf(mn, m0), fminf(fminf(m1, m2), m3));
+}
+// the two k halves' minima of a column, then pdist3's clamp (it commutes with the minimum)
+__device__ __forceinline__ float mc_finish(float mn) {
+  const float m = fminf(mn, __shfl_xor(mn, 32, 64));
+  return m < 0.0f ? 0.0f : m;
+}
+
+// ---- fp64 3-vectors of the rotation solvers (plain IEEE operations in the order written; nothing contracts)
+__device__ __forceinline__ double dot3(const double a[3], const double b[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
+__device__ __forceinline__ void cross3(const double a[3], const double b[3], double c[3]) {
+  c[0] = a[1] * b[2] - a[2] * b[1];
+  c[1] = a[2] * b[0] - a[0] * b[2];
+  c[2] = a[0] * b[1] - a[1] * b[0];
+}
+// q = the part orthogonal to the unit vector e1 of the coordinate axis least aligned with it; returns |q| (the caller divides): how a
+// frame is completed where the data give no second direction -- finite, deterministic, a proper rotation
+__device__ __forceinline__ double orthogonal_part(const double (&e1)[3], double (&q)[3]) {
+  const int a = (fabs(e1[0]) <= fabs(e1[1]) && fabs(e1[0]) <= fabs(e1[2])) ? 0 : (fabs(e1[1]) <= fabs(e1[2]) ? 1 : 2);
+  const double d = e1[a];
+  q[0] = (a == 0 ? 1.0 : 0.0) - d * e1[0];
+  q[1] = (a == 1 ? 1.0 : 0.0) - d * e1[1];
+  q[2] = (a == 2 ? 1.0 : 0.0) - d * e1[2];
+  return sqrt(dot3(q, q));
+}
 
 // =========================================================================================================
 // Soft assignment  S = softmax(att, dim=2) * softmax(att, dim=1)   (model_utils.py:229-233, 320-324)
@@ -42,12 +214,10 @@ __global__ __launch_bounds__(256) void sa_row_stats_kernel(const float* __restri
 #pragma unroll
     for (int k = 0; k < SA_RPL; ++k)
       if (lane + 64 * k < C) s += expf(v[k] - mx);
+    s = wave_sum(s);
   } else {
-    for (int c = lane; c < C; c += 64) mx = fmaxf(mx, a[c]);
-    mx = wave_max(mx);
-    for (int c = lane; c < C; c += 64) s += expf(a[c] - mx);
+    sa_row_stats(a, C, lane, mx, s);
   }
-  s = wave_sum(s);
   if (lane == 0) {
     rmax[row] = mx;
     rsum[row] = s;
@@ -69,13 +239,8 @@ __global__ __launch_bounds__(256) void sa_col_stats_part_kernel(const float* __r
   const int per = (R + SA_RS - 1) / SA_RS;
   const int r0 = rs * per, r1 = min(R, r0 + per);
   const float* a = att + (size_t)b * R * C + c;
-  // (unrolled: the strided loads of 8 rows are in flight together; the fp32 sum itself stays sequential in row order)
-  float mx = -INFINITY;
-#pragma unroll 8
-  for (int r = r0; r < r1; ++r) mx = fmaxf(mx, a[(size_t)r * C]);
-  float s = 0.f;
-#pragma unroll 8
-  for (int r = r0; r < r1; ++r) s += expf(a[(size_t)r * C] - mx);
+  float mx, s;
+  sa_col_stats<8, 8>(a, C, r0, r1, mx, s);  // the strided loads of 8 rows in flight together
   pmax[((size_t)b * SA_RS + rs) * C + c] = mx;
   psum[((size_t)b * SA_RS + rs) * C + c] = s;
 }
@@ -130,17 +295,10 @@ __global__ __launch_bounds__(256) void sa_row_labels_kernel(const float* __restr
   const float rm = rmax[b * R + r], rs = rsum[b * R + r];
   const float* cm = cmax + b * C;
   const float* cs = csum + b * C;
-  float best = -INFINITY;
-  int bi = 0x7fffffff;
-  for (int c = lane; c < C; c += 64) {
-    const float v = sa_val<FAST>(a[c], rm, rs, cm[c], cs[c]);
-    if (v > best) {
-      best = v;
-      bi = c;
-    }
-  }
-  wave_argmax_first(best, bi);
-  if (lane == 0) label1[w] = (bi == 0x7fffffff) ? 0 : bi;
+  FirstMax fm;
+  for (int c = lane; c < C; c += 64) fm.take(sa_val<FAST>(a[c], rm, rs, cm[c], cs[c]), c);
+  fm.wave_merge();
+  if (lane == 0) label1[w] = fm.label();
 }
 
 // label2[b, c-1] = argmax_r S[b, r, c] (first maximum), c = 1..C-1: row-sliced like the column statistics; the merge
@@ -159,18 +317,11 @@ __global__ __launch_bounds__(256) void sa_col_labels_part_kernel(const float* __
   const float cm = cmax[(size_t)b * C + c], cs = csum[(size_t)b * C + c];
   const float* rm = rmax + (size_t)b * R;
   const float* rsm = rsum + (size_t)b * R;
-  float best = -INFINITY;
-  int bi = 0x7fffffff;
+  FirstMax fm;
 #pragma unroll 8
-  for (int r = r0; r < r1; ++r) {
-    const float v = sa_val<FAST>(a[(size_t)r * C], rm[r], rsm[r], cm, cs);
-    if (v > best) {
-      best = v;
-      bi = r;
-    }
-  }
-  pbest[((size_t)b * SA_RS + rs) * C + c] = best;
-  pidx[((size_t)b * SA_RS + rs) * C + c] = bi;
+  for (int r = r0; r < r1; ++r) fm.take(sa_val<FAST>(a[(size_t)r * C], rm[r], rsm[r], cm, cs), r);
+  pbest[((size_t)b * SA_RS + rs) * C + c] = fm.best;
+  pidx[((size_t)b * SA_RS + rs) * C + c] = fm.bi;
 }
 
 __global__ __launch_bounds__(256) void sa_col_labels_merge_kernel(const float* __restrict__ pbest, const int* __restrict__ pidx,
@@ -178,16 +329,10 @@ __global__ __launch_bounds__(256) void sa_col_labels_merge_kernel(const float* _
   const int b = blockIdx.y;
   const int c = blockIdx.x * 256 + threadIdx.x + 1;
   if (c >= C) return;
-  float best = -INFINITY;
-  int bi = 0x7fffffff;
-  for (int rs = 0; rs < SA_RS; ++rs) {  // slices are in increasing row order: strict > keeps the first maximum
-    const float v = pbest[((size_t)b * SA_RS + rs) * C + c];
-    if (v > best) {
-      best = v;
-      bi = pidx[((size_t)b * SA_RS + rs) * C + c];
-    }
-  }
-  label2[(size_t)b * (C - 1) + (c - 1)] = (bi == 0x7fffffff) ? 0 : bi;
+  FirstMax fm;
+  for (int rs = 0; rs < SA_RS; ++rs)  // slices are in increasing row order: strict > keeps the first maximum
+    fm.take(pbest[((size_t)b * SA_RS + rs) * C + c], &pidx[((size_t)b * SA_RS + rs) * C + c]);
+  label2[(size_t)b * (C - 1) + (c - 1)] = fm.label();
 }
 
 extern "C" int sam6d_soft_assign(const float* att, int B, int R, int C, float* rmax, float* rsum, float* cmax, float* csum,
@@ -205,17 +350,10 @@ extern "C" int sam6d_soft_assign(const float* att, int B, int R, int C, float* r
   hipLaunchKernelGGL(sa_col_stats_part_kernel, dim3(cdiv(C, 256), B, SA_RS), dim3(256), 0, s, att, R, C, SA_RS, p0, p1);
   hipLaunchKernelGGL(sa_col_stats_merge_kernel, dim3(cdiv(C, 256), B), dim3(256), 0, s, p0, p1, C, SA_RS, cmax, csum);
   const long lrows = (long)B * (R - 1);
-  if (R > 256) {  // fine-stage sizes: hardware exp / rcp (see sa_val)
-    hipLaunchKernelGGL(sa_row_labels_kernel<true>, dim3((unsigned)((lrows + 3) / 4)), dim3(256), 0, s, att, R, C, lrows, rmax, rsum,
-                       cmax, csum, label1);
-    hipLaunchKernelGGL(sa_col_labels_part_kernel<true>, dim3(cdiv(C - 1, 256), B, SA_RS), dim3(256), 0, s, att, R, C, SA_RS, rmax,
-                       rsum, cmax, csum, p0, reinterpret_cast<int*>(p1));
-  } else {
-    hipLaunchKernelGGL(sa_row_labels_kernel<false>, dim3((unsigned)((lrows + 3) / 4)), dim3(256), 0, s, att, R, C, lrows, rmax, rsum,
-                       cmax, csum, label1);
-    hipLaunchKernelGGL(sa_col_labels_part_kernel<false>, dim3(cdiv(C - 1, 256), B, SA_RS), dim3(256), 0, s, att, R, C, SA_RS, rmax,
-                       rsum, cmax, csum, p0, reinterpret_cast<int*>(p1));
-  }
+  sa_launch(R > 256, sa_row_labels_kernel<true>, sa_row_labels_kernel<false>, dim3((unsigned)((lrows + 3) / 4)), s, att, R, C, lrows, rmax,
+            rsum, cmax, csum, label1);
+  sa_launch(R > 256, sa_col_labels_part_kernel<true>, sa_col_labels_part_kernel<false>, dim3(cdiv(C - 1, 256), B, SA_RS), s, att, R, C,
+            SA_RS, rmax, rsum, cmax, csum, p0, reinterpret_cast<int*>(p1));
   hipLaunchKernelGGL(sa_col_labels_merge_kernel, dim3(cdiv(C - 1, 256), B), dim3(256), 0, s, p0, reinterpret_cast<const int*>(p1),
                      C, SA_RS, label2);
   SAM6D_LAUNCH_CHECK("soft_assign");
@@ -235,11 +373,9 @@ __global__ __launch_bounds__(256) void coarse_weights_kernel(const float* __rest
   const int r = (int)(br % n1) + 1;
   const long b = br / n1;
   const float a = att[((size_t)b * R + r) * C + c];
-  float v = sa_value(a, rmax[b * R + r], rsum[b * R + r], cmax[b * C + c], csum[b * C + c]);
-  const float f1 = label1[b * n1 + (r - 1)] > 0 ? 1.f : 0.f;
-  const float f2 = label2[b * n2 + (c - 1)] > 0 ? 1.f : 0.f;
-  v = (v * f1) * f2;
-  weights[e] = sa_pow15(v);
+  const float v = sa_value(a, rmax[b * R + r], rsum[b * R + r], cmax[b * C + c], csum[b * C + c]);
+  const float f1 = sa_flag(label1[b * n1 + (r - 1)]);
+  weights[e] = sa_weight(v, f1, sa_flag(label2[b * n2 + (c - 1)]));
   if (c == 1) w1[b * n1 + (r - 1)] = f1;
 }
 
@@ -281,12 +417,8 @@ __global__ __launch_bounds__(1024) void coarse_assign_kernel(const float* __rest
   if (wave < 12) {
     // ---- row statistics (sa_row_stats_kernel, C <= 2304 form): waves 0..11
     for (int r = wave; r < R; r += 12) {
-      const float* row = m + (size_t)r * C;
-      float mx = -INFINITY, s = 0.f;
-      for (int c = lane; c < C; c += 64) mx = fmaxf(mx, row[c]);
-      mx = wave_max(mx);
-      for (int c = lane; c < C; c += 64) s += expf(row[c] - mx);
-      s = wave_sum(s);
+      float mx, s;
+      sa_row_stats(m + (size_t)r * C, C, lane, mx, s);
       if (lane == 0) {
         rm[r] = mx;
         rs[r] = s;
@@ -296,11 +428,8 @@ __global__ __launch_bounds__(1024) void coarse_assign_kernel(const float* __rest
     // ---- column statistics (sa_col_stats_part_kernel with one slice), beside the row pass: one thread per column, sequential in row
     // order
     for (int c = t - 768; c < C; c += 256) {
-      float mx = -INFINITY;
-      for (int r = 0; r < R; ++r) mx = fmaxf(mx, m[(size_t)r * C + c]);
-      float s = 0.f;
-#pragma unroll 4
-      for (int r = 0; r < R; ++r) s += expf(m[(size_t)r * C + c] - mx);
+      float mx, s;
+      sa_col_stats<8, 4>(m + c, C, 0, R, mx, s);  // (8: what the compiler chose for the max loop when it stood here without a pragma)
       cm[c] = mx;
       cs[c] = s;
     }
@@ -316,31 +445,17 @@ __global__ __launch_bounds__(1024) void coarse_assign_kernel(const float* __rest
   // ---- row labels (sa_row_labels_kernel<false>): first maximum over the columns
   for (int r = 1 + wave; r < R; r += 16) {
     const float* row = m + (size_t)r * C;
-    float best = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int c = lane; c < C; c += 64) {
-      const float v = row[c];
-      if (v > best) {
-        best = v;
-        bi = c;
-      }
-    }
-    wave_argmax_first(best, bi);
-    if (lane == 0) l1[r] = (bi == 0x7fffffff) ? 0 : bi;
+    FirstMax fm;
+    for (int c = lane; c < C; c += 64) fm.take(row[c], c);
+    fm.wave_merge();
+    if (lane == 0) l1[r] = fm.label();
   }
   // ---- column labels: first maximum over the rows (a wave per column; ties -> the lower row, as the sequential scan keeps)
   for (int c = 1 + wave; c < C; c += 16) {
-    float best = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int r = lane; r < R; r += 64) {
-      const float v = m[(size_t)r * C + c];
-      if (v > best) {
-        best = v;
-        bi = r;
-      }
-    }
-    wave_argmax_first(best, bi);
-    if (lane == 0) l2[c] = (bi == 0x7fffffff) ? 0 : bi;
+    FirstMax fm;
+    for (int r = lane; r < R; r += 64) fm.take(m[(size_t)r * C + c], r);
+    fm.wave_merge();
+    if (lane == 0) l2[c] = fm.label();
   }
   __syncthreads();
   // ---- outputs: statistics, labels, weights (coarse_weights_kernel)
@@ -349,7 +464,7 @@ __global__ __launch_bounds__(1024) void coarse_assign_kernel(const float* __rest
     rsum[(size_t)b * R + i] = rs[i];
     if (i >= 1) {
       label1[(size_t)b * (R - 1) + i - 1] = l1[i];
-      w1[(size_t)b * (R - 1) + i - 1] = l1[i] > 0 ? 1.f : 0.f;
+      w1[(size_t)b * (R - 1) + i - 1] = sa_flag(l1[i]);
     }
   }
   for (int i = t; i < C; i += 1024) {
@@ -361,11 +476,7 @@ __global__ __launch_bounds__(1024) void coarse_assign_kernel(const float* __rest
   float* wb = weights + (size_t)b * n1 * n2;
   for (int e = t; e < n1 * n2; e += 1024) {
     const int c = e % n2 + 1, r = e / n2 + 1;
-    float v = m[(size_t)r * C + c];
-    const float f1 = l1[r] > 0 ? 1.f : 0.f;
-    const float f2 = l2[c] > 0 ? 1.f : 0.f;
-    v = (v * f1) * f2;
-    wb[e] = sa_pow15(v);
+    wb[e] = sa_weight(m[(size_t)r * C + c], sa_flag(l1[r]), sa_flag(l2[c]));
   }
 }
 
@@ -529,29 +640,23 @@ __device__ void rotation_from_H(const double H[9], double R[9]) {
   double v2[3] = {v[0][i1], v[1][i1], v[2][i1]};
   double u1[3], u2[3];
   for (int i = 0; i < 3; ++i) {
-    u1[i] = H[i * 3 + 0] * v1[0] + H[i * 3 + 1] * v1[1] + H[i * 3 + 2] * v1[2];
-    u2[i] = H[i * 3 + 0] * v2[0] + H[i * 3 + 1] * v2[1] + H[i * 3 + 2] * v2[2];
+    u1[i] = dot3(&H[i * 3], v1);
+    u2[i] = dot3(&H[i * 3], v2);
   }
-  const double n1 = sqrt(u1[0] * u1[0] + u1[1] * u1[1] + u1[2] * u1[2]);
+  const double n1 = sqrt(dot3(u1, u1));
   if (!(n1 > 1e-150)) {  // H == 0: no information, identity
     for (int i = 0; i < 9; ++i) R[i] = (i % 4 == 0) ? 1.0 : 0.0;
     return;
   }
   for (int i = 0; i < 3; ++i) u1[i] /= n1;
-  const double d12 = u1[0] * u2[0] + u1[1] * u2[1] + u1[2] * u2[2];
+  const double d12 = dot3(u1, u2);
   for (int i = 0; i < 3; ++i) u2[i] -= d12 * u1[i];
-  double n2 = sqrt(u2[0] * u2[0] + u2[1] * u2[1] + u2[2] * u2[2]);
-  if (!(n2 > 1e-12 * n1)) {  // rank-1 H (degenerate hypothesis): any unit vector orthogonal to u1 (finite, deterministic)
-    const int k = (fabs(u1[0]) <= fabs(u1[1]) && fabs(u1[0]) <= fabs(u1[2])) ? 0 : (fabs(u1[1]) <= fabs(u1[2]) ? 1 : 2);
-    double e[3] = {0, 0, 0};
-    e[k] = 1.0;
-    const double d = u1[k];
-    for (int i = 0; i < 3; ++i) u2[i] = e[i] - d * u1[i];
-    n2 = sqrt(u2[0] * u2[0] + u2[1] * u2[1] + u2[2] * u2[2]);
-  }
+  double n2 = sqrt(dot3(u2, u2));
+  if (!(n2 > 1e-12 * n1)) n2 = orthogonal_part(u1, u2);  // rank-1 H (degenerate hypothesis): any unit vector orthogonal to u1
   for (int i = 0; i < 3; ++i) u2[i] /= n2;
-  const double u3[3] = {u1[1] * u2[2] - u1[2] * u2[1], u1[2] * u2[0] - u1[0] * u2[2], u1[0] * u2[1] - u1[1] * u2[0]};
-  const double v3[3] = {v1[1] * v2[2] - v1[2] * v2[1], v1[2] * v2[0] - v1[0] * v2[2], v1[0] * v2[1] - v1[1] * v2[0]};
+  double u3[3], v3[3];
+  cross3(u1, u2, u3);
+  cross3(v1, v2, v3);
   for (int i = 0; i < 3; ++i)
     for (int j = 0; j < 3; ++j) R[i * 3 + j] = v1[i] * u1[j] + v2[i] * u2[j] + v3[i] * u3[j];
 }
@@ -570,7 +675,7 @@ __device__ void rotation_from_H(const double H[9], double R[9]) {
 __device__ __forceinline__ void frame3(const double p[3][3], double e[3][3]) {
   double n[3];
 #pragma unroll
-  for (int k = 0; k < 3; ++k) n[k] = p[k][0] * p[k][0] + p[k][1] * p[k][1] + p[k][2] * p[k][2];
+  for (int k = 0; k < 3; ++k) n[k] = dot3(p[k], p[k]);
   const int k0 = (n[0] >= n[1] && n[0] >= n[2]) ? 0 : (n[1] >= n[2] ? 1 : 2);
   double e1[3] = {1.0, 0.0, 0.0};
   double n1 = 0.0;
@@ -584,42 +689,27 @@ __device__ __forceinline__ void frame3(const double p[3][3], double e[3][3]) {
   double q[3] = {0.0, 0.0, 0.0}, qn = -1.0;
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    const double d = p[k][0] * e1[0] + p[k][1] * e1[1] + p[k][2] * e1[2];
+    const double d = dot3(p[k], e1);
     const double x = p[k][0] - d * e1[0], y = p[k][1] - d * e1[1], z = p[k][2] - d * e1[2];
     const double m = x * x + y * y + z * z;
     if (m > qn) { qn = m; q[0] = x; q[1] = y; q[2] = z; }
   }
   double n2 = sqrt(qn > 0.0 ? qn : 0.0);
-  if (!(n2 > 1e-12 * n1) || !(n1 > 1e-150)) {  // collinear / coincident: complete the frame from the axis least aligned with e1
-    const int a = (fabs(e1[0]) <= fabs(e1[1]) && fabs(e1[0]) <= fabs(e1[2])) ? 0 : (fabs(e1[1]) <= fabs(e1[2]) ? 1 : 2);
-    const double d = e1[a];
-    q[0] = (a == 0 ? 1.0 : 0.0) - d * e1[0];
-    q[1] = (a == 1 ? 1.0 : 0.0) - d * e1[1];
-    q[2] = (a == 2 ? 1.0 : 0.0) - d * e1[2];
-    n2 = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2]);
-  }
-  const double e2[3] = {q[0] / n2, q[1] / n2, q[2] / n2};
-#pragma unroll
-  for (int i = 0; i < 3; ++i) { e[0][i] = e1[i]; e[1][i] = e2[i]; }
-  e[2][0] = e1[1] * e2[2] - e1[2] * e2[1];
-  e[2][1] = e1[2] * e2[0] - e1[0] * e2[2];
-  e[2][2] = e1[0] * e2[1] - e1[1] * e2[0];
-}
-
-// frame whose first axis is the direction of v (completed from the coordinate axis least aligned with it); v = 0 -> the identity frame
-__device__ __forceinline__ void frame_from_dir(const double v[3], double e[3][3]) {
-  const double n = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-  double e1[3] = {1.0, 0.0, 0.0};
-  if (n > 1e-150) { e1[0] = v[0] / n; e1[1] = v[1] / n; e1[2] = v[2] / n; }
-  const int a = (fabs(e1[0]) <= fabs(e1[1]) && fabs(e1[0]) <= fabs(e1[2])) ? 0 : (fabs(e1[1]) <= fabs(e1[2]) ? 1 : 2);
-  const double d = e1[a];
-  double q[3] = {(a == 0 ? 1.0 : 0.0) - d * e1[0], (a == 1 ? 1.0 : 0.0) - d * e1[1], (a == 2 ? 1.0 : 0.0) - d * e1[2]};
-  const double n2 = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2]);
+  if (!(n2 > 1e-12 * n1) || !(n1 > 1e-150)) n2 = orthogonal_part(e1, q);  // collinear / coincident
 #pragma unroll
   for (int i = 0; i < 3; ++i) { e[0][i] = e1[i]; e[1][i] = q[i] / n2; }
-  e[2][0] = e[0][1] * e[1][2] - e[0][2] * e[1][1];
-  e[2][1] = e[0][2] * e[1][0] - e[0][0] * e[1][2];
-  e[2][2] = e[0][0] * e[1][1] - e[0][1] * e[1][0];
+  cross3(e[0], e[1], e[2]);
+}
+
+// frame whose first axis is the direction of v, completed by orthogonal_part; v = 0 -> the identity frame
+__device__ __forceinline__ void frame_from_dir(const double v[3], double e[3][3]) {
+  const double n = sqrt(dot3(v, v));
+  double e1[3] = {1.0, 0.0, 0.0}, q[3];
+  if (n > 1e-150) { e1[0] = v[0] / n; e1[1] = v[1] / n; e1[2] = v[2] / n; }
+  const double n2 = orthogonal_part(e1, q);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) { e[0][i] = e1[i]; e[1][i] = q[i] / n2; }
+  cross3(e[0], e[1], e[2]);
 }
 
 // a, b: the triples centred on their TRUE means ma, mb (see coarse_hyp_kernel)
@@ -628,8 +718,8 @@ __device__ void rotation_3pt(const double a[3][3], const double b[3][3], const d
   double na = 0.0, nb = 0.0;
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    na = fmax(na, a[k][0] * a[k][0] + a[k][1] * a[k][1] + a[k][2] * a[k][2]);
-    nb = fmax(nb, b[k][0] * b[k][0] + b[k][1] * b[k][1] + b[k][2] * b[k][2]);
+    na = fmax(na, dot3(a[k], a[k]));
+    nb = fmax(nb, dot3(b[k], b[k]));
   }
   if (!(na > 1e-300) || !(nb > 1e-300)) {
     // one of the triples is a single point sampled three times: H0 = 0, and what is left of the reference's H is the rank-1 trace of its
@@ -648,10 +738,7 @@ __device__ void rotation_3pt(const double a[3][3], const double b[3][3], const d
   double M[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    const double a1 = a[k][0] * E[0][0] + a[k][1] * E[0][1] + a[k][2] * E[0][2];
-    const double a2 = a[k][0] * E[1][0] + a[k][1] * E[1][1] + a[k][2] * E[1][2];
-    const double b1 = b[k][0] * F[0][0] + b[k][1] * F[0][1] + b[k][2] * F[0][2];
-    const double b2 = b[k][0] * F[1][0] + b[k][1] * F[1][1] + b[k][2] * F[1][2];
+    const double a1 = dot3(a[k], E[0]), a2 = dot3(a[k], E[1]), b1 = dot3(b[k], F[0]), b2 = dot3(b[k], F[1]);
     M[0][0] += a1 * b1; M[0][1] += a1 * b2; M[1][0] += a2 * b1; M[1][1] += a2 * b2;
   }
   const bool rot = (M[0][0] * M[1][1] - M[0][1] * M[1][0]) >= 0.0;
@@ -710,7 +797,7 @@ __global__ __launch_bounds__(256) void coarse_hyp_kernel(const int* __restrict__
   }
   double R[9], t[3];
   rotation_3pt(ca, cb, ma, mb, R);
-  for (int i = 0; i < 3; ++i) t[i] = rc[i] - (R[i * 3] * sc[0] + R[i * 3 + 1] * sc[1] + R[i * 3 + 2] * sc[2]);
+  for (int i = 0; i < 3; ++i) t[i] = rc[i] - dot3(&R[i * 3], sc);
   double acc = 0.0;
   for (int k = 0; k < 3; ++k) {
     double r2 = 0.0;
@@ -920,16 +1007,11 @@ __global__ __launch_bounds__(256) void score_hyp_kernel(const int* __restrict__ 
                                                         const float* __restrict__ w1, const float* __restrict__ model,
                                                         const float* __restrict__ radius, int N1, int P, int nh, int k,
                                                         float* __restrict__ scores) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];  // [P*4]: x,y,z,|m|^2
+  extern __shared__ __attribute__((aligned(16))) float sm[];  // cad_stage_aos
   __shared__ float sRt[SH_G][12];
   __shared__ float red[2][SH_G][4];
   const int b = blockIdx.y, s0 = blockIdx.x * SH_G, t = threadIdx.x;
-  const float den = radius[b] + 1e-6f;
-  const float* mb = model + (size_t)b * P * 3;
-  for (int i = t; i < P; i += 256) {
-    const float x = mb[i * 3] / den, y = mb[i * 3 + 1] / den, z = mb[i * 3 + 2] / den;
-    sm[i * 4] = x; sm[i * 4 + 1] = y; sm[i * 4 + 2] = z; sm[i * 4 + 3] = sqnorm3(x, y, z);
-  }
+  cad_stage_aos(sm, model, radius, b, P, t, 256);
   if (t < SH_G * 12) {
     const int g = t / 12, e = t % 12;
     const int s = min(s0 + g, k - 1);
@@ -940,37 +1022,7 @@ __global__ __launch_bounds__(256) void score_hyp_kernel(const int* __restrict__ 
   const int g = t % SH_G;
   float sw_t = 0.f, sdw_t = 0.f;
   for (int i = t / SH_G; i < N1; i += 256 / SH_G) {
-    const float* R = sRt[g];
-    const float* p = pts1 + ((size_t)b * N1 + i) * 3;
-    const float d0 = p[0] - R[9], d1 = p[1] - R[10], d2 = p[2] - R[11];
-    const float x0 = fmaf(d2, R[6], fmaf(d1, R[3], d0 * R[0]));
-    const float x1 = fmaf(d2, R[7], fmaf(d1, R[4], d0 * R[1]));
-    const float x2 = fmaf(d2, R[8], fmaf(d1, R[5], d0 * R[2]));
-    const float sx = sqnorm3(x0, x1, x2);
-    // min over the CAD points of pdist3, six VALU instructions per pair instead of eight, same bits: 2*xy is exact, so
-    // sx - 2*xy = fma(-2, xy, sx); and min_m max(d_m, 0) = max(min_m d_m, 0), so the clamp moves out of the loop
-    auto raw = [&](float qx, float qy, float qz, float qw) {
-      const float xy = fmaf(x2, qz, fmaf(x1, qy, x0 * qx));
-      return fmaf(-2.0f, xy, sx) + qw;
-    };
-    float mn0 = INFINITY, mn1 = INFINITY, mn2 = INFINITY, mn3 = INFINITY;
-    int m = 0;
-    for (; m + 4 <= P; m += 4) {
-      const float4 q0 = *reinterpret_cast<const float4*>(&sm[m * 4]);
-      const float4 q1 = *reinterpret_cast<const float4*>(&sm[m * 4 + 4]);
-      const float4 q2 = *reinterpret_cast<const float4*>(&sm[m * 4 + 8]);
-      const float4 q3 = *reinterpret_cast<const float4*>(&sm[m * 4 + 12]);
-      mn0 = fminf(mn0, raw(q0.x, q0.y, q0.z, q0.w));
-      mn1 = fminf(mn1, raw(q1.x, q1.y, q1.z, q1.w));
-      mn2 = fminf(mn2, raw(q2.x, q2.y, q2.z, q2.w));
-      mn3 = fminf(mn3, raw(q3.x, q3.y, q3.z, q3.w));
-    }
-    for (; m < P; ++m) {
-      const float4 q = *reinterpret_cast<const float4*>(&sm[m * 4]);
-      mn0 = fminf(mn0, raw(q.x, q.y, q.z, q.w));
-    }
-    float mn = fminf(fminf(mn0, mn1), fminf(mn2, mn3));
-    mn = mn < 0.0f ? 0.0f : mn;
+    const float mn = cad_min_vec<4>(sm, 0, P, pose_apply(pts1 + ((size_t)b * N1 + i) * 3, sRt[g], sRt[g] + 9));
     const float wv = w1[(size_t)b * N1 + i];
     sw_t += wv;
     sdw_t += sqrtf(mn) * wv;
@@ -996,15 +1048,10 @@ __global__ __launch_bounds__(64) void pick_best_kernel(const float* __restrict__
                                                        const float* __restrict__ Rs, const float* __restrict__ ts, int nh, int k,
                                                        float* __restrict__ R, float* __restrict__ t, int* __restrict__ best_out) {
   const int b = blockIdx.x, lane = threadIdx.x;
-  float best = -INFINITY;
-  int bi = 0x7fffffff;
-  for (int i = lane; i < k; i += 64) {
-    const float v = scores[(size_t)b * k + i];
-    if (v > best) { best = v; bi = i; }
-  }
-  wave_argmax_first(best, bi);
-  if (bi == 0x7fffffff) bi = 0;
-  const int h = sel[(size_t)b * k + bi];
+  FirstMax fm;
+  for (int i = lane; i < k; i += 64) fm.take(scores[(size_t)b * k + i], i);
+  fm.wave_merge();
+  const int h = sel[(size_t)b * k + fm.label()];
   if (lane < 9) R[b * 9 + lane] = Rs[((size_t)b * nh + h) * 9 + lane];
   if (lane < 3) t[b * 3 + lane] = ts[((size_t)b * nh + h) * 3 + lane];
   if (lane == 0 && best_out) best_out[b] = h;
@@ -1028,77 +1075,44 @@ __global__ __launch_bounds__(SM_WAVES * 64) void score_hyp_mfma_kernel(const int
                                                                       const float* __restrict__ w1, const float* __restrict__ model,
                                                                       const float* __restrict__ radius, int N1, int P, int Ppad, int nh,
                                                                       int k, float* __restrict__ dw) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];  // [4][Ppad]: -2 y0 | -2 y1 | -2 y2 | 1;  then [Ppad]: |y|^2 (+inf padding)
+  extern __shared__ __attribute__((aligned(16))) float sm[];  // cad_stage_planes
   const int b = blockIdx.y, t = threadIdx.x, lane = t & 63, wave = t >> 6, j = lane & 31, kk = lane >> 5;
-  const float den = radius[b] + 1e-6f;
-  const float* mb = model + (size_t)b * P * 3;
-  for (int i = t; i < Ppad; i += SM_WAVES * 64) {
-    float x = 0.f, y = 0.f, z = 0.f, sq = INFINITY;
-    if (i < P) {
-      x = mb[i * 3] / den; y = mb[i * 3 + 1] / den; z = mb[i * 3 + 2] / den;
-      sq = sqnorm3(x, y, z);
-    }
-    sm[i] = -2.0f * x; sm[Ppad + i] = -2.0f * y; sm[2 * Ppad + i] = -2.0f * z; sm[3 * Ppad + i] = 1.0f;
-    sm[4 * Ppad + i] = sq;
-  }
+  cad_stage_planes(sm, model, radius, b, P, Ppad, t, SM_WAVES * 64);
   const long total = (long)k * N1;
   const long e0 = ((long)(blockIdx.x * SM_WAVES + wave) * SM_CT) * 32 + j;
-  float b1[SM_CT], b2[SM_CT], mn[SM_CT];
+  McItem it[SM_CT];
+  float mn[SM_CT];
 #pragma unroll
   for (int c = 0; c < SM_CT; ++c) {
     const long e = e0 + 32 * c;
-    float x0 = 0.f, x1 = 0.f, x2 = 0.f, sx = 0.f;
+    Posed x = {0.f, 0.f, 0.f, 0.f};
     if (e < total) {
       const int s = (int)(e / N1), i = (int)(e - (long)s * N1);
       const int h = sel[(size_t)b * k + s];
-      const float* R = Rs + ((size_t)b * nh + h) * 9;
-      const float* T = ts + ((size_t)b * nh + h) * 3;
-      const float* p = pts1 + ((size_t)b * N1 + i) * 3;
-      const float d0 = p[0] - T[0], d1 = p[1] - T[1], d2 = p[2] - T[2];
-      x0 = fmaf(d2, R[6], fmaf(d1, R[3], d0 * R[0]));
-      x1 = fmaf(d2, R[7], fmaf(d1, R[4], d0 * R[1]));
-      x2 = fmaf(d2, R[8], fmaf(d1, R[5], d0 * R[2]));
-      sx = sqnorm3(x0, x1, x2);
+      x = pose_apply(pts1 + ((size_t)b * N1 + i) * 3, Rs + ((size_t)b * nh + h) * 9, ts + ((size_t)b * nh + h) * 3);
     }
-    b1[c] = kk ? x1 : x0;
-    b2[c] = kk ? sx : x2;
+    it[c] = McItem(x, kk);
     mn[c] = INFINITY;
   }
   __syncthreads();
-  f32x16 zero;
-#pragma unroll
-  for (int v = 0; v < 16; ++v) zero[v] = 0.f;
-  const float* a1p = sm + kk * Ppad + j;
-  const float* a2p = sm + (2 + kk) * Ppad + j;
-  const float* syp = sm + 4 * Ppad + kk * 4;
+  const f32x16 zero = mc_zero();
+  const McPlanes cad(sm, Ppad, j, kk);
   for (int r = 0; r < Ppad; r += 32) {
-    const float a1 = a1p[r], a2 = a2p[r];
-    const float4 s0 = *reinterpret_cast<const float4*>(syp + r), s1 = *reinterpret_cast<const float4*>(syp + r + 8);
-    const float4 s2 = *reinterpret_cast<const float4*>(syp + r + 16), s3 = *reinterpret_cast<const float4*>(syp + r + 24);
+    const McTile tile = cad.load(r);
     // software pipeline over the column tiles: the two instructions of tile c + 1 are issued before the vector work on tile c, into
     // the other of two accumulator sets (one set: MFMA -> MFMA -> wait -> 26 vector instructions, strictly in series per wave)
-    f32x16 acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1[0], zero, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a2, b2[0], acc, 0, 0, 0);
+    f32x16 acc = mc_pair(tile, it[0], zero);
 #pragma unroll
     for (int c = 0; c < SM_CT; ++c) {
       f32x16 nxt = zero;
-      if (c + 1 < SM_CT) {
-        nxt = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1[c + 1], zero, 0, 0, 0);
-        nxt = __builtin_amdgcn_mfma_f32_32x32x2f32(a2, b2[c + 1], nxt, 0, 0, 0);
-      }
-      // accumulator register v of this lane: CAD row r + 8 (v >> 2) + 4 kk + (v & 3), column j
-      const float m0 = fminf(fminf(acc[0] + s0.x, acc[1] + s0.y), fminf(acc[2] + s0.z, acc[3] + s0.w));
-      const float m1 = fminf(fminf(acc[4] + s1.x, acc[5] + s1.y), fminf(acc[6] + s1.z, acc[7] + s1.w));
-      const float m2 = fminf(fminf(acc[8] + s2.x, acc[9] + s2.y), fminf(acc[10] + s2.z, acc[11] + s2.w));
-      const float m3 = fminf(fminf(acc[12] + s3.x, acc[13] + s3.y), fminf(acc[14] + s3.z, acc[15] + s3.w));
-      mn[c] = fminf(fminf(mn[c], m0), fminf(fminf(m1, m2), m3));
+      if (c + 1 < SM_CT) nxt = mc_pair(tile, it[c + 1], zero);
+      mn[c] = mc_fold(mn[c], acc, tile);
       acc = nxt;
     }
   }
 #pragma unroll
   for (int c = 0; c < SM_CT; ++c) {
-    float m = fminf(mn[c], __shfl_xor(mn[c], 32, 64));
-    m = m < 0.0f ? 0.0f : m;
+    const float m = mc_finish(mn[c]);
     const long e = e0 + 32 * c;
     if (kk == 0 && e < total) {
       const int i = (int)(e % N1);
@@ -1185,11 +1199,10 @@ __global__ __launch_bounds__(256) void fine_assign_kernel(const float* __restric
   const float* cs = csum + b * C;
   const int* l2 = label2 + b * (C - 1);
   const float* p2 = pts2 + b * (C - 1) * 3;
-  const float f1 = label1[w] > 0 ? 1.f : 0.f;
+  const float f1 = sa_flag(label1[w]);
   float sa = 0.f, sx = 0.f, sy = 0.f, sz = 0.f;
   for (int c = 1 + lane; c < C; c += 64) {
-    float v = sa_val<FAST>(a[c], rm, rs, cm[c], cs[c]);
-    v = (v * f1) * (l2[c - 1] > 0 ? 1.f : 0.f);
+    const float v = sa_mask(sa_val<FAST>(a[c], rm, rs, cm[c], cs[c]), f1, sa_flag(l2[c - 1]));
     sa += v;
     sx = fmaf(v, p2[(c - 1) * 3], sx);
     sy = fmaf(v, p2[(c - 1) * 3 + 1], sy);
@@ -1211,12 +1224,8 @@ extern "C" int sam6d_fine_assign(const float* att, int B, int R, int C, const fl
   SAM6D_REQUIRE(att && rmax && rsum && cmax && csum && label1 && label2 && pts2 && pred && weight, "fine_assign: null pointer");
   const long rows = (long)B * (R - 1);
   if (rows == 0) return 0;
-  if (R > 256)
-    hipLaunchKernelGGL(fine_assign_kernel<true>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, att, R, C, rows,
-                       rmax, rsum, cmax, csum, label1, label2, pts2, pred, weight);
-  else
-    hipLaunchKernelGGL(fine_assign_kernel<false>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, att, R, C, rows,
-                       rmax, rsum, cmax, csum, label1, label2, pts2, pred, weight);
+  sa_launch(R > 256, fine_assign_kernel<true>, fine_assign_kernel<false>, dim3((unsigned)((rows + 3) / 4)), (hipStream_t)stream, att, R, C,
+            rows, rmax, rsum, cmax, csum, label1, label2, pts2, pred, weight);
   SAM6D_LAUNCH_CHECK("fine_assign");
 }
 
@@ -1339,7 +1348,7 @@ __global__ __launch_bounds__(256) void procrustes_kernel(const float* __restrict
     double R[9];
     rotation_from_H(H, R);
     for (int i = 0; i < 9; ++i) Rout[b * 9 + i] = (float)R[i];
-    for (int i = 0; i < 3; ++i) tout[b * 3 + i] = (float)(c[3 + i] - (R[i * 3] * c[0] + R[i * 3 + 1] * c[1] + R[i * 3 + 2] * c[2]));
+    for (int i = 0; i < 3; ++i) tout[b * 3 + i] = (float)(c[3 + i] - dot3(&R[i * 3], c));
   }
 }
 
@@ -1359,31 +1368,16 @@ __global__ __launch_bounds__(256) void fine_near_kernel(const float* __restrict_
                                                         const float* __restrict__ t, const float* __restrict__ model,
                                                         const float* __restrict__ radius, const int* __restrict__ label1, int N,
                                                         int P, float thr, float* __restrict__ cnt) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
+  extern __shared__ __attribute__((aligned(16))) float sm[];  // cad_stage_aos
   __shared__ float part[4][64];
   const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const float den = radius[b] + 1e-6f;
-  const float* mb = model + (size_t)b * P * 3;
-  for (int i = tid; i < P; i += 256) {
-    const float x = mb[i * 3] / den, y = mb[i * 3 + 1] / den, z = mb[i * 3 + 2] / den;
-    sm[i * 4] = x; sm[i * 4 + 1] = y; sm[i * 4 + 2] = z; sm[i * 4 + 3] = sqnorm3(x, y, z);
-  }
+  cad_stage_aos(sm, model, radius, b, P, tid, 256);
   __syncthreads();
   const int i = blockIdx.x * 64 + lane;
   float mn = INFINITY;
   if (i < N) {
-    const float* Rb = R + b * 9;
-    const float* p = pts1 + ((size_t)b * N + i) * 3;
-    const float d0 = p[0] - t[b * 3], d1 = p[1] - t[b * 3 + 1], d2 = p[2] - t[b * 3 + 2];
-    const float x0 = fmaf(d2, Rb[6], fmaf(d1, Rb[3], d0 * Rb[0]));
-    const float x1 = fmaf(d2, Rb[7], fmaf(d1, Rb[4], d0 * Rb[1]));
-    const float x2 = fmaf(d2, Rb[8], fmaf(d1, Rb[5], d0 * Rb[2]));
-    const float sx = sqnorm3(x0, x1, x2);
     const int chunk = (P + 3) >> 2, m0 = wave * chunk, m1 = min(P, m0 + chunk);
-    for (int m = m0; m < m1; ++m) {
-      const float4 q = *reinterpret_cast<const float4*>(&sm[m * 4]);
-      mn = fminf(mn, pdist3(x0, x1, x2, sx, q.x, q.y, q.z, q.w));
-    }
+    mn = cad_min_vec<2>(sm, m0, m1, pose_apply(pts1 + ((size_t)b * N + i) * 3, R + b * 9, t + b * 3));
   }
   part[wave][lane] = mn;
   __syncthreads();
@@ -1403,76 +1397,40 @@ __global__ __launch_bounds__(256) void fine_near_kernel(const float* __restrict_
   }
 }
 
-// The same count on the fp32 matrix cores, in the arithmetic of score_hyp_mfma_kernel (two v_mfma_f32_32x32x2_f32 on a zero accumulator
-// give rn(|x|^2 - 2 xy) in the fma order of pdist3, the vector ALU adds |y|^2 and keeps the running minimum: the same bits as
-// fine_near_kernel, whose thread walks the P CAD points with ~8 vector instructions per pair -- 31 us for 32 x 2048 x 1024 pairs).
-// A wave owns FN_CT column tiles of 32 scene points and walks the 32-row tiles of the CAD points.
+// The same count on the fp32 matrix cores, in the steps and the arithmetic of score_hyp_mfma_kernel: the same bits as fine_near_kernel
+// (31 us for 32 x 2048 x 1024 pairs there).  A wave owns FN_CT column tiles of 32 scene points and walks the 32-row tiles of the CAD points.
 #define FN_CT 2
 __global__ __launch_bounds__(256) void fine_near_mfma_kernel(const float* __restrict__ pts1, const float* __restrict__ R,
                                                              const float* __restrict__ t, const float* __restrict__ model,
                                                              const float* __restrict__ radius, const int* __restrict__ label1, int N,
                                                              int P, int Ppad, float thr, float* __restrict__ cnt) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];  // [4][Ppad]: -2 y0 | -2 y1 | -2 y2 | 1;  then [Ppad]: |y|^2 (+inf padding)
+  extern __shared__ __attribute__((aligned(16))) float sm[];  // cad_stage_planes
   __shared__ float red[2][4];
   const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 31, kk = lane >> 5;
-  const float den = radius[b] + 1e-6f;
-  const float* mb = model + (size_t)b * P * 3;
-  for (int i = tid; i < Ppad; i += 256) {
-    float x = 0.f, y = 0.f, z = 0.f, sq = INFINITY;
-    if (i < P) {
-      x = mb[i * 3] / den; y = mb[i * 3 + 1] / den; z = mb[i * 3 + 2] / den;
-      sq = sqnorm3(x, y, z);
-    }
-    sm[i] = -2.0f * x; sm[Ppad + i] = -2.0f * y; sm[2 * Ppad + i] = -2.0f * z; sm[3 * Ppad + i] = 1.0f;
-    sm[4 * Ppad + i] = sq;
-  }
+  cad_stage_planes(sm, model, radius, b, P, Ppad, tid, 256);
   const int e0 = (blockIdx.x * 4 + wave) * FN_CT * 32 + j;
-  const float* Rb = R + b * 9;
-  float b1[FN_CT], b2[FN_CT], mn[FN_CT];
+  McItem it[FN_CT];
+  float mn[FN_CT];
 #pragma unroll
   for (int c = 0; c < FN_CT; ++c) {
     const int i = e0 + 32 * c;
-    float x0 = 0.f, x1 = 0.f, x2 = 0.f, sx = 0.f;
-    if (i < N) {
-      const float* p = pts1 + ((size_t)b * N + i) * 3;
-      const float d0 = p[0] - t[b * 3], d1 = p[1] - t[b * 3 + 1], d2 = p[2] - t[b * 3 + 2];
-      x0 = fmaf(d2, Rb[6], fmaf(d1, Rb[3], d0 * Rb[0]));
-      x1 = fmaf(d2, Rb[7], fmaf(d1, Rb[4], d0 * Rb[1]));
-      x2 = fmaf(d2, Rb[8], fmaf(d1, Rb[5], d0 * Rb[2]));
-      sx = sqnorm3(x0, x1, x2);
-    }
-    b1[c] = kk ? x1 : x0;
-    b2[c] = kk ? sx : x2;
+    Posed x = {0.f, 0.f, 0.f, 0.f};
+    if (i < N) x = pose_apply(pts1 + ((size_t)b * N + i) * 3, R + b * 9, t + b * 3);
+    it[c] = McItem(x, kk);
     mn[c] = INFINITY;
   }
   __syncthreads();
-  f32x16 zero;
-#pragma unroll
-  for (int v = 0; v < 16; ++v) zero[v] = 0.f;
-  const float* a1p = sm + kk * Ppad + j;
-  const float* a2p = sm + (2 + kk) * Ppad + j;
-  const float* syp = sm + 4 * Ppad + kk * 4;
+  const f32x16 zero = mc_zero();
+  const McPlanes cad(sm, Ppad, j, kk);
   for (int r = 0; r < Ppad; r += 32) {
-    const float a1 = a1p[r], a2 = a2p[r];
-    const float4 s0 = *reinterpret_cast<const float4*>(syp + r), s1 = *reinterpret_cast<const float4*>(syp + r + 8);
-    const float4 s2 = *reinterpret_cast<const float4*>(syp + r + 16), s3 = *reinterpret_cast<const float4*>(syp + r + 24);
+    const McTile tile = cad.load(r);
 #pragma unroll
-    for (int c = 0; c < FN_CT; ++c) {
-      f32x16 acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1[c], zero, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a2, b2[c], acc, 0, 0, 0);
-      // accumulator register v of this lane: CAD row r + 8 (v >> 2) + 4 kk + (v & 3), column j
-      const float m0 = fminf(fminf(acc[0] + s0.x, acc[1] + s0.y), fminf(acc[2] + s0.z, acc[3] + s0.w));
-      const float m1 = fminf(fminf(acc[4] + s1.x, acc[5] + s1.y), fminf(acc[6] + s1.z, acc[7] + s1.w));
-      const float m2 = fminf(fminf(acc[8] + s2.x, acc[9] + s2.y), fminf(acc[10] + s2.z, acc[11] + s2.w));
-      const float m3 = fminf(fminf(acc[12] + s3.x, acc[13] + s3.y), fminf(acc[14] + s3.z, acc[15] + s3.w));
-      mn[c] = fminf(fminf(mn[c], m0), fminf(fminf(m1, m2), m3));
-    }
+    for (int c = 0; c < FN_CT; ++c) mn[c] = mc_fold(mn[c], mc_pair(tile, it[c], zero), tile);
   }
   float near = 0.f, mk = 0.f;
 #pragma unroll
   for (int c = 0; c < FN_CT; ++c) {
-    float m = fminf(mn[c], __shfl_xor(mn[c], 32, 64));
-    m = m < 0.0f ? 0.0f : m;  // pdist3's clamp (it commutes with the minimum)
+    const float m = mc_finish(mn[c]);
     const int i = e0 + 32 * c;
     if (kk == 0 && i < N) {
       const float k1 = label1[(size_t)b * N + i] > 0 ? 1.f : 0.f;

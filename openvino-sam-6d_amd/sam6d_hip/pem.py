@@ -1046,10 +1046,16 @@ def feature_similarity(F, B, n, out_proj, temp):
     return att
 
 
+def _assign_buffers(att):
+    """the statistics and labels of a soft assignment of att (B,R,C): rmax / rsum (B,R), cmax / csum (B,C), l1 (B,R-1), l2 (B,C-1)"""
+    B, R, Cn = att.shape
+    return dict(rmax=_empty((B, R), att), rsum=_empty((B, R), att), cmax=_empty((B, Cn), att), csum=_empty((B, Cn), att),
+                l1=_empty((B, R - 1), att, torch.int32), l2=_empty((B, Cn - 1), att, torch.int32))
+
+
 def soft_assign(att):
     B, R, Cn = att.shape
-    st = dict(rmax=_empty((B, R), att), rsum=_empty((B, R), att), cmax=_empty((B, Cn), att), csum=_empty((B, Cn), att),
-              l1=_empty((B, R - 1), att, torch.int32), l2=_empty((B, Cn - 1), att, torch.int32))
+    st = _assign_buffers(att)
     ws = _empty((32 * B * Cn,), att)
     _lib.call("sam6d_soft_assign", _p(att), B, R, Cn, _p(st["rmax"]), _p(st["rsum"]), _p(st["cmax"]), _p(st["csum"]),
               _p(st["l1"]), _p(st["l2"]), _p(ws), ws.numel(), _s())
@@ -1068,8 +1074,7 @@ def compute_coarse_Rt(att, pts1, pts2, model, radius, rand, n_proposal1=6000, n_
     w1 = _empty((B, N1), att)
     if (R * Cn + 3 * R + 3 * Cn) * 4 <= 160 * 1024:
         # the whole soft assignment of a proposal from LDS, one launch (bit-identical to the two calls below)
-        st = dict(rmax=_empty((B, R), att), rsum=_empty((B, R), att), cmax=_empty((B, Cn), att), csum=_empty((B, Cn), att),
-                  l1=_empty((B, R - 1), att, torch.int32), l2=_empty((B, Cn - 1), att, torch.int32))
+        st = _assign_buffers(att)
         _lib.call("sam6d_coarse_soft_assign", _p(att), B, R, Cn, _p(st["rmax"]), _p(st["rsum"]), _p(st["cmax"]), _p(st["csum"]),
                   _p(st["l1"]), _p(st["l2"]), _p(w), _p(w1), _s())
     else:
@@ -1131,6 +1136,18 @@ def weighted_procrustes(src, ref, weights=None, weight_thresh=0.0, eps=1e-5):
     return R, t
 
 
+def _fine_pose_tail(pred, wgt, l1, pts1, model, radius, dis_thres):
+    """The tail of both fine-pose forms (PEM/utils/model_utils.py:331-341): the weighted Procrustes pred -> pts1, then the share of the
+    labelled scene points within dis_thres of the CAD cloud.  -> R (B,3,3), t (B,3) times (radius + 1e-6), score (B,)"""
+    B, N = wgt.shape
+    R, t = weighted_procrustes(pred, pts1, wgt, 0.0)
+    cnt = _empty((B, 2), pred)
+    score = _empty((B,), pred)
+    _lib.call("sam6d_fine_score", _p(pts1), _p(R), _p(t), _p(model), _p(radius), _p(l1), B, N, model.shape[1], float(dis_thres),
+              _p(cnt), _p(score), _s())
+    return R, t, score
+
+
 @on_tensor_device
 def compute_fine_Rt(att, pts1, pts2, model, radius, dis_thres=0.15):
     """PEM/utils/model_utils.py:308-341 + the translation rescale of fine_point_matching.py:78.
@@ -1141,12 +1158,7 @@ def compute_fine_Rt(att, pts1, pts2, model, radius, dis_thres=0.15):
     wgt = _empty((B, R_ - 1), att)
     _lib.call("sam6d_fine_assign", _p(att), B, R_, Cn, _p(st["rmax"]), _p(st["rsum"]), _p(st["cmax"]), _p(st["csum"]),
               _p(st["l1"]), _p(st["l2"]), _p(pts2), _p(pred), _p(wgt), _s())
-    R, t = weighted_procrustes(pred, pts1, wgt, 0.0)
-    cnt = _empty((B, 2), att)
-    score = _empty((B,), att)
-    _lib.call("sam6d_fine_score", _p(pts1), _p(R), _p(t), _p(model), _p(radius), _p(st["l1"]), B, R_ - 1, model.shape[1],
-              float(dis_thres), _p(cnt), _p(score), _s())
-    return R, t, score
+    return _fine_pose_tail(pred, wgt, st["l1"], pts1, model, radius, dis_thres)
 
 
 @on_tensor_device
@@ -1188,11 +1200,7 @@ def compute_fine_Rt_fused(f, B, n, temp, pts1, pts2, model, radius, dis_thres=0.
     """compute_feature_similarity + compute_fine_Rt (PEM/utils/model_utils.py:131-153, 308-341) from the out_proj features."""
     pts2 = pts2.contiguous()
     l1, l2, pred, wgt = fine_match(f, B, n, temp, pts2)
-    R, t = weighted_procrustes(pred, pts1, wgt, 0.0)
-    cnt = _empty((B, 2), pts2)
-    score = _empty((B,), pts2)
-    _lib.call("sam6d_fine_score", _p(pts1), _p(R), _p(t), _p(model), _p(radius), _p(l1), B, n - 1, model.shape[1], float(dis_thres),
-              _p(cnt), _p(score), _s())
+    R, t, score = _fine_pose_tail(pred, wgt, l1, pts1, model, radius, dis_thres)
     if return_aux:
         return R, t, score, dict(l1=l1, l2=l2, pred=pred, weights=wgt)
     return R, t, score

@@ -448,3 +448,39 @@ def direction_error(R, src, ref, w):
     dr = (ref[:, 1] - ref[:, 0]).double()
     ds, dr = ds / ds.norm(dim=-1, keepdim=True), dr / dr.norm(dim=-1, keepdim=True)
     return ((R.double() @ ds[:, :, None])[:, :, 0] - dr).abs().amax(-1)
+
+
+# ------------------------------------------------------------------------------------------------------- fine pose score
+# (N, P, thr): P = 31 / 33 / 97 (the +inf padding of the matrix-core planes to 32 rows, one and several row tiles; the tail of the vector
+# minimum), N = 63 / 65 / 300 (a wave's column tiles and the vector kernel's 64 points on both sides of a workgroup, several workgroups),
+# P = 3264 the last cloud on the matrix cores and P = 3265 the first on the vector ALU
+FINE_SCORE_CASES = [(63, 31, 0.3), (65, 33, 0.3), (300, 97, 0.2), (257, 3264, 0.05), (257, 3265, 0.05)]
+FINE_SCORE_SWITCH = (257, 3264, 0.05)  # the cloud that gets one duplicate point to cross the route switch
+FINE_SCORE_RADIUS = (1.0, 0.5)
+FINE_SCORE_GAP = 1e-5  # every float64 nearest distance stays this far from thr; the fp32 recipe errs by ~1e-7 / (2 d) = 2e-6 at d = 0.05
+
+
+def fine_score64(p1, R, t, model, radius, l1, thr):
+    """PEM/utils/model_utils.py:331-339 in float64 (model / (radius + 1e-6): PEM/model/fine_point_matching.py) -> near (B,), mask (B,)
+    counts, score (B,), gap: the smallest |nearest distance - thr|"""
+    m = model.double() / (radius.double().reshape(-1, 1, 1) + 1e-6)
+    x = (p1.double() - t.double()[:, None, :]) @ R.double()
+    d = torch.cdist(x, m, compute_mode="donot_use_mm_for_euclid_dist").min(2).values
+    mask = l1.double()
+    near, mk = ((d < thr).double() * mask).sum(1), mask.sum(1)
+    return dict(near=near, mask=mk, score=near / (mk + 1e-8) * mask.mean(1), gap=float((d - thr).abs().min()))
+
+
+@functools.lru_cache(maxsize=None)
+def fine_score_case(N, P, thr, B=2):
+    """seeded scene of one sam6d_fine_score case with its float64 counts under "want"; the draws come from one generator in this order"""
+    g = gen(1000 * N + P)
+    p1 = torch.rand(B, N, 3, generator=g) - 0.5
+    model = torch.rand(B, P, 3, generator=g) - 0.5
+    R = torch.linalg.qr(torch.randn(B, 3, 3, generator=g)).Q.contiguous()
+    t = (torch.rand(B, 3, generator=g) - 0.5) * 0.1
+    l1 = (torch.rand(B, N, generator=g) > 0.3).to(torch.int32)
+    radius = torch.tensor(FINE_SCORE_RADIUS)
+    d = dict(p1=p1.contiguous(), model=model.contiguous(), R=R, t=t.contiguous(), l1=l1.contiguous(), radius=radius, thr=thr, B=B, N=N, P=P)
+    d["want"] = fine_score64(p1, R, t, model, radius, l1, thr)
+    return d

@@ -345,3 +345,43 @@ def test_weighted_procrustes_all_weights_cut(dev, N):
     src_d, ref_d, w_d = d["src"].to(dev), d["ref"].to(dev), (d["w"] * 0.25).to(dev)
     Rg, tg = pem.weighted_procrustes(src_d, ref_d, w_d, R.W_THRESH)
     assert torch.equal(Rg.cpu(), torch.eye(3).expand(Rg.shape[0], 3, 3)) and float(tg.abs().max()) == 0.0
+
+
+# ------------------------------------------------------------------------------------------------------- 8. fine pose score
+def _fine_score(dev, d, model=None):
+    """sam6d_fine_score -> cnt (B,2) = (near, mask) counts, score (B,), t (B,3) rescaled, all on the host"""
+    from sam6d_hip import _lib
+    model = d["model"] if model is None else model
+    p1, Rm, model_d, radius, l1 = (x.to(dev).contiguous() for x in (d["p1"], d["R"], model, d["radius"], d["l1"]))
+    t = d["t"].to(dev).clone()
+    cnt = torch.full((d["B"], 2), float("nan"), device=dev)
+    score = torch.full((d["B"],), float("nan"), device=dev)
+    _lib.call("sam6d_fine_score", p1.data_ptr(), Rm.data_ptr(), t.data_ptr(), model_d.data_ptr(), radius.data_ptr(), l1.data_ptr(), d["B"], d["N"],
+              model.shape[1], float(d["thr"]), cnt.data_ptr(), score.data_ptr(), _stream())
+    torch.cuda.synchronize()
+    return cnt.cpu(), score.cpu(), t.cpu()
+
+
+@pytest.mark.parametrize("case", R.FINE_SCORE_CASES, ids=R.sa_id)
+def test_fine_score_counts_vs_float64(dev, case):
+    """both CAD layouts of sam6d_fine_score at their edges: P = 31 / 33 / 97 (padding to 32 rows, the vector minimum's tail), N = 63 / 65 /
+    300, P = 3264 (the last cloud on the matrix cores) and 3265 (the first on the vector ALU).  Every float64 nearest distance keeps
+    FINE_SCORE_GAP from the threshold (tests/test_pose_shapes_host.py), ten times the fp32 recipe's error: the counts are exact."""
+    d = R.fine_score_case(*case)
+    w = d["want"]
+    cnt, score, t = _fine_score(dev, d)
+    print("%s: near %s (float64 %s), mask %s (float64 %s)" % (case, cnt[:, 0].tolist(), w["near"].tolist(), cnt[:, 1].tolist(), w["mask"].tolist()))
+    assert torch.equal(cnt[:, 0].double(), w["near"]) and torch.equal(cnt[:, 1].double(), w["mask"])
+    _rel(score, w["score"], 4 * 2.0 ** -24, "fine score %s" % (case,))  # two divisions and a product of exact counts
+    _abs(t, d["t"].double() * (d["radius"].double()[:, None] + 1e-6), 2.0 ** -24, "rescaled t %s" % (case,))  # |t| <= 0.05 * 1.000001: within an ulp of 0.0625
+
+
+def test_fine_score_route_switch_keeps_the_bits(dev):
+    """the P = 3264 cloud (matrix cores) and the same cloud plus a copy of its first point (P = 3265: vector ALU): a duplicate cannot
+    change a minimum, so counts and score are bit-equal across the route switch"""
+    d = R.fine_score_case(*R.FINE_SCORE_SWITCH)
+    longer = torch.cat([d["model"], d["model"][:, :1]], 1).contiguous()
+    assert longer.shape[1] == 3265
+    a, b = _fine_score(dev, d), _fine_score(dev, d, longer)
+    assert torch.equal(_bits(a[0]), _bits(b[0])) and torch.equal(_bits(a[1]), _bits(b[1])) and torch.equal(_bits(a[2]), _bits(b[2]))
+    assert torch.equal(a[0][:, 0].double(), d["want"]["near"])

@@ -240,3 +240,25 @@ def test_procrustes_all_weights_cut(N):
     assert float(w.max()) < R.W_THRESH - R.W_CLEAR
     Rr, t, H = R.procrustes64(d["src"], d["ref"], w, R.W_THRESH)
     assert float(H.abs().max()) == 0.0 and float(t.abs().max()) == 0.0, "no weight survives: H = 0 and both centroids are 0"
+
+
+# ------------------------------------------------------------------------------------------------------- fine pose score
+@pytest.mark.parametrize("case", R.FINE_SCORE_CASES, ids=R.sa_id)
+def test_fine_score_inputs_clear_the_threshold(case):
+    """what the exact count comparison of the GPU test rests on: no float64 nearest distance within FINE_SCORE_GAP of the threshold, and
+    in every proposal some masked points are near and some are not"""
+    N, P, thr = case
+    d = R.fine_score_case(N, P, thr)
+    w = d["want"]
+    print("%s: smallest |distance - thr| %.2e; near %s of mask %s" % (case, w["gap"], w["near"].tolist(), w["mask"].tolist()))
+    assert w["gap"] >= R.FINE_SCORE_GAP
+    assert ((w["near"] > 0) & (w["near"] < w["mask"])).all()
+    assert len(R.FINE_SCORE_RADIUS) == d["B"] and d["p1"].shape == (d["B"], N, 3) and d["model"].shape == (d["B"], P, 3)
+    Rm = d["R"].double()
+    assert float((Rm @ Rm.transpose(1, 2) - torch.eye(3, dtype=torch.float64)).abs().max()) <= 1e-5, "R is orthogonal: distances are kept"
+
+
+def test_fine_score_route_switch_shape():
+    """Ppad * 20 bytes of planes within 64 KB - 64 B: P = 3264 is the last matrix-core cloud, one more point the first vector one"""
+    pad = lambda P: (P + 31) & ~31
+    assert R.FINE_SCORE_SWITCH[1] == 3264 and pad(3264) * 20 <= 65536 - 64 < pad(3265) * 20
