@@ -663,6 +663,44 @@ int sam6d_amg_mask_stats(const float* low, const unsigned char* live, int M, int
 int sam6d_amg_unpack_masks(const unsigned* bits, const long long* idx, long n_src, int K, int out_h, int out_w, int x0, int y0,
                            int H, int W, int as_f32, void* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * SAM's mask decoder for point prompts (ISM/segment_anything/modeling/mask_decoder.py:112-149, its TwoWayTransformer
+ * ISM/segment_anything/modeling/transformer.py:62-106): what lies between the dense projections over the P x 4096 image rows, which are
+ * sam6d_gemm_nt / _w16 launches.  Specialised for transformer_dim 256, 8 heads, 7 tokens per prompt and a 64 x 64 grid: every entry
+ * takes (dim, heads, tokens, grid_h, grid_w) and refuses anything else without a launch.  fp32 throughout.  P <= 65535.
+ * (New entries only, so SAM6D_ABI_VERSION stays.)
+ * ---------------------------------------------------------------------------------------------------------- */
+
+/* The image -> token half of a TwoWayAttentionBlock (ISM/segment_anything/modeling/transformer.py:175-180, Attention.forward :218-240)
+ * with out_proj folded into the values: q (row n of prompt p at q + p sq + n ldq, 128 floats; sq = 0: one table for every prompt) is
+ * q_proj(keys + key_pe); ktok (P,7,128) = k_proj(queries + query_pe); fold (P,56,256), row 8 j + h = out_proj.weight[:, 16h:16h+16] .
+ * v_proj(queries)[j, 16h:16h+16]; bias (256) = out_proj.bias.  Per image row: 8 x 7 scores / 4, softmax over the 7 tokens of each head,
+ * the 56 -> 256 contraction, + bias + keys (row n of prompt p at keys + p skeys + 256 n; skeys = 0: the same image rows for every
+ * prompt, as in layer 0), norm4 = LayerNorm(256, eps) with gamma / beta -> out (P,4096,256).  Neither the probabilities nor a
+ * 128-wide attention output reach memory.  q, out, gamma, beta 16-byte aligned, ldq and sq multiples of 4. */
+int sam6d_samdec_image_to_token(const float* q, long ldq, long sq, const float* ktok, const float* fold, const float* bias,
+                                const float* keys, long skeys, const float* gamma, const float* beta, float eps, float* out, int P,
+                                int dim, int heads, int tokens, int grid_h, int grid_w, void* stream);
+/* The token -> image attention of a TwoWayAttentionBlock and the final one (ISM/segment_anything/modeling/transformer.py:163-167,
+ * :100-102, Attention.forward :225-237) up to, not including, out_proj: q (P,7,128) = q_proj(queries + query_pe); k, v: row n of prompt p
+ * at k + p skv + n ld and v + p skv + n ld (128 floats each; skv = 0: per-image tables shared by every prompt) -> out (P,7,128) =
+ * softmax(q_h k_h^T / 4) v_h for the 8 heads of 16 channels, in _recombine_heads order.  The 4096 keys of a prompt are split over 32
+ * workgroups that leave partial (max, sum, weighted v) in ws (sam6d_samdec_token_to_image_workspace_bytes(P) bytes); a second launch
+ * merges them.  The scores do not reach memory.  k 16-byte aligned, ld and skv multiples of 4. */
+size_t sam6d_samdec_token_to_image_workspace_bytes(int P);
+int sam6d_samdec_token_to_image(const float* q, const float* k, const float* v, long ld, long skv, float* out, int P, int dim, int heads,
+                                int tokens, int grid_h, int grid_w, void* ws, size_t ws_bytes, void* stream);
+/* output_upscaling after its first ConvTranspose2d, and the mask product (ISM/segment_anything/modeling/mask_decoder.py:53-59, :137-144;
+ * LayerNorm2d ISM/segment_anything/modeling/common.py:38-43) for multimask_output=True: ct1 (row n of prompt p at ct1 + p sp + n ld, 256
+ * floats = sub-pixel 2 kh + kw times 64 channels, bias included) is ConvTranspose2d(256, 64, 2, 2) of the keys as a GEMM; per
+ * sub-pixel LayerNorm2d over the 64 channels (biased variance, eps) and erf GELU, ConvTranspose2d(64, 32, 2, 2) with w2 (128,64), row
+ * 32 (2 kh + kw) + o = weight[:, o, kh, kw], and b2 (128) = bias tiled, GELU, and the dot products with hyper (P,3,32) = hyper_in[:, 1:4]
+ * -> low (P,3,256,256).  Image token (y, x) writes the 4 x 4 block at (4y, 4x).  Neither upscaled tensor reaches memory, and mask
+ * token 0's map is not computed.  ct1 16-byte aligned, ld and sp multiples of 4. */
+int sam6d_samdec_upscale_masks(const float* ct1, long ld, long sp, const float* ln_gamma, const float* ln_beta, float eps, const float* w2,
+                               const float* b2, const float* hyper, float* low, int P, int dim, int heads, int tokens, int grid_h,
+                               int grid_w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,8 @@
 tail after the mask decoder on sam6d_hip.amg (one fused launch per point batch instead of the 1024 x 1024 logits, the RLE round trip
 through the host and torchvision's NMS).
 
-The SAM network is not part of this project.  It is reached only through the `sam` object the caller passes in:
+With hip_decoder (SAM6D_HIP_SAMDEC=1; off by default) prompt encoder and mask decoder run on sam6d_hip.samdec as well.  Otherwise the SAM
+network is reached only through the `sam` object the caller passes in:
     sam.image_encoder (.img_size; called on the preprocessed image), sam.prompt_encoder (called with points / boxes / masks keywords;
     .get_dense_pe()), sam.mask_decoder (called with the reference's keywords, returns (low_res_masks, iou_predictions)),
     sam.preprocess, sam.mask_threshold, sam.image_format, sam.device.
@@ -11,6 +12,7 @@ through `encode_image(sam, image) -> (features, input_size)`; without one, segme
 image arrives.  Nothing here imports segment_anything, torchvision, cv2 or pycocotools at module import.
 """
 import logging
+import os
 import os.path as osp
 
 import numpy as np
@@ -37,13 +39,33 @@ def load_sam(model_type, checkpoint_dir):
 
 class Predictor:
     """SamPredictor's part in the mask generator (ISM/segment_anything/predictor.py:34-90, 168-235): holds the model and the features of
-    the current crop, and runs prompt encoder + mask decoder for a batch of points up to `low_res_masks`."""
+    the current crop, and runs prompt encoder + mask decoder for a batch of points up to `low_res_masks`.  hip_decoder: those two run
+    on the library (sam6d_hip.samdec: the decoder's weights are packed here, the per-image tables in set_image) instead of being
+    called as modules."""
 
-    def __init__(self, sam_model, encode_image=None):
+    def __init__(self, sam_model, encode_image=None, hip_decoder=False):
         self.model = sam_model
         self.encode_image = encode_image
         self._sam_predictor = None
+        self.hip_decoder = bool(hip_decoder)
+        self._samdec = self._decoder_weights = None
+        if self.hip_decoder:
+            self._pack_decoder()
         self.reset_image()
+
+    def _pack_decoder(self):
+        """The library route of prompt encoder + mask decoder (sam6d_hip.samdec): refuses, never falls back."""
+        from sam6d_hip import samdec
+        pe, md = self.model.prompt_encoder, self.model.mask_decoder
+        if not (hasattr(pe, "state_dict") and hasattr(md, "state_dict")):
+            raise TypeError("hip_decoder: sam.prompt_encoder and sam.mask_decoder must be modules with the reference's state dicts "
+                            "(got %s and %s)" % (type(pe).__name__, type(md).__name__))
+        samdec.check_state_dicts(pe.state_dict(), md.state_dict(), md.transformer.num_heads, pe.image_embedding_size)
+        if torch.device(self.device).type != "cuda":
+            raise RuntimeError("hip_decoder: the model is on %s; the library route needs it on a HIP device (hip_decoder=False or "
+                               "SAM6D_HIP_SAMDEC=0 keeps the eager decoder)" % (self.device,))
+        self._samdec = samdec
+        self._decoder_weights = samdec.SamDecoderWeights(pe, md, self.device)
 
     @property
     def device(self):
@@ -52,6 +74,7 @@ class Predictor:
     def reset_image(self):
         self.is_image_set = False
         self.features = None
+        self.tables = None
         self.original_size = None
         self.input_size = None
 
@@ -80,6 +103,8 @@ class Predictor:
         want = amg.preprocess_shape(self.original_size[0], self.original_size[1], self.model.image_encoder.img_size)
         if self.input_size != want:
             raise ValueError("set_image: the encoder's input is %s, a %s image resizes to %s" % (self.input_size, self.original_size, want))
+        if self.hip_decoder:
+            self.tables = self._samdec.image_tables(self.features, self._decoder_weights)
         self.is_image_set = True
 
     @torch.no_grad()
@@ -91,6 +116,8 @@ class Predictor:
             raise RuntimeError("An image must be set with .set_image(...) before mask prediction.")
         coords = amg.apply_coords(points, self.original_size, self.model.image_encoder.img_size)
         in_points = torch.as_tensor(coords, device=self.device)
+        if self.hip_decoder:
+            return self._samdec.predict_low(in_points, self.tables, self._decoder_weights)
         in_labels = torch.ones(in_points.shape[0], dtype=torch.int, device=in_points.device)
         sparse, dense = self.model.prompt_encoder(points=(in_points[:, None, :], in_labels[:, None]), boxes=None, masks=None)
         return self.model.mask_decoder(image_embeddings=self.features, image_pe=self.model.prompt_encoder.get_dense_pe(),
@@ -109,6 +136,7 @@ class CustomSamAutomaticMaskGenerator:
         segmentor_width_size=None,
         pred_iou_thresh: float = 0.88,
         encode_image=None,
+        hip_decoder=None,
     ):
         # SamAutomaticMaskGenerator's own defaults for what the reference's subclass does not pass on
         self.points_per_side = 32
@@ -118,7 +146,9 @@ class CustomSamAutomaticMaskGenerator:
         self.crop_n_points_downscale_factor = 1
         self.output_mode = "binary_mask"
         self.point_grids = amg.layer_point_grids(self.points_per_side, self.crop_n_layers, self.crop_n_points_downscale_factor)
-        self.predictor = Predictor(sam, encode_image)
+        if hip_decoder is None:  # the library route of prompt encoder + mask decoder is opt-in
+            hip_decoder = os.environ.get("SAM6D_HIP_SAMDEC", "0") == "1"
+        self.predictor = Predictor(sam, encode_image, hip_decoder)
         self.points_per_batch = points_per_batch
         self.pred_iou_thresh = pred_iou_thresh
         self.stability_score_thresh = stability_score_thresh
