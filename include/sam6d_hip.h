@@ -96,7 +96,10 @@ int sam6d_gather_rows_lead(const float* feats, const int* idx, int B, int N, int
  * replaces nn.Linear / 1x1-conv call sites (PEM/model/transformer.py:127-129,186-188,390-393,548-550;
  * PEM/model/coarse_point_matching.py:35-38) and the similarity contraction (PEM/utils/model_utils.py:144-150).
  * A (M,K) lda; W (N,K) ldw; C (M,N) ldc; residual (M,N) ldr or NULL; bias/colscale (N) or NULL; act 0 none / 1 ReLU /
- * 2 exact erf GELU (nn.GELU of the ViT MLP, PEM/model/feature_extraction.py:21-35), + 16 marks a geometric operand (the proj_p / Chebyshev folds of the RPE query) that keeps the fp16 x3 split in matmul mode 2;
+ * 2 exact erf GELU (nn.GELU of the ViT MLP, PEM/model/feature_extraction.py:21-35), + 16 marks a geometric operand (the proj_p / Chebyshev folds of the RPE query) that keeps the fp16 x3 split in matmul mode 2,
+ * + 32 asks for the whole-tile kernel where M and N are multiples of 128 and K of 32, with pre-split weights in matmul modes 1 and 2 (mode 0
+ * ignores it): 128 x 128 tiles from 256 of them on (instead of 1024) and the unchecked whole-tile kernel also with act 2 (SAM's image encoder, 4096 rows per image,
+ * ISM/segment_anything/modeling/image_encoder.py:166-182; no effect on other shapes);
  * `batch` independent problems with strides sA/sW/sC/sR (floats).  divisor = 1 disables the division. */
 int sam6d_gemm_nt(const float* A, const float* W, const float* bias, const float* colscale, const float* residual,
                   float* C, int M, int N, int K, long lda, long ldw, long ldc, long ldr, int batch, long sA, long sW,
@@ -700,6 +703,41 @@ int sam6d_samdec_token_to_image(const float* q, const float* k, const float* v, 
 int sam6d_samdec_upscale_masks(const float* ct1, long ld, long sp, const float* ln_gamma, const float* ln_beta, float eps, const float* w2,
                                const float* b2, const float* hyper, float* low, int P, int dim, int heads, int tokens, int grid_h,
                                int grid_w, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * SAM's ViT-H image encoder (ISM/segment_anything/modeling/image_encoder.py:17-116 ImageEncoderViT): what lies around the dense
+ * projections, which are sam6d_gemm_nt / _w16 launches.  Specialised for a 1024 x 1024 image in 16 x 16 patches (a 64 x 64 token grid),
+ * width 1280 in heads of 80, 14 x 14 windows and a neck to 256 channels; `heads` is an argument (the rows are 3 * 80 * heads wide) so
+ * that a kernel can be run on a slice of the heads.  fp16 x3 split MFMA products with power-of-two operand scales, fp32 softmax, in
+ * matmul modes 0 and 1 alike.  B <= 65535.  (New entries only, so SAM6D_ABI_VERSION stays.)
+ * ---------------------------------------------------------------------------------------------------------- */
+
+/* PatchEmbed's Conv2d(3, 1280, 16, stride 16) as GEMM rows (image_encoder.py:387-395): img (B,3,1024,1024) -> A (B*4096, 768), row
+ * 64 py + px = the patch's values in the weight's (c, kh, kw) order.  There is no cls row; pos_embed (image_encoder.py:108-109) is the
+ * patch GEMM's residual. */
+int sam6d_sam_patch_rows(const float* img, float* A, int B, void* stream);
+/* nn.LayerNorm(1280, eps) of Block.norm1 / norm2 (image_encoder.py:151, 161, 168, 180); arguments as sam6d_vit_layernorm768. */
+int sam6d_sam_layernorm1280(const float* x, const float* gamma, const float* beta, float* y, int nimg, int rows, long ldx, long sx,
+                            long ldy, long sy, float eps, void* stream);
+/* Attention.forward of a windowed Block between its qkv and proj Linears, with the window partition around it
+ * (image_encoder.py:170-177, 224-237, window_partition :243-264, window_unpartition :267-289, add_decomposed_rel_pos :325-361):
+ * qkv (B*4096, 3*80*heads) = [q | k | v] in image row order, head h at columns 80h .. 80h+79 of each part -> out (B*4096, 80*heads).
+ * The grid is padded to 70 x 70 = 5 x 5 windows of 14 x 14 by index arithmetic.  A padded position is a key like any other: the
+ * reference pads after norm1, so its token is zero and its k and v are the bias of the qkv Linear, pad_qkv (3*80*heads); it enters
+ * every softmax of its window with its own relative-position terms, and is never a query.  Score of (query, key) in a window:
+ * (q . k) / sqrt(80) + q . rel_h[qh - kh + 13] + q . rel_w[qw - kw + 13], the last two with the unscaled q; rel_h, rel_w (27, 80).
+ * Neither a (B*25*196, ...) tensor nor the probabilities reach memory.  All pointers 16-byte aligned. */
+int sam6d_sam_window_attention(const float* qkv, const float* pad_qkv, const float* rel_h, const float* rel_w, float* out, int B,
+                               int heads, void* stream);
+/* The same for a global Block (window_size 0; image_encoder.py:224-237, :325-361): 4096 queries x 4096 keys per (image, head), tables
+ * rel_h, rel_w (127, 80) and offset 63; online softmax over tiles of 64 keys, neither scores nor probabilities reach memory.  The k
+ * and v tiles are cut into fp16 halves by every workgroup that reads them: no workspace. */
+int sam6d_sam_global_attention(const float* qkv, const float* rel_h, const float* rel_w, float* out, int B, int heads, void* stream);
+/* The neck's Conv2d(256, 256, 3, padding 1, no bias) as a gather for one GEMM (image_encoder.py:96-102): x (B*4096, 256), the
+ * channel-last 64 x 64 map -> rows (B*4096, 2304), columns 256 (3 ky + kx) + c of row (y, x) = x at (y + ky - 1, x + kx - 1), zeros
+ * outside the grid.  The 1 x 1 convolution is a GEMM, LayerNorm2d (common.py:38-43) is sam6d_layernorm256 on channel-last rows (the
+ * same biased variance) and the (B, 256, 64, 64) output is a sam6d_transpose.  B <= 4096. */
+int sam6d_sam_neck_gather(const float* x, float* rows, int B, void* stream);
 
 #ifdef __cplusplus
 }

@@ -216,8 +216,9 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const float* __restrict__ 
 // weight-load time (sam6d_split_f16) -- so staging it is a copy: the per-k-step VALU split of the weight tile (half of the
 // kernel's vector work at K = 256) disappears, and so does its range check (the pack scale puts max |W| into [2^13, 2^14)).
 // FAST: whole tiles (M % BM == 0 per batch entry, N % BN == 0, K % 32 == 0), 16-byte aligned operands, three products, the wide
-// epilogue without divisor / column scale / activation -- every guard of the general form is then a compile-time constant.
-template <int BM, int BN, bool WS, bool FAST = false>
+// epilogue without divisor / column scale and with the compile-time activation FACT (0, or 2 = erf GELU for callers that ask for whole
+// tiles with act + 32) -- every guard of the general form is then a compile-time constant.
+template <int BM, int BN, bool WS, bool FAST = false, int FACT = 0>
 __global__ __launch_bounds__(256, FAST ? 3 : 2) void gemm_nt_h3_kernel(const float* __restrict__ A, const float* __restrict__ W,
                                                          const float* __restrict__ bias, const float* __restrict__ colscale,
                                                          const float* __restrict__ residual, float* __restrict__ C, int M,
@@ -231,7 +232,7 @@ __global__ __launch_bounds__(256, FAST ? 3 : 2) void gemm_nt_h3_kernel(const flo
   __shared__ __attribute__((aligned(16))) _Float16 smem[L::HALVES];  // also the epilogue's transpose slabs
   const SpPlanes pl{smem + L::AH, smem + L::AL, smem + L::BH, smem + L::BL};
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int wide = FAST ? 1 : wide_, half = FAST ? 0 : half_, act = FAST ? 0 : act_;
+  const int wide = FAST ? 1 : wide_, half = FAST ? 0 : half_, act = FAST ? FACT : act_;
   const float divisor = FAST ? 1.0f : divisor_;
   if (FAST) colscale = nullptr;
   int zz, tm_, tn_;
@@ -523,8 +524,9 @@ static int gemm_pick(GemmRoute& r, const float* A, const float* W, const float* 
                 K, batch, b2.n2);
   SAM6D_REQUIRE(lda >= K && ldw >= K && ldc >= N, "gemm_nt: leading dimension smaller than the row length");
   const int keep_split = act & 16;  // geometric operand: stays at fp16 x3 in matmul mode 2 (sam6d_hip.h)
-  act &= ~16;
-  SAM6D_REQUIRE(act == 0 || act == 1 || act == 2, "gemm_nt: act must be 0 (none), 1 (ReLU) or 2 (erf GELU), optionally + 16");
+  const int whole = act & 32;       // the caller's rows are whole 128 x 128 tiles and it asks for the whole-tile kernel (sam6d_hip.h)
+  act &= ~48;
+  SAM6D_REQUIRE(act == 0 || act == 1 || act == 2, "gemm_nt: act must be 0 (none), 1 (ReLU) or 2 (erf GELU), optionally + 16 and + 32");
   SAM6D_REQUIRE((long)batch * b2.n2 <= 65535, "gemm_nt: batch (x batch2) must be <= 65535");
   r = GemmRoute{};
   r.empty = (M == 0 || N == 0 || batch == 0);
@@ -533,6 +535,12 @@ static int gemm_pick(GemmRoute& r, const float* A, const float* W, const float* 
   const long blocks128 = (long)cdiv(M, 128) * cdiv(N, 128) * r.nz;
   // big tiles when they fill the chip (>= 4 workgroups per CU) and do not mostly pad (M = 197 would waste 42 % of a 2 x 128 split)
   r.big = blocks128 >= 1024 && (M > 256 || M % 128 == 0);
+  // act + 32, on the pre-split split-precision route only: whole tiles take the large tile from one per CU on.  SAM's image encoder at
+  // one image (4096 rows, 320 ... 1280 tiles per GEMM), both settings alternated in one process: 27.1 against 33.7 ms per image in
+  // matmul mode 1; with the exact kernel of mode 0 the large tile was the slower one (59.6 against 54.5 ms), so mode 0 ignores the
+  // request ("f8 measured").  No other caller passes it, so their routes are what they were.
+  const bool split = sam6d_get_matmul_mode() >= 1 && K >= 32;
+  if (whole && split && Wh && Wl && M % 128 == 0 && N % 128 == 0 && K % 32 == 0 && blocks128 >= 256) r.big = true;
   // (64 x 256 tiles -- the whole output row in one workgroup, every A row read and split once -- were measured on the fine in_proj,
   // M = 131 136, N = K = 256 with pre-split weights: 128 us against 115 us for 128 x 128 tiles; the epilogue keeps its two-pass form)
   const int bm = r.big ? 128 : 64, bn = r.big ? 128 : 64;
@@ -544,7 +552,7 @@ static int gemm_pick(GemmRoute& r, const float* A, const float* W, const float* 
   r.order = fold ? SAM6D_GEMM_ROUTE_FOLD : colgroup ? SAM6D_GEMM_ROUTE_COLGROUP : SAM6D_GEMM_ROUTE_PLAIN;
   r.tiles = fold ? (long)cdiv(r.nz, 8) * 8 * r.tm * r.tn : colgroup ? (long)cdiv(r.tm, 8) * 8 * r.tn : (long)r.tm * r.tn;
   SAM6D_REQUIRE(r.tiles < 2147483647L, "gemm_nt: too many tiles for one launch");
-  if (sam6d_get_matmul_mode() >= 1 && K >= 32) {
+  if (split) {
     r.half = sam6d_half_for(0) && !keep_split;
     // 16-byte epilogue accesses need 4-float alignment of every row start and of the per-column vectors
     r.wide = (N & 3) == 0 && (ldc & 3) == 0 && (sC & 3) == 0 && (b2.sC2 & 3) == 0 && (((size_t)C) & 15) == 0 &&
@@ -554,7 +562,7 @@ static int gemm_pick(GemmRoute& r, const float* A, const float* W, const float* 
       r.kernel = SAM6D_GEMM_ROUTE_H3_W16;
       r.fast = r.big && r.wide && !r.half && (M % 128) == 0 && (N % 128) == 0 && (K % 32) == 0 && (lda & 3) == 0 && (ldw & 3) == 0 &&
                ((((size_t)A | (size_t)W) & 15) == 0) && ((((size_t)Wh | (size_t)Wl) & 7) == 0) && (sA & 3) == 0 && (b2.sA2 & 3) == 0 &&
-               (sW & 3) == 0 && (b2.sW2 & 3) == 0 && divisor == 1.0f && !colscale && act == 0;
+               (sW & 3) == 0 && (b2.sW2 & 3) == 0 && divisor == 1.0f && !colscale && (act == 0 || (whole && act == 2));
     } else {
       r.kernel = SAM6D_GEMM_ROUTE_H3;
     }
@@ -573,7 +581,7 @@ static int gemm_launch(const float* A, const float* W, const float* bias, const 
                            Wh, Wl);
   if (rc != 0) return rc;
   if (r.empty) return 0;
-  act &= ~16;
+  act &= ~48;
   const bool fold = r.order == SAM6D_GEMM_ROUTE_FOLD;
   dim3 grid((unsigned)r.tiles, 1, fold ? 1 : r.nz);
   b2.fold_nz = fold ? r.nz : 0;
@@ -586,7 +594,8 @@ static int gemm_launch(const float* A, const float* W, const float* bias, const 
   hipLaunchKernelGGL(KERNEL, grid, dim3(256), 0, st, A, W, bias, colscale, residual, C, M, N, K, lda, ldw, ldc, ldr, sA, sW, \
                      sC, sR, divisor, act, b2, ##__VA_ARGS__)
   if (r.kernel == SAM6D_GEMM_ROUTE_H3_W16) {
-    if (r.fast) GEMM_LAUNCH((gemm_nt_h3_kernel<128, 128, true, true>), wide, half, wh, wl, wu);
+    if (r.fast && act == 2) GEMM_LAUNCH((gemm_nt_h3_kernel<128, 128, true, true, 2>), wide, half, wh, wl, wu);
+    else if (r.fast) GEMM_LAUNCH((gemm_nt_h3_kernel<128, 128, true, true>), wide, half, wh, wl, wu);
     else if (r.big) GEMM_LAUNCH((gemm_nt_h3_kernel<128, 128, true>), wide, half, wh, wl, wu);
     else GEMM_LAUNCH((gemm_nt_h3_kernel<64, 64, true>), wide, half, wh, wl, wu);
   } else if (r.kernel == SAM6D_GEMM_ROUTE_H3) {

@@ -28,15 +28,15 @@
 #define VIT_GRID 14
 #define VIT_PATCHES 196
 
-// ---- patch rows of an encoder of width C with P x P patches: workgroup (patch p, image b); p == NP writes the image's cls row of X
-// instead ---------------------------------------------------------------------------------------------------------------------------
-template <int C, int P, int KPAD>
+// ---- patch rows of an encoder of width C with P x P patches of an IMG x IMG image: workgroup (patch p, image b); with CLS, p == NP
+// writes the image's cls row of X instead (SAM's encoder has no cls token: CLS = false, cls / pos / X unused) -----------------------
+template <int C, int P, int KPAD, int IMG = VIT_IMG, bool CLS = true>
 __global__ __launch_bounds__(256) void patch_rows_kernel(const float* __restrict__ img, const float* __restrict__ cls,
                                                          const float* __restrict__ pos, float* __restrict__ A, float* __restrict__ X) {
-  constexpr int GRID = VIT_IMG / P, NP = GRID * GRID, K = 3 * P * P;
-  static_assert(C % 256 == 0 && VIT_IMG % P == 0 && KPAD >= K, "patch_rows_kernel: bad instantiation");
+  constexpr int GRID = IMG / P, NP = GRID * GRID, K = 3 * P * P;
+  static_assert(C % 256 == 0 && IMG % P == 0 && KPAD >= K, "patch_rows_kernel: bad instantiation");
   const int p = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
-  if (p == NP) {
+  if (CLS && p == NP) {
     float* dst = X + (size_t)b * (NP + 1) * C;
 #pragma unroll
     for (int u = 0; u < C / 256; ++u) dst[t + 256 * u] = cls[t + 256 * u] + pos[t + 256 * u];
@@ -48,7 +48,7 @@ __global__ __launch_bounds__(256) void patch_rows_kernel(const float* __restrict
     float v = 0.f;
     if (col < K) {
       const int c = col / (P * P), k = col % (P * P), kh = k / P, kw = k % P;
-      v = img[(((size_t)b * 3 + c) * VIT_IMG + py * P + kh) * VIT_IMG + px * P + kw];
+      v = img[(((size_t)b * 3 + c) * IMG + py * P + kh) * IMG + px * P + kw];
     }
     dst[col] = v;
   }
@@ -132,6 +132,16 @@ static int rows_layernorm(const char* name, const float* x, const float* gamma, 
   SAM6D_LAUNCH_CHECK(name);
 }
 
+// SAM ViT-H: 1024 x 1024 image, 64 x 64 patches of 16 x 16, no cls row (pos_embed is the patch GEMM's residual)
+extern "C" int sam6d_sam_patch_rows(const float* img, float* A, int B, void* stream) {
+  SAM6D_REQUIRE(img && A && B >= 0, "sam_patch_rows: null pointer");
+  SAM6D_REQUIRE(B <= 65535, "sam_patch_rows: B <= 65535");
+  if (B == 0) return 0;
+  hipLaunchKernelGGL((patch_rows_kernel<1280, 16, 768, 1024, false>), dim3(4096, B), dim3(256), 0, (hipStream_t)stream, img,
+                     (const float*)nullptr, (const float*)nullptr, A, (float*)nullptr);
+  SAM6D_LAUNCH_CHECK("sam_patch_rows");
+}
+
 extern "C" int sam6d_vit_layernorm768(const float* x, const float* gamma, const float* beta, float* y, int nimg, int rows, long ldx,
                                       long sx, long ldy, long sy, float eps, void* stream) {
   return rows_layernorm<768>("vit_layernorm768", x, gamma, beta, y, nimg, rows, ldx, sx, ldy, sy, eps, stream);
@@ -139,6 +149,11 @@ extern "C" int sam6d_vit_layernorm768(const float* x, const float* gamma, const 
 extern "C" int sam6d_dino_layernorm1024(const float* x, const float* gamma, const float* beta, float* y, int nimg, int rows, long ldx,
                                         long sx, long ldy, long sy, float eps, void* stream) {
   return rows_layernorm<1024>("dino_layernorm1024", x, gamma, beta, y, nimg, rows, ldx, sx, ldy, sy, eps, stream);
+}
+
+extern "C" int sam6d_sam_layernorm1280(const float* x, const float* gamma, const float* beta, float* y, int nimg, int rows, long ldx,
+                                       long sx, long ldy, long sy, float eps, void* stream) {
+  return rows_layernorm<1280>("sam_layernorm1280", x, gamma, beta, y, nimg, rows, ldx, sx, ldy, sy, eps, stream);
 }
 
 // ---- output_upscaling -> bilinear (56 -> 224, align_corners = False) -> chosen pixels.

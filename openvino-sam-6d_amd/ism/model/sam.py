@@ -2,8 +2,10 @@
 tail after the mask decoder on sam6d_hip.amg (one fused launch per point batch instead of the 1024 x 1024 logits, the RLE round trip
 through the host and torchvision's NMS).
 
-With hip_decoder (SAM6D_HIP_SAMDEC=1; off by default) prompt encoder and mask decoder run on sam6d_hip.samdec as well.  Otherwise the SAM
-network is reached only through the `sam` object the caller passes in:
+With hip_decoder (SAM6D_HIP_SAMDEC=1; off by default) prompt encoder and mask decoder run on sam6d_hip.samdec as well, and with
+hip_encoder (SAM6D_HIP_SAMENC=1; off by default) the ViT-H image encoder runs on sam6d_hip.samenc: `encode_image` and SamPredictor then
+see a view of `sam` whose image_encoder is the library's; the caller's `sam` is not changed.  Otherwise the SAM network is reached only
+through the `sam` object the caller passes in:
     sam.image_encoder (.img_size; called on the preprocessed image), sam.prompt_encoder (called with points / boxes / masks keywords;
     .get_dense_pe()), sam.mask_decoder (called with the reference's keywords, returns (low_res_masks, iou_predictions)),
     sam.preprocess, sam.mask_threshold, sam.image_format, sam.device.
@@ -37,21 +39,50 @@ def load_sam(model_type, checkpoint_dir):
     return sam_model_registry[model_type](checkpoint=osp.join(checkpoint_dir, pretrained_weight_dict[model_type]))
 
 
+class _SamView:
+    """`sam` with another image_encoder: every other attribute (preprocess, image_format, device, mask_threshold, prompt_encoder,
+    mask_decoder ...) is the caller's object's, which is left as it is."""
+
+    def __init__(self, sam, image_encoder):
+        self._sam = sam
+        self.image_encoder = image_encoder
+
+    def __getattr__(self, name):
+        return getattr(self._sam, name)
+
+
 class Predictor:
     """SamPredictor's part in the mask generator (ISM/segment_anything/predictor.py:34-90, 168-235): holds the model and the features of
     the current crop, and runs prompt encoder + mask decoder for a batch of points up to `low_res_masks`.  hip_decoder: those two run
     on the library (sam6d_hip.samdec: the decoder's weights are packed here, the per-image tables in set_image) instead of being
-    called as modules."""
+    called as modules.  hip_encoder: the image encoder is the library's (sam6d_hip.samenc, weights packed here), for the
+    `encode_image` hook and for the SamPredictor path alike; preprocess and the resize stay the network side's."""
 
-    def __init__(self, sam_model, encode_image=None, hip_decoder=False):
+    def __init__(self, sam_model, encode_image=None, hip_decoder=False, hip_encoder=False):
         self.model = sam_model
         self.encode_image = encode_image
         self._sam_predictor = None
         self.hip_decoder = bool(hip_decoder)
+        self.hip_encoder = bool(hip_encoder)
         self._samdec = self._decoder_weights = None
+        self._encoder_model = self.model  # what encodes an image: `sam`, or its view with the library's encoder
         if self.hip_decoder:
             self._pack_decoder()
+        if self.hip_encoder:
+            self._pack_encoder()
         self.reset_image()
+
+    def _pack_encoder(self):
+        """The library route of the image encoder (sam6d_hip.samenc): refuses, never falls back."""
+        from sam6d_hip import samenc
+        ie = self.model.image_encoder
+        if not hasattr(ie, "state_dict"):
+            raise TypeError("hip_encoder: sam.image_encoder must be a module with the reference's state dict (got %s)" % type(ie).__name__)
+        samenc.check(ie)
+        if torch.device(self.device).type != "cuda":
+            raise RuntimeError("hip_encoder: the model is on %s; the library route needs it on a HIP device (hip_encoder=False or "
+                               "SAM6D_HIP_SAMENC=0 keeps the eager encoder)" % (self.device,))
+        self._encoder_model = _SamView(self.model, samenc.EncoderView(samenc.SamEncoderWeights(ie, self.device)))
 
     def _pack_decoder(self):
         """The library route of prompt encoder + mask decoder (sam6d_hip.samdec): refuses, never falls back."""
@@ -84,17 +115,17 @@ class Predictor:
         if self.encode_image is not None:
             if image_format != self.model.image_format:
                 image = image[..., ::-1]
-            self.features, input_size = self.encode_image(self.model, image)
+            self.features, input_size = self.encode_image(self._encoder_model, image)
             self.input_size = tuple(int(v) for v in input_size)
         else:
-            if self._sam_predictor is None or self._sam_predictor.model is not self.model:
+            if self._sam_predictor is None or self._sam_predictor.model is not self._encoder_model:
                 try:
                     from segment_anything import SamPredictor
                 except ImportError as e:
                     raise ImportError("CustomSamAutomaticMaskGenerator: encoding an image needs either an `encode_image(sam, image)` "
                                       "callable or the segment_anything package (its SamPredictor.set_image resizes the image through "
                                       "torchvision and PIL): %s" % e)
-                self._sam_predictor = SamPredictor(self.model)
+                self._sam_predictor = SamPredictor(self._encoder_model)
             self._sam_predictor.set_image(image, image_format)
             self.features = self._sam_predictor.features
             self.input_size = tuple(self._sam_predictor.input_size)
@@ -137,6 +168,7 @@ class CustomSamAutomaticMaskGenerator:
         pred_iou_thresh: float = 0.88,
         encode_image=None,
         hip_decoder=None,
+        hip_encoder=None,
     ):
         # SamAutomaticMaskGenerator's own defaults for what the reference's subclass does not pass on
         self.points_per_side = 32
@@ -148,7 +180,9 @@ class CustomSamAutomaticMaskGenerator:
         self.point_grids = amg.layer_point_grids(self.points_per_side, self.crop_n_layers, self.crop_n_points_downscale_factor)
         if hip_decoder is None:  # the library route of prompt encoder + mask decoder is opt-in
             hip_decoder = os.environ.get("SAM6D_HIP_SAMDEC", "0") == "1"
-        self.predictor = Predictor(sam, encode_image, hip_decoder)
+        if hip_encoder is None:  # ... and so is the library route of the image encoder
+            hip_encoder = os.environ.get("SAM6D_HIP_SAMENC", "0") == "1"
+        self.predictor = Predictor(sam, encode_image, hip_decoder, hip_encoder)
         self.points_per_batch = points_per_batch
         self.pred_iou_thresh = pred_iou_thresh
         self.stability_score_thresh = stability_score_thresh

@@ -142,6 +142,11 @@ SIGNATURES = {
     "sam6d_samdec_token_to_image_workspace_bytes": [c_i],
     "sam6d_samdec_token_to_image": [c_p, c_p, c_p, c_l, c_l, c_p] + [c_i] * 6 + [c_p, ctypes.c_size_t, c_p],
     "sam6d_samdec_upscale_masks": [c_p, c_l, c_l, c_p, c_p, c_f, c_p, c_p, c_p, c_p] + [c_i] * 6 + [c_p],
+    "sam6d_sam_patch_rows": [c_p, c_p, c_i, c_p],
+    "sam6d_sam_layernorm1280": [c_p] * 4 + [c_i, c_i, c_l, c_l, c_l, c_l, c_f, c_p],
+    "sam6d_sam_window_attention": [c_p] * 5 + [c_i, c_i, c_p],
+    "sam6d_sam_global_attention": [c_p] * 4 + [c_i, c_i, c_p],
+    "sam6d_sam_neck_gather": [c_p, c_p, c_i, c_p],
 }
 
 _lib = None

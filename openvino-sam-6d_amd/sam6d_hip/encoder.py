@@ -1,7 +1,8 @@
 """What the library's ViT encoders share on the host: PEM's ViT-B/16 (vit.py) and ISM's DINOv2 ViT-L/14 (dinov2.py) are two `Encoder`
 descriptions driving one launch sequence.  torch provides device buffers only.
 
-Layout: the residual stream is X (B*NT, D) fp32, row 0 of each image the cls token.  Per block:
+Layout: the residual stream is X (B*NT, D) fp32, row 0 of each image the cls token (SAM's ViT-H, samenc.py, is a third description: no
+cls token, and an attention launch of its own per block).  Per block:
     LN1 -> qkv GEMM -> attention -> proj GEMM (+ X, in place) -> LN2 -> fc1 GEMM (GELU) -> fc2 GEMM (+ X, in place)
 In-place residual: every GEMM route loads the residual element it adds before it stores that same element of C (the stored value
 depends on it), and each element of C belongs to exactly one lane, so C == residual is safe (tests/test_vit_gpu.py checks every route).
@@ -29,6 +30,8 @@ class Encoder(NamedTuple):
     patch_rows: str
     layernorm: str
     attention: str
+    cls: bool = True  # row 0 of each image is the cls token; False: NT == NP, patch_rows writes the patch rows only
+    whole_tiles: bool = False  # the block GEMMs ask for the whole-tile kernel (act + 32): an image's rows are a multiple of 128
 
     def require_mode(self):
         if _flags().mode == 2:
@@ -41,23 +44,33 @@ class Encoder(NamedTuple):
     def embed(self, images, W, X, A):
         """X (B*NT, D) = [cls_token; patch_embed(images)] + pos; A (>= B*NP*K floats) is the patch-row workspace."""
         B, D, K = images.shape[0], self.D, self.K
-        _lib.call(self.patch_rows, _p(images), _p(W.cls), _p(W.pos), _p(A), _p(X), B, _s())
+        if self.cls:
+            _lib.call(self.patch_rows, _p(images), _p(W.cls), _p(W.pos), _p(A), _p(X), B, _s())
+        else:
+            _lib.call(self.patch_rows, _p(images), _p(A), B, _s())
         # one problem per image: rows land one below the image's cls row, pos[1:] is the residual (batch stride 0)
-        gemm(A, W.patch.w, W.patch.b, X, self.NP, D, K, K, K, D, c_off=D, residual=W.pos, r_off=D, ldr=D, batch=B, sA=self.NP * K,
+        off = D if self.cls else 0
+        gemm(A, W.patch.w, W.patch.b, X, self.NP, D, K, K, K, D, c_off=off, residual=W.pos, r_off=off, ldr=D, batch=B, sA=self.NP * K,
              sW=0, sC=self.NT * D, sR=0, w16=W.patch.w16())
+
+    def attend(self, T, Y, B, n, blk):
+        """Y (B*n, D) = the multi-head attention of the qkv rows T (B*n, 3 D); blk: the block's weights, for an attention with operands
+        of its own."""
+        _lib.call(self.attention, _p(T), _p(Y), B, n, _s())
 
     def block(self, X, blk, B, Y, T, n=None):
         """One block on X (B*n, D) in place; Y (B*n, D) and T (>= B*n*HID floats) are workspaces."""
         D, HID = self.D, self.HID
         n = self.NT if n is None else n
         M = B * n
+        wt = 32 if self.whole_tiles else 0
         self.ln(X, blk["n1"], Y, 1, M, D, 0, D, 0)
-        gemm(Y, blk["qkv"].w, blk["qkv"].b, T, M, 3 * D, D, D, D, 3 * D, w16=blk["qkv"].w16())
-        _lib.call(self.attention, _p(T), _p(Y), B, n, _s())
-        gemm(Y, blk["proj"].w, blk["proj"].b, X, M, D, D, D, D, D, residual=X, ldr=D, w16=blk["proj"].w16())
+        gemm(Y, blk["qkv"].w, blk["qkv"].b, T, M, 3 * D, D, D, D, 3 * D, act=wt, w16=blk["qkv"].w16())
+        self.attend(T, Y, B, n, blk)
+        gemm(Y, blk["proj"].w, blk["proj"].b, X, M, D, D, D, D, D, residual=X, ldr=D, act=wt, w16=blk["proj"].w16())
         self.ln(X, blk["n2"], Y, 1, M, D, 0, D, 0)
-        gemm(Y, blk["fc1"].w, blk["fc1"].b, T, M, HID, D, D, D, HID, act=2, w16=blk["fc1"].w16())
-        gemm(T, blk["fc2"].w, blk["fc2"].b, X, M, D, HID, HID, HID, D, residual=X, ldr=D, w16=blk["fc2"].w16())
+        gemm(Y, blk["fc1"].w, blk["fc1"].b, T, M, HID, D, D, D, HID, act=2 + wt, w16=blk["fc1"].w16())
+        gemm(T, blk["fc2"].w, blk["fc2"].b, X, M, D, HID, HID, HID, D, residual=X, ldr=D, act=wt, w16=blk["fc2"].w16())
 
 
 # ------------------------------------------------------------------------------------------------- weights
