@@ -68,6 +68,13 @@ int sam6d_ball_query2(const float* new_xyz, const float* xyz, int B, int N, int 
 size_t sam6d_ball_query2_grid_workspace_bytes(int B, int N);
 int sam6d_ball_query2_grid(const float* new_xyz, const float* xyz, int B, int N, int M, float radius1, int nsample1, int* idx1,
                            float radius2, int nsample2, int* idx2, void* ws, size_t ws_bytes, void* stream);
+/* sam6d_ball_query2_grid (PEM/model/fine_point_matching.py:108-131; EXT/src/ball_query.cpp:16-62) that also reports how many slots of
+ * a query hold hits: cnt1, cnt2 (B,M) i32, cnt = clamp(hits, 1, nsample).  The slots from cnt on repeat slot 0, as the reference pads
+ * them (ball_query.cpp:44-49); an empty ball counts 1, its slots all being index 0.  idx1 / idx2 are those of sam6d_ball_query2_grid.
+ * (New entry only, so SAM6D_ABI_VERSION stays.) */
+int sam6d_ball_query2_grid_counts(const float* new_xyz, const float* xyz, int B, int N, int M, float radius1, int nsample1, int* idx1,
+                                  float radius2, int nsample2, int* idx2, void* ws, size_t ws_bytes, int* cnt1, int* cnt2,
+                                  void* stream);
 
 /* replaces `at::Tensor group_points(at::Tensor points, at::Tensor idx)` (EXT/src/group_points.cpp:79-108; loop :20-45).
  * points (B,C,N) f32, idx (B,M,S) i32 -> out (B,C,M,S) f32. */
@@ -329,6 +336,17 @@ int sam6d_pe_mlp_max(const float* pts, const int* idx, int B, int N, int S, cons
 int sam6d_pe_mlp_max_wg(const float* pts, const int* idx, int B, int N, int S, const float* W1, const float* sc1, const float* sh1,
                         const float* W2, const float* sc2, const float* sh2, const float* W3, const float* sc3, const float* sh3,
                         float* out, long ldo, int off, int max_wg, void* stream);
+/* sam6d_pe_mlp_max_wg (PEM/model/fine_point_matching.py:126-139) for indices whose padding is counted, as
+ * sam6d_ball_query2_grid_counts returns them (the reference pads a ball's unused slots with its first hit, EXT/src/ball_query.cpp:44-49).
+ * CONTRACT: cnt (B,N) i32 with 1 <= cnt[p] <= S for every point, and every slot l >= cnt[p] of row p of idx repeats an index that
+ * occurs in a slot < cnt[p] of that row.  Under this contract the output equals sam6d_pe_mlp_max_wg on the same idx bit for bit: the
+ * split-precision modes evaluate only the first cnt[p] slots of a point (rounded up to 8), packed four points' 8-slot pieces to a
+ * 32-row tile -- a repeated neighbour cannot change a maximum.  Matmul mode 0 runs the exact-fp32 kernel over all slots and ignores
+ * cnt.  A count outside [1, S] is clamped; indices that break the contract give the maximum over the counted slots only.
+ * (New entry only, so SAM6D_ABI_VERSION stays.) */
+int sam6d_pe_mlp_max_counted(const float* pts, const int* idx, int B, int N, int S, const float* W1, const float* sc1, const float* sh1,
+                             const float* W2, const float* sc2, const float* sh2, const float* W3, const float* sc3, const float* sh3,
+                             float* out, long ldo, int off, int max_wg, const int* cnt, void* stream);
 
 /* y = (x - t) @ R per batch element (PEM/model/fine_point_matching.py:45). */
 int sam6d_rigid_inverse(const float* x, const float* R, const float* t, int B, int N, float* y, void* stream);

@@ -134,6 +134,17 @@ __device__ __forceinline__ float wave_min_dpp(float v) {
   v = fminf(v, xor32_f32(v));
   return v;
 }
+// inclusive prefix sum over the 64 lanes on the DPP path (no ds_bpermute round trips): Hillis-Steele inside each 16-lane row (row_shr
+// 1, 2, 4, 8 with zero fill), then the row totals of the rows before (row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2 and 3)
+__device__ __forceinline__ int wave_incl_scan_i32_dpp(int v) {
+  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);  // row_shr:1
+  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);  // row_shr:2
+  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true);  // row_shr:4
+  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true);  // row_shr:8
+  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false); // row_bcast:15 -> rows 1, 3
+  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false); // row_bcast:31 -> rows 2, 3
+  return v;
+}
 // max / min do not depend on the order of the reduction: the DPP form everywhere (round 4; the ds_bpermute butterfly cost six LDS round
 // trips per call in the latency-bound per-proposal kernels)
 __device__ __forceinline__ float wave_max(float v) { return wave_max_dpp(v); }

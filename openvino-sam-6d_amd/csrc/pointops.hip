@@ -612,6 +612,8 @@ extern "C" int sam6d_ball_query2(const float* new_xyz, const float* xyz, int B, 
 // bit `index` of a per-query bit mask in LDS (ds_or_b32), and the ordered output is read off the mask afterwards: a prefix sum of the
 // words' popcounts over the wave gives every set bit its output slot.  The order inside a cell (the scatter uses LDS atomics) never
 // matters.  Workspace per cloud: N float4 (x, y, z, index) sorted by cell | G^3 + 1 cell starts | origin, 1 / c.
+// The read-out knows how many slots it filled with hits: sam6d_ball_query2_grid_counts stores that count per query (clamped to
+// [1, nsample]) for a consumer that wants to skip the padded tail.
 // ---------------------------------------------------------------------------------------------------------
 #define BQG_G 16
 #define BQG_CELLS (BQG_G * BQG_G * BQG_G)
@@ -619,17 +621,6 @@ extern "C" int sam6d_ball_query2(const float* new_xyz, const float* xyz, int B, 
 #define BQG_QPW 4            // queries per wave
 __host__ __device__ inline size_t bqg_cloud_bytes(int N) { return (size_t)N * 16 + (size_t)(BQG_CELLS + 1) * 4 + 12 + 16; }
 
-// inclusive prefix sum over the 64 lanes on the DPP path (no ds_bpermute round trips): Hillis-Steele inside each 16-lane row (row_shr
-// 1, 2, 4, 8 with zero fill), then the row totals of the rows before (row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2 and 3)
-__device__ __forceinline__ int wave_incl_scan_i32_dpp(int v) {
-  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);  // row_shr:1
-  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);  // row_shr:2
-  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true);  // row_shr:4
-  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true);  // row_shr:8
-  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false); // row_bcast:15 -> rows 1, 3
-  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false); // row_bcast:31 -> rows 2, 3
-  return v;
-}
 __device__ __forceinline__ int wave_min_i32(int v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
@@ -707,7 +698,8 @@ __global__ __launch_bounds__(1024) void bqg_build_kernel(const float* __restrict
 template <int WPL>  // mask words per lane: N <= 2048 * WPL
 __global__ __launch_bounds__(256) void bqg_query_kernel(const float* __restrict__ new_xyz, int N, int M, float r2a, int nsa,
                                                         int* __restrict__ idxa, float r2b, int nsb, int* __restrict__ idxb,
-                                                        const unsigned char* __restrict__ ws) {
+                                                        const unsigned char* __restrict__ ws, int* __restrict__ cnta,
+                                                        int* __restrict__ cntb) {
   __shared__ unsigned maskA[4][64 * WPL];
   __shared__ unsigned maskB[4][64 * WPL];
   const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -746,7 +738,7 @@ __global__ __launch_bounds__(256) void bqg_query_kernel(const float* __restrict_
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // the wave's LDS atomics are ordered before the reads below
     // ordered read-out of a mask: lane L owns words L*WPL .. L*WPL+WPL-1 (ascending indices)
-    auto emit = [&](const unsigned* m, int ns, int* out) {
+    auto emit = [&](const unsigned* m, int ns, int* out, int* nhit) {
       unsigned w[WPL];
       int cnt = 0;
 #pragma unroll
@@ -770,9 +762,11 @@ __global__ __launch_bounds__(256) void bqg_query_kernel(const float* __restrict_
         }
       }
       for (int l = min(total, ns) + lane; l < ns; l += 64) out[l] = first;
+      // slots filled with hits; an empty ball counts 1: its slots all hold index 0, one row for whoever evaluates the ball
+      if (nhit && lane == 0) *nhit = max(min(total, ns), 1);
     };
-    emit(mA, nsa, idxa + ((size_t)b * M + q) * nsa);
-    emit(mB, nsb, idxb + ((size_t)b * M + q) * nsb);
+    emit(mA, nsa, idxa + ((size_t)b * M + q) * nsa, cnta ? cnta + (size_t)b * M + q : nullptr);
+    emit(mB, nsb, idxb + ((size_t)b * M + q) * nsb, cntb ? cntb + (size_t)b * M + q : nullptr);
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   }
 }
@@ -781,28 +775,61 @@ extern "C" size_t sam6d_ball_query2_grid_workspace_bytes(int B, int N) {
   return (size_t)B * ((bqg_cloud_bytes(N) + 15) & ~(size_t)15);
 }
 
-extern "C" int sam6d_ball_query2_grid(const float* new_xyz, const float* xyz, int B, int N, int M, float radius1, int nsample1, int* idx1,
-                                      float radius2, int nsample2, int* idx2, void* ws, size_t ws_bytes, void* stream) {
+// cnt[q] = 1 + the number of slots l >= 1 of query q that differ from slot 0: hits are strictly increasing and the tail repeats the
+// first, so this is clamp(hits, 1, nsample) -- for the all-pairs fallback, whose kernel does not report its counts
+__global__ __launch_bounds__(256) void bq_count_kernel(const int* __restrict__ idx, int ns, long total, int* __restrict__ cnt) {
+  const long q = (long)blockIdx.x * 256 + threadIdx.x;
+  if (q >= total) return;
+  const int* r = idx + q * ns;
+  const int first = r[0];
+  int n = 1;
+  for (int l = 1; l < ns; ++l) n += r[l] != first;
+  cnt[q] = n;
+}
+
+// cnt1 / cnt2: null (the plain entry) or B*M counts of the slots that hold hits
+static int ball_query2_grid_impl(const float* new_xyz, const float* xyz, int B, int N, int M, float radius1, int nsample1, int* idx1,
+                                 float radius2, int nsample2, int* idx2, void* ws, size_t ws_bytes, int* cnt1, int* cnt2, void* stream) {
   SAM6D_REQUIRE(new_xyz && xyz && idx1 && idx2 && ws, "ball_query2_grid: null pointer");
   SAM6D_REQUIRE(B >= 0 && N > 0 && M >= 0 && nsample1 > 0 && nsample2 > 0 && B <= 65535, "ball_query2_grid: bad sizes");
   SAM6D_REQUIRE((((size_t)ws) & 15) == 0 && ws_bytes >= sam6d_ball_query2_grid_workspace_bytes(B, N),
                 "ball_query2_grid: workspace too small / not 16-byte aligned (sam6d_ball_query2_grid_workspace_bytes)");
   const float rmax = radius1 > radius2 ? radius1 : radius2;
-  if (N > BQG_MAXN || !(rmax > 0.f) || !(rmax < 1.0e30f))  // outside the pruned kernel's range: the all-pairs scan, same results
-    return sam6d_ball_query2(new_xyz, xyz, B, N, M, radius1, nsample1, idx1, radius2, nsample2, idx2, stream);
-  if (B == 0 || M == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
+  if (N > BQG_MAXN || !(rmax > 0.f) || !(rmax < 1.0e30f)) {  // outside the pruned kernel's range: the all-pairs scan, same results
+    if (int rc = sam6d_ball_query2(new_xyz, xyz, B, N, M, radius1, nsample1, idx1, radius2, nsample2, idx2, stream)) return rc;
+    const long total = (long)B * M;
+    if (!cnt1 || total == 0) return 0;
+    hipLaunchKernelGGL(bq_count_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, idx1, nsample1, total, cnt1);
+    hipLaunchKernelGGL(bq_count_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, idx2, nsample2, total, cnt2);
+    SAM6D_LAUNCH_CHECK("ball_query2_grid_counts(count)");
+  }
+  if (B == 0 || M == 0) return 0;
   hipLaunchKernelGGL(bqg_build_kernel, dim3(B), dim3(1024), 0, s, xyz, N, rmax * 1.001f, (unsigned char*)ws);
   SAM6D_LAUNCH_CHECK_CONT("ball_query2_grid(build)");
   const dim3 grid(cdiv(M, 4 * BQG_QPW), B);
   const float r2a = radius1 * radius1, r2b = radius2 * radius2;  // fp32 products, as the reference (ball_query.cpp:20)
+  const unsigned char* wsc = (const unsigned char*)ws;
   if (N <= 2048)
-    hipLaunchKernelGGL((bqg_query_kernel<1>), grid, dim3(256), 0, s, new_xyz, N, M, r2a, nsample1, idx1, r2b, nsample2, idx2, (const unsigned char*)ws);
+    hipLaunchKernelGGL((bqg_query_kernel<1>), grid, dim3(256), 0, s, new_xyz, N, M, r2a, nsample1, idx1, r2b, nsample2, idx2, wsc, cnt1, cnt2);
   else if (N <= 4096)
-    hipLaunchKernelGGL((bqg_query_kernel<2>), grid, dim3(256), 0, s, new_xyz, N, M, r2a, nsample1, idx1, r2b, nsample2, idx2, (const unsigned char*)ws);
+    hipLaunchKernelGGL((bqg_query_kernel<2>), grid, dim3(256), 0, s, new_xyz, N, M, r2a, nsample1, idx1, r2b, nsample2, idx2, wsc, cnt1, cnt2);
   else
-    hipLaunchKernelGGL((bqg_query_kernel<4>), grid, dim3(256), 0, s, new_xyz, N, M, r2a, nsample1, idx1, r2b, nsample2, idx2, (const unsigned char*)ws);
+    hipLaunchKernelGGL((bqg_query_kernel<4>), grid, dim3(256), 0, s, new_xyz, N, M, r2a, nsample1, idx1, r2b, nsample2, idx2, wsc, cnt1, cnt2);
   SAM6D_LAUNCH_CHECK("ball_query2_grid");
+}
+
+extern "C" int sam6d_ball_query2_grid(const float* new_xyz, const float* xyz, int B, int N, int M, float radius1, int nsample1, int* idx1,
+                                      float radius2, int nsample2, int* idx2, void* ws, size_t ws_bytes, void* stream) {
+  return ball_query2_grid_impl(new_xyz, xyz, B, N, M, radius1, nsample1, idx1, radius2, nsample2, idx2, ws, ws_bytes, nullptr, nullptr,
+                               stream);
+}
+
+extern "C" int sam6d_ball_query2_grid_counts(const float* new_xyz, const float* xyz, int B, int N, int M, float radius1, int nsample1,
+                                             int* idx1, float radius2, int nsample2, int* idx2, void* ws, size_t ws_bytes, int* cnt1,
+                                             int* cnt2, void* stream) {
+  SAM6D_REQUIRE(cnt1 && cnt2, "ball_query2_grid_counts: null pointer");
+  return ball_query2_grid_impl(new_xyz, xyz, B, N, M, radius1, nsample1, idx1, radius2, nsample2, idx2, ws, ws_bytes, cnt1, cnt2, stream);
 }
 
 extern "C" int sam6d_ball_query(const float* new_xyz, const float* xyz, int B, int N, int M, float radius, int nsample,

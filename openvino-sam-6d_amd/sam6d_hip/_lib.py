@@ -25,6 +25,7 @@ SIGNATURES = {
     "sam6d_ball_query2": [c_p, c_p, c_i, c_i, c_i, c_f, c_i, c_p, c_f, c_i, c_p, c_p],
     "sam6d_ball_query2_grid_workspace_bytes": [c_i, c_i],
     "sam6d_ball_query2_grid": [c_p, c_p, c_i, c_i, c_i, c_f, c_i, c_p, c_f, c_i, c_p, c_p, ctypes.c_size_t, c_p],
+    "sam6d_ball_query2_grid_counts": [c_p, c_p, c_i, c_i, c_i, c_f, c_i, c_p, c_f, c_i, c_p, c_p, ctypes.c_size_t, c_p, c_p, c_p],
     "sam6d_group_points": [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p],
     "sam6d_gather_rows": [c_p, c_p, c_i, c_i, c_i, c_i, c_l, c_l, c_i, c_p, c_p],
     "sam6d_gather_rows_lead": [c_p, c_p, c_i, c_i, c_i, c_i, c_l, c_l, c_i, c_p, c_l, c_p, c_p],
@@ -56,6 +57,7 @@ SIGNATURES = {
     "sam6d_linattn_focus_q": [c_p, c_p, c_p, c_i, c_l, c_l, c_p],
     "sam6d_pe_mlp_max": [c_p, c_p, c_i, c_i, c_i] + [c_p] * 10 + [c_l, c_i, c_p],
     "sam6d_pe_mlp_max_wg": [c_p, c_p, c_i, c_i, c_i] + [c_p] * 10 + [c_l, c_i, c_i, c_p],
+    "sam6d_pe_mlp_max_counted": [c_p, c_p, c_i, c_i, c_i] + [c_p] * 10 + [c_l, c_i, c_i, c_p, c_p],
     "sam6d_rigid_inverse": [c_p, c_p, c_p, c_i, c_i, c_p, c_p],
     "sam6d_put_rows": [c_p, c_l, c_l, c_p, c_l, c_l, c_i, c_i, c_i, c_p],
     "sam6d_prepend_bg_point": [c_p, c_i, c_i, c_p, c_p],

@@ -999,31 +999,34 @@ def sparse_to_dense_transformer(D, E, fps_idx, T, lead=None, write_bg=True, retu
 
 
 def pe_group(pts, r1=0.1, r2=0.2, ns1=32, ns2=64):
-    """The two ball queries of PositionalEncoding (fine_point_matching.py:108-131; new_xyz = pts + 1e-8, :117) in one pass."""
+    """The two ball queries of PositionalEncoding (fine_point_matching.py:108-131; new_xyz = pts + 1e-8, :117) in one pass:
+    ((idx1, idx2), (cnt1, cnt2)), cnt = the slots of a point that hold hits (the rest repeat slot 0)."""
     Bp, N, _ = pts.shape
     q = _empty((Bp, N, 3), pts)
     _lib.call("sam6d_add_scalar", _p(pts), 0.00000001, Bp * N * 3, _p(q), _s())
     idx12 = (_empty((Bp, N, ns1), pts, torch.int32), _empty((Bp, N, ns2), pts, torch.int32))
     nbytes = int(_lib.load().sam6d_ball_query2_grid_workspace_bytes(Bp, N))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=pts.device)
+    cnt12 = (_empty((Bp, N), pts, torch.int32), _empty((Bp, N), pts, torch.int32))
     with _Timed("ball_query"):
-        _lib.call("sam6d_ball_query2_grid", _p(q), _p(pts), Bp, N, N, float(r1), ns1, _p(idx12[0]), float(r2), ns2, _p(idx12[1]),
-                  ws.data_ptr(), nbytes, _s())
-    return idx12
+        _lib.call("sam6d_ball_query2_grid_counts", _p(q), _p(pts), Bp, N, N, float(r1), ns1, _p(idx12[0]), float(r2), ns2, _p(idx12[1]),
+                  ws.data_ptr(), nbytes, _p(cnt12[0]), _p(cnt12[1]), _s())
+    return idx12, cnt12
 
 
-def pe_apply(pts, idx12, W, dst, dst_off, dst_sb, max_wg=0):
-    """dst rows += mlp3(cat(max_s mlp1(group_r1), max_s mlp2(group_r2))) for the groups of pe_group.  max_wg: bound on the persistent
-    workgroups of the MLP kernels (0 = fill the chip) for launches that share the chip with another stream."""
+def pe_apply(pts, grp, W, dst, dst_off, dst_sb, max_wg=0):
+    """dst rows += mlp3(cat(max_s mlp1(group_r1), max_s mlp2(group_r2))) for the groups (indices, counts) of pe_group.  max_wg: bound on
+    the persistent workgroups of the MLP kernels (0 = fill the chip) for launches that share the chip with another stream."""
     Bp, N, _ = pts.shape
+    idx12, cnt12 = grp
     feat = _empty((Bp * N, 2 * 128), pts)
     for k in range(2):
         idx = idx12[k]
         L = W.pe["mlp"][k]
         with _Timed("pe_mlp"):
-            _lib.call("sam6d_pe_mlp_max_wg", _p(pts), _p(idx), Bp, N, idx.shape[2], _p(L[0]["w"]), _p(L[0]["scale"]), _p(L[0]["shift"]),
+            _lib.call("sam6d_pe_mlp_max_counted", _p(pts), _p(idx), Bp, N, idx.shape[2], _p(L[0]["w"]), _p(L[0]["scale"]), _p(L[0]["shift"]),
                       _p(L[1]["w"]), _p(L[1]["scale"]), _p(L[1]["shift"]), _p(L[2]["w"]), _p(L[2]["scale"]), _p(L[2]["shift"]),
-                      _p(feat), 2 * 128, k * 128, int(max_wg), _s())
+                      _p(feat), 2 * 128, k * 128, int(max_wg), _p(cnt12[k]), _s())
     m3 = W.pe["mlp3"]
     gemm(feat, m3.w, m3.b, dst, N, C, C, C, C, C, c_off=dst_off, residual=dst, r_off=dst_off, ldr=C, batch=Bp, sA=N * C,
          sC=dst_sb, sR=dst_sb, w16=m3.w16())

@@ -14,7 +14,7 @@ lib = _lib.load(); lib.sam6d_pe_debug_stamps.argtypes = [ctypes.c_void_p]
 names = ["prefetch issue", "layer 1 MFMA issue", "layer-1 epilogue", "layer 2", "layer 3", "max epilogue", "rotation (coord wait)"]
 for k in (0, 1):
     feat = torch.empty(32 * 2048, 256, device=dev)
-    L = W.pe["mlp"][k]; idx = grp[k]
+    L = W.pe["mlp"][k]; idx = grp[0][k]
     for _ in range(2):
         _lib.call("sam6d_pe_mlp_max_wg", pem._p(pts), pem._p(idx), 32, 2048, idx.shape[2], pem._p(L[0]["w"]), pem._p(L[0]["scale"]), pem._p(L[0]["shift"]),
                   pem._p(L[1]["w"]), pem._p(L[1]["scale"]), pem._p(L[1]["shift"]), pem._p(L[2]["w"]), pem._p(L[2]["scale"]), pem._p(L[2]["shift"]),
