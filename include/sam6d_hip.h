@@ -757,6 +757,28 @@ int sam6d_sam_global_attention(const float* qkv, const float* rel_h, const float
  * same biased variance) and the (B, 256, 64, 64) output is a sam6d_transpose.  B <= 4096. */
 int sam6d_sam_neck_gather(const float* x, float* rows, int B, void* stream);
 
+#define SAM6D_SAM_FRONT_X 0    /* the `layout` argument of sam6d_sam_front */
+#define SAM6D_SAM_FRONT_ROWS 1
+/* SAM's image front in one launch: B uint8 images (H, W, 3) of one size -> what the image encoder is called on.  That is
+ * ResizeLongestSide.apply_image (ISM/segment_anything/utils/transforms.py:26-31, get_preprocess_shape :91-102: the longest side to
+ * `side` through torchvision's resize of a PIL image, i.e. Pillow's 8-bit bilinear ImagingResample), the predictor's channel flip
+ * for another image_format (ISM/segment_anything/predictor.py:56-58; reverse != 0 reads channel 2 - c) and Sam.preprocess
+ * (ISM/segment_anything/modeling/sam.py:164-173): (x - mean) / std in fp32, zeros below and to the right up to side x side.
+ * Pixel (y, x) of image b is at img + b image_stride + y row_stride + 3 x (strides in bytes, row_stride >= 3 W: a crop view works).
+ * xtab (for W -> ow) and ytab (for H -> oh), int32 in device memory, are Pillow's fixed-point coefficients, computed on the host in
+ * double: for an axis with n outputs and t = xtaps / ytaps table columns, lo[n] (first source index), count[n], k[n][t] (22-bit
+ * coefficients, zeros behind the count).  A pass is byte = min((2^21 + sum_j pixel[lo + j] k[j]) >> 22, 255), horizontal first,
+ * rounded to a byte before the vertical pass; the intermediate image stays in LDS.  Always horizontal first: Pillow's Image.resize
+ * (12.2.0) runs the vertical pass first for H > 100 W when the image shrinks vertically, which the caller has to keep away.  Indices
+ * derived from the tables are clamped to the buffers.
+ * layout SAM6D_SAM_FRONT_X: out (B, 3, side, side), Sam.preprocess's tensor.  SAM6D_SAM_FRONT_ROWS: out (B * (side / 16)^2, 768), what
+ * sam6d_sam_patch_rows makes of that tensor (row (side / 16) py + px, columns in (c, kh, kw) order; image_encoder.py:387-395) without
+ * the tensor.  H, W 1 .. 4096; side a multiple of 16, 16 .. 1024; at most 9 taps per axis (shrinking by up to 4); out 16-byte
+ * aligned; B <= 65535.  Anything else returns non-zero without a launch.  (A new entry, so SAM6D_ABI_VERSION stays.) */
+int sam6d_sam_front(const unsigned char* img, long row_stride, long image_stride, int B, int H, int W, int reverse, const int* xtab,
+                    int xtaps, const int* ytab, int ytaps, float mean0, float mean1, float mean2, float std0, float std1, float std2,
+                    int side, float* out, int layout, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,8 +4,11 @@ through the host and torchvision's NMS).
 
 With hip_decoder (SAM6D_HIP_SAMDEC=1; off by default) prompt encoder and mask decoder run on sam6d_hip.samdec as well, and with
 hip_encoder (SAM6D_HIP_SAMENC=1; off by default) the ViT-H image encoder runs on sam6d_hip.samenc: `encode_image` and SamPredictor then
-see a view of `sam` whose image_encoder is the library's; the caller's `sam` is not changed.  Otherwise the SAM network is reached only
-through the `sam` object the caller passes in:
+see a view of `sam` whose image_encoder is the library's; the caller's `sam` is not changed.  With hip_front (SAM6D_HIP_SAMFRONT=1; off
+by default) the encoder's input comes from sam6d_hip.samfront: the uint8 image is uploaded and one launch resizes it as
+ResizeLongestSide.apply_image does (Pillow's bilinear resample, bit for bit), normalises with sam.pixel_mean / sam.pixel_std and pads
+-- `set_image` then needs neither an `encode_image` hook nor SamPredictor, and with hip_encoder as well the launch writes the encoder's
+patch rows directly.  Otherwise the SAM network is reached only through the `sam` object the caller passes in:
     sam.image_encoder (.img_size; called on the preprocessed image), sam.prompt_encoder (called with points / boxes / masks keywords;
     .get_dense_pe()), sam.mask_decoder (called with the reference's keywords, returns (low_res_masks, iou_predictions)),
     sam.preprocess, sam.mask_threshold, sam.image_format, sam.device.
@@ -56,21 +59,50 @@ class Predictor:
     the current crop, and runs prompt encoder + mask decoder for a batch of points up to `low_res_masks`.  hip_decoder: those two run
     on the library (sam6d_hip.samdec: the decoder's weights are packed here, the per-image tables in set_image) instead of being
     called as modules.  hip_encoder: the image encoder is the library's (sam6d_hip.samenc, weights packed here), for the
-    `encode_image` hook and for the SamPredictor path alike; preprocess and the resize stay the network side's."""
+    `encode_image` hook and for the SamPredictor path alike; preprocess and the resize stay the network side's, unless hip_front:
+    then resize, normalisation and padding are the library's (sam6d_hip.samfront) and no hook or SamPredictor is involved."""
 
-    def __init__(self, sam_model, encode_image=None, hip_decoder=False, hip_encoder=False):
+    def __init__(self, sam_model, encode_image=None, hip_decoder=False, hip_encoder=False, hip_front=False):
         self.model = sam_model
         self.encode_image = encode_image
         self._sam_predictor = None
         self.hip_decoder = bool(hip_decoder)
         self.hip_encoder = bool(hip_encoder)
+        self.hip_front = bool(hip_front)
         self._samdec = self._decoder_weights = None
+        self._samfront = self._pixel_stats = None
         self._encoder_model = self.model  # what encodes an image: `sam`, or its view with the library's encoder
         if self.hip_decoder:
             self._pack_decoder()
         if self.hip_encoder:
             self._pack_encoder()
+        if self.hip_front:
+            self._pack_front()
         self.reset_image()
+
+    def _pack_front(self):
+        """The library route of the encoder's input (sam6d_hip.samfront): refuses, never falls back."""
+        if self.encode_image is not None:
+            raise ValueError("hip_front: an `encode_image` callable was passed as well; the library's front takes its place, so pass "
+                             "one or the other (hip_front=False or SAM6D_HIP_SAMFRONT=0 keeps the callable)")
+        from sam6d_hip import samfront
+        self._pixel_stats = samfront.pixel_stats(self.model)  # (AttributeError naming the missing buffer)
+        if torch.device(self.device).type != "cuda":
+            raise RuntimeError("hip_front: the model is on %s; the library route needs it on a HIP device (hip_front=False or "
+                               "SAM6D_HIP_SAMFRONT=0 keeps the host resize)" % (self.device,))
+        self._samfront = samfront
+
+    def _front_features(self, image, image_format):
+        """image (H, W, 3) uint8 -> the encoder's features through the library's front: the patch rows straight into the library's
+        encoder when that is on as well, else the preprocessed tensor into sam.image_encoder."""
+        sf, (mean, std) = self._samfront, self._pixel_stats
+        side = int(self.model.image_encoder.img_size)
+        img = sf.upload(image, self.device)
+        reverse = image_format != self.model.image_format
+        if self.hip_encoder:
+            rows = sf.preprocess(img, mean, std, side=side, layout="rows", reverse=reverse)
+            return self._encoder_model.image_encoder.from_rows(rows)
+        return self.model.image_encoder(sf.preprocess(img, mean, std, side=side, layout="x", reverse=reverse))
 
     def _pack_encoder(self):
         """The library route of the image encoder (sam6d_hip.samenc): refuses, never falls back."""
@@ -112,7 +144,10 @@ class Predictor:
     @torch.no_grad()
     def set_image(self, image, image_format="RGB"):
         self.reset_image()
-        if self.encode_image is not None:
+        if self.hip_front:
+            self.features = self._front_features(image, image_format)
+            self.input_size = amg.preprocess_shape(image.shape[0], image.shape[1], self.model.image_encoder.img_size)
+        elif self.encode_image is not None:
             if image_format != self.model.image_format:
                 image = image[..., ::-1]
             self.features, input_size = self.encode_image(self._encoder_model, image)
@@ -169,6 +204,7 @@ class CustomSamAutomaticMaskGenerator:
         encode_image=None,
         hip_decoder=None,
         hip_encoder=None,
+        hip_front=None,
     ):
         # SamAutomaticMaskGenerator's own defaults for what the reference's subclass does not pass on
         self.points_per_side = 32
@@ -182,7 +218,9 @@ class CustomSamAutomaticMaskGenerator:
             hip_decoder = os.environ.get("SAM6D_HIP_SAMDEC", "0") == "1"
         if hip_encoder is None:  # ... and so is the library route of the image encoder
             hip_encoder = os.environ.get("SAM6D_HIP_SAMENC", "0") == "1"
-        self.predictor = Predictor(sam, encode_image, hip_decoder, hip_encoder)
+        if hip_front is None:    # ... and the library route of the encoder's input (resize, normalise, pad)
+            hip_front = os.environ.get("SAM6D_HIP_SAMFRONT", "0") == "1"
+        self.predictor = Predictor(sam, encode_image, hip_decoder, hip_encoder, hip_front)
         self.points_per_batch = points_per_batch
         self.pred_iou_thresh = pred_iou_thresh
         self.stability_score_thresh = stability_score_thresh

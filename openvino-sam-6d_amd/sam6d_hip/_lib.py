@@ -149,6 +149,7 @@ SIGNATURES = {
     "sam6d_sam_window_attention": [c_p] * 5 + [c_i, c_i, c_p],
     "sam6d_sam_global_attention": [c_p] * 4 + [c_i, c_i, c_p],
     "sam6d_sam_neck_gather": [c_p, c_p, c_i, c_p],
+    "sam6d_sam_front": [c_p, c_l, c_l] + [c_i] * 4 + [c_p, c_i, c_p, c_i] + [c_f] * 6 + [c_i, c_p, c_i, c_p],
 }
 
 _lib = None

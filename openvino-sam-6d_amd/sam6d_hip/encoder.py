@@ -43,11 +43,17 @@ class Encoder(NamedTuple):
 
     def embed(self, images, W, X, A):
         """X (B*NT, D) = [cls_token; patch_embed(images)] + pos; A (>= B*NP*K floats) is the patch-row workspace."""
-        B, D, K = images.shape[0], self.D, self.K
+        B = images.shape[0]
         if self.cls:
             _lib.call(self.patch_rows, _p(images), _p(W.cls), _p(W.pos), _p(A), _p(X), B, _s())
         else:
             _lib.call(self.patch_rows, _p(images), _p(A), B, _s())
+        self.embed_rows(A, W, X, B)
+
+    def embed_rows(self, A, W, X, B):
+        """The patch GEMM alone: X's patch rows = A (B*NP, K), the images' patch rows, times the patch weight + bias + pos.  With a cls
+        token the cls rows of X are the patch-rows kernel's to write (`embed`)."""
+        D, K = self.D, self.K
         # one problem per image: rows land one below the image's cls row, pos[1:] is the residual (batch stride 0)
         off = D if self.cls else 0
         gemm(A, W.patch.w, W.patch.b, X, self.NP, D, K, K, K, D, c_off=off, residual=W.pos, r_off=off, ldr=D, batch=B, sA=self.NP * K,

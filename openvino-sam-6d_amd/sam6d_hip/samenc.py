@@ -346,6 +346,23 @@ def _neck(X, W, B, Y, T, out, o_off):
     _lib.call("sam6d_transpose", _p(T), OUT, NP * OUT, B, NP, OUT, _p(out, o_off), NP, OUT * NP, _s())
 
 
+def _encode(W, B, like, embed):
+    """The launch sequence behind `encode` and `encode_rows`: embed(i0, b, X) fills X (b*4096, 1280) for images i0 .. i0 + b - 1."""
+    from .pem import _empty
+    out = _empty((B, OUT, GRID, GRID), like)
+    if B == 0:
+        return out
+    S = min(SLICE, B)
+    X, Y, T = (_empty((S * NP, c), like) for c in (D, D, HID))
+    for i0 in range(0, B, S):
+        b = min(S, B - i0)
+        embed(i0, b, X)
+        for blk in W.blocks:
+            ENC.block(X, blk, b, Y, T)
+        _neck(X, W, b, Y, T, out, i0 * OUT * NP)
+    return out
+
+
 @_library_call
 def encode(x, W):
     """x (B, 3, 1024, 1024) float32 on the HIP device, preprocessed as `sam.image_encoder` expects it -> (B, 256, 64, 64)."""
@@ -353,19 +370,22 @@ def encode(x, W):
     W.require_library()
     check_images(x)
     x = x.contiguous()
-    B = x.shape[0]
-    out = _empty((B, OUT, GRID, GRID), x)
-    if B == 0:
-        return out
-    S = min(SLICE, B)
-    X, Y, T, A = (_empty((S * NP, c), x) for c in (D, D, HID, K))
-    for i0 in range(0, B, S):
-        b = min(S, B - i0)
-        ENC.embed(x[i0:i0 + b], W, X, A)
-        for blk in W.blocks:
-            ENC.block(X, blk, b, Y, T)
-        _neck(X, W, b, Y, T, out, i0 * OUT * NP)
-    return out
+    A = _empty((min(SLICE, x.shape[0]) * NP, K), x)
+    return _encode(W, x.shape[0], x, lambda i0, b, X: ENC.embed(x[i0:i0 + b], W, X, A))
+
+
+@_library_call
+def encode_rows(A, W):
+    """`encode` from the patch rows: A (B*4096, 768) float32 on the HIP device, row 4096 b + 64 py + px = the patch's values of the
+    preprocessed image in (c, kh, kw) order (samfront.preprocess(..., layout="rows"), or sam6d_sam_patch_rows) -> (B, 256, 64, 64).  The
+    same launches as `encode` without the patch-rows one."""
+    W.require_library()
+    if A.dim() != 2 or A.shape[1] != K or A.shape[0] % NP:
+        raise ValueError("sam6d_hip.samenc: the patch rows must be (B*%d, %d), got %s" % (NP, K, tuple(A.shape)))
+    if A.dtype != torch.float32:
+        raise ValueError("sam6d_hip.samenc: the patch rows must be float32, got %s" % A.dtype)
+    A = A.contiguous()
+    return _encode(W, A.shape[0] // NP, A, lambda i0, b, X: ENC.embed_rows(A[i0 * NP:(i0 + b) * NP], W, X, b))
 
 
 def block_gemm_routes(W, B=1):
@@ -451,3 +471,6 @@ class EncoderView:
 
     def __call__(self, x):
         return encode(x, self.W, options=self.options)
+
+    def from_rows(self, A):
+        return encode_rows(A, self.W, options=self.options)
