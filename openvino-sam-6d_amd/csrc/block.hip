@@ -927,7 +927,7 @@ __global__ __launch_bounds__(512) void token_tail_kernel(TbArgs a) {
 #pragma unroll
   for (int i = 0; i < RPW; ++i) {
     const int tok = wave * RPW + i;
-    const float m = wave_max_dpp(fmaxf(fmaxf(fabsf(xv[i].x), fabsf(xv[i].y)), fmaxf(fabsf(xv[i].z), fabsf(xv[i].w))));
+    const float m = wave_max_dpp(amax4(xv[i]));
     const float sx = pow2_scale(m);
     if (lane == 0) sxs[tok] = sx;
     unsigned h0, l0, h1, l1;

@@ -260,6 +260,20 @@ __device__ __forceinline__ void sam6d_split2_f16(float a, float b, unsigned& hi2
   asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(lo2) : "v"(la), "v"(lb));
 }
 
+// max |.| of four values
+__device__ __forceinline__ float amax4(float a, float b, float c, float d) { return fmaxf(fmaxf(fabsf(a), fabsf(b)), fmaxf(fabsf(c), fabsf(d))); }
+__device__ __forceinline__ float amax4(float4 v) { return amax4(v.x, v.y, v.z, v.w); }
+__device__ __forceinline__ float amax4(f32x4 v) { return amax4(v[0], v[1], v[2], v[3]); }
+
+// four values at once: the hi halves and the lo halves, each as one 8-byte group
+__device__ __forceinline__ void split4(const float4 v, half4& hi, half4& lo) {
+  unsigned h0, h1, l0, l1;
+  sam6d_split2_f16(v.x, v.y, h0, l0);
+  sam6d_split2_f16(v.z, v.w, h1, l1);
+  hi = __builtin_bit_cast(half4, u32x2{h0, h1});
+  lo = __builtin_bit_cast(half4, u32x2{l0, l1});
+}
+
 // ---- shared steps of the split-precision panel kernels (block.hip, xattn.hip) ------------------------------------
 // compile-time loop: f(std::integral_constant<int, I>) for I = B .. E-1
 template <int B, int E, class F>
@@ -299,8 +313,8 @@ __device__ __forceinline__ float split_row256(const float* __restrict__ src, int
   float m = 0.f;
 #pragma unroll
   for (int s = 0; s < 8; ++s) {
-    m = fmaxf(m, fmaxf(fmaxf(fabsf(va[s][0]), fabsf(va[s][1])), fmaxf(fabsf(va[s][2]), fabsf(va[s][3]))));
-    m = fmaxf(m, fmaxf(fmaxf(fabsf(vb[s][0]), fabsf(vb[s][1])), fmaxf(fabsf(vb[s][2]), fabsf(vb[s][3]))));
+    m = fmaxf(m, amax4(va[s]));
+    m = fmaxf(m, amax4(vb[s]));
   }
   const float sx = pow2_scale(tok_max(m));
 #pragma unroll
@@ -322,6 +336,178 @@ __device__ __forceinline__ void dma_pieces(const unsigned char* src, unsigned ch
     __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)(src + (size_t)pc * 1024 + lane * 16),
                                      (void __attribute__((address_space(3)))*)(dst + pc * 1024), 16, 0, 0);
   });
+}
+
+// ---- shared steps of the register-chained attention kernels (xattn.hip, dinov2.hip, samenc.hip) ------------------
+// One scheme, five kernels (xattn_kernel, sattn_kernel, dino_attention_kernel, sam_window_attention_kernel,
+// sam_global_attention_kernel): k and v are cut once into fp16 hi / lo LDS images with a power-of-two scale per image; a 16-token group
+// forms S^T = k . q^T on v_mfma_f32_16x16x32_f16 in three products, the softmax runs in registers over the lane's tiles and its three
+// partner lanes, the probabilities are scaled by 2^14 and split in place (the accumulator layout of S^T is the B-operand layout of the
+// second product: k-slot 8 g + e of step s stands for key 32 s + 16 (e >> 2) + 4 g + (e & 3)), and out^T = v^T . P^T leaves as four
+// floats per lane and tile.  Every kernel keeps its own schedule (what is loaded when, how the logits are formed); the steps between
+// are these.  profiles/README.md, "Attention-kernel helpers", has the compiled-code comparison and the shapes it refused.
+
+// acc += a . b of one 16x16x32 step from the split operands: al . bh, then ah . bl, then ah . bh
+__device__ __forceinline__ f32x4 mfma3_16(half8 ah, half8 al, half8 bh, half8 bl, f32x4 acc) {
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, acc, 0, 0, 0);
+  return __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, acc, 0, 0, 0);
+}
+// single (launch-uniform): matmul mode 2 keeps the hi . hi product only
+__device__ __forceinline__ f32x4 mfma3_16(half8 ah, half8 al, half8 bh, half8 bl, f32x4 acc, bool single) {
+  if (!single) {
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, acc, 0, 0, 0);
+  }
+  return __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, acc, 0, 0, 0);
+}
+
+// The image scales of a workgroup of eight waves, in two halves with the caller's barrier (and whatever else it has to do) between
+// them: every wave puts its max |k| and max |v| into red[16]; afterwards every thread takes the power-of-two scales of the two maxima.
+__device__ __forceinline__ void wg_amax_put(float mk, float mv, float* red, int wave, int lane) {
+  mk = wave_max_dpp(mk);
+  mv = wave_max_dpp(mv);
+  if (lane == 0) { red[wave] = mk; red[8 + wave] = mv; }
+}
+__device__ __forceinline__ void wg_scales_get(const float* red, float& sk, float& sv) {
+  sk = sv = 0.f;
+#pragma unroll
+  for (int w = 0; w < 8; ++w) { sk = fmaxf(sk, red[w]); sv = fmaxf(sv, red[8 + w]); }
+  sk = pow2_scale(sk);
+  sv = pow2_scale(sv);
+}
+
+// 8 floats times pre times s as one split operand (pre: a literal prescale such as the softmax's 1 / 8, applied first as the kernels
+// always did; 1 costs nothing)
+__device__ __forceinline__ void split8(float4 a, float4 b, float pre, float s, half8& hi8, half8& lo8) {
+  const float e8[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    _Float16 hi, lo;
+    sam6d_split_f16(e8[u] * pre * s, hi, lo);
+    hi8[u] = hi;
+    lo8[u] = lo;
+  }
+}
+
+// The HD channels of the fp32 row at `src`, times pre, as the split B operand of (HD + 31) / 32 k-steps in the contiguous-slot layout:
+// slot 8 fg + e of step ks = channel 32 ks + 8 fg + e, zero from channel HD on.  Returns the row's own power-of-two scale (over the
+// four lanes of the token).
+template <int HD>
+__device__ __forceinline__ float split_q_row(const float* __restrict__ src, int fg, float pre, half8* qh, half8* ql) {
+  constexpr int KS = (HD + 31) / 32;
+  float4 a[KS], b[KS];
+  float m = 0.f;
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) {
+    const int c = 32 * ks + 8 * fg;
+    a[ks] = b[ks] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (HD % 32 == 0 || c < HD) {
+      a[ks] = *reinterpret_cast<const float4*>(src + c);
+      b[ks] = *reinterpret_cast<const float4*>(src + c + 4);
+    }
+    const float mks = fmaxf(amax4(a[ks]), amax4(b[ks]));
+    m = ks ? fmaxf(m, mks) : mks;  // (not fmaxf(0, .) in the first step: an instruction the 64-channel caller never had)
+  }
+  const float sq = pow2_scale(tok_max(m * pre));
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) split8(a[ks], b[ks], pre, sq, qh[ks], ql[ks]);
+  return sq;
+}
+
+// The plain (row-major, unswizzled) images.  k: row = key, channel c at byte 2 c of a row of KROW bytes per plane, rows 0 .. NROW - 1
+// all written.  v^T: row = channel, key j at byte 2 j of a row of VROW bytes per plane, keys 0 .. 4 NQ - 1 all written.  Both are zero
+// from key nkeys on.  Key j's HD channels are src(j)[off .. off + HD); NTH threads share the work (t: the thread's index).
+template <int HD, int NROW, int KROW, int NTH, class Src>
+__device__ __forceinline__ void attn_build_k(unsigned char* kh, unsigned char* kl, int t, int nkeys, float sk, Src&& src, int off) {
+  for (int e = t; e < NROW * (HD / 4); e += NTH) {
+    const int j = e / (HD / 4), c4 = e % (HD / 4);
+    float4 kv = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (j < nkeys) kv = *reinterpret_cast<const float4*>(src(j) + off + 4 * c4);
+    half4 hi4, lo4;
+    split4(make_float4(kv.x * sk, kv.y * sk, kv.z * sk, kv.w * sk), hi4, lo4);
+    *reinterpret_cast<half4*>(kh + (size_t)j * KROW + 8 * c4) = hi4;
+    *reinterpret_cast<half4*>(kl + (size_t)j * KROW + 8 * c4) = lo4;
+  }
+}
+template <int HD, int NQ, int VROW, int NTH, class Src>
+__device__ __forceinline__ void attn_build_vt(unsigned char* vh, unsigned char* vl, int t, int nkeys, float sv, Src&& src, int off) {
+  for (int e = t; e < NQ * HD; e += NTH) {
+    const int d = e % HD, jq = e / HD;  // (a wave reads consecutive channels of one key)
+    float x4[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int j = 4 * jq + u;
+      x4[u] = (j < nkeys) ? src(j)[off + d] * sv : 0.f;
+    }
+    half4 hi4, lo4;
+    split4(make_float4(x4[0], x4[1], x4[2], x4[3]), hi4, lo4);
+    *reinterpret_cast<half4*>(vh + (size_t)d * VROW + 8 * jq) = hi4;
+    *reinterpret_cast<half4*>(vl + (size_t)d * VROW + 8 * jq) = lo4;
+  }
+}
+
+// Softmax over a token's keys from the finished logits s (masked keys at -inf) and the lane's maximum of them: the token's maximum,
+// exp(x - max) in place, the token's sum.  Returns 2^14 / sum: the probabilities go to the second product times 2^14 (<= 2^14:
+// fp16-safe) and the caller folds the 2^-14 into its output scale.
+template <int NT>
+__device__ __forceinline__ float attn_softmax(f32x4 (&s)[NT], float mx) {
+  mx = tok_max(mx);
+  float sum = 0.f;
+#pragma unroll
+  for (int i = 0; i < NT; ++i)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      s[i][r] = __builtin_amdgcn_exp2f((s[i][r] - mx) * 1.4426950408889634f);
+      sum += s[i][r];
+    }
+  sum = tok_sum(sum);
+  return 16384.0f / sum;
+}
+
+// s[i] * pscale as the split B operand of VS k-steps of 32 keys (two tiles per step; zero from tile NT on).  Returned by value: filled
+// in through references, the halves are assembled where they are computed and not where they are used, which moves registers
+// (README, as above)
+template <int VS>
+struct SplitB {
+  half8 h[VS], l[VS];
+};
+template <int NT, int VS>
+__device__ __forceinline__ SplitB<VS> attn_pack_probs(const f32x4 (&s)[NT], float pscale) {
+  SplitB<VS> p;
+#pragma unroll
+  for (int i = 0; i < 2 * VS; ++i)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float pv = i < NT ? s[i < NT ? i : 0][r] * pscale : 0.f;
+      _Float16 hi, lo;
+      sam6d_split_f16(pv, hi, lo);
+      p.h[i >> 1][4 * (i & 1) + r] = hi;
+      p.l[i >> 1][4 * (i & 1) + r] = lo;
+    }
+  return p;
+}
+
+// A operand of k-step st of the out^T product from a plain v^T image (attn_build_vt; the swizzled images of xattn.hip go through
+// xa_mma): keys 32 st + 4 g .. + 3 and 32 st + 16 + 4 g .. + 3 of channel `row`, two 8-byte reads 32 bytes apart per plane.  By value,
+// as SplitB; the product loops around it stay in the kernels (README, as above).
+struct HiLo8 {
+  half8 h, l;
+};
+template <int VROW>
+__device__ __forceinline__ HiLo8 attn_vt_frag(const unsigned char* vh, const unsigned char* vl, int row, int st, int fg) {
+  const size_t off = (size_t)row * VROW + 2 * (32 * st + 4 * fg);
+  const half4 h0 = *reinterpret_cast<const half4*>(vh + off), h1 = *reinterpret_cast<const half4*>(vh + off + 32);
+  const half4 l0 = *reinterpret_cast<const half4*>(vl + off), l1 = *reinterpret_cast<const half4*>(vl + off + 32);
+  return HiLo8{half8{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]}, half8{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]}};
+}
+
+// the lane's four channels 16 i + 4 fg .. + 3 of every out^T tile, times scale, to the token's output row
+template <int NO>
+__device__ __forceinline__ void attn_store(float* dst, const f32x4 (&o)[NO], float scale, int fg) {
+#pragma unroll
+  for (int i = 0; i < NO; ++i)
+    *reinterpret_cast<float4*>(dst + 16 * i + 4 * fg) = make_float4(o[i][0] * scale, o[i][1] * scale, o[i][2] * scale, o[i][3] * scale);
 }
 
 // ---- shared steps of the 32x32x16 split-product tile kernels (gemm.hip, ism.hip, finematch.hip) ------------------
@@ -359,14 +545,6 @@ struct SpLayout {
 struct SpPlanes {
   _Float16 *Ah, *Al, *Bh, *Bl;
 };
-
-__device__ __forceinline__ void split4(const float4 v, half4& hi, half4& lo) {
-  unsigned h0, h1, l0, l1;
-  sam6d_split2_f16(v.x, v.y, h0, l0);
-  sam6d_split2_f16(v.z, v.w, h1, l1);
-  hi = __builtin_bit_cast(half4, u32x2{h0, h1});
-  lo = __builtin_bit_cast(half4, u32x2{l0, l1});
-}
 
 // The products of one staged chunk into the wave's TM x TN accumulators, per accumulator al . bh, then ah . bl, then ah . bh.  The
 // wave's tile starts at row wm of the A planes and row wn of the B planes; lane = (fr = lane & 31, fk = lane >> 5).

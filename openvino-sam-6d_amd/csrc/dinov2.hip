@@ -96,10 +96,10 @@ extern "C" int sam6d_dino_crop_proposals(const unsigned char* image, const float
 }
 
 // ---- self-attention, up to 272 tokens, 16 heads of 64 ---------------------------------------------------------------------------
-// One workgroup (8 waves) per (image, head), the scheme of xattn.hip's sattn_kernel at 17 key tiles, as a kernel of its own: that
-// kernel's register plan (13 score tiles, 7 probability k-steps and the prefetched next group beside them) and its two-groups-per-wave
-// schedule are built around 208 keys; 272 keys need 17 tiles, 9 k-steps and up to three token groups per wave, and keeping one source
-// for both would have changed the code generated for the 197-token callers.  Here:
+// One workgroup (8 waves) per (image, head), the register-chained scheme whose steps are in common.h ("shared steps of the
+// register-chained attention kernels") at 17 key tiles, with a schedule of its own: the 197-token kernels of xattn.hip plan their
+// registers (13 score tiles, 7 probability k-steps and the prefetched next group beside them) and their two groups per wave around 208
+// keys; 272 keys need 17 tiles, 9 k-steps and up to three token groups per wave.  Here:
 //   k_h (272 x 64) and v_h^T (64 x 288) are cut ONCE into fp16 hi / lo images in LDS (power-of-two scale per image; rows / keys
 //   beyond n are zero), in plain row-major order with 16 bytes of padding per row (no swizzle);
 //   every 16-token group of a wave runs   S^T (keys x tok) = k_h . (q / 8)^T     17 tiles x 2 k-steps
@@ -119,8 +119,6 @@ extern "C" int sam6d_dino_crop_proposals(const unsigned char* image, const float
 #define DA_VPLANE (64 * DA_VROW)          // 37 888
 #define DA_LDS (2 * DA_KPLANE + 2 * DA_VPLANE + 64)  // 154 176 bytes of the 160 KiB
 
-__device__ __forceinline__ float da_amax4(float4 v) { return fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))); }
-
 __global__ __launch_bounds__(DA_WAVES * 64) void dino_attention_kernel(const float* __restrict__ qkv, float* __restrict__ out, int n) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   unsigned char* kh = lds;
@@ -138,8 +136,8 @@ __global__ __launch_bounds__(DA_WAVES * 64) void dino_attention_kernel(const flo
   float mk = 0.f, mv = 0.f;
   for (int e = t; e < n * 16; e += DA_WAVES * 64) {
     const int j = e >> 4, c4 = e & 15;
-    mk = fmaxf(mk, da_amax4(*reinterpret_cast<const float4*>(kb + (size_t)j * (3 * DN_C) + 4 * c4)));
-    mv = fmaxf(mv, da_amax4(*reinterpret_cast<const float4*>(vb + (size_t)j * (3 * DN_C) + 4 * c4)));
+    mk = fmaxf(mk, amax4(*reinterpret_cast<const float4*>(kb + (size_t)j * (3 * DN_C) + 4 * c4)));
+    mv = fmaxf(mv, amax4(*reinterpret_cast<const float4*>(vb + (size_t)j * (3 * DN_C) + 4 * c4)));
   }
   mk = wave_max_dpp(mk);
   mv = wave_max_dpp(mv);
@@ -151,43 +149,15 @@ __global__ __launch_bounds__(DA_WAVES * 64) void dino_attention_kernel(const flo
   sk = pow2_scale(sk);
   sv = pow2_scale(sv);
 
-  // ---- k_h image: row = key, channel c at byte 2 c; every (key < 272, channel) slot is written (zeros beyond n)
-  for (int e = t; e < DA_MAXN * 16; e += DA_WAVES * 64) {
-    const int j = e >> 4, c4 = e & 15;
-    float4 kv = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (j < n) kv = *reinterpret_cast<const float4*>(kb + (size_t)j * (3 * DN_C) + 4 * c4);  // (second read: L2)
-    const float e4[4] = {kv.x * sk, kv.y * sk, kv.z * sk, kv.w * sk};
-    half4 hi4, lo4;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      _Float16 hi, lo;
-      sam6d_split_f16(e4[u], hi, lo);
-      hi4[u] = hi;
-      lo4[u] = lo;
-    }
-    *reinterpret_cast<half4*>(kh + (size_t)j * DA_KROW + 8 * c4) = hi4;
-    *reinterpret_cast<half4*>(kl + (size_t)j * DA_KROW + 8 * c4) = lo4;
-  }
-  // ---- v_h^T image: row = channel d, key j at byte 2 j; every (channel, key < 288) slot is written (zeros beyond n).  A wave reads
-  // 64 consecutive channels of one key.
-  for (int e = t; e < (DA_VS * 32 / 4) * 64; e += DA_WAVES * 64) {
-    const int d = e & 63, jq = e >> 6;
-    half4 hi4, lo4;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int j = 4 * jq + u;
-      const float x = (j < n) ? vb[(size_t)j * (3 * DN_C) + d] * sv : 0.f;
-      _Float16 hi, lo;
-      sam6d_split_f16(x, hi, lo);
-      hi4[u] = hi;
-      lo4[u] = lo;
-    }
-    *reinterpret_cast<half4*>(vh + (size_t)d * DA_VROW + 8 * jq) = hi4;
-    *reinterpret_cast<half4*>(vl + (size_t)d * DA_VROW + 8 * jq) = lo4;
-  }
+  // ---- k_h image (272 rows) and v_h^T image (288 keys), zeros beyond n (second read of k and v: L2)
+  auto src = [&](int j) -> const float* { return kb + (size_t)j * (3 * DN_C); };
+  attn_build_k<64, DA_MAXN, DA_KROW, DA_WAVES * 64>(kh, kl, t, n, sk, src, 0);
+  attn_build_vt<64, DA_VS * 32 / 4, DA_VROW, DA_WAVES * 64>(vh, vl, t, n, sv, src, DN_C);
   __syncthreads();
 
   const float inv_k = 1.0f / sk, inv_v = (1.0f / sv) * (1.0f / 16384.0f);
+  // (the group loop keeps its own text: on the shared softmax / split / fragment / store steps it measured 1.3 % slower, see
+  // profiles/README.md, "Attention-kernel helpers")
   for (int grp = wave; grp < ngroups; grp += DA_WAVES) {  // (wave-uniform)
     const int tok = min(grp * 16 + fr, n - 1);
     // q / 8 (the softmax scale 1 / sqrt(64): a power of two) as split B fragments: k-slot 8 g + e of step ks = channel 32 ks + 8 g + e
@@ -198,7 +168,7 @@ __global__ __launch_bounds__(DA_WAVES * 64) void dino_attention_kernel(const flo
       qa[ks] = *reinterpret_cast<const float4*>(qsrc + 32 * ks + 8 * fg);
       qb[ks] = *reinterpret_cast<const float4*>(qsrc + 32 * ks + 8 * fg + 4);
     }
-    float qm = fmaxf(fmaxf(da_amax4(qa[0]), da_amax4(qb[0])), fmaxf(da_amax4(qa[1]), da_amax4(qb[1])));
+    float qm = fmaxf(fmaxf(amax4(qa[0]), amax4(qb[0])), fmaxf(amax4(qa[1]), amax4(qb[1])));
     const float sq = pow2_scale(tok_max(qm * 0.125f));
     half8 qh[2], ql[2];
 #pragma unroll

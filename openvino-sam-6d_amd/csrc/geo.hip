@@ -100,7 +100,7 @@ __global__ __launch_bounds__(256) void geo_index_kernel(const float* __restrict_
   idx4[e] = make_float4(out[0], out[1], out[2], out[3]);
   // embedding arguments are index * omega with omega <= 1: remember when an index leaves the range of the branch-free
   // sincos (never for radius-normalised clouds: the largest index is the bg-point distance, ~870)
-  const float m = fmaxf(fmaxf(fabsf(out[0]), fabsf(out[1])), fmaxf(fabsf(out[2]), fabsf(out[3])));
+  const float m = amax4(out[0], out[1], out[2], out[3]);
   if (!(m < SAM6D_FAST_SINCOS_LIMIT)) atomicMax(maxflag, 1);
 }
 

@@ -173,8 +173,8 @@ __global__ __launch_bounds__(768) void rpe_score_kernel(const float4* __restrict
       float am = 0.f;
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
-        am = fmaxf(am, fmaxf(fmaxf(fabsf(a[u].x), fabsf(a[u].y)), fmaxf(fabsf(a[u].z), fabsf(a[u].w))));
-        am = fmaxf(am, fmaxf(fmaxf(fabsf(b[u].x), fabsf(b[u].y)), fmaxf(fabsf(b[u].z), fabsf(b[u].w))));
+        am = fmaxf(am, amax4(a[u]));
+        am = fmaxf(am, amax4(b[u]));
       }
       am = wave_max_dpp(am);
       int k2 = 14 - __builtin_amdgcn_frexp_expf(am);  // am * 2^k2 in [2^13, 2^14)

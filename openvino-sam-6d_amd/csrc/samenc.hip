@@ -2,8 +2,8 @@
 // :166-182 Block.forward, :224-240 Attention.forward, :243-289 window_partition / window_unpartition, :292-361 get_rel_pos /
 // add_decomposed_rel_pos; common.py:38-43 LayerNorm2d): the attention with decomposed relative-position bias, 16 heads of 80, on the
 // 64 x 64 token grid of a 1024 x 1024 image, in its two forms, and the gather of the neck's 3 x 3 convolution.
-//   window   14 x 14 windows of the grid padded to 70 x 70: one workgroup per (window, head, image), the scheme of dinov2.hip's
-//            dino_attention_kernel at 13 key tiles.  Partition and un-partition are index arithmetic; a padded position is a key whose
+//   window   14 x 14 windows of the grid padded to 70 x 70: one workgroup per (window, head, image), the register-chained scheme of
+//            common.h ("shared steps of the register-chained attention kernels") at 13 key tiles.  Partition and un-partition are index arithmetic; a padded position is a key whose
 //            k and v are the qkv bias (the reference pads after norm1, so the padded token is zero) and is never a query.
 //   global   4096 keys: one workgroup per (128 queries, head, image), online softmax over 64 tiles of 64 keys = one grid row each.
 //            Every workgroup cuts the k and v tiles it reads into fp16 hi / lo images itself (scale per tile): no pre-pass, no
@@ -13,7 +13,7 @@
 // is T^T = R . q^T, two small MFMA products per 16-query group (R split in registers from global memory), re-indexed through a
 // wave-private LDS table U[token][k position]; q . k is evaluated unscaled and multiplied by 1 / sqrt(80) in fp32.  Products are
 // v_mfma_f32_16x16x32_f16 with three terms (lo.hi, hi.lo, hi.hi) and power-of-two operand scales; softmax in fp32; the probabilities
-// never leave the registers (accumulator layout of S^T = B-operand layout of the second product, see dinov2.hip).  Head width 80 is
+// never leave the registers (accumulator layout of S^T = B-operand layout of the second product, see common.h).  Head width 80 is
 // zero-padded to three k-steps of 32 in the fragments, not in memory.  The kernels do not distinguish matmul modes 0 and 1 (as
 // sattn_kernel and dino_attention_kernel).
 //
@@ -31,50 +31,9 @@
 #define SE_SCALE 0.11180339887498948f  // 80^-0.5
 #define SE_LOG2E 1.4426950408889634f
 
-__device__ __forceinline__ float se_amax4(float4 v) { return fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))); }
-
-__device__ __forceinline__ f32x4 se_mfma3(half8 ah, half8 al, half8 bh, half8 bl, f32x4 acc) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, acc, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, acc, 0, 0, 0);
-}
-
 __device__ __forceinline__ void se_wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
-}
-
-// 8 floats, scaled, as one split operand
-__device__ __forceinline__ void se_split8(float4 a, float4 b, float s, half8& hi8, half8& lo8) {
-  const float e8[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-#pragma unroll
-  for (int u = 0; u < 8; ++u) {
-    _Float16 hi, lo;
-    sam6d_split_f16(e8[u] * s, hi, lo);
-    hi8[u] = hi;
-    lo8[u] = lo;
-  }
-}
-
-// The 80 channels of a row at `src` as the split operand of three k-steps: slot 8 fg + e of step ks = channel 32 ks + 8 fg + e, zero
-// from channel 80 on.  The row's own scale (over the four lanes of the token) is returned.
-__device__ __forceinline__ float se_split_q(const float* __restrict__ src, int fg, half8* qh, half8* ql) {
-  float4 a[3], b[3];
-  float m = 0.f;
-#pragma unroll
-  for (int ks = 0; ks < 3; ++ks) {
-    const int c = 32 * ks + 8 * fg;
-    a[ks] = b[ks] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (c < SE_HD) {
-      a[ks] = *reinterpret_cast<const float4*>(src + c);
-      b[ks] = *reinterpret_cast<const float4*>(src + c + 4);
-    }
-    m = fmaxf(m, fmaxf(se_amax4(a[ks]), se_amax4(b[ks])));
-  }
-  const float sq = pow2_scale(tok_max(m));
-#pragma unroll
-  for (int ks = 0; ks < 3; ++ks) se_split8(a[ks], b[ks], sq, qh[ks], ql[ks]);
-  return sq;
 }
 
 // A operand of k-step ks from a k image (rows of SE_KROW bytes per plane): channels 32 ks + 8 fg .. + 7 of `row`, zero from 80 on
@@ -90,7 +49,7 @@ __device__ __forceinline__ void se_k_frag(const unsigned char* kh, const unsigne
 // power-of-two scale of a relative-position table (nr x 80 fp32): every wave scans it on its own
 __device__ __forceinline__ float se_table_scale(const float* __restrict__ rel, int nr, int lane) {
   float m = 0.f;
-  for (int e = lane; e < nr * (SE_HD / 4); e += 64) m = fmaxf(m, se_amax4(*reinterpret_cast<const float4*>(rel + 4 * e)));
+  for (int e = lane; e < nr * (SE_HD / 4); e += 64) m = fmaxf(m, amax4(*reinterpret_cast<const float4*>(rel + 4 * e)));
   return pow2_scale(wave_max_dpp(m));
 }
 
@@ -109,8 +68,8 @@ __device__ __forceinline__ f32x4 se_rel_tile(const float* __restrict__ rel, int 
       b = *reinterpret_cast<const float4*>(rel + (size_t)row * SE_HD + c + 4);
     }
     half8 ah, al;
-    se_split8(a, b, sr, ah, al);
-    acc = se_mfma3(ah, al, qh[ks], ql[ks], acc);
+    split8(a, b, 1.0f, sr, ah, al);
+    acc = mfma3_16(ah, al, qh[ks], ql[ks], acc);
   }
   return acc;
 }
@@ -156,43 +115,17 @@ __global__ __launch_bounds__(SW_WAVES * 64) void sam_window_attention_kernel(con
   for (int e = t; e < SW_TOK * (SE_HD / 4); e += SW_WAVES * 64) {
     const int j = e / (SE_HD / 4), c4 = e % (SE_HD / 4);
     const float* row = src(j);
-    mk = fmaxf(mk, se_amax4(*reinterpret_cast<const float4*>(row + D + 4 * c4)));
-    mv = fmaxf(mv, se_amax4(*reinterpret_cast<const float4*>(row + 2 * D + 4 * c4)));
+    mk = fmaxf(mk, amax4(*reinterpret_cast<const float4*>(row + D + 4 * c4)));
+    mv = fmaxf(mv, amax4(*reinterpret_cast<const float4*>(row + 2 * D + 4 * c4)));
   }
-  mk = wave_max_dpp(mk);
-  mv = wave_max_dpp(mv);
-  if (lane == 0) { red[wave] = mk; red[8 + wave] = mv; }
+  wg_amax_put(mk, mv, red, wave, lane);
   __syncthreads();
-  float sk = 0.f, sv = 0.f;
-#pragma unroll
-  for (int w = 0; w < SW_WAVES; ++w) { sk = fmaxf(sk, red[w]); sv = fmaxf(sv, red[8 + w]); }
-  sk = pow2_scale(sk);
-  sv = pow2_scale(sv);
+  float sk, sv;
+  wg_scales_get(red, sk, sv);
 
-  // ---- k image: row = key, channel c at byte 2 c (zeros from key 196 on; the row padding is never read)
-  for (int e = t; e < 16 * SW_NT * (SE_HD / 4); e += SW_WAVES * 64) {
-    const int j = e / (SE_HD / 4), c4 = e % (SE_HD / 4);
-    float4 kv = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (j < SW_TOK) kv = *reinterpret_cast<const float4*>(src(j) + D + 4 * c4);
-    half4 hi4, lo4;
-    split4(make_float4(kv.x * sk, kv.y * sk, kv.z * sk, kv.w * sk), hi4, lo4);
-    *reinterpret_cast<half4*>(kh + (size_t)j * SE_KROW + 8 * c4) = hi4;
-    *reinterpret_cast<half4*>(kl + (size_t)j * SE_KROW + 8 * c4) = lo4;
-  }
-  // ---- v^T image: row = channel d, key j at byte 2 j (zeros from key 196 to 223)
-  for (int e = t; e < (SW_VS * 32 / 4) * SE_HD; e += SW_WAVES * 64) {
-    const int d = e % SE_HD, jq = e / SE_HD;
-    float x4[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int j = 4 * jq + u;
-      x4[u] = (j < SW_TOK) ? src(j)[2 * D + d] * sv : 0.f;
-    }
-    half4 hi4, lo4;
-    split4(make_float4(x4[0], x4[1], x4[2], x4[3]), hi4, lo4);
-    *reinterpret_cast<half4*>(vh + (size_t)d * SW_VROW + 8 * jq) = hi4;
-    *reinterpret_cast<half4*>(vl + (size_t)d * SW_VROW + 8 * jq) = lo4;
-  }
+  // ---- k image (208 rows, zeros from key 196 on; the row padding is never read) and v^T image (zeros from key 196 to 223)
+  attn_build_k<SE_HD, 16 * SW_NT, SE_KROW, SW_WAVES * 64>(kh, kl, t, SW_TOK, sk, src, D);
+  attn_build_vt<SE_HD, SW_VS * 32 / 4, SW_VROW, SW_WAVES * 64>(vh, vl, t, SW_TOK, sv, src, 2 * D);
   const float srh = se_table_scale(rel_h, 2 * SW_WIN - 1, lane), srw = se_table_scale(rel_w, 2 * SW_WIN - 1, lane);
   __syncthreads();
 
@@ -205,7 +138,7 @@ __global__ __launch_bounds__(SW_WAVES * 64) void sam_window_attention_kernel(con
     const int gy = SW_WIN * wy + qy, gx = SW_WIN * wx + qx;
     const bool real = grp * 16 + fr < SW_TOK && gy < SE_GRID && gx < SE_GRID;
     half8 qh[3], ql[3];
-    const float sq = se_split_q(src(tq), fg, qh, ql);
+    const float sq = split_q_row<SE_HD>(src(tq), fg, 1.0f, qh, ql);
     // (lane coordinates the optimiser cannot see through: what the bias needs that does not depend on the group -- the split table
     // fragments, the 104 (ky, kx) pairs of the lane's keys -- would otherwise be hoisted out of this loop into ~200 registers)
     int fro = fr, fgo = fg;
@@ -239,7 +172,7 @@ __global__ __launch_bounds__(SW_WAVES * 64) void sam_window_attention_kernel(con
       for (int ks = 0; ks < 3; ++ks) {
         half8 ah, al;
         se_k_frag(kh, kl, 16 * i + fr, ks, fg, ah, al);
-        acc = se_mfma3(ah, al, qh[ks], ql[ks], acc);
+        acc = mfma3_16(ah, al, qh[ks], ql[ks], acc);
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -254,49 +187,21 @@ __global__ __launch_bounds__(SW_WAVES * 64) void sam_window_attention_kernel(con
       }
     }
     se_wave_sync();  // the table is read; the next group may write it
-    mx = tok_max(mx);
-    float sum = 0.f;
-#pragma unroll
-    for (int i = 0; i < SW_NT; ++i)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        s[i][r] = __builtin_amdgcn_exp2f((s[i][r] - mx) * SE_LOG2E);
-        sum += s[i][r];
-      }
-    sum = tok_sum(sum);
-    const float pscale = 16384.0f / sum;  // probabilities times 2^14 (fp16-safe), the 2^-14 is in inv_v
-    half8 ph[SW_VS], pl[SW_VS];
-#pragma unroll
-    for (int i = 0; i < 2 * SW_VS; ++i)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float pv = i < SW_NT ? s[i < SW_NT ? i : 0][r] * pscale : 0.f;
-        _Float16 hi, lo;
-        sam6d_split_f16(pv, hi, lo);
-        ph[i >> 1][4 * (i & 1) + r] = hi;
-        pl[i >> 1][4 * (i & 1) + r] = lo;
-      }
-    // out^T tiles: rows = channels 16 i + fr (A operand from the v^T image: keys 32 s + 4 g .. + 3 and 32 s + 16 + 4 g .. + 3)
+    const float pscale = attn_softmax(s, mx);
+    const SplitB<SW_VS> p = attn_pack_probs<SW_NT, SW_VS>(s, pscale);
     f32x4 o[SE_HD / 16];
 #pragma unroll
     for (int i = 0; i < SE_HD / 16; ++i) {
       f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int st = 0; st < SW_VS; ++st) {
-        const size_t off = (size_t)(16 * i + fr) * SW_VROW + 2 * (32 * st + 4 * fg);
-        const half4 h0 = *reinterpret_cast<const half4*>(vh + off), h1 = *reinterpret_cast<const half4*>(vh + off + 32);
-        const half4 l0 = *reinterpret_cast<const half4*>(vl + off), l1 = *reinterpret_cast<const half4*>(vl + off + 32);
-        const half8 ah = half8{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-        const half8 al = half8{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
-        acc = se_mfma3(ah, al, ph[st], pl[st], acc);
+        const HiLo8 a = attn_vt_frag<SW_VROW>(vh, vl, 16 * i + fr, st, fg);
+        acc = mfma3_16(a.h, a.l, p.h[st], p.l[st], acc);
       }
       o[i] = acc;
     }
     if (real) {
-      float* dst = out + ((size_t)b * SE_NTOK + gy * SE_GRID + gx) * D + SE_HD * h;
-#pragma unroll
-      for (int i = 0; i < SE_HD / 16; ++i)
-        *reinterpret_cast<float4*>(dst + 16 * i + 4 * fg) = make_float4(o[i][0] * inv_v, o[i][1] * inv_v, o[i][2] * inv_v, o[i][3] * inv_v);
+      attn_store(out + ((size_t)b * SE_NTOK + gy * SE_GRID + gx) * D + SE_HD * h, o, inv_v, fg);
     }
   }
 }
@@ -356,7 +261,7 @@ __global__ __launch_bounds__(SG_WAVES * 64) void sam_global_attention_kernel(con
   const int qy = tok / SE_GRID, qx = tok % SE_GRID;
 
   half8 qh[3], ql[3];
-  const float sq = se_split_q(base + (size_t)tok * ld, fg, qh, ql);
+  const float sq = split_q_row<SE_HD>(base + (size_t)tok * ld, fg, 1.0f, qh, ql);
   // ---- bias tables of the wave's 16 queries: U[k position] = q . R[q position - k position + 63].  The w table first: the lane keeps
   // the 16 columns it adds in every key tile (key 16 i + 4 fg + r of a tile is grid column 16 i + 4 fg + r) in registers; the h table
   // stays in LDS, one value per tile.
@@ -408,19 +313,14 @@ __global__ __launch_bounds__(SG_WAVES * 64) void sam_global_attention_kernel(con
         const float* vp = vb + (size_t)(4 * jq) * ld + d;
         vv[u] = make_float4(vp[0], vp[ld], vp[2 * ld], vp[3 * ld]);
       }
-      mk = fmaxf(mk, se_amax4(kv[u]));
-      mv = fmaxf(mv, se_amax4(vv[u]));
+      mk = fmaxf(mk, amax4(kv[u]));
+      mv = fmaxf(mv, amax4(vv[u]));
     }
-    mk = wave_max_dpp(mk);
-    mv = wave_max_dpp(mv);
     float* rd = red + 16 * (kt & 1);
-    if (lane == 0) { rd[wave] = mk; rd[8 + wave] = mv; }
+    wg_amax_put(mk, mv, rd, wave, lane);
     __syncthreads();  // every wave is through with the previous tile's images
-    float sk = 0.f, sv = 0.f;
-#pragma unroll
-    for (int w = 0; w < SG_WAVES; ++w) { sk = fmaxf(sk, rd[w]); sv = fmaxf(sv, rd[8 + w]); }
-    sk = pow2_scale(sk);
-    sv = pow2_scale(sv);
+    float sk, sv;
+    wg_scales_get(rd, sk, sv);
 #pragma unroll
     for (int u = 0; u < SG_PER; ++u) {
       const int e = t + SG_WAVES * 64 * u;
@@ -450,7 +350,7 @@ __global__ __launch_bounds__(SG_WAVES * 64) void sam_global_attention_kernel(con
       for (int ks = 0; ks < 3; ++ks) {
         half8 ah, al;
         se_k_frag(kh, kl, 16 * i + fr, ks, fg, ah, al);
-        acc = se_mfma3(ah, al, qh[ks], ql[ks], acc);
+        acc = mfma3_16(ah, al, qh[ks], ql[ks], acc);
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -481,22 +381,15 @@ __global__ __launch_bounds__(SG_WAVES * 64) void sam_global_attention_kernel(con
       f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int st = 0; st < 2; ++st) {
-        const size_t off = (size_t)(16 * i + fr) * SG_VROW + 2 * (32 * st + 4 * fg);
-        const half4 h0 = *reinterpret_cast<const half4*>(vh + off), h1 = *reinterpret_cast<const half4*>(vh + off + 32);
-        const half4 l0 = *reinterpret_cast<const half4*>(vl + off), l1 = *reinterpret_cast<const half4*>(vl + off + 32);
-        const half8 ah = half8{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-        const half8 al = half8{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
-        acc = se_mfma3(ah, al, ph[st], pl[st], acc);
+        const HiLo8 a = attn_vt_frag<SG_VROW>(vh, vl, 16 * i + fr, st, fg);
+        acc = mfma3_16(a.h, a.l, ph[st], pl[st], acc);
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r) o[i][r] = o[i][r] * alpha + acc[r] * inv_v;
     }
   }
   const float rl = 1.0f / tok_sum(lrun);
-  float* dst = out + ((size_t)b * SE_NTOK + tok) * D + SE_HD * h;
-#pragma unroll
-  for (int i = 0; i < SE_HD / 16; ++i)
-    *reinterpret_cast<float4*>(dst + 16 * i + 4 * fg) = make_float4(o[i][0] * rl, o[i][1] * rl, o[i][2] * rl, o[i][3] * rl);
+  attn_store(out + ((size_t)b * SE_NTOK + tok) * D + SE_HD * h, o, rl, fg);
 }
 
 extern "C" int sam6d_sam_global_attention(const float* qkv, const float* rel_h, const float* rel_w, float* out, int B, int heads,

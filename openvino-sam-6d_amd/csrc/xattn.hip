@@ -15,6 +15,8 @@
 //     S^T (keys x tok) = k_h (208 x 64)  . q^T          2 k-steps, 13 key tiles; softmax over the lane's 52 values + 3 partner lanes
 //     out^T (64 x tok) = v_h^T (64 x 224) . P^T         7 k-steps
 // fp16 x3 split products with power-of-two operand scales (per token row for x, q, P; per image for Wq, k, v): range-safe, ~1e-6.
+// The steps this file's two kernels share with dinov2.hip and samenc.hip (three-product MFMA, image scales, softmax, probability
+// split, output store) are in common.h, "shared steps of the register-chained attention kernels".
 #include "common.h"
 #include <stdlib.h>
 #include "../../include/sam6d_hip.h"
@@ -58,11 +60,7 @@ __device__ __forceinline__ void xa_mma_step(f32x4& acc, unsigned rb, int row, in
   constexpr int cur = S % (XA_FD + 1);
   xa_wait<2 * newer>(fh[cur], fl[cur]);
   const half8 ah = __builtin_bit_cast(half8, fh[cur]), al = __builtin_bit_cast(half8, fl[cur]);
-  if (!half) {  // (launch-uniform) matmul mode 2 keeps the hi . hi product only
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, xh[S], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, xl[S], acc, 0, 0, 0);
-  }
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, xh[S], acc, 0, 0, 0);
+  acc = mfma3_16(ah, al, xh[S], xl[S], acc, half);  // (launch-uniform) matmul mode 2 keeps the hi . hi product only
   if constexpr (S + 1 < KS) xa_mma_step<ROWB, LOCH, KS, S + 1>(acc, rb, row, fg, xh, xl, fh, fl, half);
 }
 template <int ROWB, int LOCH, int KS>
@@ -146,23 +144,18 @@ __global__ __launch_bounds__(XA_WAVES * 64) void xattn_kernel(XaArgs a) {
           const float4 bv = *reinterpret_cast<const float4*>(a.bkv + 256 + 64 * h + 16 * i + 4 * fg);
           kacc[gi][i] = f32x4{ak[0] * inv + bk.x, ak[1] * inv + bk.y, ak[2] * inv + bk.z, ak[3] * inv + bk.w};
           vacc[gi][i] = f32x4{av[0] * inv + bv.x, av[1] * inv + bv.y, av[2] * inv + bv.z, av[3] * inv + bv.w};
-          mk = fmaxf(mk, fmaxf(fmaxf(fabsf(kacc[gi][i][0]), fabsf(kacc[gi][i][1])), fmaxf(fabsf(kacc[gi][i][2]), fabsf(kacc[gi][i][3]))));
-          mv = fmaxf(mv, fmaxf(fmaxf(fabsf(vacc[gi][i][0]), fabsf(vacc[gi][i][1])), fmaxf(fabsf(vacc[gi][i][2]), fabsf(vacc[gi][i][3]))));
+          mk = fmaxf(mk, amax4(kacc[gi][i]));
+          mv = fmaxf(mv, amax4(vacc[gi][i]));
         }
       } else {
 #pragma unroll
         for (int i = 0; i < 4; ++i) kacc[gi][i] = vacc[gi][i] = f32x4{0.f, 0.f, 0.f, 0.f};
       }
     }
-    mk = wave_max_dpp(mk);
-    mv = wave_max_dpp(mv);
-    if (lane == 0) { red[wave] = mk; red[8 + wave] = mv; }
+    wg_amax_put(mk, mv, red, wave, lane);
     __syncthreads();  // every wave is done with both weight images
     dma64(a.wq + (size_t)h * XA_WQ_BYTES, regA);
-#pragma unroll
-    for (int w = 0; w < XA_WAVES; ++w) { sk = fmaxf(sk, red[w]); sv = fmaxf(sv, red[8 + w]); }
-    sk = pow2_scale(sk);
-    sv = pow2_scale(sv);
+    wg_scales_get(red, sk, sv);
     // k_h image rows of this wave's tokens, over the Wv image (rows >= m are never read unmasked)
 #pragma unroll
     for (int gi = 0; gi < 2; ++gi) {
@@ -202,14 +195,9 @@ __global__ __launch_bounds__(XA_WAVES * 64) void xattn_kernel(XaArgs a) {
       mk = fmaxf(mk, fabsf(kreg[i]));
       mv = fmaxf(mv, fabsf(vreg[i]));
     }
-    mk = wave_max_dpp(mk);
-    mv = wave_max_dpp(mv);
-    if (lane == 0) { red[wave] = mk; red[8 + wave] = mv; }
+    wg_amax_put(mk, mv, red, wave, lane);
     __syncthreads();
-#pragma unroll
-    for (int w = 0; w < XA_WAVES; ++w) { sk = fmaxf(sk, red[w]); sv = fmaxf(sv, red[8 + w]); }
-    sk = pow2_scale(sk);
-    sv = pow2_scale(sv);
+    wg_scales_get(red, sk, sv);
     // k_h image: every (key < 208, channel) slot is written (zeros beyond m), so no separate clearing pass
 #pragma unroll
     for (int i = 0; i < XA_EPT; ++i) {
@@ -251,8 +239,8 @@ __global__ __launch_bounds__(XA_WAVES * 64) void xattn_kernel(XaArgs a) {
         float mx = 0.f;
 #pragma unroll
         for (int s = 0; s < 8; ++s) {
-          mx = fmaxf(mx, fmaxf(fmaxf(fabsf(va[s].x), fabsf(va[s].y)), fmaxf(fabsf(va[s].z), fabsf(va[s].w))));
-          mx = fmaxf(mx, fmaxf(fmaxf(fabsf(vb4[s].x), fabsf(vb4[s].y)), fmaxf(fabsf(vb4[s].z), fabsf(vb4[s].w))));
+          mx = fmaxf(mx, amax4(va[s]));
+          mx = fmaxf(mx, amax4(vb4[s]));
         }
         const float sx = pow2_scale(tok_max(mx));
 #pragma unroll
@@ -282,7 +270,7 @@ __global__ __launch_bounds__(XA_WAVES * 64) void xattn_kernel(XaArgs a) {
           acc[i][1] = acc[i][1] * inv + bb.y * 0.125f;
           acc[i][2] = acc[i][2] * inv + bb.z * 0.125f;
           acc[i][3] = acc[i][3] * inv + bb.w * 0.125f;
-          qm = fmaxf(qm, fmaxf(fmaxf(fabsf(acc[i][0]), fabsf(acc[i][1])), fmaxf(fabsf(acc[i][2]), fabsf(acc[i][3]))));
+          qm = fmaxf(qm, amax4(acc[i]));
         }
         sq[gi] = pow2_scale(tok_max(qm));
 #pragma unroll
@@ -361,41 +349,16 @@ __global__ __launch_bounds__(XA_WAVES * 64) void xattn_kernel(XaArgs a) {
           s[i][r] = key < m ? s[i][r] * inv : -INFINITY;
           mx = fmaxf(mx, s[i][r]);
         }
-      mx = tok_max(mx);
-      float sum = 0.f;
-#pragma unroll
-      for (int i = 0; i < XA_NT; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          s[i][r] = __builtin_amdgcn_exp2f((s[i][r] - mx) * 1.4426950408889634f);
-          sum += s[i][r];
-        }
-      sum = tok_sum(sum);
-      const float pscale = 16384.0f / sum;  // probabilities times 2^14 (<= 2^14: fp16-safe), the 2^-14 is in inv_v
-      half8 ph[7], pl[7];
-#pragma unroll
-      for (int i = 0; i < 14; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float pv = i < XA_NT ? s[i < XA_NT ? i : 0][r] * pscale : 0.f;
-          _Float16 hi, lo;
-          sam6d_split_f16(pv, hi, lo);
-          ph[i >> 1][4 * (i & 1) + r] = hi;
-          pl[i >> 1][4 * (i & 1) + r] = lo;
-        }
+      const float pscale = attn_softmax(s, mx);  // probabilities times 2^14, the 2^-14 is in inv_v
+      const SplitB<7> p = attn_pack_probs<XA_NT, 7>(s, pscale);
       f32x4 o[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         o[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-        xa_mma<1024, 32, 7>(o[i], regA, 16 * i, ph, pl, fr, fg, half);
+        xa_mma<1024, 32, 7>(o[i], regA, 16 * i, p.h, p.l, fr, fg, half);
       }
       const int tok = grp * 16 + fr;
-      if (tok < n) {
-        float* dst = a.out + ((size_t)b * n + tok) * 256 + 64 * h;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-          *reinterpret_cast<float4*>(dst + 16 * i + 4 * fg) = make_float4(o[i][0] * inv_v, o[i][1] * inv_v, o[i][2] * inv_v, o[i][3] * inv_v);
-      }
+      if (tok < n) attn_store(a.out + ((size_t)b * n + tok) * 256 + 64 * h, o, inv_v, fg);
     }
   }
 }
@@ -495,11 +458,7 @@ __device__ __forceinline__ void xa_rows_step(f32x4* acc, unsigned kb, int fr, in
   xa_wait<2 * newer>(fh[cur], fl[cur]);
   const half8 ah = __builtin_bit_cast(half8, fh[cur]), al = __builtin_bit_cast(half8, fl[cur]);
   f32x4& c = acc[S >> 1];
-  if (!half) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, xh[S & 1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, xl[S & 1], c, 0, 0, 0);
-  }
-  c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, xh[S & 1], c, 0, 0, 0);
+  c = mfma3_16(ah, al, xh[S & 1], xl[S & 1], c, half);
   if constexpr (S + 1 < 2 * NT) xa_rows_step<NT, S + 1>(acc, kb, fr, fg, xh, xl, fh, fl, half);
 }
 
@@ -583,20 +542,18 @@ __global__ __launch_bounds__(XA_WAVES * 64) void sattn_kernel(SaArgs a) {
   for (int i = t; i < XA_WQ_BYTES / 16; i += XA_WAVES * 64) reinterpret_cast<uint4*>(regA)[i] = make_uint4(0u, 0u, 0u, 0u);
   float mk = 0.f, mv = 0.f;
 #pragma unroll
-  for (int i = 0; i < XA_KT; ++i) mk = fmaxf(mk, fmaxf(fmaxf(fabsf(kreg[i].x), fabsf(kreg[i].y)), fmaxf(fabsf(kreg[i].z), fabsf(kreg[i].w))));
+  for (int i = 0; i < XA_KT; ++i) mk = fmaxf(mk, amax4(kreg[i]));
 #pragma unroll
-  for (int i = 0; i < XA_VT; ++i) mv = fmaxf(mv, fmaxf(fmaxf(fabsf(vreg[i][0]), fabsf(vreg[i][1])), fmaxf(fabsf(vreg[i][2]), fabsf(vreg[i][3]))));
+  for (int i = 0; i < XA_VT; ++i) mv = fmaxf(mv, amax4(vreg[i][0], vreg[i][1], vreg[i][2], vreg[i][3]));
+  // (wg_amax_put open-coded: the stamp sits between its two steps, and the call costs this kernel a register)
   mk = wave_max_dpp(mk);
   mv = wave_max_dpp(mv);
   SA_ST(1);
   if (lane == 0) { red[wave] = mk; red[8 + wave] = mv; }
   __syncthreads();
   SA_ST(2);
-  float sk = 0.f, sv = 0.f;
-#pragma unroll
-  for (int w = 0; w < XA_WAVES; ++w) { sk = fmaxf(sk, red[w]); sv = fmaxf(sv, red[8 + w]); }
-  sk = pow2_scale(sk);
-  sv = pow2_scale(sv);
+  float sk, sv;
+  wg_scales_get(red, sk, sv);
   // k_h image: channels 4 c .. 4 c + 3 of key j are four consecutive slots (8 bytes) of its row; every (key < 208, channel) slot is
   // written (zeros beyond m)
 #pragma unroll
@@ -644,21 +601,12 @@ __global__ __launch_bounds__(XA_WAVES * 64) void sattn_kernel(SaArgs a) {
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {
         const float4 u = qa[gi][s2], w = qb[gi][s2];
-        qm = fmaxf(qm, fmaxf(fmaxf(fabsf(u.x), fabsf(u.y)), fmaxf(fabsf(u.z), fabsf(u.w))));
-        qm = fmaxf(qm, fmaxf(fmaxf(fabsf(w.x), fabsf(w.y)), fmaxf(fabsf(w.z), fabsf(w.w))));
+        qm = fmaxf(qm, amax4(u));
+        qm = fmaxf(qm, amax4(w));
       }
       const float sq = pow2_scale(tok_max(qm * 0.125f));
 #pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        const float e8[8] = {qa[gi][s2].x, qa[gi][s2].y, qa[gi][s2].z, qa[gi][s2].w, qb[gi][s2].x, qb[gi][s2].y, qb[gi][s2].z, qb[gi][s2].w};
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          _Float16 hi, lo;
-          sam6d_split_f16(e8[u] * 0.125f * sq, hi, lo);
-          qh[s2][u] = hi;
-          ql[s2][u] = lo;
-        }
-      }
+      for (int s2 = 0; s2 < 2; ++s2) split8(qa[gi][s2], qb[gi][s2], 0.125f, sq, qh[s2], ql[s2]);
       f32x4 s[XA_NT];
 #pragma unroll
       for (int i = 0; i < XA_NT; ++i) s[i] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -681,28 +629,8 @@ __global__ __launch_bounds__(XA_WAVES * 64) void sattn_kernel(SaArgs a) {
           mx = fmaxf(mx, s[i][r]);
         }
       }
-      mx = tok_max(mx);
-      float sum = 0.f;
-#pragma unroll
-      for (int i = 0; i < XA_NT; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          s[i][r] = __builtin_amdgcn_exp2f((s[i][r] - mx) * 1.4426950408889634f);
-          sum += s[i][r];
-        }
-      sum = tok_sum(sum);
-      const float pscale = 16384.0f / sum;  // probabilities times 2^14 (fp16-safe), the 2^-14 is in inv_v
-      half8 ph[7], pl[7];
-#pragma unroll
-      for (int i = 0; i < 14; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float pv = i < XA_NT ? s[i < XA_NT ? i : 0][r] * pscale : 0.f;
-          _Float16 hi, lo;
-          sam6d_split_f16(pv, hi, lo);
-          ph[i >> 1][4 * (i & 1) + r] = hi;
-          pl[i >> 1][4 * (i & 1) + r] = lo;
-        }
+      const float pscale = attn_softmax(s, mx);  // probabilities times 2^14, the 2^-14 is in inv_v
+      const SplitB<7> p = attn_pack_probs<XA_NT, 7>(s, pscale);
       if (gi == 0) {  // the next group's inputs: in flight under this group's P.v and store and the next group's score tiles
         load_g(1);      // (requested earlier, beside the logits and the probability halves, they do not fit the register file)
         load_q(1);
@@ -712,15 +640,10 @@ __global__ __launch_bounds__(XA_WAVES * 64) void sattn_kernel(SaArgs a) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         o[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-        xa_mma<1024, 32, 7>(o[i], regA, 16 * i, ph, pl, fr, fg, half);
+        xa_mma<1024, 32, 7>(o[i], regA, 16 * i, p.h, p.l, fr, fg, half);
       }
       SA_ST(8 + 5 * gi);
-      if (grp * 16 + fr < n) {
-        float* dst = a.out + ((size_t)b * n + tok) * L::C + 64 * h;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-          *reinterpret_cast<float4*>(dst + 16 * i + 4 * fg) = make_float4(o[i][0] * inv_v, o[i][1] * inv_v, o[i][2] * inv_v, o[i][3] * inv_v);
-      }
+      if (grp * 16 + fr < n) attn_store(a.out + ((size_t)b * n + tok) * L::C + 64 * h, o, inv_v, fg);
       SA_ST(9 + 5 * gi);
     }
   };

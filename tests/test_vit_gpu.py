@@ -113,18 +113,21 @@ def test_one_block(model, dev, mode):
     assert _rel(got, ref) <= BOUND[mode]
 
 
-@pytest.mark.parametrize("B", [1, 3])
-def test_attention_alone(dev, B):
-    g = torch.Generator().manual_seed(11 + B)
-    qkv = torch.randn(B * 197, 2304, generator=g) * 3.0
+# (B, n): the encoder's 197 tokens; one token; one full 16-token group; a group plus one token; every key tile full and both groups of
+# every wave in use
+@pytest.mark.parametrize("B,n", [(1, 197), (3, 197), (2, 1), (2, 16), (2, 17), (1, 208)])
+def test_attention_alone(dev, B, n):
+    g = torch.Generator().manual_seed(11 + B + (n if n != 197 else 0))
+    qkv = torch.randn(B * n, 2304, generator=g) * 3.0
     got = vit.attention(qkv.to(dev), B)
-    q, k, v = qkv.double().reshape(B, 197, 3, 12, 64).permute(2, 0, 3, 1, 4)
-    ref = F.scaled_dot_product_attention(q, k, v).transpose(1, 2).reshape(B * 197, 768)
+    q, k, v = qkv.double().reshape(B, n, 3, 12, 64).permute(2, 0, 3, 1, 4)
+    ref = F.scaled_dot_product_attention(q, k, v).transpose(1, 2).reshape(B * n, 768)
     q32, k32, v32 = (t.float().to(dev) for t in (q, k, v))
-    eager = F.scaled_dot_product_attention(q32, k32, v32).transpose(1, 2).reshape(B * 197, 768)
+    eager = F.scaled_dot_product_attention(q32, k32, v32).transpose(1, 2).reshape(B * n, 768)
     e, e_eager = _rel(got, ref), _rel(eager, ref)
-    print("\n[vit] attention B=%d: max|HIP - f64| / max|f64| = %.3e, eager fp32 SDPA: %.3e" % (B, e, e_eager))
-    assert e <= 1e-5  # logits up to ~70 here: fp32's own rounding of them is ~4e-6 relative in the probabilities
+    print("\n[vit] attention B=%d n=%d: max|HIP - f64| / max|f64| = %.3e, eager fp32 SDPA: %.3e" % (B, n, e, e_eager))
+    assert got.shape == (B * n, 768)
+    assert e <= 1e-5  # logits up to ~70 at n = 197 (fewer keys: smaller): fp32's own rounding of them is ~4e-6 relative in the probabilities
 
 
 def test_attention_outliers(dev):
