@@ -684,6 +684,31 @@ int sam6d_amg_mask_stats(const float* low, const unsigned char* live, int M, int
 int sam6d_amg_unpack_masks(const unsigned* bits, const long long* idx, long n_src, int K, int out_h, int out_w, int x0, int y0,
                            int H, int W, int as_f32, void* out, void* stream);
 
+/* 8-connected component labelling of K binary masks, what cv2.connectedComponentsWithStats(.., 8) is asked for in remove_small_regions
+ * (ISM/segment_anything/utils/amg.py:267-291), in a canonical form: masks (K, H, W) u8, foreground = masks != 0 (invert == 0) or
+ * masks == 0 (invert != 0);
+ *   labels (K, H, W) i32 = 0 off the foreground, else 1 + the smallest row-major pixel index (y * W + x) of the pixel's component,
+ *   areas  (K, H, W) i32 = the pixel count of the pixel's component, 0 off the foreground.
+ * The result is a function of the mask alone (it does not depend on scheduling).  1 <= K <= 65535, H * W <= 2^31 - 2.
+ * ws: sam6d_mask_components_workspace_bytes(K, H, W) bytes of device memory (two i32 planes; 0 = sizes the entry refuses).
+ * (New entries only, so SAM6D_ABI_VERSION stays.) */
+size_t sam6d_mask_components_workspace_bytes(int K, int H, int W);
+int sam6d_mask_components(const unsigned char* masks, int K, int H, int W, int invert, int* labels, int* areas, void* ws,
+                          size_t ws_bytes, void* stream);
+/* replaces the per-mask host loop of postprocess_small_regions (ISM/segment_anything/automatic_mask_generator.py:324-372) with its two
+ * remove_small_regions calls (ISM/segment_anything/utils/amg.py:267-291) and the batched_mask_to_box after it (amg.py:303-346): masks
+ * (K, H, W) u8 are cleaned in place to 0 / 1.  First every 8-connected component of ~m with fewer than min_area pixels is filled
+ * (components that touch the image border included), then, on that result, m becomes the union of its components with at least
+ * min_area pixels, or, if there is none, its largest component (among equals the one whose first pixel in row-major order comes
+ * first: the library's rule, cv2's label numbering decides in the reference).  A pass that finds no component below min_area leaves
+ * the mask as it is.  changed (K) u8 = 1 where either pass found one; box (K, 4) i32 = (x0, y0, x1, y1) of the cleaned mask
+ * (inclusive; [0, 0, 0, 0] for an empty mask).  1 <= K <= 65535, H * W <= 2^31 - 2, min_area >= 1 (a size s is below a float
+ * threshold t exactly when s < ceil(t): the caller passes the ceiling).
+ * ws: sam6d_amg_small_regions_workspace_bytes(K, H, W) bytes of 8-byte aligned device memory (0 = sizes the entry refuses). */
+size_t sam6d_amg_small_regions_workspace_bytes(int K, int H, int W);
+int sam6d_amg_small_regions(unsigned char* masks, int K, int H, int W, int min_area, unsigned char* changed, int* box, void* ws,
+                            size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * SAM's mask decoder for point prompts (ISM/segment_anything/modeling/mask_decoder.py:112-149, its TwoWayTransformer
  * ISM/segment_anything/modeling/transformer.py:62-106): what lies between the dense projections over the P x 4096 image rows, which are

@@ -1,6 +1,7 @@
 """Drop-in for ISM/model/sam.py: CustomSamAutomaticMaskGenerator with the reference's constructor and `generate_masks` contract, its
 tail after the mask decoder on sam6d_hip.amg (one fused launch per point batch instead of the 1024 x 1024 logits, the RLE round trip
-through the host and torchvision's NMS).
+through the host and torchvision's NMS), and with it the min_mask_region_area clean-up (postprocess_small_regions: connected components, both
+passes, boxes and the second NMS on the device instead of cv2 per mask on the host).
 
 With hip_decoder (SAM6D_HIP_SAMDEC=1; off by default) prompt encoder and mask decoder run on sam6d_hip.samdec as well, and with
 hip_encoder (SAM6D_HIP_SAMENC=1; off by default) the ViT-H image encoder runs on sam6d_hip.samenc: `encode_image` and SamPredictor then
@@ -298,11 +299,15 @@ class CustomSamAutomaticMaskGenerator:
         self.predictor.reset_image()
         return amg.finish_crop(state, crop_box, orig_size, self.box_nms_thresh, mask_dtype)
 
-    # ---- min_mask_region_area > 0: the reference's host route (needs cv2), not part of the HIP path ----------------------------------
+    # ---- min_mask_region_area > 0: on a HIP device the library's route (sam6d_hip.amg.postprocess_small_regions: labelling, both passes,
+    # boxes and NMS on the device; governed by SAM6D_HIP_AMG like the tail); on the CPU, or with SAM6D_HIP_AMG=0, the reference's host
+    # route below, which needs cv2 ------------------------------------------------------------------------------------------------------
     @staticmethod
     def postprocess_small_regions(mask_data, min_area, nms_thresh):
         if len(mask_data["masks"]) == 0:
             return mask_data
+        if amg.hip_enabled(mask_data["masks"].device):
+            return amg.postprocess_small_regions(mask_data, min_area, nms_thresh)
         import cv2
 
         def clean(mask, holes):

@@ -140,6 +140,10 @@ SIGNATURES = {
     "sam6d_amg_mask_stats_workspace_bytes": [c_i] * 6,
     "sam6d_amg_mask_stats": [c_p, c_p] + [c_i] * 8 + [c_f, c_f] + [c_p] * 7 + [ctypes.c_size_t, c_p],
     "sam6d_amg_unpack_masks": [c_p, c_p, c_l] + [c_i] * 8 + [c_p, c_p],
+    "sam6d_mask_components_workspace_bytes": [c_i] * 3,
+    "sam6d_mask_components": [c_p] + [c_i] * 4 + [c_p, c_p, c_p, ctypes.c_size_t, c_p],
+    "sam6d_amg_small_regions_workspace_bytes": [c_i] * 3,
+    "sam6d_amg_small_regions": [c_p] + [c_i] * 4 + [c_p, c_p, c_p, ctypes.c_size_t, c_p],
     "sam6d_samdec_image_to_token": [c_p, c_l, c_l, c_p, c_p, c_p, c_p, c_l, c_p, c_p, c_f, c_p] + [c_i] * 6 + [c_p],
     "sam6d_samdec_token_to_image_workspace_bytes": [c_i],
     "sam6d_samdec_token_to_image": [c_p, c_p, c_p, c_l, c_l, c_p] + [c_i] * 6 + [c_p, ctypes.c_size_t, c_p],

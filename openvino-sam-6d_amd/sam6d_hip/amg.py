@@ -8,6 +8,10 @@ mask per live proposal; the keep decisions are small vector ops on the device; a
 launch (sam6d_amg_unpack_masks) that writes the surviving masks in the image frame.  A crop costs two 4-byte read-backs (how many
 proposals the filters kept, how many NMS kept), whatever the number of batches and masks.
 
+The min_mask_region_area clean-up behind the generator (automatic_mask_generator.py:324-372, utils/amg.py:267-291) is here as well:
+`mask_components` (8-connected labelling in a canonical form), `remove_small_regions` (both passes for all masks, in place on the device)
+and `postprocess_small_regions` (clean-up, boxes, NMS; one 4-byte read-back) on sam6d_mask_components / sam6d_amg_small_regions.
+
 `eager_tail` is the same tail in plain torch ops on any device: the CPU path, the SAM6D_HIP_AMG=0 path and the timing baseline.
 The geometry helpers (point grids, crop boxes, apply_coords) are the reference's arithmetic restated on the host.
 """
@@ -152,6 +156,99 @@ def unpack_masks(bits, idx, crop_size, crop_box, orig_size, dtype=torch.bool):
             _lib.call("sam6d_amg_unpack_masks", _ptr(bits), idx.data_ptr() + 8 * k0, bits.shape[0], k, oh, ow, x0, y0, H, W, int(f32),
                       out.data_ptr() + k0 * H * W * out.element_size(), _stream())
     return out.view(torch.bool) if dtype == torch.bool else out
+
+
+# ------------------------------------------------------------------------------------------------- min_mask_region_area
+REGIONS_WS_BYTES = 256 << 20   # the most workspace one launch group gets; K is processed in slices that fit (one mask always does)
+REGIONS_MAX_K = 65535
+
+
+def _masks_u8(masks, who):
+    """(K, H, W) bool / uint8 / float32 on a HIP device -> a fresh contiguous uint8 tensor of 0 / 1 that the entries may overwrite."""
+    _need_hip(masks, who)
+    if masks.dim() != 3 or masks.dtype not in (torch.bool, torch.uint8, torch.float32):
+        raise ValueError("%s: masks must be (K, H, W) bool, uint8 or float32, got %s %s" % (who, tuple(masks.shape), masks.dtype))
+    if masks.shape[1] == 0 or masks.shape[2] == 0:
+        raise ValueError("%s: empty image %s" % (who, tuple(masks.shape)))
+    if masks.dtype == torch.bool:
+        return masks.contiguous().view(torch.uint8).clone()
+    return (masks != 0).to(torch.uint8)
+
+
+def _region_slices(K, H, W, bytes_of):
+    """K in slices whose workspace stays under REGIONS_WS_BYTES (and under the entries' K <= 65535): (k0, k, workspace bytes)."""
+    per = int(bytes_of(1, H, W))
+    if per == 0:
+        raise ValueError("masks of %d x %d: H * W must be at most 2^31 - 2" % (H, W))
+    step = max(1, min(REGIONS_MAX_K, REGIONS_WS_BYTES // per))
+    return [(k0, min(step, K - k0), int(bytes_of(min(step, K - k0), H, W))) for k0 in range(0, K, step)]
+
+
+def mask_components(masks, invert=False):
+    """sam6d_mask_components.  masks (K, H, W) bool / uint8 / float32 on a HIP device; the foreground is masks != 0, or masks == 0 with
+    `invert` -> (labels, areas), both (K, H, W) int32: labels = 0 off the foreground, else 1 + the smallest row-major pixel index of the
+    pixel's 8-connected component; areas = that component's pixel count, 0 off the foreground.  Asynchronous."""
+    m8 = _masks_u8(masks, "mask_components")
+    K, H, W = m8.shape
+    dev = m8.device
+    labels = torch.empty((K, H, W), dtype=torch.int32, device=dev)
+    areas = torch.empty((K, H, W), dtype=torch.int32, device=dev)
+    if K == 0:
+        return labels, areas
+    with torch.cuda.device(dev):
+        slices = _region_slices(K, H, W, _lib.load().sam6d_mask_components_workspace_bytes)
+        ws = torch.empty((slices[0][2],), dtype=torch.uint8, device=dev)  # the first slice is the largest
+        for k0, k, nbytes in slices:
+            _lib.call("sam6d_mask_components", _ptr(m8[k0:]), k, H, W, int(bool(invert)), _ptr(labels[k0:]), _ptr(areas[k0:]), _ptr(ws),
+                      nbytes, _stream())
+    return labels, areas
+
+
+def region_threshold(min_area):
+    """The integer threshold of `size < min_area` for integer sizes: ceil(min_area), at least 1 (nothing is below a threshold <= 0, and
+    nothing is below 1 either: a component has at least one pixel)."""
+    return max(1, int(math.ceil(min_area)))
+
+
+def remove_small_regions(masks, min_area):
+    """remove_small_regions (ISM/segment_anything/utils/amg.py:267-291) in its two modes, as postprocess_small_regions chains them
+    (automatic_mask_generator.py:344-349), for all masks at once: holes smaller than min_area are filled, then islands smaller than
+    min_area are dropped (the largest island stays where all are smaller; among equals, the first in row-major order).  masks
+    (K, H, W) bool / uint8 / float32 (0 / 1) on a HIP device -> (cleaned masks of the same dtype, changed (K) bool, boxes (K, 4) int64
+    xyxy of the cleaned masks, [0, 0, 0, 0] for an empty one).  The input is left as it is.  Asynchronous."""
+    m8 = _masks_u8(masks, "remove_small_regions")
+    K, H, W = m8.shape
+    dev = m8.device
+    thr = region_threshold(min_area)
+    if thr > 2147483647:
+        thr = 2147483647  # above every possible size
+    changed = torch.zeros((K,), dtype=torch.uint8, device=dev)
+    box = torch.zeros((K, 4), dtype=torch.int32, device=dev)
+    if K == 0:
+        return masks.clone(), changed.view(torch.bool), box.long()
+    with torch.cuda.device(dev):
+        slices = _region_slices(K, H, W, _lib.load().sam6d_amg_small_regions_workspace_bytes)
+        ws = torch.empty((slices[0][2],), dtype=torch.uint8, device=dev)  # the first slice is the largest
+        for k0, k, nbytes in slices:
+            _lib.call("sam6d_amg_small_regions", _ptr(m8[k0:]), k, H, W, thr, _ptr(changed[k0:]), _ptr(box[k0:]), _ptr(ws), nbytes, _stream())
+    cleaned = m8.view(torch.bool) if masks.dtype == torch.bool else m8.to(masks.dtype)
+    return cleaned, changed.view(torch.bool), box.long()
+
+
+def postprocess_small_regions(mask_data, min_area, nms_thresh):
+    """postprocess_small_regions (ISM/segment_anything/automatic_mask_generator.py:324-372) on the device: mask_data = {"masks" (K, H, W),
+    "boxes" (K, 4)} -> {"masks", "boxes"} of the survivors of an NMS over the cleaned masks' boxes that prefers unchanged masks (score
+    1) to changed ones (score 0), in NMS order (score descending, stable by index); a changed survivor carries its new box, an
+    unchanged one the box it came with.  One 4-byte read-back (how many the NMS kept)."""
+    masks = mask_data["masks"]
+    if len(masks) == 0:
+        return mask_data
+    from .ism import nms
+    cleaned, changed, boxes = remove_small_regions(masks, min_area)
+    keep = nms(boxes.float(), (~changed).float(), nms_thresh)
+    old = mask_data["boxes"]
+    out_boxes = torch.where(changed[:, None], boxes.to(old.dtype), old)
+    return {"masks": cleaned[keep], "boxes": out_boxes[keep]}
 
 
 # ------------------------------------------------------------------------------------------------- one crop
