@@ -12,7 +12,8 @@ import torch.nn as nn
 from torch.nn import functional as F
 
 from model_utils import get_chosen_pixel_feats, sample_pts_feats
-from sam6d_hip import pem as _pem
+from sam6d_hip import inputs as _inputs
+from sam6d_hip import runtime as _runtime
 from sam6d_hip import vit as _vit
 from transformer import _sig
 
@@ -138,7 +139,7 @@ class ViTEncoder(nn.Module):
         if dense_po is None or dense_fo is None:
             raise ValueError('dense_po and dense_fo must be provided for export/inference')
         dense_fm = self.get_img_feats(rgb, rgb_choose)
-        dense_pm, dense_po, radius = _pem.radius_normalize(pts, dense_po)  # feature_extraction.py:133-137, on the GPU
+        dense_pm, dense_po, radius = _inputs.radius_normalize(pts, dense_po)  # feature_extraction.py:133-137, on the GPU
         return dense_pm, dense_fm, dense_po, dense_fo, radius
 
     def _vit_weights(self):
@@ -153,13 +154,13 @@ class ViTEncoder(nn.Module):
         return self._vit_pack
 
     def get_img_feats(self, img, choose):
-        if _pem._flags().hip_vit:
+        if _runtime._flags().hip_vit:
             return _vit.image_features(img, choose, self._vit_weights())
         return get_chosen_pixel_feats(self.rgb_net(img)[0], choose)
 
     def get_obj_feats(self, tem_rgb_list, tem_pts_list, tem_choose_list, npoint=None):
         npoint = npoint or self.npoint
-        if isinstance(tem_rgb_list, list) and _pem._flags().hip_vit:
+        if isinstance(tem_rgb_list, list) and _runtime._flags().hip_vit:
             # the T template images in one batch (each keeps its own choose); features in the list form's (B, T*N) order
             T, B = len(tem_rgb_list), tem_rgb_list[0].shape[0]
             ns = [c.shape[1] for c in tem_choose_list]

@@ -23,6 +23,8 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
+from .ism import mask_to_indices, nms
+from .runtime import _p, _s
 
 MASKS_PER_POINT = 3   # multimask_output=True
 EDGE_ATOL = 20.0      # is_box_near_crop_edge's default
@@ -84,14 +86,6 @@ def crop_boxes(im_size, n_layers, overlap_ratio):
 
 
 # ------------------------------------------------------------------------------------------------- the two bindings
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
 def _need_hip(t, who):
     if not t.is_cuda:
         raise RuntimeError("%s: needs HIP device tensors (eager_tail is the CPU path)" % who)
@@ -128,9 +122,9 @@ def mask_stats(low, live, input_size, crop_size, img_size, thr, offset, out=None
         lg = torch.empty((M, oh, ow), dtype=torch.float32, device=dev) if logits else None
         nbytes = int(_lib.load().sam6d_amg_mask_stats_workspace_bytes(M, lh, lw, int(img_size), in_h, oh))
         ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)
-        _lib.call("sam6d_amg_mask_stats", _ptr(low), _ptr(live8), M, lh, lw, int(img_size), in_h, in_w, oh, ow, float(thr), float(offset),
-                  _ptr(out["n_hi"]), _ptr(out["n_lo"]), _ptr(out["area"]), _ptr(out["box"]), _ptr(out["bits"]), _ptr(lg), _ptr(ws), nbytes,
-                  _stream())
+        _lib.call("sam6d_amg_mask_stats", _p(low), _p(live8), M, lh, lw, int(img_size), in_h, in_w, oh, ow, float(thr), float(offset),
+                  _p(out["n_hi"]), _p(out["n_lo"]), _p(out["area"]), _p(out["box"]), _p(out["bits"]), _p(lg), _p(ws), nbytes,
+                  _s())
     if logits:
         out = dict(out, logits=lg)
     return out
@@ -153,8 +147,8 @@ def unpack_masks(bits, idx, crop_size, crop_box, orig_size, dtype=torch.bool):
         out = torch.empty((K, H, W), dtype=torch.float32 if f32 else torch.uint8, device=bits.device)
         for k0 in range(0, K, 65535):
             k = min(65535, K - k0)
-            _lib.call("sam6d_amg_unpack_masks", _ptr(bits), idx.data_ptr() + 8 * k0, bits.shape[0], k, oh, ow, x0, y0, H, W, int(f32),
-                      out.data_ptr() + k0 * H * W * out.element_size(), _stream())
+            _lib.call("sam6d_amg_unpack_masks", _p(bits), idx.data_ptr() + 8 * k0, bits.shape[0], k, oh, ow, x0, y0, H, W, int(f32),
+                      out.data_ptr() + k0 * H * W * out.element_size(), _s())
     return out.view(torch.bool) if dtype == torch.bool else out
 
 
@@ -199,8 +193,8 @@ def mask_components(masks, invert=False):
         slices = _region_slices(K, H, W, _lib.load().sam6d_mask_components_workspace_bytes)
         ws = torch.empty((slices[0][2],), dtype=torch.uint8, device=dev)  # the first slice is the largest
         for k0, k, nbytes in slices:
-            _lib.call("sam6d_mask_components", _ptr(m8[k0:]), k, H, W, int(bool(invert)), _ptr(labels[k0:]), _ptr(areas[k0:]), _ptr(ws),
-                      nbytes, _stream())
+            _lib.call("sam6d_mask_components", _p(m8[k0:]), k, H, W, int(bool(invert)), _p(labels[k0:]), _p(areas[k0:]), _p(ws),
+                      nbytes, _s())
     return labels, areas
 
 
@@ -230,7 +224,7 @@ def remove_small_regions(masks, min_area):
         slices = _region_slices(K, H, W, _lib.load().sam6d_amg_small_regions_workspace_bytes)
         ws = torch.empty((slices[0][2],), dtype=torch.uint8, device=dev)  # the first slice is the largest
         for k0, k, nbytes in slices:
-            _lib.call("sam6d_amg_small_regions", _ptr(m8[k0:]), k, H, W, thr, _ptr(changed[k0:]), _ptr(box[k0:]), _ptr(ws), nbytes, _stream())
+            _lib.call("sam6d_amg_small_regions", _p(m8[k0:]), k, H, W, thr, _p(changed[k0:]), _p(box[k0:]), _p(ws), nbytes, _s())
     cleaned = m8.view(torch.bool) if masks.dtype == torch.bool else m8.to(masks.dtype)
     return cleaned, changed.view(torch.bool), box.long()
 
@@ -243,7 +237,6 @@ def postprocess_small_regions(mask_data, min_area, nms_thresh):
     masks = mask_data["masks"]
     if len(masks) == 0:
         return mask_data
-    from .ism import nms
     cleaned, changed, boxes = remove_small_regions(masks, min_area)
     keep = nms(boxes.float(), (~changed).float(), nms_thresh)
     old = mask_data["boxes"]
@@ -351,7 +344,6 @@ def finish_crop(state, crop_box=None, orig_size=None, box_nms_thresh=0.7, mask_d
         raise ValueError("finish_crop: orig_size %s is not the state's %s" % (tuple(orig_size), state.orig_size))
     if not state.hip:
         return _eager_finish(state.parts, state, box_nms_thresh, mask_dtype)
-    from .ism import mask_to_indices, nms
     n = state.filled
     if n == 0:
         return _empty_result(state, state.device, mask_dtype)
@@ -376,7 +368,6 @@ def merge_crops(results, crop_box_list, crop_nms_thresh=0.7):
     if len(results) > 1:
         scores = (1 / ((cb[:, 2] - cb[:, 0]) * (cb[:, 3] - cb[:, 1]))).to(dev)
         if hip_enabled(dev):
-            from .ism import nms
             keep = nms(data["boxes"].float(), scores, crop_nms_thresh)
         else:
             keep = nms_torch(data["boxes"].float(), scores, crop_nms_thresh)

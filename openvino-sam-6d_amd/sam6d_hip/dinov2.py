@@ -19,7 +19,8 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib, encoder
-from .pem import Linear, _empty, _getter, _p, _s, on_tensor_device
+from .ism import masked_patch_features
+from .runtime import Linear, _empty, _getter, _p, _s, on_tensor_device
 
 D = 1024       # embed_dim of vit_large
 HEADS = 16
@@ -275,7 +276,6 @@ def encode(images, W, options=None):
 def descriptors(images, masks224, W, patch_size=PATCH, validpatch_thresh=0.5, options=None):
     """compute_cls_and_patch_features (ISM/model/dinov2.py:308-326): images (N, 3, 224, 224), masks224 (N, 224, 224) ->
     (cls (N, 1024), masked, L2-normalised patch descriptors (N, 256, 1024))."""
-    from .ism import masked_patch_features
     cls, tok = encode(images, W)
     if tok.shape[0] == 0:
         return cls, tok

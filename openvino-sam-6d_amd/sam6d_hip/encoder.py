@@ -13,7 +13,7 @@ from typing import NamedTuple
 import torch
 
 from . import _lib
-from .pem import Linear, _empty, _flags, _p, _s, gemm, on_tensor_device
+from .runtime import Linear, _empty, _p, _s, gemm, on_tensor_device, require_mode
 
 
 class Encoder(NamedTuple):
@@ -34,8 +34,7 @@ class Encoder(NamedTuple):
     whole_tiles: bool = False  # the block GEMMs ask for the whole-tile kernel (act + 32): an image's rows are a multiple of 128
 
     def require_mode(self):
-        if _flags().mode == 2:
-            raise NotImplementedError("%s: matmul mode 2 is not implemented for the %s (modes 0 and 1 are)" % (self.name, self.role))
+        require_mode(self.name, self.role)
 
     def ln(self, x, gb, y, nimg, rows, ldx, sx, ldy, sy, x_off=0, y_off=0):
         """Row r of image b: x + x_off + b sx + r ldx -> y + y_off + b sy + r ldy (floats), gb = (gamma, beta)."""

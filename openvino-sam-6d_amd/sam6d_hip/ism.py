@@ -4,7 +4,8 @@ compute_geometric_score and model.loss.*  (ISM = SAM-6D/Instance_Segmentation_Mo
 import torch
 
 from . import _lib
-from .pem import _empty, _p, _s, gemm, on_tensor_device
+from .ops import _chk
+from .runtime import _empty, _p, _s, gemm, on_tensor_device
 
 _MODES = {"avg_5": 0, "mean": 1, "max": 2}
 
@@ -80,7 +81,6 @@ class PatchScores:
 def patch_scores_fused(q_appe, ref_appe, pred_obj, best_pose, q_index=None):
     """q_appe (Nq,P,D) query patch descriptors (rows q_index when given, else Nq == Ns), ref_appe (No,Nt,P,D) ALL templates' patch
     descriptors, pred_obj / best_pose (Ns,) i64 -> PatchScores.  One GEMM launch whose tiles end in row / column maxima."""
-    from .ops import _chk
     q_appe = q_appe.contiguous()
     ref_appe = ref_appe.contiguous()
     _chk(q_appe, "q_appe", torch.float32, 3)
@@ -198,7 +198,6 @@ def masked_patch_features(patch_features, masks, patch_size=14, validpatch_thres
     masks (N,H,W) -> (N,P,D)."""
     N, P, D = patch_features.shape
     H, W = masks.shape[1], masks.shape[2]
-    from .ops import _chk
     f = patch_features.contiguous()
     m = masks.to(torch.float32).contiguous()
     _chk(f, "patch_features", torch.float32, 3)
@@ -213,7 +212,6 @@ def masked_patch_features(patch_features, masks, patch_size=14, validpatch_thres
 @on_tensor_device
 def small_detection_keep(boxes, masks, min_box_size, min_mask_size):
     """ISM/model/utils.py:96-102: bool (N,) -- box area and mask area (as fractions of the image) above the thresholds."""
-    from .ops import _chk
     boxes = boxes.contiguous()
     masks = masks.to(torch.float32).contiguous()
     _chk(boxes, "boxes", torch.int64, 2)
@@ -259,7 +257,6 @@ def take_rows(src, idx):
 def nms(boxes, scores, iou_threshold, object_ids=None):
     """torchvision.ops.nms as ISM/model/utils.py:107-126 calls it; with object_ids the per-id variant (ids ascending,
     survivors of each id in descending score order).  Returns int64 indices."""
-    from .ops import _chk
     boxes = boxes.to(torch.float32).contiguous()
     scores = scores.to(torch.float32).contiguous()
     _chk(boxes, "boxes", torch.float32, 2)

@@ -6,10 +6,7 @@ Device memory, streams and allocation are torch's (plumbing); all arithmetic hap
 import torch
 
 from . import _lib
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
+from .runtime import _p, _s
 
 
 def _chk(t, name, dtype, ndim=None):
@@ -31,10 +28,6 @@ def _same_dev(a, b, na, nb):
         raise RuntimeError("%s and %s must be on the same device" % (na, nb))
 
 
-def p(t):
-    return t.data_ptr()
-
-
 def furthest_point_sampling(xyz, m):
     """(B,N,3) f32 -> (B,m) i32.  Bit-exact with EXT/src/sampling.cpp:76-118."""
     _chk(xyz, "points", torch.float32, 3)
@@ -44,8 +37,7 @@ def furthest_point_sampling(xyz, m):
     with torch.cuda.device(xyz.device):
         out = torch.empty(B, m, dtype=torch.int32, device=xyz.device)
         temp = torch.empty(B, N, dtype=torch.float32, device=xyz.device) if N > 4096 else None
-        _lib.call("sam6d_furthest_point_sampling", p(xyz), B, N, m, p(temp) if temp is not None else None, p(out),
-                  _stream())
+        _lib.call("sam6d_furthest_point_sampling", _p(xyz), B, N, m, _p(temp), _p(out), _s())
     return out
 
 
@@ -58,7 +50,7 @@ def gather_points(points, idx):
     M = idx.shape[1]
     with torch.cuda.device(points.device):
         out = torch.empty(B, C, M, dtype=torch.float32, device=points.device)
-        _lib.call("sam6d_gather_points", p(points), p(idx), B, C, N, M, p(out), _stream())
+        _lib.call("sam6d_gather_points", _p(points), _p(idx), B, C, N, M, _p(out), _s())
     return out
 
 
@@ -71,7 +63,7 @@ def ball_query(new_xyz, xyz, radius, nsample):
     N = xyz.shape[1]
     with torch.cuda.device(xyz.device):
         out = torch.empty(B, M, nsample, dtype=torch.int32, device=xyz.device)
-        _lib.call("sam6d_ball_query", p(new_xyz), p(xyz), B, N, M, float(radius), int(nsample), p(out), _stream())
+        _lib.call("sam6d_ball_query", _p(new_xyz), _p(xyz), B, N, M, float(radius), int(nsample), _p(out), _s())
     return out
 
 
@@ -84,7 +76,7 @@ def group_points(points, idx):
     _, M, S = idx.shape
     with torch.cuda.device(points.device):
         out = torch.empty(B, C, M, S, dtype=torch.float32, device=points.device)
-        _lib.call("sam6d_group_points", p(points), p(idx), B, C, N, M, S, p(out), _stream())
+        _lib.call("sam6d_group_points", _p(points), _p(idx), B, C, N, M, S, _p(out), _s())
     return out
 
 
@@ -97,5 +89,5 @@ def gather_rows(feats, idx, idx_off=0, out=None):
     with torch.cuda.device(feats.device):
         if out is None:
             out = torch.empty(B, M, C, dtype=torch.float32, device=feats.device)
-        _lib.call("sam6d_gather_rows", p(feats), p(idx), B, N, M, C, N * C, out.stride(0), idx_off, p(out), _stream())
+        _lib.call("sam6d_gather_rows", _p(feats), _p(idx), B, N, M, C, N * C, out.stride(0), idx_off, _p(out), _s())
     return out

@@ -6,209 +6,30 @@ path.  Everything that shares weights between the scene cloud and the template c
 RPE self layers, the dense linear-attention layers, out_proj) runs ONCE on a stacked (2B, ...) batch; only the
 sequential cross-attention halves (PEM/model/transformer.py:520-521) are issued per cloud.
 
+What is here: the PEM weight set and its packed images, the pipeline's own primitives (`linear` with the panel route, `gemm` =
+runtime.gemm behind bench.py's PROFILE hook), the layers, the pose solvers, and pem_match / PemGraph on top of them.  The plumbing
+underneath (Options, on_tensor_device, Linear, the GEMM launch) is runtime.py's; the model's input tensors are built in inputs.py.
+
 Citations: PEM = SAM-6D/Pose_Estimation_Model in the reference.
 """
 import math
-import os
-import threading
 import types
 
+import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, runtime
+from .ops import _chk
+from .runtime import (C, Linear, Options, _empty, _flags, _getter, _p, _pow2_scale, _s, on_tensor_device, split_w16,
+                      gemm_route)  # noqa: F401  (gemm_route: the route `gemm` and gemm_b2 below take, without the launch)
 
-C = 256
 H = 4
 
 
-def _s():
-    return torch.cuda.current_stream().cuda_stream
-
-
-class Options:
-    """The explicit choice of arithmetic and kernel routes for a launch sequence.  An Options object travels with a weight set
-    (`PemWeights(sd, dev, options=...)`) or with one call (`pem_match(..., options=...)`, any @on_tensor_device entry point); two weight
-    sets in one process can therefore run different arithmetic.  Without one, `Options.from_env()` is resolved once per outermost entry
-    point.  Fields (environment variable in ENV):
-      matmul_mode   None = the library's process default (sam6d_set_matmul_mode / SAM6D_MATMUL_MODE), resolved into `mode` when the
-                    object is built; else 0 exact fp32 MFMA, 1 fp16 x3 split, 2 fp16 single product (experimental).  Applied as the
-                    calling thread's mode for the duration of the entry point (sam6d_set_thread_matmul_mode)
-      fused_block   fused transformer-block kernels (csrc/block.hip); off = the launch-per-op path
-      fused_rpe / rpe_products / fused_fine / overlap / microbatch   pipeline shape of pem_match (cfg keys of the same name win)
-      hip_vit       the drop-in ViTEncoder's image features on the library (sam6d_hip/vit.py) instead of eager PyTorch (off by default)
-    The object keeps the values it was given; the split-precision routes (fused_block, fused_rpe) read as off in mode 0, so
-    `replace(matmul_mode=1)` starts again from what the caller asked for.  Read-only routes that follow from the fields: w16 (pre-split
-    fp16 weight halves in the GEMMs: modes 1 and 2) and fused_front / fused_out / rows_linear (the RPE front kernel, the fine out_proj
-    + normalize + split pass and the sparse-token panel kernel: with fused_block)."""
-    DEFAULTS = dict(
-        matmul_mode=None,
-        fused_block=True,   # fused transformer-block kernels (csrc/block.hip)
-        rpe_products=0,     # 0: what the weight set allows (geo_cheb_a_packed); 3: always three stage-1 products
-        fused_rpe=True,     # RPE attention without the embedding tensor
-        fused_fine=True,    # fine similarity + soft assignment as one pipeline (finematch.hip)
-        overlap=True,       # pose-independent fine work on a second HIP stream
-        microbatch=1,
-        hip_vit=False,      # ViTEncoder.get_img_feats / get_obj_feats through sam6d_hip.vit
-    )
-    ENV = dict(matmul_mode="SAM6D_MATMUL_MODE", fused_block="SAM6D_FUSED_BLOCK", rpe_products="SAM6D_RPE_PRODUCTS",
-               fused_rpe="SAM6D_FUSED_RPE", fused_fine="SAM6D_FUSED_FINE", overlap="SAM6D_OVERLAP", microbatch="SAM6D_MICROBATCH",
-               hip_vit="SAM6D_HIP_VIT")
-    __slots__ = ("_kw", "mode")
-
-    def __init__(self, **kw):
-        bad = set(kw) - set(self.DEFAULTS)
-        if bad:
-            raise TypeError("Options: unknown field(s) %s" % sorted(bad))
-        self._kw = dict(self.DEFAULTS, **kw)
-        m = self._kw["matmul_mode"]
-        self.mode = int(_lib.load().sam6d_get_matmul_mode()) if m is None else int(m)
-        if self.mode not in (0, 1, 2):
-            raise ValueError("Options.matmul_mode must be None, 0, 1 or 2")
-
-    matmul_mode = property(lambda self: self._kw["matmul_mode"])
-    fused_block = property(lambda self: bool(self._kw["fused_block"]) and self.mode >= 1)
-    fused_rpe = property(lambda self: bool(self._kw["fused_rpe"]) and self.mode >= 1)
-    rpe_products = property(lambda self: int(self._kw["rpe_products"]))
-    fused_fine = property(lambda self: self._kw["fused_fine"])
-    overlap = property(lambda self: self._kw["overlap"])
-    microbatch = property(lambda self: int(self._kw["microbatch"]))
-    hip_vit = property(lambda self: bool(self._kw["hip_vit"]))
-    w16 = property(lambda self: self.mode >= 1)
-    fused_front = fused_out = rows_linear = fused_block
-
-    @classmethod
-    def from_env(cls, **over):
-        """The environment's switches (read now), overridden by keyword arguments."""
-        kw = {}
-        for k, name in cls.ENV.items():
-            v = os.environ.get(name)
-            if v is None:
-                continue
-            d = cls.DEFAULTS[k]
-            kw[k] = int(v) if (d is None or (isinstance(d, int) and not isinstance(d, bool))) else (v == "1")
-        kw.update(over)
-        return cls(**kw)
-
-    def replace(self, **over):
-        """A copy with some fields changed, built from the values this object was given."""
-        return Options(**dict(self._kw, **over))
-
-    def describe(self):
-        return {k: getattr(self, k) for k in self.DEFAULTS if k != "matmul_mode"} | {"matmul_mode": self.mode}
-
-
-class _Tls(threading.local):
-    """Per-thread state of the entry points: the Options of the outermost call in flight and its nesting depth -- the library's matmul
-    mode is per thread too (sam6d_set_thread_matmul_mode), so two threads may drive two models at once."""
-    flags = None
-    depth = 0
-
-
-_TLS = _Tls()
-
-
-def _flags():
-    """Inside a public entry point (on_tensor_device): the Options it was entered with; outside: the environment's, read afresh."""
-    if _TLS.flags is not None:
-        return _TLS.flags
-    return Options.from_env()
-
-
-def _find_options(args, kwargs):
-    o = kwargs.pop("options", None)
-    if o is not None:
-        return o
-    for a in list(args) + list(kwargs.values()):
-        o = getattr(a, "options", None)
-        if isinstance(o, Options):
-            return o
-    return None
-
-
-def on_tensor_device(fn):
-    """Run `fn` with the device of its first tensor argument current: the launches go to torch's current stream OF THAT DEVICE and
-    torch.empty workspaces land there, also when the caller's current device is another GPU of the node.  The outermost decorated call
-    also fixes the Options of its whole launch sequence -- the `options=` keyword, else the `.options` of a weight-set argument, else
-    the environment's -- and makes their arithmetic mode the calling thread's (sam6d_set_thread_matmul_mode) until it returns."""
-    import functools
-
-    @functools.wraps(fn)
-    def wrapper(*args, **kwargs):
-        dev = next((a.device for a in args if torch.is_tensor(a)), None)
-        if dev is None or dev.type != "cuda":
-            raise RuntimeError("%s: needs HIP device tensors (this build has no CPU path)" % fn.__name__)
-        opts = _find_options(args, kwargs)
-        outer = _TLS.depth == 0
-        if outer:
-            _TLS.flags = opts if opts is not None else Options.from_env()
-            prev_mode = int(_lib.load().sam6d_get_thread_matmul_mode())
-            _lib.call("sam6d_set_thread_matmul_mode", _TLS.flags.mode)
-        _TLS.depth += 1
-        try:
-            with torch.cuda.device(dev):
-                return fn(*args, **kwargs)
-        finally:
-            _TLS.depth -= 1
-            if outer:
-                _TLS.flags = None
-                _lib.call("sam6d_set_thread_matmul_mode", prev_mode)
-    return wrapper
-
-
-def _p(t, off=0):
-    return t.data_ptr() + 4 * off if t is not None else None
-
-
-def _empty(shape, like, dtype=torch.float32):
-    return torch.empty(shape, dtype=dtype, device=like.device)
-
-
 # --------------------------------------------------------------------------------------------- weight packing
-class Linear:
-    __slots__ = ("w", "b", "_w16", "_pimg")
-
-    def __init__(self, w, b):
-        self.w, self.b = w.contiguous(), (b.contiguous() if b is not None else None)
-        self._w16 = None
-        self._pimg = None
-
-    def pimg(self):
-        """(image, 1 / scale, panels): the weight (256 or 512 rows x K = 256) as the 32-row panel image of csrc/block.hip's
-        rows_linear_kernel (sam6d_pack_panels), or None for another shape."""
-        if self._pimg is None:
-            N, K = self.w.shape
-            if K != C or N not in (C, 2 * C):
-                self._pimg = False
-            else:
-                sc = _pow2_scale(self.w.abs().max())
-                img = torch.zeros((N // 32) * 32768, dtype=torch.uint8, device=self.w.device)
-                _lib.call("sam6d_pack_panels", _p(self.w), K, N, 0, 8, float(sc), img.data_ptr(), _s())
-                self._pimg = (img, 1.0 / sc, N // 32)
-        return self._pimg or None
-
-    def w16(self):
-        """(hi, lo, scale): the weight cut into fp16 halves once (sam6d_split_f16) for sam6d_gemm_nt_w16; scale = the power of
-        two that puts max |w| into [2^13, 2^14)."""
-        if self._w16 is None:
-            sc = _pow2_scale(self.w.abs().max())
-            hi = torch.empty(self.w.shape, dtype=torch.float16, device=self.w.device)
-            lo = torch.empty_like(hi)
-            _lib.call("sam6d_split_f16", _p(self.w), self.w.numel(), float(sc), hi.data_ptr(), lo.data_ptr(), _s())
-            self._w16 = (hi, lo, float(sc))
-        return self._w16
-
-
 TB_P256, TB_P128, TB_P64 = 32768, 16384, 8192  # panel bytes of csrc/block.hip (32 rows x K = 256 / 128 / 64, fp16 hi + lo)
 TB_CHUNK = 4 * TB_P256 + 8 * TB_P128
 TB_Q_OFF = 8 * TB_P256 + 4 * TB_CHUNK
-
-
-def _pow2_scale(amax):
-    """Power of two s with amax * s in [2^13, 2^14) (the fp16 split then neither overflows nor reaches subnormals)."""
-    amax = float(amax)
-    if not (amax > 0.0 and math.isfinite(amax)):
-        return 1.0
-    return 2.0 ** (14 - math.frexp(amax)[1])
 
 
 def pack_token_block(L, q=None, scale=None):
@@ -254,11 +75,6 @@ def pack_token_block(L, q=None, scale=None):
     cst[2048:2304], cst[2304:2560] = L["n2"]
     cst[2560:2565] = torch.tensor([1.0 / s_q, 1.0 / s_lin, 1.0 / s_exp, 1.0 / (s_sq * s_h), s_h], device=dev)
     return dict(img=img, cst=cst, mode=mode)
-
-
-def split_w16(w):
-    """(hi, lo, scale) of a weight tensor for sam6d_gemm_nt_w16 (see Linear.w16)."""
-    return Linear(w, None).w16()
 
 
 def pack_cross_query(q):
@@ -371,10 +187,6 @@ class PemWeights:
         return dict(mlp=mlp, mlp3=Linear(g(pe + ".mlp3.conv.weight").reshape(C, C), g(pe + ".mlp3.conv.bias")))
 
 
-def _getter(sd, device):
-    return lambda k: sd[k].detach().to(device=device, dtype=torch.float32).contiguous()
-
-
 # The drop-in sub-modules pack only their own part of the weights, into a plain namespace holding the PemWeights attributes their
 # launches read (pem/transformer.py, pem/coarse_point_matching.py, pem/fine_point_matching.py).
 def pack_geo(sd, device, p="geo_embedding"):
@@ -397,43 +209,15 @@ def pack_pe(sd, device, pe):
 
 
 # ------------------------------------------------------------------------------------------------- primitives
-def gemm(A, W, bias, out, M, N, K, lda, ldw, ldc, *, a_off=0, w_off=0, c_off=0, residual=None, r_off=0, ldr=0,
-         colscale=None, batch=1, sA=0, sW=0, sC=0, sR=0, divisor=1.0, act=0, w16=None):
-    """w16 = Linear.w16() of the weight `W` belongs to: the pre-split halves are used in the split-precision modes."""
-    def launch():
-        if w16 is not None and K >= 32 and _flags().w16:
-            hi, lo, sc = w16
-            _lib.call("sam6d_gemm_nt_w16", _p(A, a_off), _p(W, w_off), hi.data_ptr() + 2 * w_off, lo.data_ptr() + 2 * w_off, sc, _p(bias),
-                      _p(colscale), _p(residual, r_off), _p(out, c_off), M, N, K, lda, ldw, ldc, ldr, batch, sA, sW, sC, sR,
-                      float(divisor), act, _s())
-            return
-        _lib.call("sam6d_gemm_nt", _p(A, a_off), _p(W, w_off), _p(bias), _p(colscale), _p(residual, r_off), _p(out, c_off),
-                  M, N, K, lda, ldw, ldc, ldr, batch, sA, sW, sC, sR, float(divisor), act, _s())
-
+def gemm(A, W, bias, out, M, N, K, lda, ldw, ldc, *, residual=None, batch=1, **kw):
+    """runtime.gemm, timed for bench.py where it is one of the dense-token projections."""
     if PROFILE is not None and batch == 1 and N == C and K == C and M >= 65536:
         # bench.py's second roofline: the dense-token projections (M = 2B x 2049 rows, 256 -> 256) are HBM streams
         PROFILE.setdefault("gemm_dense_256_bytes", []).append(4 * M * (K + N + (N if residual is not None else 0)) + 4 * N * K)
         with _Timed("gemm_dense_256"):
-            launch()
+            runtime.gemm(A, W, bias, out, M, N, K, lda, ldw, ldc, residual=residual, batch=batch, **kw)
     else:
-        launch()
-
-
-def gemm_route(A, W, bias, out, M, N, K, lda, ldw, ldc, *, a_off=0, w_off=0, c_off=0, residual=None, r_off=0, ldr=0, colscale=None,
-               batch=1, sA=0, sW=0, sC=0, sR=0, divisor=1.0, act=0, w16=None, batch2=1, sA2=0, sW2=0, sC2=0):
-    """The SAM6D_GEMM_ROUTE_* bit code of the kernel `gemm` (batch2 > 1: `gemm_b2`) launches with these arguments, in the calling
-    thread's matmul mode (sam6d_gemm_route; nothing is launched).  The pre-split weights count as `gemm` would use them."""
-    wh = wl = None
-    sc = 0.0
-    if w16 is not None and K >= 32 and _flags().w16:
-        hi, lo, sc = w16
-        wh, wl = hi.data_ptr() + 2 * w_off, lo.data_ptr() + 2 * w_off
-    rc = _lib.load().sam6d_gemm_route(_p(A, a_off), _p(W, w_off), wh, wl, float(sc), _p(bias), _p(colscale), _p(residual, r_off),
-                                      _p(out, c_off), M, N, K, lda, ldw, ldc, ldr, batch, sA, sW, sC, sR, float(divisor), act, batch2,
-                                      sA2, sW2, sC2)
-    if rc < 0:
-        raise RuntimeError("sam6d_gemm_route failed (rc=%d): %s" % (rc, _lib.load().sam6d_last_error().decode()))
-    return rc
+        runtime.gemm(A, W, bias, out, M, N, K, lda, ldw, ldc, residual=residual, batch=batch, **kw)
 
 
 def linear(x2d, lin, *, act=0, residual=None, out=None, cloud_rows=0):
@@ -560,7 +344,6 @@ def cheb_coefficients(weight, div_term, xmax=GEO_XMAX, K=GEO_CHEB_K):
     """Chebyshev interpolant (degree K-1, float64) of x -> weight @ sinusoid(x) on [0, xmax], one row per output column:
     returns c (cols, K) with  weight @ [sin(w0 x), cos(w0 x), sin(w1 x), ...] ~= sum_p c[:, p] T_p(2x/xmax - 1)
     (SinusoidalPositionalEmbedding: PEM/model/transformer.py:259-285; error ~4e-12 for xmax = 24, K = 32)."""
-    import numpy as np
     Wm = weight.detach().double().cpu().numpy()  # (cols, 256) over interleaved [sin, cos]
     om = div_term.detach().double().cpu().numpy()  # (128,)
     k = np.arange(K)
@@ -579,7 +362,6 @@ def geo_cheb_packed(W):
     fp16 halves of (c * 1024); built once per weight set on the host in float64."""
     pk = getattr(W, "_geo_cheb", None)
     if pk is None:
-        import numpy as np
         c = np.stack([cheb_coefficients(W.geo_d.w, W.div_term), cheb_coefficients(W.geo_a.w, W.div_term)], 0) * 1024.0
         # the images hold (coefficient x 1024) and (weight x 1024) as fp16 hi / lo halves: both matrices of both must stay finite there
         wmax = max(float(W.geo_d.w.abs().max()), float(W.geo_a.w.abs().max())) * 1024.0
@@ -611,7 +393,6 @@ def geo_cheb_a_packed(W, sigma_a=15):
     key = float(sigma_a)
     hit = cache.get(key)
     if hit is None:
-        import numpy as np
         xmax_a = min(float(GEO_XMAX), (180.0 / float(sigma_a)) * (1.0 + 2.0 ** -6))
         c = cheb_coefficients(W.geo_a.w, W.div_term, xmax=xmax_a)  # (256, 32) float64
         bound = np.abs(c).sum(axis=1)
@@ -1116,7 +897,6 @@ def compute_coarse_Rt(att, pts1, pts2, model, radius, rand, n_proposal1=6000, n_
 @on_tensor_device
 def pairwise_distance(x, y):
     """PEM/utils/model_utils.py:101-128 on (B,N,3) x (B,M,3) -> (B,N,M) squared distances, torch-CPU bit recipe."""
-    from .ops import _chk
     _chk(x, "x", torch.float32, 3)
     _chk(y, "y", torch.float32, 3)
     B, N, _ = x.shape
@@ -1705,181 +1485,6 @@ def template_is_shared(dense_po, dense_fo):
     _lib.call("sam6d_batch_rows_equal", _p(dense_fo.contiguous()), B, dense_fo[0].numel(), flags.data_ptr() + 4, _s())
     f = flags.cpu()
     return bool(f[0]) and bool(f[1])
-
-
-@on_tensor_device
-def radius_normalize(pts, dense_po):
-    """ViTEncoder.forward's radius normalisation (PEM/model/feature_extraction.py:133-137):
-    -> dense_pm (B,M,3), dense_po (B,N,3) both divided by (radius + 1e-6), radius (B,)."""
-    from .ops import _chk
-    pts = pts.contiguous()
-    dense_po = dense_po.contiguous()
-    _chk(pts, "pts", torch.float32, 3)
-    _chk(dense_po, "dense_po", torch.float32, 3)
-    B, N, _ = dense_po.shape
-    M = pts.shape[1]
-    radius = _empty((B,), pts)
-    po = _empty((B, N, 3), pts)
-    pm = _empty((B, M, 3), pts)
-    _lib.call("sam6d_radius_normalize", _p(dense_po), _p(pts), B, N, M, _p(radius), _p(po), _p(pm), _s())
-    return pm, po, radius
-
-
-@on_tensor_device
-def depth_to_cloud(depth, K, bbox=None):
-    """get_point_cloud_from_depth (PEM/utils/data_utils.py:92-110) on a device depth map (H,W) f32 -> (h,w,3)."""
-    from .ops import _chk
-    depth = depth.contiguous()
-    _chk(depth, "depth", torch.float32, 2)
-    H, W = depth.shape
-    r0, r1, c0, c1 = (0, H, 0, W) if bbox is None else [int(v) for v in bbox]
-    out = _empty((r1 - r0, c1 - c0, 3), depth)
-    _lib.call("sam6d_depth_to_cloud", _p(depth), H, W, r0, r1, c0, c1, float(K[0][0]), float(K[1][1]), float(K[0][2]),
-              float(K[1][2]), _p(out), _s())
-    return out
-
-
-@on_tensor_device
-def proposal_geometry(masks, depth, K, radius, cap=None):
-    """The per-proposal geometry of get_test_data before the random choice (PEM/run_inference_custom_pytorch.py:316-337):
-    masks (N,H,W) uint8/bool, depth (H,W) f32 metres, K 3x3, radius = max CAD point norm.
-    -> dict(bbox (N,4) i32, count (N), choose (N,cap) i32, cloud (N,cap,3), n_keep (N), center (N,3)); proposals with count <= 32
-    or n_keep < 4 are the ones the reference skips (:320-324, :334-335) -- the caller filters on those two vectors."""
-    from .ops import _chk
-    masks = masks.to(torch.uint8).contiguous()
-    depth = depth.contiguous()
-    _chk(masks, "masks", torch.uint8, 3)
-    _chk(depth, "depth", torch.float32, 2)
-    N, H, Wd = masks.shape
-    bbox = _empty((N, 4), depth, torch.int32)
-    count = _empty((N,), depth, torch.int32)
-    _lib.call("sam6d_mask_bbox", _p(masks), _p(depth), N, H, Wd, _p(bbox), _p(count), _s())
-    cap = int(cap) if cap is not None else min(H, Wd) ** 2  # the crop is a square of side <= min(H, W)
-    choose = _empty((N, cap), depth, torch.int32)
-    cloud = _empty((N, cap, 3), depth)
-    n_valid = _empty((N,), depth, torch.int32)
-    _lib.call("sam6d_crop_masked_points", _p(masks), _p(depth), N, H, Wd, _p(bbox), float(K[0][0]), float(K[1][1]), float(K[0][2]),
-              float(K[1][2]), cap, _p(choose), _p(cloud), _p(n_valid), _s())
-    n_keep = _empty((N,), depth, torch.int32)
-    center = _empty((N, 3), depth)
-    _lib.call("sam6d_radius_filter", N, cap, _p(n_valid), float(radius), _p(choose), _p(cloud), _p(n_keep), _p(center), _s())
-    return dict(bbox=bbox, count=count, choose=choose, cloud=cloud, n_valid=n_valid, n_keep=n_keep, center=center, cap=cap)
-
-
-def proposal_choose(geom, sel, img_size=224):
-    """pts (N,ns,3) and rgb_choose (N,ns) i64 for the caller's random choice sel (N,ns) into the kept points of each proposal
-    (PEM/run_inference_custom_pytorch.py:339-355, get_resize_rgb_choose PEM/utils/data_utils.py:113-123)."""
-    sel = sel.to(torch.int32).contiguous()
-    N, ns = sel.shape
-    pts = _empty((N, ns, 3), geom["cloud"])
-    rc = _empty((N, ns), geom["cloud"], torch.int64)
-    _lib.call("sam6d_choose_points", N, geom["cap"], _p(geom["choose"]), _p(geom["cloud"]), _p(geom["bbox"]), _p(sel), ns, int(img_size),
-              _p(pts), _p(rc), _s())
-    return pts, rc
-
-
-def _rgb_crop_resize(images, stride, C, masks, depth, mask_mode, bbox, img_size, return_uint8, check):
-    """sam6d_rgb_crop_resize over bbox.shape[0] items of images (..., H, W, C) u8 (stride: 1 = one image per item, 0 = shared)."""
-    from .ops import _chk
-    bbox = bbox.contiguous()
-    _chk(bbox, "bbox", torch.int32, 2)
-    N = bbox.shape[0]
-    H, Wd = images.shape[-3:-1] if C == 3 else images.shape[-2:]
-    S = int(img_size)
-    out = _empty((N, 3, S, S), images)
-    u8 = _empty((N, S, S, 3), images, torch.uint8) if return_uint8 else None
-    status = _empty((N,), images, torch.int32) if check else None
-    _lib.call("sam6d_rgb_crop_resize", images.data_ptr(), stride * H * Wd * C, C, H, Wd, masks.data_ptr() if masks is not None else None,
-              depth.data_ptr() if depth is not None else None, mask_mode, N, _p(bbox), S, _p(out), u8.data_ptr() if u8 is not None else None,
-              _p(status), _s())
-    if check and N and bool(status.any()):
-        bad = [i for i, v in enumerate(status.cpu().tolist()) if v]
-        raise RuntimeError("rgb crop: the bbox of item(s) %s is not inside the %dx%d image" % (bad[:8], H, Wd))
-    return (out, u8) if return_uint8 else out
-
-
-def _image_channels(img, name, lead):
-    """3 for (..., H, W, 3), 1 for a grayscale (..., H, W) u8 stack with `lead` leading dimensions"""
-    from .ops import _chk
-    _chk(img, name, torch.uint8)
-    if img.dim() == lead + 3 and img.shape[-1] == 3:
-        return 3
-    if img.dim() == lead + 2:
-        return 1
-    raise RuntimeError("%s must be %s(H, W, 3) or %s(H, W) uint8, got %s" % (name, "(T, " * lead, "(T, " * lead, tuple(img.shape)))
-
-
-@on_tensor_device
-def proposal_rgb(image, masks, depth, geom, img_size=224, rgb_mask_flag=True, return_uint8=False, check=True):
-    """The rgb input of get_test_data (PEM/run_inference_custom_pytorch.py:344-350) for every proposal in one launch: the crop
-    geom["bbox"] (from proposal_geometry, or any (N,4) i32 (y1, y2, x1, x2)) of image (H,W,3) u8 RGB or (H,W) grayscale (:293-294),
-    channels reversed, times (mask > 0) & (depth > 0) (:318) when rgb_mask_flag, cv2.resize INTER_LINEAR to img_size, ToTensor +
-    Normalize.  -> rgb (N,3,S,S) f32, and with return_uint8 also the resized crops (N,S,S,3) u8.  check: one read-back of a status
-    vector, RuntimeError for a bbox outside the image (boxes from proposal_geometry always lie inside; inputs.test_data skips it)."""
-    from .ops import _chk
-    image = image.contiguous()
-    masks = masks.to(torch.uint8).contiguous()
-    depth = depth.contiguous()
-    C = _image_channels(image, "image", 0)
-    _chk(masks, "masks", torch.uint8, 3)
-    _chk(depth, "depth", torch.float32, 2)
-    if tuple(depth.shape) != tuple(masks.shape[1:]) or tuple(image.shape[:2]) != tuple(depth.shape):
-        raise RuntimeError("image %s, masks %s and depth %s disagree on (H, W)" % (tuple(image.shape), tuple(masks.shape), tuple(depth.shape)))
-    if geom["bbox"].shape[0] != masks.shape[0]:
-        raise RuntimeError("geom has %d boxes for %d masks" % (geom["bbox"].shape[0], masks.shape[0]))
-    if rgb_mask_flag:
-        return _rgb_crop_resize(image, 0, C, masks, depth, 1, geom["bbox"], img_size, return_uint8, check)
-    return _rgb_crop_resize(image, 0, C, None, None, 0, geom["bbox"], img_size, return_uint8, check)
-
-
-@on_tensor_device
-def template_geometry(masks, xyz_mm, cap=None):
-    """The crop of each template before the random choice (_get_template, PEM/run_inference_custom_pytorch.py:199-214): masks (T,H,W)
-    u8 (mask == 255 is the object, :201), xyz_mm (T,H,W,3) f32 millimetres.  -> dict(bbox (T,4) i32 = get_bbox(mask == 255),
-    count (T) mask pixels, choose (T,cap) i32 raster-order mask pixels of the crop, cloud (T,cap,3) = their xyz / 1000, n_valid (T),
-    cap).  cap defaults to min(H, W)^2, the largest crop; n_valid[t] is the len(choose) the caller draws from (0: the reference's
-    get_bbox would fail on that template)."""
-    from .ops import _chk
-    masks = masks.to(torch.uint8).contiguous()
-    xyz_mm = xyz_mm.contiguous()
-    _chk(masks, "masks", torch.uint8, 3)
-    _chk(xyz_mm, "xyz_mm", torch.float32, 4)
-    T, H, Wd = masks.shape
-    if tuple(xyz_mm.shape) != (T, H, Wd, 3):
-        raise RuntimeError("xyz_mm must be (%d, %d, %d, 3), got %s" % (T, H, Wd, tuple(xyz_mm.shape)))
-    bbox = _empty((T, 4), masks, torch.int32)
-    count = _empty((T,), masks, torch.int32)
-    _lib.call("sam6d_template_bbox", _p(masks), T, H, Wd, _p(bbox), _p(count), _s())
-    cap = int(cap) if cap is not None else min(H, Wd) ** 2
-    choose = _empty((T, cap), masks, torch.int32)
-    cloud = _empty((T, cap, 3), masks)
-    n_valid = _empty((T,), masks, torch.int32)
-    _lib.call("sam6d_template_crop_points", _p(masks), _p(xyz_mm), T, H, Wd, _p(bbox), cap, _p(choose), _p(cloud), _p(n_valid), _s())
-    return dict(bbox=bbox, count=count, choose=choose, cloud=cloud, n_valid=n_valid, cap=cap)
-
-
-@on_tensor_device
-def template_inputs(images, masks, xyz_mm, sel, img_size=224, rgb_mask_flag=True, geom=None):
-    """rgb, rgb_choose, xyz of _get_template (PEM/run_inference_custom_pytorch.py:199-222) for T templates at once: images (T,H,W,3)
-    u8 RGB (or (T,H,W) grayscale), masks (T,H,W) u8 (mask == 255 is the object), xyz_mm (T,H,W,3) f32 millimetres, sel (T,ns) the
-    caller's random choice into each template's n_valid crop pixels (:215-218).  -> rgb (T,3,S,S) f32, rgb_choose (T,ns) i64, xyz
-    (T,ns,3) f32 metres.  geom: template_geometry(masks, xyz_mm) when the caller already has it (it draws sel from n_valid)."""
-    images = images.contiguous()
-    C = _image_channels(images, "images", 1)
-    if geom is None:
-        geom = template_geometry(masks, xyz_mm)
-    masks = masks.to(torch.uint8).contiguous()
-    T, H, Wd = masks.shape
-    if tuple(images.shape[:3]) != (T, H, Wd):
-        raise RuntimeError("images %s do not match masks %s" % (tuple(images.shape), tuple(masks.shape)))
-    if not torch.is_tensor(sel) or sel.dim() != 2 or sel.shape[0] != T:
-        raise RuntimeError("sel must be a (%d, ns) tensor" % T)
-    xyz, rgb_choose = proposal_choose(geom, sel.to(masks.device), img_size)
-    if rgb_mask_flag:
-        rgb = _rgb_crop_resize(images, 1, C, masks, None, 2, geom["bbox"], img_size, False, False)
-    else:
-        rgb = _rgb_crop_resize(images, 1, C, None, None, 0, geom["bbox"], img_size, False, False)
-    return rgb, rgb_choose, xyz
 
 
 def _cat0(a, b):

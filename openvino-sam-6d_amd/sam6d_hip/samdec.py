@@ -27,6 +27,9 @@ import types
 import torch
 import torch.nn.functional as F
 
+from . import _lib
+from .runtime import Linear, _empty, _p, _s, gemm, library_call, linear
+
 CONFIG = dict(dim=256, heads=8, depth=2, mlp=2048, grid=(64, 64), mask_tokens=4)
 T = 7  # tokens per prompt: iou, 4 mask tokens, the point, the padding point
 
@@ -75,7 +78,7 @@ def check_state_dicts(prompt_sd, decoder_sd, num_heads, grid=(64, 64), boxes=Non
 class SamDecoderWeights:
     """The weights of a prompt encoder and a mask decoder (modules, or their state dicts with num_heads / input_image_size / grid given)
     on `device` in `dtype`, the dense positional encoding, and the stacked / rearranged operands of the restructured sequence, made
-    once.  The fp16 halves of the GEMM weights are cut when the library first uses them (pem.Linear.w16)."""
+    once.  The fp16 halves of the GEMM weights are cut when the library first uses them (Linear.w16)."""
 
     def __init__(self, prompt_encoder, mask_decoder, device, dtype=torch.float32, num_heads=None, input_image_size=None, grid=None,
                  options=None):
@@ -136,11 +139,10 @@ class SamDecoderWeights:
         return self.md[name + ".weight"], self.md[name + ".bias"]
 
     def linear(self, name, bias=True):
-        """The pem.Linear (weight, bias, fp16 halves on demand) of `name`; stacked image-side operands carry no bias (their table is the
+        """The Linear (weight, bias, fp16 halves on demand) of `name`; stacked image-side operands carry no bias (their table is the
         GEMM's residual)."""
         lin = self._linears.get(name)
         if lin is None:
-            from .pem import Linear
             w, b = self.wb(name)
             lin = self._linears[name] = Linear(w, b if bias else None)
         return lin
@@ -324,8 +326,7 @@ class HipOps:
     """The same steps on the library: sam6d_gemm_nt(_w16) for every projection, the three kernels of csrc/samdec.hip for the rest."""
 
     def __init__(self, W):
-        from . import _lib, pem
-        self.W, self.lib, self.pem = W, _lib, pem
+        self.W = W
         self.shape = (W.dim, W.heads, T, W.grid[0], W.grid[1])
         self.ws = None
 
@@ -333,61 +334,61 @@ class HipOps:
         lin = self.W.linear(name)
         x2 = x.reshape(-1, x.shape[-1]).contiguous()
         r2 = None if residual is None else residual.reshape(-1, residual.shape[-1]).contiguous()
-        y = self.pem.linear(x2, lin, act=act, residual=r2)
+        y = linear(x2, lin, act=act, residual=r2)
         return y.view(*x.shape[:-1], y.shape[-1])
 
     def big(self, keys, name):
         """keys (P, N, C) . stacked weight^T + per-image table, one launch: a batch of P problems that share weight and table."""
-        pem, W = self.pem, self.W
+        W = self.W
         lin, table = W.linear(name, bias=False), W.wb(name)[1]
         P, N, C, NO = keys.shape[0], W.N, W.dim, lin.w.shape[0]
         keys = keys.contiguous()
-        out = pem._empty((P, N, NO), keys)
-        pem.gemm(keys, lin.w, None, out, N, NO, C, C, C, NO, residual=table, ldr=NO, batch=P, sA=N * C, sW=0, sC=N * NO, sR=0,
-                 w16=lin.w16())
+        out = _empty((P, N, NO), keys)
+        gemm(keys, lin.w, None, out, N, NO, C, C, C, NO, residual=table, ldr=NO, batch=P, sA=N * C, sW=0, sC=N * NO, sR=0,
+             w16=lin.w16())
         return out
 
     def fold(self, vtok, name):
         """(P, 56, 256), row 8 j + h = out_proj.weight[:, 16h:16h+16] . v[j, 16h:16h+16]: one problem per head (K = 16: the exact loop)."""
-        pem, W = self.pem, self.W
+        W = self.W
         P, ci = vtok.shape[0], vtok.shape[2]
         d, C, H = ci // W.heads, W.dim, W.heads
         vtok = vtok.contiguous()
-        out = pem._empty((P, T * H, C), vtok)
-        pem.gemm(vtok, W.md[name + ".weight"], None, out, P * T, C, d, ci, ci, H * C, batch=H, sA=d, sW=d, sC=C)
+        out = _empty((P, T * H, C), vtok)
+        gemm(vtok, W.md[name + ".weight"], None, out, P * T, C, d, ci, ci, H * C, batch=H, sA=d, sW=d, sC=C)
         return out
 
     def t2i(self, q, G, k_off, v_off):
-        pem, W = self.pem, self.W
+        W = self.W
         P = q.shape[0]
         q = q.contiguous()
         ld = G.shape[2]
-        need = self.lib.load().sam6d_samdec_token_to_image_workspace_bytes(P)
+        need = _lib.load().sam6d_samdec_token_to_image_workspace_bytes(P)
         if self.ws is None or self.ws.numel() * 4 < need:
-            self.ws = pem._empty(((need + 3) // 4,), q)
-        out = pem._empty((P, T, q.shape[2]), q)
-        self.lib.call("sam6d_samdec_token_to_image", pem._p(q), pem._p(G, k_off), pem._p(G, v_off), ld, 0 if G.shape[0] == 1 else W.N * ld,
-                      pem._p(out), P, *self.shape, self.ws.data_ptr(), self.ws.numel() * 4, pem._s())
+            self.ws = _empty(((need + 3) // 4,), q)
+        out = _empty((P, T, q.shape[2]), q)
+        _lib.call("sam6d_samdec_token_to_image", _p(q), _p(G, k_off), _p(G, v_off), ld, 0 if G.shape[0] == 1 else W.N * ld,
+                  _p(out), P, *self.shape, self.ws.data_ptr(), self.ws.numel() * 4, _s())
         return out
 
     def i2t(self, G, q_off, ktok, fold, p, keys):
-        pem, W, md = self.pem, self.W, self.W.md
+        W, md = self.W, self.W.md
         P, ld = ktok.shape[0], G.shape[2]
-        out = pem._empty((P, W.N, W.dim), ktok)
-        self.lib.call("sam6d_samdec_image_to_token", pem._p(G, q_off), ld, 0 if G.shape[0] == 1 else W.N * ld, pem._p(ktok.contiguous()),
-                      pem._p(fold), pem._p(md[p + "cross_attn_image_to_token.out_proj.bias"]), pem._p(keys),
-                      0 if keys.shape[0] == 1 else W.N * W.dim, pem._p(md[p + "norm4.weight"]), pem._p(md[p + "norm4.bias"]), 1e-5,
-                      pem._p(out), P, *self.shape, pem._s())
+        out = _empty((P, W.N, W.dim), ktok)
+        _lib.call("sam6d_samdec_image_to_token", _p(G, q_off), ld, 0 if G.shape[0] == 1 else W.N * ld, _p(ktok.contiguous()),
+                  _p(fold), _p(md[p + "cross_attn_image_to_token.out_proj.bias"]), _p(keys),
+                  0 if keys.shape[0] == 1 else W.N * W.dim, _p(md[p + "norm4.weight"]), _p(md[p + "norm4.bias"]), 1e-5,
+                  _p(out), P, *self.shape, _s())
         return out
 
     def upscale(self, G, off, hyper):
-        pem, W, md = self.pem, self.W, self.W.md
+        W, md = self.W, self.W.md
         P, ld = G.shape[0], G.shape[2]
         w2, b2 = W.wb("up2")
-        low = pem._empty((P, 3, 4 * W.grid[0], 4 * W.grid[1]), G)
-        self.lib.call("sam6d_samdec_upscale_masks", pem._p(G, off), ld, W.N * ld, pem._p(md["output_upscaling.1.weight"]),
-                      pem._p(md["output_upscaling.1.bias"]), 1e-6, pem._p(w2), pem._p(b2), pem._p(hyper.contiguous()), pem._p(low), P,
-                      *self.shape, pem._s())
+        low = _empty((P, 3, 4 * W.grid[0], 4 * W.grid[1]), G)
+        _lib.call("sam6d_samdec_upscale_masks", _p(G, off), ld, W.N * ld, _p(md["output_upscaling.1.weight"]),
+                  _p(md["output_upscaling.1.bias"]), 1e-6, _p(w2), _p(b2), _p(hyper.contiguous()), _p(low), P,
+                  *self.shape, _s())
         return low
 
 
@@ -444,21 +445,10 @@ def restructured(points, features, W):
     return _forward(ops, points, _tables(ops, features, W), W)
 
 
-def _library_call(fn):
-    def run(*args, options=None):
-        from . import pem
-
-        @pem.on_tensor_device
-        def inner(*a, **kw):
-            if pem._flags().mode == 2:
-                raise NotImplementedError("sam6d_hip.samdec: matmul mode 2 is not implemented for the SAM mask decoder (modes 0 and 1 are)")
-            return fn(*a)
-        return inner(*args, options=options)
-    run.__doc__, run.__name__ = fn.__doc__, fn.__name__
-    return run
+_entry = library_call("sam6d_hip.samdec", "SAM mask decoder")
 
 
-@_library_call
+@_entry
 def image_tables(features, W):
     """features (1, 256, 64, 64) on the HIP device -> the per-image tables of layer 0 (src = embedding + no_mask_embed, and its k / v /
     q projections with the positional part added), once per set_image."""
@@ -474,7 +464,7 @@ def predict_low(points, tables, W, options=None):
     return _predict_low(tables.src, points, tables, W, options=options)
 
 
-@_library_call
+@_entry
 def _predict_low(_src, points, tables, W):
     W.require_library()
     return _forward(HipOps(W), points, tables, W)

@@ -19,7 +19,8 @@ from typing import NamedTuple
 import torch
 import torch.nn.functional as F
 
-from . import encoder
+from . import _lib, encoder
+from .runtime import Linear, _empty, _p, _s, gemm, gemm_route, library_call
 
 CONFIG = dict(embed_dim=1280, num_heads=16, mlp_dim=5120, patch_size=16, grid=64, window_size=14, out_chans=256, eps=1e-6)
 D, HEADS, HD, HID, PATCH, GRID, WIN, OUT, EPS = 1280, 16, 80, 5120, 16, 64, 14, 256, 1e-6
@@ -117,8 +118,6 @@ class _SamEncoder(encoder.Encoder):
     __slots__ = ()
 
     def attend(self, T, Y, B, n, blk):
-        from . import _lib
-        from .pem import _p, _s
         heads = blk["qkv"].w.shape[0] // (3 * HD)
         if blk["window"]:
             _lib.call(self.attention, _p(T), _p(blk["qkv"].b), _p(blk["rel_h"]), _p(blk["rel_w"]), _p(Y), B, heads, _s())
@@ -149,7 +148,6 @@ class SamEncoderWeights(encoder.Weights):
                 self._pack()
 
     def _pack(self):
-        from .pem import Linear
         sd = self.sd
         g = lambda k: sd[_ref_key(k)]  # noqa: E731
         self.patch = Linear(g("patch_embed.proj.weight").reshape(D, K), g("patch_embed.proj.bias"))
@@ -320,23 +318,11 @@ def restructured(x, W):
 
 
 # ------------------------------------------------------------------------------------------------- the library
-def _library_call(fn):
-    def run(*args, options=None):
-        from . import pem
-
-        @pem.on_tensor_device
-        def inner(*a, **kw):
-            ENC.require_mode()
-            return fn(*a)
-        return inner(*args, options=options)
-    run.__doc__, run.__name__ = fn.__doc__, fn.__name__
-    return run
+_entry = library_call(ENC.name, ENC.role)
 
 
 def _neck(X, W, B, Y, T, out, o_off):
     """X (B*4096, 1280) -> out[o_off:] as (B, 256, 64, 64); Y (>= B*4096*256 floats) and T (>= B*4096*2560) are workspaces."""
-    from . import _lib
-    from .pem import _p, _s, gemm
     M = B * NP
     gemm(X, W.neck1.w, None, Y, M, OUT, D, D, D, OUT, w16=W.neck1.w16())
     _lib.call("sam6d_layernorm256", _p(Y), _p(W.norms[0][0]), _p(W.norms[0][1]), _p(T), M, OUT, OUT, 1e-6, _s())
@@ -348,7 +334,6 @@ def _neck(X, W, B, Y, T, out, o_off):
 
 def _encode(W, B, like, embed):
     """The launch sequence behind `encode` and `encode_rows`: embed(i0, b, X) fills X (b*4096, 1280) for images i0 .. i0 + b - 1."""
-    from .pem import _empty
     out = _empty((B, OUT, GRID, GRID), like)
     if B == 0:
         return out
@@ -363,10 +348,9 @@ def _encode(W, B, like, embed):
     return out
 
 
-@_library_call
+@_entry
 def encode(x, W):
     """x (B, 3, 1024, 1024) float32 on the HIP device, preprocessed as `sam.image_encoder` expects it -> (B, 256, 64, 64)."""
-    from .pem import _empty
     W.require_library()
     check_images(x)
     x = x.contiguous()
@@ -374,7 +358,7 @@ def encode(x, W):
     return _encode(W, x.shape[0], x, lambda i0, b, X: ENC.embed(x[i0:i0 + b], W, X, A))
 
 
-@_library_call
+@_entry
 def encode_rows(A, W):
     """`encode` from the patch rows: A (B*4096, 768) float32 on the HIP device, row 4096 b + 64 py + px = the patch's values of the
     preprocessed image in (c, kh, kw) order (samfront.preprocess(..., layout="rows"), or sam6d_sam_patch_rows) -> (B, 256, 64, 64).  The
@@ -391,7 +375,6 @@ def encode_rows(A, W):
 def block_gemm_routes(W, B=1):
     """The SAM6D_GEMM_ROUTE_* codes of the four GEMMs of a block at B images, in the calling thread's matmul mode (nothing is
     launched): [qkv, proj, fc1, fc2]."""
-    from .pem import _empty, gemm_route
     W.require_library()
     blk, M = W.blocks[0], B * NP
     a = _empty((16,), blk["qkv"].w)
@@ -404,21 +387,19 @@ class _Pieces:
     """Single stages behind the public entry-point conventions, for the tests (as encoder.pieces)."""
 
     @staticmethod
-    @_library_call
+    @_entry
     def window_attention(qkv, pad_qkv, rel_h, rel_w, B):
         """qkv (B*4096, 3*80*heads), pad_qkv (3*80*heads), rel_h / rel_w (27, 80) -> (B*4096, 80*heads)."""
         return _Pieces._attention("sam6d_sam_window_attention", qkv, pad_qkv, rel_h, rel_w, B, 2 * WIN - 1)
 
     @staticmethod
-    @_library_call
+    @_entry
     def global_attention(qkv, rel_h, rel_w, B):
         """qkv (B*4096, 3*80*heads), rel_h / rel_w (127, 80) -> (B*4096, 80*heads)."""
         return _Pieces._attention("sam6d_sam_global_attention", qkv, None, rel_h, rel_w, B, 2 * GRID - 1)
 
     @staticmethod
     def _attention(name, qkv, pad_qkv, rel_h, rel_w, B, nrel):
-        from . import _lib
-        from .pem import _empty, _p, _s
         if qkv.dim() != 2 or B < 1 or qkv.shape[0] != B * NP or qkv.shape[1] % (3 * HD):
             raise ValueError("sam6d_hip.samenc: qkv must be (B*%d, 3*%d*heads), got %s for B = %d" % (NP, HD, tuple(qkv.shape), B))
         heads = qkv.shape[1] // (3 * HD)
@@ -434,10 +415,9 @@ class _Pieces:
         return out
 
     @staticmethod
-    @_library_call
+    @_entry
     def block(x, blk):
         """x (B, 4096, 1280) -> one block (a `pack_block` dictionary, or W.blocks[i]) applied to a copy."""
-        from .pem import _empty
         if x.dim() != 3 or tuple(x.shape[1:]) != (NP, D) or x.dtype != torch.float32:
             raise ValueError("sam6d_hip.samenc: x must be float32 (B, %d, %d), got %s %s" % (NP, D, tuple(x.shape), x.dtype))
         B = x.shape[0]
@@ -446,10 +426,9 @@ class _Pieces:
         return X.view(B, NP, D)
 
     @staticmethod
-    @_library_call
+    @_entry
     def neck(x, W):
         """x (B, 4096, 1280), the residual stream after the last block -> (B, 256, 64, 64)."""
-        from .pem import _empty
         W.require_library()
         if x.dim() != 3 or tuple(x.shape[1:]) != (NP, D) or x.dtype != torch.float32:
             raise ValueError("sam6d_hip.samenc: x must be float32 (B, %d, %d), got %s %s" % (NP, D, tuple(x.shape), x.dtype))

@@ -17,8 +17,8 @@ import functools
 import numpy as np
 import torch
 
-from . import amg
-from .pem import on_tensor_device
+from . import _lib, amg
+from .runtime import _empty, _p, _s, on_tensor_device
 
 PRECISION_BITS = 22
 MAX_TAPS = 9
@@ -111,8 +111,6 @@ def preprocess(image, mean, std, side=1024, layout="x", reverse=False, options=N
     layout "x":    (B, 3, side, side) float32 = sam.preprocess of the resized image (B = 1 for a single image).
     layout "rows": (B * (side / 16)^2, 768) float32 = the patch rows of that tensor (what sam6d_sam_patch_rows writes from it; for
                    side = 1024, samenc.encode_rows takes them)."""
-    from . import _lib
-    from .pem import _empty, _p, _s
     img, (oh, ow) = _check(image, side, layout)
     mean, std = _floats3(mean, "mean"), _floats3(std, "std")
     if img.stride(3) != 1 or img.stride(2) != 3 or img.stride(1) < 3 * img.shape[2] or (img.shape[0] > 1 and img.stride(0) < 0):

@@ -11,7 +11,7 @@ After blocks 2, 5, 8 and 11 the final norm writes the 196 patch rows of each ima
 import torch
 
 from . import _lib, encoder
-from .pem import Linear, _empty, _getter, _p, _s, gemm, on_tensor_device
+from .runtime import Linear, _empty, _getter, _p, _s, gemm, on_tensor_device
 
 D = 768        # embed_dim of vit_base
 NP = 196       # patches of a 224 x 224 image

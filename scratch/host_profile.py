@@ -3,12 +3,12 @@ import os, sys, time, cProfile, pstats
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "openvino-sam-6d_amd"))
 import torch
-from sam6d_hip import pem, synth, _lib
+from sam6d_hip import pem, runtime, synth, _lib
 ncalls = [0]
 def fake(name, *a):
     ncalls[0] += 1
 _lib.call = fake; pem._lib.call = fake
-pem._s = lambda: 0
+pem._s = runtime._s = lambda: 0  # (pem binds its own name at import; Linear and gemm read runtime's)
 sd = synth.make_pem_weights(1)
 W = pem.PemWeights(sd, torch.device("cpu"))
 inp = synth.config2_inputs(B=4, seed=1)

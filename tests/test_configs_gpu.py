@@ -49,15 +49,15 @@ def W(sd, dev):
 def test_config1_test_data_geometry_bit_exact(dev):
     """Real depth map + camera: depth -> cloud, mask & depth > 0, crop box, radius filter, the caller's 2048 random picks and the
     resized-crop indices (PEM/run_inference_custom_pytorch.py:292-355), bit-exact against the reference's own helpers."""
-    from sam6d_hip import pem
+    from sam6d_hip import inputs
     g = golden("config1")
     depth = (g["depth_u16"].astype(np.float32) * np.float32(g["depth_scale"]) / np.float32(1000.0)).astype(np.float32)
     mask = np.unpackbits(g["mask_bits"])[: 480 * 640].reshape(1, 480, 640)
-    geom = pem.proposal_geometry(torch.from_numpy(mask).to(dev), torch.from_numpy(depth).to(dev), g["K"], float(g["model_radius"]))
+    geom = inputs.proposal_geometry(torch.from_numpy(mask).to(dev), torch.from_numpy(depth).to(dev), g["K"], float(g["model_radius"]))
     assert geom["bbox"][0].cpu().tolist() == [int(v) for v in g["bbox"]]
     assert int(geom["n_keep"][0]) == int(g["n_keep"])
     assert np.array_equal(geom["center"][0].cpu().numpy(), g["center"])
-    pts, rc = pem.proposal_choose(geom, torch.from_numpy(g["choose_idx"])[None].to(dev), 224)
+    pts, rc = inputs.proposal_choose(geom, torch.from_numpy(g["choose_idx"])[None].to(dev), 224)
     assert np.array_equal(pts[0].cpu().numpy(), g["pts"]), "observed points"
     assert np.array_equal(rc[0].cpu().numpy(), g["rgb_choose"]), "rgb_choose"
 
@@ -65,13 +65,13 @@ def test_config1_test_data_geometry_bit_exact(dev):
 def test_config1_template_fps_and_radius_bit_exact(dev):
     """5000 CAD surface points -> 2048 by FPS (get_obj_feats' sample_pts_feats) and ViTEncoder.forward's radius normalisation
     (PEM/model/feature_extraction.py:133-137) on the real CAD geometry."""
-    from sam6d_hip import ops, pem
+    from sam6d_hip import inputs, ops
     g = golden("config1")
     tem = torch.from_numpy(g["tem_pts"])[None].to(dev)
     idx = ops.furthest_point_sampling(tem, 2048)
     assert np.array_equal(idx.cpu().numpy().astype(np.int16), g["tem_idx"])
     po_raw = tem[0][idx[0].long()][None].contiguous()
-    pm, po, radius = pem.radius_normalize(torch.from_numpy(g["pts"])[None].to(dev), po_raw)
+    pm, po, radius = inputs.radius_normalize(torch.from_numpy(g["pts"])[None].to(dev), po_raw)
     assert np.array_equal(radius.cpu().numpy(), g["radius"])
     assert np.array_equal(pm.cpu().numpy(), g["dense_pm"]) and np.array_equal(po.cpu().numpy(), g["dense_po"])
 

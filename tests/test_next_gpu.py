@@ -13,21 +13,21 @@ pytestmark = pytest.mark.gpu
 @pytest.mark.parametrize("B,Npo,Npm", [(1, 1, 1), (3, 2048, 2048), (2, 5000, 777), (32, 2048, 2048)])
 def test_radius_normalize_bit_exact(dev, B, Npo, Npm):
     from oracle import pem_oracle as O
-    from sam6d_hip import pem
+    from sam6d_hip import inputs
     g = torch.Generator().manual_seed(B * 131 + Npo)
     po = (torch.rand(B, Npo, 3, generator=g) - 0.5) * torch.rand(B, 1, 1, generator=g) * 0.4
     pts = torch.randn(B, Npm, 3, generator=g) * 0.1
     pm_w, po_w, r_w = O.radius_normalize(pts, po)
-    pm, po_g, r = pem.radius_normalize(pts.to(dev), po.to(dev))
+    pm, po_g, r = inputs.radius_normalize(pts.to(dev), po.to(dev))
     assert torch.equal(r.cpu(), r_w), "radius differs: %s vs %s" % (r.cpu(), r_w)
     assert torch.equal(pm.cpu(), pm_w)
     assert torch.equal(po_g.cpu(), po_w)
 
 
 def test_radius_normalize_rejects_cpu_tensor():
-    from sam6d_hip import pem
+    from sam6d_hip import inputs
     with pytest.raises((RuntimeError, ValueError, AssertionError)):
-        pem.radius_normalize(torch.zeros(1, 4, 3), torch.zeros(1, 4, 3))
+        inputs.radius_normalize(torch.zeros(1, 4, 3), torch.zeros(1, 4, 3))
 
 
 @pytest.mark.parametrize("N,D,HW,patch", [(1, 1024, 224, 14), (5, 1024, 224, 14), (3, 64, 56, 7), (42, 1024, 224, 14)])
@@ -74,22 +74,22 @@ def test_vit_encoder_forward_uses_hip_radius(dev):
     import importlib
     fe = importlib.import_module("feature_extraction")
     src = open(fe.__file__).read()
-    assert "_pem.radius_normalize" in src and "torch.norm(dense_po" not in src
+    assert "_inputs.radius_normalize" in src and "torch.norm(dense_po" not in src
 
 
 # ---------------------------------------------------------------------------- depth back-projection (row f2)
 def test_depth_to_cloud_golden_bit_exact(dev):
     from tests._util import golden
-    from sam6d_hip import pem
+    from sam6d_hip import inputs
     g = golden("depth_cloud")
     depth = torch.from_numpy(g["depth"]).to(dev)
-    crop = pem.depth_to_cloud(depth, g["K"], [int(v) for v in g["bbox"]]).cpu().numpy()
+    crop = inputs.depth_to_cloud(depth, g["K"], [int(v) for v in g["bbox"]]).cpu().numpy()
     assert np.array_equal(crop, g["crop"])
     import hashlib
-    full = pem.depth_to_cloud(depth, g["K"]).cpu().numpy()
+    full = inputs.depth_to_cloud(depth, g["K"]).cpu().numpy()
     assert hashlib.sha256(np.ascontiguousarray(full).tobytes()).hexdigest() == str(g["full_sha"])
     with pytest.raises(RuntimeError):
-        pem.depth_to_cloud(depth, g["K"], [0, 121, 0, 10])  # bbox outside the map
+        inputs.depth_to_cloud(depth, g["K"], [0, 121, 0, 10])  # bbox outside the map
 
 
 # ---------------------------------------------------------------------------- Detections bookkeeping (row f3)
@@ -198,11 +198,11 @@ def test_proposal_geometry_golden_bit_exact(dev):
     values composed from the reference's own helpers (tests/golden/test_data.npz)."""
     import hashlib
     from tests._util import golden
-    from sam6d_hip import pem
+    from sam6d_hip import inputs
     g = golden("test_data")
     masks = torch.from_numpy(g["masks"]).to(dev)
     depth = torch.from_numpy(g["depth"]).to(dev)
-    geom = pem.proposal_geometry(masks, depth, g["K"], float(g["radius"]))
+    geom = inputs.proposal_geometry(masks, depth, g["K"], float(g["radius"]))
     kept = [int(i) for i in g["kept"]]
     count = geom["count"].cpu().numpy(); n_keep = geom["n_keep"].cpu().numpy()
     ours = [i for i in range(masks.shape[0]) if count[i] > 32 and n_keep[i] >= 4]
@@ -211,7 +211,7 @@ def test_proposal_geometry_golden_bit_exact(dev):
     sel = torch.zeros(masks.shape[0], ns, dtype=torch.int32)
     for i in kept:
         sel[i] = torch.from_numpy(g["p%d_sel" % i].astype(np.int32))
-    pts, rc = pem.proposal_choose(geom, sel.to(dev), int(g["img_size"]))
+    pts, rc = inputs.proposal_choose(geom, sel.to(dev), int(g["img_size"]))
     for i in kept:
         assert geom["bbox"][i].cpu().tolist() == [int(v) for v in g["p%d_bbox" % i]]
         k = int(g["p%d_n_keep" % i])
@@ -227,7 +227,7 @@ def test_proposal_geometry_golden_bit_exact(dev):
 
 def test_proposal_geometry_random_masks_vs_oracle(dev):
     from oracle import pem_oracle as O
-    from sam6d_hip import pem
+    from sam6d_hip import inputs
     g = np.random.default_rng(3)
     H, Wd, N = 96, 128, 12
     yy, xx = np.mgrid[0:H, 0:Wd]
@@ -238,7 +238,7 @@ def test_proposal_geometry_random_masks_vs_oracle(dev):
         cy, cx, r = g.integers(0, H), g.integers(0, Wd), g.integers(3, 40)
         masks[i] = (((xx - cx) ** 2 + (yy - cy) ** 2) < r * r) & (g.random((H, Wd)) > 0.2)
     K = np.array([[150.0, 0, 64.0], [0, 150.0, 48.0], [0, 0, 1]], np.float32)
-    geom = pem.proposal_geometry(torch.from_numpy(masks).to(dev), torch.from_numpy(depth).to(dev), K, 0.11)
+    geom = inputs.proposal_geometry(torch.from_numpy(masks).to(dev), torch.from_numpy(depth).to(dev), K, 0.11)
     for i in range(N):
         o = O.proposal_geometry(masks[i], depth, K, np.float32(0.11))
         cnt, nk = int(geom["count"][i]), int(geom["n_keep"][i])

@@ -1,4 +1,4 @@
-"""The rgb input of Net.forward on the device (pem.proposal_rgb / template_inputs) and the assembled inputs (sam6d_hip.inputs) against
+"""The rgb input of Net.forward on the device (inputs.proposal_rgb / template_inputs) and the assembled inputs (sam6d_hip.inputs) against
 the numpy restatement of the reference's preprocessing (tests/cv2_linear.py): resized crops byte for byte, normalised tensors and
 every other input bitwise, and the (R, t, score) the network computes from either."""
 import importlib
@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from tests import cv2_linear as CV
-from sam6d_hip import inputs, pem, synth
+from sam6d_hip import inputs, synth
 
 pytestmark = pytest.mark.gpu
 
@@ -45,8 +45,8 @@ def _want_u8(img, depth, masks, bbox, S, flag):
 
 def _check(dev, img, depth, masks, bbox, S=224, flag=True):
     geom = dict(bbox=torch.tensor(bbox, dtype=torch.int32, device=dev))
-    rgb, u8 = pem.proposal_rgb(torch.from_numpy(img).to(dev), torch.from_numpy(masks).to(dev), torch.from_numpy(depth).to(dev), geom,
-                               S, flag, return_uint8=True)
+    rgb, u8 = inputs.proposal_rgb(torch.from_numpy(img).to(dev), torch.from_numpy(masks).to(dev), torch.from_numpy(depth).to(dev), geom,
+                                  S, flag, return_uint8=True)
     got = u8.cpu().numpy()
     want = _want_u8(img, depth, masks, bbox, S, flag)
     for i in range(len(bbox)):
@@ -80,7 +80,7 @@ def test_resize_mask_flag_off_grayscale_and_rectangles(dev):
 @pytest.mark.parametrize("N", [1, 32])
 def test_resize_proposals_from_geometry(dev, N):
     img, depth, masks = _scene(20 + N, N)
-    geom = pem.proposal_geometry(torch.from_numpy(masks).to(dev), torch.from_numpy(depth).to(dev), K, 0.1)
+    geom = inputs.proposal_geometry(torch.from_numpy(masks).to(dev), torch.from_numpy(depth).to(dev), K, 0.1)
     _check(dev, img, depth, masks, geom["bbox"].cpu().tolist())
 
 
@@ -195,20 +195,20 @@ def test_error_contract(dev):
     geom = dict(bbox=torch.tensor([[0, 10, 0, 10], [0, 10, 0, 10]], dtype=torch.int32, device=dev))
     ti, tm, td = torch.from_numpy(img), torch.from_numpy(masks), torch.from_numpy(depth)
     with pytest.raises(RuntimeError):
-        pem.proposal_rgb(ti, tm, td, dict(bbox=geom["bbox"].cpu()))
+        inputs.proposal_rgb(ti, tm, td, dict(bbox=geom["bbox"].cpu()))
     with pytest.raises(RuntimeError):
-        pem.proposal_rgb(ti.to(dev).float(), tm.to(dev), td.to(dev), geom)
+        inputs.proposal_rgb(ti.to(dev).float(), tm.to(dev), td.to(dev), geom)
     with pytest.raises(RuntimeError):
-        pem.proposal_rgb(ti.to(dev), tm.to(dev), td.to(dev).double(), geom)
+        inputs.proposal_rgb(ti.to(dev), tm.to(dev), td.to(dev).double(), geom)
     with pytest.raises(RuntimeError):
-        pem.proposal_rgb(ti.to(dev), tm.to(dev), td.to(dev), dict(bbox=geom["bbox"].float()))
+        inputs.proposal_rgb(ti.to(dev), tm.to(dev), td.to(dev), dict(bbox=geom["bbox"].float()))
     for bad in ([0, 10, 630, 641], [-1, 9, 0, 10], [470, 481, 0, 10], [20, 10, 0, 10]):
         b = torch.tensor([[0, 10, 0, 10], bad], dtype=torch.int32, device=dev)
         with pytest.raises(RuntimeError):
-            pem.proposal_rgb(ti.to(dev), tm.to(dev), td.to(dev), dict(bbox=b))
+            inputs.proposal_rgb(ti.to(dev), tm.to(dev), td.to(dev), dict(bbox=b))
     imgs, tmasks, xyz = _templates(2, T=2)
     with pytest.raises(RuntimeError):
-        pem.template_inputs(torch.from_numpy(imgs), torch.from_numpy(tmasks), torch.from_numpy(xyz), torch.zeros(2, 8, dtype=torch.int32))
+        inputs.template_inputs(torch.from_numpy(imgs), torch.from_numpy(tmasks), torch.from_numpy(xyz), torch.zeros(2, 8, dtype=torch.int32))
     with pytest.raises(RuntimeError):
-        pem.template_inputs(torch.from_numpy(imgs).to(dev), torch.from_numpy(tmasks).to(dev), torch.from_numpy(xyz).to(dev).double(),
-                            torch.zeros(2, 8, dtype=torch.int32, device=dev))
+        inputs.template_inputs(torch.from_numpy(imgs).to(dev), torch.from_numpy(tmasks).to(dev), torch.from_numpy(xyz).to(dev).double(),
+                               torch.zeros(2, 8, dtype=torch.int32, device=dev))
