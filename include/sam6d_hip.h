@@ -710,6 +710,25 @@ int sam6d_amg_small_regions(unsigned char* masks, int K, int H, int W, int min_a
                             size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * The two resizes of `segmentor_width_size` round the mask generator (ISM/model/sam.py:77-100; csrc/segresize.hip).  Both refuse
+ * without a launch: a non-zero return writes nothing.  (New entries only, so SAM6D_ABI_VERSION stays.)
+ * ---------------------------------------------------------------------------------------------------------- */
+
+/* preprocess_resize (ISM/model/sam.py:77-83): dst (h, w, 3) u8, contiguous, = cv2.resize(src, (w, h)) with the default INTER_LINEAR of a
+ * CV_8UC3 image as OpenCV 4.x computes it (imgproc/src/resize.cpp: 11-bit fixed point, the vectorised vertical pass for every column;
+ * the recipe is written down in csrc/rgbprep.hip).  Pixel (y, x) of src is at src + y row_stride + 3 x (bytes, row_stride >= 3 W: a
+ * crop view is read in place).  H == 2 h and W == 2 w is OpenCV's INTER_AREA fast path, the rounded 2 x 2 mean; equal sizes copy.
+ * H, W, h, w 1 .. 4096 (h = int(width * H / W) can be 0, where cv2 raises: refused); channels must be 3; dst must not overlap src. */
+int sam6d_image_resize_linear(const unsigned char* src, long row_stride, int H, int W, int channels, unsigned char* dst, int h, int w,
+                              void* stream);
+/* postprocess_resize (ISM/model/sam.py:85-100), its masks: masks (K, h, w) u8, any non-zero byte = 1 (a bool tensor's bytes) -> out
+ * (K, H, W) f32, contiguous, = F.interpolate(masks.unsqueeze(1).float(), size=(H, W), mode="bilinear", align_corners=False)[:, 0],
+ * enlarging or shrinking (two taps per axis, no antialiasing): upsample_bilinear2d's fp32 expression, written down in
+ * csrc/segresize.hip, a function of (mask, y, x) alone.  K 0 .. 65535 (0: no launch), sizes 1 .. 8192, out 4-byte aligned (16 bytes
+ * and W % 4 == 0 for 16-byte stores).  K H W may pass 2^31. */
+int sam6d_masks_resize_bilinear(const unsigned char* masks, int K, int h, int w, int H, int W, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * SAM's mask decoder for point prompts (ISM/segment_anything/modeling/mask_decoder.py:112-149, its TwoWayTransformer
  * ISM/segment_anything/modeling/transformer.py:62-106): what lies between the dense projections over the P x 4096 image rows, which are
  * sam6d_gemm_nt / _w16 launches.  Specialised for transformer_dim 256, 8 heads, 7 tokens per prompt and a 64 x 64 grid: every entry

@@ -29,15 +29,7 @@
 #define AMG_LDS_BYTES (48 * 1024)
 #define AMG_BIG 0x7fffffff
 
-__host__ __device__ __forceinline__ void amg_tap(float scale, int dst, int n, int& i0, int& i1, float& l0, float& l1) {
-  float src = scale * ((float)dst + 0.5f) - 0.5f;
-  if (src < 0.f) src = 0.f;
-  i0 = (int)src;
-  if (i0 > n - 1) i0 = n - 1;  // never taken for a valid size (src < n - 0.5); keeps every index in range
-  i1 = i0 + (i0 < n - 1 ? 1 : 0);
-  l1 = src - (float)i0;
-  l0 = 1.0f - l1;
-}
+// amg_tap: common.h (segresize.hip samples with the same tap)
 
 // first and last low-resolution row that output rows [y0, y1) read
 __host__ __device__ __forceinline__ void amg_band_rows(int y0, int y1, int lh, int S, int in_h, int out_h, int& r_lo, int& r_hi) {

@@ -198,6 +198,29 @@ __device__ __forceinline__ float pdist3(float x0, float x1, float x2, float sx, 
   return d < 0.0f ? 0.0f : d;
 }
 
+// One axis of torch's upsample_bilinear2d with align_corners=False (ATen UpSampleBilinear2d.cu, area_pixel_compute_source_index):
+// output index dst of an axis of n source pixels, scale = (float)n / n_out -> the two source indices and their fp32 weights.  The
+// recipe of csrc/amg.hip ("THE VALUE OF A PIXEL") and csrc/segresize.hip; one copy, so both sample the same grid.
+__host__ __device__ __forceinline__ void amg_tap(float scale, int dst, int n, int& i0, int& i1, float& l0, float& l1) {
+  float src = scale * ((float)dst + 0.5f) - 0.5f;
+  if (src < 0.f) src = 0.f;
+  i0 = (int)src;
+  if (i0 > n - 1) i0 = n - 1;  // never taken for a valid size (src < n - 0.5); keeps every index in range
+  i1 = i0 + (i0 < n - 1 ? 1 : 0);
+  l1 = src - (float)i0;
+  l0 = 1.0f - l1;
+}
+
+// OpenCV's 8-bit INTER_LINEAR (imgproc/src/resize.cpp; the recipe is written down in csrc/rgbprep.hip): saturate_cast<short> of an
+// int and of rint(float), and the coordinate map of one output index, scale = 1.0 / ((double)n_out / n) -> (s, f) before any clamp.
+__device__ __forceinline__ int sat_s16(int v) { return min(max(v, -32768), 32767); }
+__device__ __forceinline__ int sat_s16f(float v) { return (int)fminf(fmaxf(rintf(v), -32768.f), 32767.f); }
+__device__ __forceinline__ void cv_coord(int d, double scale, int& s, float& f) {
+  f = (float)(((double)d + 0.5) * scale - 0.5);
+  s = (int)floorf(f);
+  f -= (float)s;
+}
+
 // sin and cos of the same fp32 argument, <= 1.5 ulp each for |x| < 1e5 (checked against fp64 over [0, 1000], the range of
 // the sinusoidal-embedding arguments: indices up to ~870 times frequencies <= 1): three-term Cody-Waite reduction by
 // pi/2 with fma, degree-9 / degree-8 minimax polynomials on [-pi/4, pi/4], quadrant fix-up.  ~30 VALU instructions,

@@ -26,15 +26,7 @@ struct XTap {
   int a;  // a0 in the low 16 bits, a1 in the high 16 bits
 };
 
-__device__ __forceinline__ int sat_s16(int v) { return min(max(v, -32768), 32767); }
-__device__ __forceinline__ int sat_s16f(float v) { return (int)fminf(fmaxf(rintf(v), -32768.f), 32767.f); }
-
-// OpenCV's coordinate map for one output index: (sy, fy) before any clamp
-__device__ __forceinline__ void cv_coord(int d, double scale, int& s, float& f) {
-  f = (float)(((double)d + 0.5) * scale - 0.5);
-  s = (int)floorf(f);
-  f -= (float)s;
-}
+// sat_s16, sat_s16f, cv_coord: common.h (segresize.hip resizes whole images by the same recipe)
 
 // mask_mode: 0 = no mask (rgb_mask_flag False), 1 = (mask > 0) & (depth > 0) (get_test_data :318), 2 = mask == 255 (_get_template :201)
 __device__ __forceinline__ unsigned load_px(const unsigned char* __restrict__ img, int C, int W, int r, int c,

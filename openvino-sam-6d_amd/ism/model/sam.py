@@ -16,6 +16,11 @@ patch rows directly.  Otherwise the SAM network is reached only through the `sam
 The encoder's input resize (ResizeLongestSide.apply_image: PIL through torchvision) belongs to the network side: `set_image` goes
 through `encode_image(sam, image) -> (features, input_size)`; without one, segment_anything.SamPredictor is imported when the first
 image arrives.  Nothing here imports segment_anything, torchvision, cv2 or pycocotools at module import.
+
+With hip_resize (SAM6D_HIP_SEGRESIZE=1; off by default) the two resizes of `segmentor_width_size` run on sam6d_hip.amg: the image is
+uploaded once and shrunk on the device as cv2.resize does (resize_image; no cv2 import), handed on as a device tensor with hip_front
+or copied back once, resized, for an `encode_image` hook or SamPredictor; the surviving bool masks go through one launch to the
+image's size (resize_masks) instead of a float copy and F.interpolate.
 """
 import logging
 import os
@@ -98,7 +103,9 @@ class Predictor:
         encoder when that is on as well, else the preprocessed tensor into sam.image_encoder."""
         sf, (mean, std) = self._samfront, self._pixel_stats
         side = int(self.model.image_encoder.img_size)
-        img = sf.upload(image, self.device)
+        dev = torch.device(self.device)
+        on_dev = torch.is_tensor(image) and image.device.type == dev.type and dev.index in (None, image.device.index)
+        img = image if on_dev else sf.upload(image, dev)  # (hip_resize hands its resized image on as a device tensor)
         reverse = image_format != self.model.image_format
         if self.hip_encoder:
             rows = sf.preprocess(img, mean, std, side=side, layout="rows", reverse=reverse)
@@ -206,6 +213,7 @@ class CustomSamAutomaticMaskGenerator:
         hip_decoder=None,
         hip_encoder=None,
         hip_front=None,
+        hip_resize=None,
     ):
         # SamAutomaticMaskGenerator's own defaults for what the reference's subclass does not pass on
         self.points_per_side = 32
@@ -221,7 +229,13 @@ class CustomSamAutomaticMaskGenerator:
             hip_encoder = os.environ.get("SAM6D_HIP_SAMENC", "0") == "1"
         if hip_front is None:    # ... and the library route of the encoder's input (resize, normalise, pad)
             hip_front = os.environ.get("SAM6D_HIP_SAMFRONT", "0") == "1"
+        if hip_resize is None:   # ... and the library route of segmentor_width_size's two resizes
+            hip_resize = os.environ.get("SAM6D_HIP_SEGRESIZE", "0") == "1"
         self.predictor = Predictor(sam, encode_image, hip_decoder, hip_encoder, hip_front)
+        self.hip_resize = bool(hip_resize)
+        if self.hip_resize and torch.device(self.predictor.device).type != "cuda":
+            raise RuntimeError("hip_resize: the model is on %s; the library route needs it on a HIP device (hip_resize=False or "
+                               "SAM6D_HIP_SEGRESIZE=0 keeps cv2.resize and F.interpolate)" % (self.predictor.device,))
         self.points_per_batch = points_per_batch
         self.pred_iou_thresh = pred_iou_thresh
         self.stability_score_thresh = stability_score_thresh
@@ -244,15 +258,25 @@ class CustomSamAutomaticMaskGenerator:
     def preprocess_resize(self, image: np.ndarray):
         orig_size = image.shape[:2]
         height, width = self._resized_shape(orig_size)
+        if self.hip_resize:
+            # one upload, the resize on the device; with the library's front the resized image stays there (a tensor that _process_crop
+            # slices and samfront.preprocess reads in place), else it is copied back once, resized, for the hook or SamPredictor
+            from sam6d_hip import samfront
+            small = amg.resize_image(samfront.upload(image, self.predictor.device), (height, width))
+            return small if self.predictor.hip_front else small.cpu().numpy()
         if (height, width) == tuple(orig_size):
             return image.copy()  # cv2.resize to the same size copies the pixels
         import cv2
         return cv2.resize(image.copy(), (width, height))
 
     def postprocess_resize(self, detections, orig_size):
-        masks = detections["masks"].float()
-        if tuple(masks.shape[-2:]) != (orig_size[0], orig_size[1]):
-            masks = F.interpolate(masks.unsqueeze(1), size=(orig_size[0], orig_size[1]), mode="bilinear", align_corners=False)[:, 0, :, :]
+        if self.hip_resize:
+            masks = detections["masks"]  # bool, from the tail or the clean-up: one launch, no float copy of the small masks
+            masks = amg.resize_masks(masks if masks.dtype in (torch.bool, torch.uint8) else masks != 0, (orig_size[0], orig_size[1]))
+        else:
+            masks = detections["masks"].float()
+            if tuple(masks.shape[-2:]) != (orig_size[0], orig_size[1]):
+                masks = F.interpolate(masks.unsqueeze(1), size=(orig_size[0], orig_size[1]), mode="bilinear", align_corners=False)[:, 0, :, :]
         detections["masks"] = masks  # same size: align_corners=False bilinear with scale 1 returns its input
         scale = orig_size[1] / self.segmentor_width_size
         detections["boxes"] = detections["boxes"].float() * scale
@@ -268,7 +292,7 @@ class CustomSamAutomaticMaskGenerator:
             orig_size = image.shape[:2]
             image = self.preprocess_resize(image)
         # masks as float32 straight from the unpack launch when postprocess_resize would cast them anyway
-        as_float = orig_size is not None and self.min_mask_region_area <= 0
+        as_float = orig_size is not None and self.min_mask_region_area <= 0 and not self.hip_resize  # (resize_masks reads the bool masks)
         mask_data = self._generate_masks(image, torch.float32 if as_float else torch.bool)
         if self.min_mask_region_area > 0:
             mask_data = self.postprocess_small_regions(mask_data, self.min_mask_region_area, max(self.box_nms_thresh, self.crop_nms_thresh))
@@ -277,7 +301,7 @@ class CustomSamAutomaticMaskGenerator:
         return mask_data
 
     def _generate_masks(self, image: np.ndarray, mask_dtype=torch.bool):
-        orig_size = image.shape[:2]
+        orig_size = (int(image.shape[0]), int(image.shape[1]))
         boxes, layer_idxs = amg.crop_boxes(orig_size, self.crop_n_layers, self.crop_overlap_ratio)
         results = [self._process_crop(image, box, layer, orig_size, mask_dtype) for box, layer in zip(boxes, layer_idxs)]
         data = amg.merge_crops(results, boxes, self.crop_nms_thresh)
@@ -286,7 +310,7 @@ class CustomSamAutomaticMaskGenerator:
     def _process_crop(self, image, crop_box, crop_layer_idx, orig_size, mask_dtype=torch.bool):
         x0, y0, x1, y1 = crop_box
         cropped = image[y0:y1, x0:x1, :]
-        cropped_size = cropped.shape[:2]
+        cropped_size = (int(cropped.shape[0]), int(cropped.shape[1]))  # (plain ints: `image` may be a device tensor)
         self.predictor.set_image(cropped)
         points = self.point_grids[crop_layer_idx] * np.array(cropped_size)[None, ::-1]
         state = amg.CropState(crop_box, orig_size, self.predictor.model.image_encoder.img_size, len(points), self.predictor.device,

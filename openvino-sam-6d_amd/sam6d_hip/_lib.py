@@ -144,6 +144,8 @@ SIGNATURES = {
     "sam6d_mask_components": [c_p] + [c_i] * 4 + [c_p, c_p, c_p, ctypes.c_size_t, c_p],
     "sam6d_amg_small_regions_workspace_bytes": [c_i] * 3,
     "sam6d_amg_small_regions": [c_p] + [c_i] * 4 + [c_p, c_p, c_p, ctypes.c_size_t, c_p],
+    "sam6d_image_resize_linear": [c_p, c_l, c_i, c_i, c_i, c_p, c_i, c_i, c_p],
+    "sam6d_masks_resize_bilinear": [c_p] + [c_i] * 5 + [c_p, c_p],
     "sam6d_samdec_image_to_token": [c_p, c_l, c_l, c_p, c_p, c_p, c_p, c_l, c_p, c_p, c_f, c_p] + [c_i] * 6 + [c_p],
     "sam6d_samdec_token_to_image_workspace_bytes": [c_i],
     "sam6d_samdec_token_to_image": [c_p, c_p, c_p, c_l, c_l, c_p] + [c_i] * 6 + [c_p, ctypes.c_size_t, c_p],

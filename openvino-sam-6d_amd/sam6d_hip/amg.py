@@ -15,6 +15,7 @@ and `postprocess_small_regions` (clean-up, boxes, NMS; one 4-byte read-back) on 
 `eager_tail` is the same tail in plain torch ops on any device: the CPU path, the SAM6D_HIP_AMG=0 path and the timing baseline.
 The geometry helpers (point grids, crop boxes, apply_coords) are the reference's arithmetic restated on the host.
 """
+import functools
 import math
 import os
 
@@ -150,6 +151,133 @@ def unpack_masks(bits, idx, crop_size, crop_box, orig_size, dtype=torch.bool):
             _lib.call("sam6d_amg_unpack_masks", _p(bits), idx.data_ptr() + 8 * k0, bits.shape[0], k, oh, ow, x0, y0, H, W, int(f32),
                       out.data_ptr() + k0 * H * W * out.element_size(), _s())
     return out.view(torch.bool) if dtype == torch.bool else out
+
+
+# ------------------------------------------------------------------------------------------------- segmentor_width_size
+IMAGE_MAX_SIZE = 4096   # sam6d_image_resize_linear: H, W, h, w
+MASKS_MAX_SIZE = 8192   # sam6d_masks_resize_bilinear: h, w, H, W
+
+
+def resized_shape(orig_size, width):
+    """The size preprocess_resize asks cv2.resize for (ISM/model/sam.py:78-80): orig_size = (H, W) -> (int(width * H / W), int(width))."""
+    return int(width * orig_size[0] / orig_size[1]), int(width)
+
+
+def _image_sizes(image, size, who):
+    if not torch.is_tensor(image) or image.dtype != torch.uint8 or image.dim() != 3:
+        raise ValueError("%s: the image must be a uint8 tensor (H, W, 3), got %s %s"
+                         % (who, getattr(image, "dtype", type(image).__name__), tuple(getattr(image, "shape", ()))))
+    if image.shape[2] != 3:
+        raise ValueError("%s: the image must have 3 channels, got %d" % (who, image.shape[2]))
+    (H, W), (h, w) = (int(v) for v in image.shape[:2]), (int(v) for v in size)
+    if not (1 <= H <= IMAGE_MAX_SIZE and 1 <= W <= IMAGE_MAX_SIZE):
+        raise ValueError("%s: H and W must be 1 .. %d, got %d x %d" % (who, IMAGE_MAX_SIZE, H, W))
+    if h < 1:
+        raise ValueError("%s: the output has %d rows: h must be at least 1 (cv2.resize raises for an empty size)" % (who, h))
+    if not (1 <= w <= IMAGE_MAX_SIZE and h <= IMAGE_MAX_SIZE):
+        raise ValueError("%s: h and w must be 1 .. %d, got %d x %d" % (who, IMAGE_MAX_SIZE, h, w))
+    return H, W, h, w
+
+
+def resize_image(image_u8, size, out=None):
+    """sam6d_image_resize_linear.  image_u8 (H, W, 3) uint8 on a HIP device (a crop view with a row stride above 3 W is read in place),
+    size = (h, w) -> (h, w, 3) uint8 = cv2.resize(image, (w, h)), default INTER_LINEAR, as OpenCV 4.x computes it for CV_8UC3 (exactly
+    2x on both axes: the INTER_AREA mean; equal sizes: a copy).  `out`: a contiguous uint8 (h, w, 3) tensor to write into, which must
+    not overlap the image.  Asynchronous."""
+    H, W, h, w = _image_sizes(image_u8, size, "resize_image")
+    if not image_u8.is_cuda:
+        raise RuntimeError("resize_image: needs a HIP device tensor (resize_image_eager is the CPU path)")
+    img = image_u8
+    if img.stride(2) != 1 or img.stride(1) != 3 or img.stride(0) < 3 * W:
+        img = img.contiguous()
+    with torch.cuda.device(img.device):
+        if out is None:
+            out = torch.empty((h, w, 3), dtype=torch.uint8, device=img.device)
+        elif tuple(out.shape) != (h, w, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != img.device:
+            raise ValueError("resize_image: out must be a contiguous uint8 (%d, %d, 3) on %s" % (h, w, img.device))
+        _lib.call("sam6d_image_resize_linear", _p(img), img.stride(0), H, W, 3, _p(out), h, w, _s())
+    return out
+
+
+@functools.lru_cache(maxsize=64)
+def _cv_axis(n_src, n_dst, clamp):
+    """OpenCV's INTER_LINEAR taps of one axis (imgproc/src/resize.cpp), n_src -> n_dst pixels: the source coordinate
+    (float)((d + 0.5) * scale - 0.5) with scale = 1.0 / ((double)n_dst / n_src), its floor and fraction in fp32, the 11-bit coefficients
+    saturate_cast<short>(rint(f * 2048)).  clamp (the x axis): s < 0 -> (0, 0) and s >= n_src - 1 -> (n_src - 1, 0); without (the y
+    axis) only the indices are clipped.  -> (i0, i1, k0, k1) int64 numpy arrays, read-only."""
+    scale = 1.0 / (float(n_dst) / float(n_src))
+    f = ((np.arange(n_dst, dtype=np.float64) + 0.5) * scale - 0.5).astype(np.float32)
+    fl = np.floor(f)
+    f = f - fl
+    s = fl.astype(np.int64)
+    if clamp:
+        f[s < 0], s[s < 0] = 0, 0
+        f[s >= n_src - 1], s[s >= n_src - 1] = 0, n_src - 1
+    k0 = np.clip(np.rint((np.float32(1.0) - f) * np.float32(2048.0)), -32768, 32767).astype(np.int64)
+    k1 = np.clip(np.rint(f * np.float32(2048.0)), -32768, 32767).astype(np.int64)
+    out = (np.clip(s, 0, n_src - 1), np.clip(s + 1, 0, n_src - 1), k0, k1)
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
+def resize_image_eager(image_u8, size):
+    """`resize_image` in plain torch on the image's device (CPU included): the same taps, the horizontal pass, the vertical pass in its
+    vectorised form and the 2 x 2 mean as int32 gathers and sums."""
+    H, W, h, w = _image_sizes(image_u8, size, "resize_image_eager")
+    if (H, W) == (h, w):
+        return image_u8.contiguous().clone()
+    dev = image_u8.device
+    v = image_u8.to(torch.int32)
+    if (H, W) == (2 * h, 2 * w):
+        return ((v[0::2, 0::2] + v[0::2, 1::2] + v[1::2, 0::2] + v[1::2, 1::2] + 2) >> 2).to(torch.uint8)
+    x0, x1, a0, a1 = (torch.from_numpy(a.copy()).to(dev) for a in _cv_axis(W, w, True))
+    y0, y1, b0, b1 = (torch.from_numpy(a.copy()).to(dev) for a in _cv_axis(H, h, False))
+    hx = v[:, x0] * a0.int()[None, :, None] + v[:, x1] * a1.int()[None, :, None]  # (H, w, 3), int32
+    hx = (hx >> 4).clamp(-32768, 32767)
+    t0 = (hx[y0] * b0.int()[:, None, None]) >> 16
+    t1 = (hx[y1] * b1.int()[:, None, None]) >> 16
+    return (((t0 + t1).clamp(-32768, 32767) + 2) >> 2).clamp(0, 255).to(torch.uint8)
+
+
+def _masks_sizes(masks, size, who):
+    if not torch.is_tensor(masks) or masks.dim() != 3 or masks.dtype not in (torch.bool, torch.uint8):
+        raise ValueError("%s: masks must be a (K, h, w) bool or uint8 tensor, got %s %s"
+                         % (who, getattr(masks, "dtype", type(masks).__name__), tuple(getattr(masks, "shape", ()))))
+    (K, h, w), (H, W) = (int(v) for v in masks.shape), (int(v) for v in size)
+    if not all(1 <= v <= MASKS_MAX_SIZE for v in (h, w, H, W)):
+        raise ValueError("%s: sizes must be 1 .. %d, got %d x %d -> %d x %d" % (who, MASKS_MAX_SIZE, h, w, H, W))
+    return K, h, w, H, W
+
+
+def resize_masks(masks, size, out=None):
+    """sam6d_masks_resize_bilinear.  masks (K, h, w) bool or uint8 on a HIP device (any non-zero byte is 1), size = (H, W) -> (K, H, W)
+    float32 = F.interpolate(masks.unsqueeze(1).float(), size=(H, W), mode="bilinear", align_corners=False)[:, 0], enlarging or
+    shrinking; neither a float copy of the input nor anything but the result is allocated.  `out`: a contiguous float32 (K, H, W)
+    tensor to write into.  Asynchronous."""
+    K, h, w, H, W = _masks_sizes(masks, size, "resize_masks")
+    if not masks.is_cuda:
+        raise RuntimeError("resize_masks: needs a HIP device tensor (resize_masks_eager is the CPU path)")
+    m8 = masks.contiguous()
+    if m8.dtype == torch.bool:
+        m8 = m8.view(torch.uint8)
+    with torch.cuda.device(m8.device):
+        if out is None:
+            out = torch.empty((K, H, W), dtype=torch.float32, device=m8.device)
+        elif tuple(out.shape) != (K, H, W) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != m8.device:
+            raise ValueError("resize_masks: out must be a contiguous float32 (%d, %d, %d) on %s" % (K, H, W, m8.device))
+        for k0 in range(0, K, 65535):
+            _lib.call("sam6d_masks_resize_bilinear", m8.data_ptr() + k0 * h * w, min(65535, K - k0), h, w, H, W,
+                      out.data_ptr() + 4 * k0 * H * W, _s())
+    return out
+
+
+def resize_masks_eager(masks, size):
+    """`resize_masks` as the reference computes it (ISM/model/sam.py:86-93), on the masks' device (CPU included)."""
+    K, h, w, H, W = _masks_sizes(masks, size, "resize_masks_eager")
+    if K == 0:
+        return torch.zeros((0, H, W), dtype=torch.float32, device=masks.device)
+    return F.interpolate((masks != 0).unsqueeze(1).float(), size=(H, W), mode="bilinear", align_corners=False)[:, 0]
 
 
 # ------------------------------------------------------------------------------------------------- min_mask_region_area
