@@ -30,8 +30,9 @@ const char* sam6d_last_error(void);
  *   1  rounds 1-3
  *   2  sam6d_set_thread_matmul_mode added; round 3's layout change made visible: sam6d_linattn_kv_pack / sam6d_linattn_kv_image write 4*B floats to `inv` (one image
  *      scale per head), sam6d_linattn_layer reads kvinv as (B,4) -- a version-1 consumer allocated B floats
- *   4  sam6d_gemm_ln256 removed (nothing selected it since its switch SAM6D_FUSED_LN was retired) */
-#define SAM6D_ABI_VERSION 4
+ *   4  sam6d_gemm_ln256 removed (nothing selected it since its switch SAM6D_FUSED_LN was retired)
+ *   5  sam6d_draw_choice added */
+#define SAM6D_ABI_VERSION 5
 int sam6d_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -589,6 +590,17 @@ int sam6d_choose_points(int N, int cap, const int* choose, const float* cloud, c
 int sam6d_template_bbox(const unsigned char* masks, int T, int H, int W, int* bbox, int* count, void* stream);
 int sam6d_template_crop_points(const unsigned char* masks, const float* xyz_mm, int T, int H, int W, const int* bbox, int cap, int* choose,
                                float* xyz, int* n_valid, void* stream);
+/* The random choice of get_test_data (PEM/run_inference_custom_pytorch.py:337-340) and of _get_template (:215-218),
+ * np.random.choice(np.arange(n), ns, replace = n > ns), drawn on the device for N rows at once.  NOT numpy's stream: a counter-based
+ * draw with an integer definition of its own, equal to the reference in distribution only.  All arithmetic modulo 2^32:
+ *   fmix(x): x ^= x >> 16; x *= 0x85ebca6b; x ^= x >> 13; x *= 0xc2b2ae35; x ^= x >> 16
+ *   a = fmix(seed ^ 0x9E3779B9), b = fmix(a + row), h(r) = fmix(fmix(r ^ b) + a), row = row0 + i for row i of this call.
+ * n (N) i32 on the device (n_keep of sam6d_radius_filter, n_valid of sam6d_template_crop_points), sel (N,ns) i32, ready for
+ * sam6d_choose_points.  n[i] > ns: the ns values r in [0, n[i]) with the smallest h(r), in ascending order of h (distinct);
+ * 1 <= n[i] <= ns: sel[i, j] = (h(j) * n[i]) >> 32 with the 64-bit product; n[i] <= 0: zeros.  n[i] above 2^24 counts as 2^24.
+ * A function of (seed, row, n[i], ns) alone.  1 <= ns <= 8192 (the chosen pairs are sorted in 64 KB of LDS) and N >= 0, anything else
+ * returns non-zero without a launch; N == 0 is a no-op, also with null pointers. */
+int sam6d_draw_choice(const int* n, int N, int ns, unsigned seed, unsigned row0, int* sel, void* stream);
 /* The rgb input (PEM/run_inference_custom_pytorch.py:344-350 proposals, :207-212 templates): img[y1:y2, x1:x2][:, :, ::-1], times the
  * mask bit, cv2.resize to (img_size, img_size) with INTER_LINEAR (OpenCV 4.x fixed point, restated; a 2*img_size crop takes OpenCV's
  * INTER_AREA fast path), then ToTensor + Normalize (:151-153).  N items in one launch.

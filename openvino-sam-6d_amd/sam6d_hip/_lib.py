@@ -11,7 +11,7 @@ LIB_PATH = os.environ.get("SAM6D_LIB") or os.path.join(os.path.dirname(_HERE), "
 
 c_f = ctypes.c_float
 c_i = ctypes.c_int
-ABI_VERSION = 4  # include/sam6d_hip.h SAM6D_ABI_VERSION (tests/test_abi.py keeps the two equal)
+ABI_VERSION = 5  # include/sam6d_hip.h SAM6D_ABI_VERSION (tests/test_abi.py keeps the two equal)
 c_l = ctypes.c_long
 c_p = ctypes.c_void_p
 
@@ -107,6 +107,7 @@ SIGNATURES = {
     "sam6d_choose_points": [c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p],
     "sam6d_template_bbox": [c_p, c_i, c_i, c_i, c_p, c_p, c_p],
     "sam6d_template_crop_points": [c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p],
+    "sam6d_draw_choice": [c_p, c_i, c_i, ctypes.c_uint, ctypes.c_uint, c_p, c_p],
     "sam6d_rgb_crop_resize": [c_p, c_l, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p],
     "sam6d_pairwise_distance": [c_p, c_p, c_i, c_i, c_i, c_p, c_p],
     "sam6d_fine_score": [c_p] * 6 + [c_i] * 3 + [c_f, c_p, c_p, c_p],

@@ -2,10 +2,15 @@
 (PEM/run_inference_custom_pytorch.py:226-367) without their per-detection host loops or cv2.
 
 File I/O (PNG, JSON, PLY), RLE decoding (ism.rle_to_mask), trimesh surface sampling and the detection-score threshold stay with the
-caller.  The random choices are drawn on the host with exactly the reference's np.random calls in the reference's order, so a seeded
-numpy state gives the reference's points; everything else runs in the library's kernels (proposal_geometry / proposal_choose /
-proposal_rgb, template_geometry / template_inputs: the tensor-level builders below, over csrc/testdata.hip, next.hip and rgbprep.hip;
-`test_data` and `templates` at the end put them together).
+caller.  By default the random choices are drawn on the host with exactly the reference's np.random calls in the reference's order,
+so a seeded numpy state gives the reference's points; everything else runs in the library's kernels (proposal_geometry /
+proposal_choose / proposal_rgb, template_geometry / template_inputs: the tensor-level builders below, over csrc/testdata.hip, next.hip
+and rgbprep.hip; `test_data` and `templates` at the end put them together).
+
+Opt-in, `rng=DeviceChoice(seed)`: the choices are drawn on the device as well (draw_choice over csrc/choice.hip), without the host
+loop, the permutation of all n candidates per detection and the upload of the indices.  That draw is NOT numpy's stream: it has an
+integer definition of its own (counter-based sort keys, restated in tests/choice_ref.py), so it matches the reference in distribution
+only and never reproduces the reference's points -- which is why it is not the default.
 """
 import numpy as np
 import torch
@@ -82,6 +87,48 @@ def proposal_choose(geom, sel, img_size=224):
     _lib.call("sam6d_choose_points", N, geom["cap"], _p(geom["choose"]), _p(geom["cloud"]), _p(geom["bbox"]), _p(sel), ns, int(img_size),
               _p(pts), _p(rc), _s())
     return pts, rc
+
+
+MAX_CHOICE = 8192  # draw_choice sorts the chosen (key, index) pairs of a row in 64 KB of LDS
+
+
+@on_tensor_device
+def _draw_choice(n, ns, seed, row0):
+    n = n.contiguous()
+    _chk(n, "n", torch.int32, 1)
+    N = n.shape[0]
+    sel = _empty((N, ns), n, torch.int32)
+    _lib.call("sam6d_draw_choice", _p(n), N, ns, int(seed) & 0xFFFFFFFF, int(row0) & 0xFFFFFFFF, _p(sel), _s())
+    return sel
+
+
+def draw_choice(n, ns, seed, row0=0):
+    """The random choice of get_test_data / _get_template (PEM/run_inference_custom_pytorch.py:337-340, :215-218) on the device, for
+    all rows in one launch: n (N) i32 HIP tensor of candidate counts (geom["n_keep"] / geom["n_valid"]) -> sel (N,ns) i32 for
+    proposal_choose / template_inputs.  Row i is row row0 + i of the stream `seed` (both modulo 2^32).  n[i] > ns: ns distinct indices
+    below n[i], a uniform subset in a uniform order; 1 <= n[i] <= ns: ns indices with replacement; n[i] <= 0: zeros; counts above 2^24
+    are taken as 2^24.  A function of (seed, row, n[i], ns) alone, defined in csrc/choice.hip and restated in tests/choice_ref.py --
+    not numpy's stream.  ns outside 1 .. 8192 raises ValueError (whatever device n is on); runs under on_tensor_device."""
+    ns = int(ns)
+    if not 1 <= ns <= MAX_CHOICE:
+        raise ValueError("draw_choice: ns = %d is not in 1 .. %d" % (ns, MAX_CHOICE))
+    return _draw_choice(n, ns, seed, row0)
+
+
+class DeviceChoice:
+    """`rng=` of test_data / templates that draws the choices on the device (draw_choice): the stream `seed`, and `row`, the next
+    unused row of it -- 0 at first, advanced by the number of rows of each call, so successive frames or objects drawn with one object
+    never reuse a row."""
+    __slots__ = ("seed", "row")
+
+    def __init__(self, seed):
+        self.seed = int(seed)
+        self.row = 0
+
+    def draw(self, n, ns):
+        sel = draw_choice(n, ns, self.seed, self.row)
+        self.row += int(n.shape[0])
+        return sel
 
 
 def _rgb_crop_resize(images, stride, C, masks, depth, mask_mode, bbox, img_size, return_uint8, check):
@@ -204,7 +251,10 @@ def test_data(image, depth_m, K, masks, scores, model_points, cfg, rng=np.random
     host floats, model_points (M,3) f32 host array (the trimesh sample / 1000).  cfg: img_size, n_sample_observed_point, rgb_mask_flag.
     -> (input_data, kept): input_data = dict(pts, rgb, rgb_choose, score, model, K) as the reference builds it, kept = the indices of
     the detections it keeps (mask & depth > 32 pixels and >= 4 points inside radius * 1.2, :319-335).
-    One host read-back, of (count, n_keep), decides the skips and the choice sizes."""
+    One host read-back, of (count, n_keep), decides the skips and the choice sizes.
+    rng: np.random (the default) or any object with its `choice`: the reference's host draw, one call per kept detection in order.
+    A DeviceChoice: the choices of all N detections are drawn on the device from geom["n_keep"], rows rng.row .. rng.row + N - 1
+    (skipped detections have their row drawn and dropped), before the read-back, which then only decides `kept`."""
     dev = masks.device
     img_size = int(_cfg(cfg, "img_size", 224))
     ns = int(_cfg(cfg, "n_sample_observed_point", 2048))
@@ -212,13 +262,18 @@ def test_data(image, depth_m, K, masks, scores, model_points, cfg, rng=np.random
     radius = np.max(np.linalg.norm(model_points, axis=1))  # :300
     K = np.asarray(K.cpu() if torch.is_tensor(K) else K, dtype=np.float64).reshape(3, 3)
     geom = proposal_geometry(masks, depth_m, K, radius)
+    device_draw = isinstance(rng, DeviceChoice)
+    if device_draw:
+        sel = rng.draw(geom["n_keep"], ns)
     cn = torch.stack([geom["count"], geom["n_keep"]]).cpu().numpy()
     kept = [i for i in range(masks.shape[0]) if cn[0, i] > 32 and cn[1, i] >= 4]
-    sel = np.zeros((masks.shape[0], ns), np.int32)  # rows of skipped detections stay 0 and are dropped below
-    for i in kept:
-        sel[i] = _draw(rng, int(cn[1, i]), ns)
+    if not device_draw:
+        sel = np.zeros((masks.shape[0], ns), np.int32)  # rows of skipped detections stay 0 and are dropped below
+        for i in kept:
+            sel[i] = _draw(rng, int(cn[1, i]), ns)
+        sel = torch.from_numpy(sel).to(dev)
     idx = torch.tensor(kept, dtype=torch.int64, device=dev)
-    pts, rgb_choose = proposal_choose(geom, torch.from_numpy(sel).to(dev), img_size)
+    pts, rgb_choose = proposal_choose(geom, sel, img_size)
     box = dict(bbox=ism.take_rows(geom["bbox"], idx))
     rgb = proposal_rgb(image, ism.take_rows(masks.to(torch.uint8), idx), depth_m, box, img_size, bool(_cfg(cfg, "rgb_mask_flag", True)),
                            check=False)
@@ -240,15 +295,19 @@ def templates(images, masks, xyz_mm, cfg, rng=np.random):
     """get_templates (PEM/run_inference_custom_pytorch.py:226-253) from device tensors: images (T,H,W,3) u8 RGB renders, masks (T,H,W)
     u8 (255 = object), xyz_mm (T,H,W,3) f32 millimetres, in the order the reference loads the views.  cfg: img_size,
     n_sample_template_point, rgb_mask_flag.  -> all_tem, all_tem_pts, all_tem_choose: lists of (1,3,S,S), (1,ns,3), (1,ns) i64, the
-    form ViTEncoder.get_obj_feats takes.  One host read-back, of the per-template pixel counts."""
+    form ViTEncoder.get_obj_feats takes.  One host read-back, of the per-template pixel counts.
+    rng: as in test_data; a DeviceChoice draws the T choices on the device from geom["n_valid"], rows rng.row .. rng.row + T - 1,
+    behind the same read-back (it still refuses a template without mask pixels before anything is drawn)."""
     img_size = int(_cfg(cfg, "img_size", 224))
     ns = int(_cfg(cfg, "n_sample_template_point", 5000))
     geom = template_geometry(masks, xyz_mm)
     n_valid = geom["n_valid"].cpu().numpy()
     if (n_valid == 0).any():
         raise RuntimeError("templates: template(s) %s have no mask pixel (mask == 255)" % np.nonzero(n_valid == 0)[0].tolist())
-    sel = np.stack([_draw(rng, int(n), ns) for n in n_valid]).astype(np.int32)
-    rgb, rgb_choose, xyz = template_inputs(images, masks, xyz_mm, torch.from_numpy(sel).to(masks.device), img_size,
-                                               bool(_cfg(cfg, "rgb_mask_flag", True)), geom=geom)
+    if isinstance(rng, DeviceChoice):
+        sel = rng.draw(geom["n_valid"], ns)
+    else:
+        sel = torch.from_numpy(np.stack([_draw(rng, int(n), ns) for n in n_valid]).astype(np.int32)).to(masks.device)
+    rgb, rgb_choose, xyz = template_inputs(images, masks, xyz_mm, sel, img_size, bool(_cfg(cfg, "rgb_mask_flag", True)), geom=geom)
     T = rgb.shape[0]
     return [rgb[t:t + 1] for t in range(T)], [xyz[t:t + 1] for t in range(T)], [rgb_choose[t:t + 1] for t in range(T)]
