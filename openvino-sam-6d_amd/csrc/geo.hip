@@ -10,6 +10,7 @@
 //                         (sin/cos of idx*omega_i, interleaved, :276-283) and contracted with proj_d / proj_a on the
 //                         fp32 matrix cores (v_mfma_f32_32x32x2_f32, exact f32); epilogue
 //                         out = (acc_d + b_d) + (max_k acc_a + b_a) entirely in registers (:350-361).
+// tests/test_geo_shapes_gpu.py pins every stage off the golden shape (n = 4 .. 256, empty and full pair lists, indices on the range ends).
 #include "common.h"
 #include "../../include/sam6d_hip.h"
 

@@ -15,6 +15,8 @@
 // maxima with the folded query (the 4 head dots).  Pairs outside [0, xmax] (the bg token: 2n-1 of n^2) take their
 // bias-free E row from the compact buffer sam6d_geo_outliers filled, old-style (one wave per row).
 // q.k comes in precomputed (one small batched GEMM), softmax happens here, P.V is a batched GEMM afterwards.
+// tests/test_geo_shapes_gpu.py pins the score term and the probabilities entry by entry off the golden shape (partial key tiles, every
+// query magnitude, empty and full pair lists).
 //
 #include "common.h"
 #include "../../include/sam6d_hip.h"
