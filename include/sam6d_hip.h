@@ -31,8 +31,9 @@ const char* sam6d_last_error(void);
  *   2  sam6d_set_thread_matmul_mode added; round 3's layout change made visible: sam6d_linattn_kv_pack / sam6d_linattn_kv_image write 4*B floats to `inv` (one image
  *      scale per head), sam6d_linattn_layer reads kvinv as (B,4) -- a version-1 consumer allocated B floats
  *   4  sam6d_gemm_ln256 removed (nothing selected it since its switch SAM6D_FUSED_LN was retired)
- *   5  sam6d_draw_choice added */
-#define SAM6D_ABI_VERSION 5
+ *   5  sam6d_draw_choice added
+ *   6  sam6d_render_views and sam6d_mesh_sample added, with their _workspace_bytes */
+#define SAM6D_ABI_VERSION 6
 int sam6d_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -834,6 +835,43 @@ int sam6d_sam_neck_gather(const float* x, float* rows, int B, void* stream);
 int sam6d_sam_front(const unsigned char* img, long row_stride, long image_stride, int B, int H, int W, int reverse, const int* xtab,
                     int xtaps, const int* ytab, int ytaps, float mean0, float mean1, float mean2, float std0, float std1, float std2,
                     int side, float* out, int layout, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Onboarding a CAD model (Render/render_custom_templates.py): rendered templates and surface samples
+ * ------------------------------------------------------------------------------------------------------------ */
+/* The template renderer's part of Render/render_custom_templates.py:55-106 (BlenderProc's render() and render_nocs() per camera pose)
+ * as a deterministic triangle rasteriser: T views of one mesh in one call.  The geometry is defined by the recipe at the top of
+ * csrc/raster.hip and is bitwise reproducible; the shading of rgb is the package's own (parity unpinned against Cycles).
+ * vertices (V,3) f32 in CAD units, faces (F,3) i32, normals (V,3) f32 or NULL (then the face normal shades), colors (V,3) u8 or NULL,
+ * view (T,3,4) f32 row-major object -> camera matrices (x right, y down, z forward), light (T,3) f32 in the camera frame, pinhole
+ * intrinsics fx fy cx cy in pixels (pixel (i, j) has its centre at (j + 0.5, i + 0.5)), near > 0, base_color the grey albedo used when
+ * colorize != 0 or colors is NULL, srgb_lut 4096 u8 on the device (the sRGB transfer of k / 4095, built on the host), wave_area: a
+ * face whose clamped bounding box has at least this many pixels is rasterised by a whole wave, 0 = the default (256).
+ * Outputs: mask (T,H,W) u8 0 / 255, face (T,H,W) i32 (-1 = background), depth (T,H,W) f32 camera z (0 = background), xyz (T,H,W,3) f32
+ * the object-space point in CAD units (0 = background; 2 * (nocs - 0.5) of :104-106), rgb (T,H,W,3) u8, n_dropped (T) i32: the faces
+ * of a view dropped whole because a vertex is nearer than `near` (there is no clipper) or an index is outside [0, V).
+ * Visibility is the per-pixel minimum of (depth bits << 32 | face id), taken with 64-bit atomic mins on the workspace: a function of
+ * the inputs alone.  H, W 1 .. 2048, T 1 .. 1024, F 1 .. 2^24, workspace 8-byte aligned and at least
+ * sam6d_render_views_workspace_bytes(T, H, W) (0 for sizes outside the limits); anything else returns non-zero without a launch or a
+ * write. */
+size_t sam6d_render_views_workspace_bytes(int T, int H, int W);
+int sam6d_render_views(const float* vertices, int V, const int* faces, int F, const float* normals, const unsigned char* colors,
+                       const float* view, const float* light, int T, float fx, float fy, float cx, float cy, int H, int W, float near,
+                       float base_color, int colorize, const unsigned char* srgb_lut, int wave_area, unsigned char* mask, int* face,
+                       float* depth, float* xyz, unsigned char* rgb, int* n_dropped, void* workspace, size_t workspace_bytes,
+                       void* stream);
+/* trimesh.sample.sample_surface as the reference calls it (Render/render_custom_templates.py:35, ISM/run_inference_custom.py:232-234,
+ * PEM/run_inference_custom_pytorch.py:298-300): n area-weighted points of the surface.  NOT trimesh's or numpy's stream: an integer
+ * definition of its own (csrc/meshsample.hip, restated in tests/meshsample_ref.py), equal to the reference in distribution only:
+ * fp32 face areas, integer weights floor(area / area_max * 2^24) (at least 1 for a face with area, 0 without), their uint64 prefix
+ * sums, and per sample three keys of sam6d_draw_choice's hash: one picks the face, two the barycentric pair.  Sample j is sample
+ * row + j of the stream `seed`, so a call with row = r continues a call that drew r samples.  points (n,3) f32, face (n) i32.
+ * n and F 1 .. 2^24, workspace 8-byte aligned and at least sam6d_mesh_sample_workspace_bytes(F) (0 for F outside the limits); a mesh
+ * whose faces all have zero area is refused before the outputs are written (one read-back of area_max: the call synchronises the
+ * stream).  Anything else returns non-zero without a launch. */
+size_t sam6d_mesh_sample_workspace_bytes(int F);
+int sam6d_mesh_sample(const float* vertices, int V, const int* faces, int F, int n, unsigned seed, unsigned row, float* points, int* face,
+                      void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

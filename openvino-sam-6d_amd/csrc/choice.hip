@@ -23,15 +23,7 @@
 #define CH_MAX_NS 8192
 #define CH_MAX_N (1 << 24)
 
-__device__ __forceinline__ unsigned ch_fmix(unsigned x) {
-  x ^= x >> 16;
-  x *= 0x85ebca6bu;
-  x ^= x >> 13;
-  x *= 0xc2b2ae35u;
-  x ^= x >> 16;
-  return x;
-}
-__device__ __forceinline__ unsigned ch_key(unsigned r, unsigned a, unsigned b) { return ch_fmix(ch_fmix(r ^ b) + a); }
+// (fmix and the key h(r) are hash_fmix / hash_key of common.h: meshsample.hip draws from the same keys)
 
 // P = the power of two >= ns (the sort's size); dynamic LDS = P pairs of 8 bytes
 __global__ __launch_bounds__(CH_THREADS) void draw_choice_kernel(const int* __restrict__ n_in, int ns, int P, unsigned seed, unsigned row0,
@@ -41,13 +33,13 @@ __global__ __launch_bounds__(CH_THREADS) void draw_choice_kernel(const int* __re
   __shared__ int s_wave[4];
   __shared__ int s_bin, s_need, s_cnt;
   const int i = blockIdx.x, t = threadIdx.x;
-  const unsigned a = ch_fmix(seed ^ 0x9E3779B9u);
-  const unsigned b = ch_fmix(a + (row0 + (unsigned)i));
+  const unsigned a = hash_fmix(seed ^ 0x9E3779B9u);
+  const unsigned b = hash_fmix(a + (row0 + (unsigned)i));
   const int n = min(n_in[i], CH_MAX_N);
   int* out = sel + (size_t)i * ns;
   if (n <= ns) {  // with replacement (n >= 1), or an empty row: a plain map
     for (int j = t; j < ns; j += CH_THREADS)
-      out[j] = n > 0 ? (int)(((unsigned long long)ch_key((unsigned)j, a, b) * (unsigned long long)(unsigned)n) >> 32) : 0;
+      out[j] = n > 0 ? (int)(((unsigned long long)hash_key((unsigned)j, a, b) * (unsigned long long)(unsigned)n) >> 32) : 0;
     return;
   }
   // ---- radix select: after the pass at `shift` the bytes of T from `shift` up are known (prefix under mask)
@@ -57,7 +49,7 @@ __global__ __launch_bounds__(CH_THREADS) void draw_choice_kernel(const int* __re
     if (t < 256) s_hist[t] = 0;
     __syncthreads();
     for (int r = t; r < n; r += CH_THREADS) {
-      const unsigned k = ch_key((unsigned)r, a, b);
+      const unsigned k = hash_key((unsigned)r, a, b);
       if ((k & mask) == prefix) atomicAdd(&s_hist[(k >> shift) & 255u], 1);
     }
     __syncthreads();
@@ -86,7 +78,7 @@ __global__ __launch_bounds__(CH_THREADS) void draw_choice_kernel(const int* __re
   for (int j = ns + t; j < P; j += CH_THREADS) ch_pairs[j] = ~0ull;  // above every real pair (r < 2^24)
   __syncthreads();
   for (int r = t; r < n; r += CH_THREADS) {
-    const unsigned k = ch_key((unsigned)r, a, b);
+    const unsigned k = hash_key((unsigned)r, a, b);
     if (k <= prefix) {
       const int slot = atomicAdd(&s_cnt, 1);
       if (slot < ns) ch_pairs[slot] = ((unsigned long long)k << 32) | (unsigned)r;  // (always: exactly ns keys are <= T)

@@ -188,6 +188,18 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
   return v;
 }
 
+// murmur3's 32-bit finaliser (a bijection modulo 2^32) and the counter-based key h(r) = fmix(fmix(r ^ b) + a) of the device draws
+// (choice.hip, meshsample.hip; a and b are hashes of the seed and the row)
+__device__ __forceinline__ unsigned hash_fmix(unsigned x) {
+  x ^= x >> 16;
+  x *= 0x85ebca6bu;
+  x ^= x >> 13;
+  x *= 0xc2b2ae35u;
+  x ^= x >> 16;
+  return x;
+}
+__device__ __forceinline__ unsigned hash_key(unsigned r, unsigned a, unsigned b) { return hash_fmix(hash_fmix(r ^ b) + a); }
+
 // squared distance in the torch-CPU K=3 matmul recipe (PEM/utils/model_utils.py:101-128):
 //   s = (p0*p0 + p1*p1) + p2*p2 (plain adds), xy = fma(x2,y2, fma(x1,y1, x0*y0)), d = max((sx - 2xy) + sy, 0)
 // The library is built with -ffp-contract=off, so only the explicit fmaf calls fuse.

@@ -1,0 +1,338 @@
+// Template rendering (Render/render_custom_templates.py:55-106: BlenderProc's render() and render_nocs() of one CAD model from the
+// predefined camera poses) as a deterministic triangle rasteriser: T views of one mesh -> mask, visible face, depth, object-space xyz
+// and a shaded rgb.  The geometry (mask, face, depth, xyz) is defined by the recipe below and restated in numpy, float32 operation by
+// operation, in tests/raster_ref.py; the shading is the package's own (parity unpinned against Cycles, equal in kind only).
+//
+// RECIPE.  All float arithmetic is IEEE fp32 in the order written (the library is built with -ffp-contract=off and this file has no
+// fused multiply-add); only + - * /, sqrt, floor and comparisons run on the device.
+//   camera   per view a row-major 3x4 matrix M (object -> camera; x right, y down, z forward) and a light position in that frame.
+//            P = ((M[r][0]*x + M[r][1]*y) + M[r][2]*z) + M[r][3] for r = 0, 1, 2.
+//   near     a face with an index outside [0, V) or with a vertex whose P.z >= near is false (nearer, or NaN) is dropped whole and
+//            counted in n_dropped[view]; there is no clipper.
+//   snap     s = f * (P.x / P.z) + c;  u = s * 256;  u = u >= -2^24 ? u : -2^24;  u = u <= 2^24 ? u : 2^24;  X = (int)floor(u + 0.5):
+//            screen coordinates in 1/256 pixel, pixel (i, j) has its centre at (256 j + 128, 256 i + 128).
+//   cover    area2 = (X1-X0)*(Y2-Y0) - (X2-X0)*(Y1-Y0) in int64.  area2 == 0 covers nothing; area2 < 0 swaps vertices 1 and 2 (both
+//            windings are drawn).  Edge a->b at the centre p: E = (bx-ax)*(py-ay) - (by-ay)*(px-ax); w0 = E_12, w1 = E_20, w2 = E_01,
+//            so w0 + w1 + w2 = area2.  p is covered when every w_i > 0, or w_i == 0 on an edge with by < ay or (by == ay and bx > ax):
+//            the top-left rule (y points down), which gives a centre on a shared edge to exactly one of the two faces.
+//   depth    q_i = (float)w_i / z_i;  qs = (q0 + q1) + q2;  depth = (float)area2 / qs;  l_i = q_i / qs (perspective-correct weights);
+//            an attribute is (l0*a0 + l1*a1) + l2*a2 with the l_i back in the face's stored vertex order.
+//   visible  per pixel the minimum over the covering faces of (bits(depth) << 32) | face id: depth is positive, so its bit pattern
+//            orders as the value does, and on a depth tie the lower face id wins.
+//   xyz      the attribute of the object-space vertices (CAD units); background 0.
+//   shading  n = the attribute of the vertex normals taken through M's 3x3 part, or without normals the face normal
+//            (P1-P0) x (P2-P0); Pc = the attribute of the camera-space vertices; n is negated when n . Pc > 0 (towards the camera);
+//            L = light - Pc, d2 = |L|^2, c = (n . L) / (sqrt(|n|^2) * sqrt(d2)), c = c > 0 ? c : 0 (a NaN gives 0);
+//            v = GAIN * c / d2; per channel lin = albedo * v clamped to [0, 1] by comparisons, rgb = lut[(int)(lin * 4095 + 0.5)],
+//            lut = the 4096-entry sRGB transfer table the host builds in float64.  albedo = the attribute of the vertex colours / 255,
+//            or base_color when colorize is set or the mesh has none.  GAIN = 1000 / (4 pi^2) = 25.330296: the script's 1000 W point
+//            light (:78) as Blender turns watts into the radiance of a diffuse surface, W / (4 pi^2 r^2).
+//
+// WHY THE RESULT IS A FUNCTION OF THE INPUTS ALONE.  The z-buffer (workspace, T*H*W 64-bit words) is filled with ~0 by a memset that
+// precedes the raster kernel in stream order.  The raster kernel touches it with one operation only: a 64-bit vector atomic min at
+// agent scope (every workgroup on every XCD meets at the same L2 line).  The set of (key, pixel) pairs offered is decided by the
+// recipe -- each covered (face, pixel) pair offers its key exactly once, from whichever path owns the face -- and min is commutative,
+// associative and idempotent, so the word a pixel ends with is the minimum of its set in whatever order the atomics land.  Nothing
+// reads the buffer inside that launch.  The resolve kernel runs after the kernel boundary, reads the winner's face id, recomputes the
+// same setup and the same weights at the pixel with the same device functions, and is the only writer of every output element.
+// n_dropped is an integer atomicAdd of ones: order-free as well.
+//
+// WORK.  One launch, one wave per 64 faces of a view.  Every lane sets up its own face; a face whose clamped bounding box has fewer
+// than wave_area pixels is walked by its lane (the thread path: a dense scan is mostly triangles of a few pixels); the rest are
+// taken one after the other by the whole wave, 64 pixels of the box at a time (the wave path: a low-poly mesh is a few triangles of
+// tens of thousands of pixels).  Both paths call rs_offer() on a face set up by rs_setup(): the arithmetic is one piece of code.
+#include "common.h"
+#include "../../include/sam6d_hip.h"
+
+#define RS_MAX_HW 2048
+#define RS_MAX_T 1024
+#define RS_MAX_F (1 << 24)
+#define RS_WAVE_AREA 256
+#define RS_GAIN 25.330296f
+#define RS_SNAP_LIMIT 16777216.0f
+
+struct RsCam {
+  float fx, fy, cx, cy, near;
+  int H, W;
+};
+
+struct RsFace {
+  int X[3], Y[3];  // snapped screen coordinates, vertices 1 and 2 swapped where the winding asked for it
+  float z[3];      // camera depth in that order
+  long long area2;
+  int b0, b1, b2;  // 0 where the edge opposite the vertex owns its points (top-left), else -1
+  int x0, x1, y0, y1;  // pixel bounding box clamped to the image; empty when x0 > x1 or y0 > y1
+  bool live;       // not dropped and area2 != 0
+  bool dropped;
+  bool swapped;
+};
+
+__device__ __forceinline__ float rs_row(const float* m, float x, float y, float z) { return ((m[0] * x + m[1] * y) + m[2] * z) + m[3]; }
+
+__device__ __forceinline__ int rs_snap(float f, float a, float z, float c) {
+  float u = (f * (a / z) + c) * 256.0f;
+  u = u >= -RS_SNAP_LIMIT ? u : -RS_SNAP_LIMIT;
+  u = u <= RS_SNAP_LIMIT ? u : RS_SNAP_LIMIT;
+  return (int)floorf(u + 0.5f);
+}
+
+__device__ __forceinline__ int rs_owner(int ax, int ay, int bx, int by) { return (by < ay || (by == ay && bx > ax)) ? 0 : -1; }
+
+__device__ __forceinline__ void rs_setup(RsFace& f, const float* __restrict__ vert, int V, const int* __restrict__ faces, int face,
+                                         const float* __restrict__ M, const RsCam& cam) {
+  f.live = false;
+  f.dropped = false;
+  f.swapped = false;
+  f.x0 = f.y0 = 0;
+  f.x1 = f.y1 = -1;
+  int id[3];
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    id[k] = faces[(size_t)face * 3 + k];
+    ok = ok && (unsigned)id[k] < (unsigned)V;
+  }
+  if (ok) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const float x = vert[(size_t)id[k] * 3], y = vert[(size_t)id[k] * 3 + 1], z = vert[(size_t)id[k] * 3 + 2];
+      const float px = rs_row(M, x, y, z), py = rs_row(M + 4, x, y, z), pz = rs_row(M + 8, x, y, z);
+      ok = ok && (pz >= cam.near);
+      f.z[k] = pz;
+      f.X[k] = rs_snap(cam.fx, px, pz, cam.cx);
+      f.Y[k] = rs_snap(cam.fy, py, pz, cam.cy);
+    }
+  }
+  if (!ok) {
+    f.dropped = true;
+    return;
+  }
+  long long a2 = (long long)(f.X[1] - f.X[0]) * (f.Y[2] - f.Y[0]) - (long long)(f.X[2] - f.X[0]) * (f.Y[1] - f.Y[0]);
+  if (a2 == 0) return;
+  if (a2 < 0) {
+    int t = f.X[1]; f.X[1] = f.X[2]; f.X[2] = t;
+    t = f.Y[1]; f.Y[1] = f.Y[2]; f.Y[2] = t;
+    const float s = f.z[1]; f.z[1] = f.z[2]; f.z[2] = s;
+    a2 = -a2;
+    f.swapped = true;
+  }
+  f.area2 = a2;
+  f.b0 = rs_owner(f.X[1], f.Y[1], f.X[2], f.Y[2]);
+  f.b1 = rs_owner(f.X[2], f.Y[2], f.X[0], f.Y[0]);
+  f.b2 = rs_owner(f.X[0], f.Y[0], f.X[1], f.Y[1]);
+  const int xmin = min(f.X[0], min(f.X[1], f.X[2])), xmax = max(f.X[0], max(f.X[1], f.X[2]));
+  const int ymin = min(f.Y[0], min(f.Y[1], f.Y[2])), ymax = max(f.Y[0], max(f.Y[1], f.Y[2]));
+  // the pixels whose centre 256 j + 128 lies in [min, max], clamped to the image before anything is addressed
+  f.x0 = max((xmin + 127) >> 8, 0);
+  f.x1 = min((xmax - 128) >> 8, cam.W - 1);
+  f.y0 = max((ymin + 127) >> 8, 0);
+  f.y1 = min((ymax - 128) >> 8, cam.H - 1);
+  f.live = true;
+}
+
+__device__ __forceinline__ long long rs_edge(int ax, int ay, int bx, int by, int px, int py) {
+  return (long long)(bx - ax) * (py - ay) - (long long)(by - ay) * (px - ax);
+}
+
+// the edge values of pixel (x, y); true when the centre is covered
+__device__ __forceinline__ bool rs_cover(const RsFace& f, int x, int y, long long& w0, long long& w1, long long& w2) {
+  const int px = 256 * x + 128, py = 256 * y + 128;
+  w0 = rs_edge(f.X[1], f.Y[1], f.X[2], f.Y[2], px, py);
+  w1 = rs_edge(f.X[2], f.Y[2], f.X[0], f.Y[0], px, py);
+  w2 = rs_edge(f.X[0], f.Y[0], f.X[1], f.Y[1], px, py);
+  return (w0 + f.b0 >= 0) && (w1 + f.b1 >= 0) && (w2 + f.b2 >= 0);
+}
+
+// perspective-correct weights l and the depth from the edge values
+__device__ __forceinline__ float rs_weights(const RsFace& f, long long w0, long long w1, long long w2, float& l0, float& l1, float& l2) {
+  const float q0 = (float)w0 / f.z[0], q1 = (float)w1 / f.z[1], q2 = (float)w2 / f.z[2];
+  const float qs = (q0 + q1) + q2;
+  l0 = q0 / qs;
+  l1 = q1 / qs;
+  l2 = q2 / qs;
+  return (float)f.area2 / qs;
+}
+
+__device__ __forceinline__ void rs_offer(const RsFace& f, int face, int x, int y, unsigned long long* __restrict__ zrow0, int W) {
+  long long w0, w1, w2;
+  if (!rs_cover(f, x, y, w0, w1, w2)) return;
+  float l0, l1, l2;
+  const float d = rs_weights(f, w0, w1, w2, l0, l1, l2);
+  const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)face;
+  __hip_atomic_fetch_min(zrow0 + (size_t)y * W + x, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// grid (ceil(F / 64), T), one wave each
+__global__ __launch_bounds__(64) void raster_faces_kernel(const float* __restrict__ vert, int V, const int* __restrict__ faces, int F,
+                                                          const float* __restrict__ view, RsCam cam, int wave_area,
+                                                          unsigned long long* __restrict__ zbuf, int* __restrict__ n_dropped) {
+  const int t = blockIdx.y, lane = threadIdx.x;
+  const int face = blockIdx.x * 64 + lane;
+  const float* M = view + (size_t)t * 12;
+  unsigned long long* z = zbuf + (size_t)t * cam.H * cam.W;
+  RsFace f;
+  f.live = false;
+  f.dropped = false;
+  f.x0 = f.y0 = 0;
+  f.x1 = f.y1 = -1;
+  if (face < F) rs_setup(f, vert, V, faces, face, M, cam);
+  if (f.dropped) atomicAdd(n_dropped + t, 1);
+  const bool boxed = f.live && f.x0 <= f.x1 && f.y0 <= f.y1;
+  const int bw = f.x1 - f.x0 + 1, bh = f.y1 - f.y0 + 1;  // at most 2048 each: the product fits an int
+  const bool big = boxed && bw * bh >= wave_area;
+  if (boxed && !big)
+    for (int y = f.y0; y <= f.y1; ++y)
+      for (int x = f.x0; x <= f.x1; ++x) rs_offer(f, face, x, y, z, cam.W);
+  unsigned long long todo = __ballot(big);
+  while (todo) {
+    const int src = __ffsll((long long)todo) - 1;
+    todo &= todo - 1;
+    const int gface = blockIdx.x * 64 + src;
+    RsFace g;
+    rs_setup(g, vert, V, faces, gface, M, cam);  // the same code on the same inputs as the owner lane ran: the same face
+    const int gw = g.x1 - g.x0 + 1, n = gw * (g.y1 - g.y0 + 1);
+    for (int i = lane; i < n; i += 64) rs_offer(g, gface, g.x0 + i % gw, g.y0 + i / gw, z, cam.W);
+  }
+}
+
+struct RsShade {
+  const float* normals;
+  const unsigned char* colors;
+  const float* light;
+  const unsigned char* lut;
+  float base_color;
+  int colorize;
+};
+
+__device__ __forceinline__ float rs_mix(float l0, float l1, float l2, float a0, float a1, float a2) { return (l0 * a0 + l1 * a1) + l2 * a2; }
+
+// one thread per pixel of every view: the only writer of the outputs
+__global__ __launch_bounds__(256) void raster_resolve_kernel(const float* __restrict__ vert, int V, const int* __restrict__ faces,
+                                                             const float* __restrict__ view, RsCam cam, RsShade sh, int T,
+                                                             const unsigned long long* __restrict__ zbuf, unsigned char* __restrict__ mask,
+                                                             int* __restrict__ face_out, float* __restrict__ depth, float* __restrict__ xyz,
+                                                             unsigned char* __restrict__ rgb) {
+  const size_t hw = (size_t)cam.H * cam.W, i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= hw * (size_t)T) return;
+  const int t = (int)(i / hw), p = (int)(i % hw), y = p / cam.W, x = p % cam.W;
+  const unsigned long long key = zbuf[i];
+  if (key == ~0ull) {
+    mask[i] = 0;
+    face_out[i] = -1;
+    depth[i] = 0.f;
+    xyz[i * 3] = xyz[i * 3 + 1] = xyz[i * 3 + 2] = 0.f;
+    rgb[i * 3] = rgb[i * 3 + 1] = rgb[i * 3 + 2] = 0;
+    return;
+  }
+  const int face = (int)(unsigned)(key & 0xffffffffull);
+  const float* M = view + (size_t)t * 12;
+  RsFace f;
+  rs_setup(f, vert, V, faces, face, M, cam);
+  long long w0, w1, w2;
+  rs_cover(f, x, y, w0, w1, w2);
+  float l0, l1, l2;
+  const float d = rs_weights(f, w0, w1, w2, l0, l1, l2);
+  // the weights in the face's stored order (a winding swap exchanged vertices 1 and 2): every attribute is mixed in that order
+  const float m1 = f.swapped ? l2 : l1, m2 = f.swapped ? l1 : l2;
+  const int* fv = faces + (size_t)face * 3;
+  const float* a = vert + (size_t)fv[0] * 3;
+  const float* b = vert + (size_t)fv[1] * 3;
+  const float* c = vert + (size_t)fv[2] * 3;
+  mask[i] = 255;
+  face_out[i] = face;
+  depth[i] = d;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) xyz[i * 3 + k] = rs_mix(l0, m1, m2, a[k], b[k], c[k]);
+  // ---- shading (the package's own)
+  float P[3][3];  // camera-space vertices, stored order
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float* v = vert + (size_t)fv[k] * 3;
+    P[k][0] = rs_row(M, v[0], v[1], v[2]);
+    P[k][1] = rs_row(M + 4, v[0], v[1], v[2]);
+    P[k][2] = rs_row(M + 8, v[0], v[1], v[2]);
+  }
+  float Pc[3], n[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) Pc[k] = rs_mix(l0, m1, m2, P[0][k], P[1][k], P[2][k]);
+  if (sh.normals) {
+    float no[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) no[k] = rs_mix(l0, m1, m2, sh.normals[(size_t)fv[0] * 3 + k], sh.normals[(size_t)fv[1] * 3 + k], sh.normals[(size_t)fv[2] * 3 + k]);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) n[k] = (M[4 * k] * no[0] + M[4 * k + 1] * no[1]) + M[4 * k + 2] * no[2];
+  } else {
+    const float e1x = P[1][0] - P[0][0], e1y = P[1][1] - P[0][1], e1z = P[1][2] - P[0][2];
+    const float e2x = P[2][0] - P[0][0], e2y = P[2][1] - P[0][1], e2z = P[2][2] - P[0][2];
+    n[0] = e1y * e2z - e1z * e2y;
+    n[1] = e1z * e2x - e1x * e2z;
+    n[2] = e1x * e2y - e1y * e2x;
+  }
+  const float facing = (n[0] * Pc[0] + n[1] * Pc[1]) + n[2] * Pc[2];
+  if (facing > 0.f) {
+    n[0] = -n[0];
+    n[1] = -n[1];
+    n[2] = -n[2];
+  }
+  const float* lp = sh.light + (size_t)t * 3;
+  const float Lx = lp[0] - Pc[0], Ly = lp[1] - Pc[1], Lz = lp[2] - Pc[2];
+  const float d2 = (Lx * Lx + Ly * Ly) + Lz * Lz;
+  const float nn = (n[0] * n[0] + n[1] * n[1]) + n[2] * n[2];
+  const float ndl = (n[0] * Lx + n[1] * Ly) + n[2] * Lz;
+  float cs = ndl / (sqrtf(nn) * sqrtf(d2));
+  cs = cs > 0.f ? cs : 0.f;
+  const float v = RS_GAIN * cs / d2;
+  const bool grey = sh.colorize || !sh.colors;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    float alb = sh.base_color;
+    if (!grey)
+      alb = rs_mix(l0, m1, m2, (float)sh.colors[(size_t)fv[0] * 3 + k] / 255.0f, (float)sh.colors[(size_t)fv[1] * 3 + k] / 255.0f,
+                   (float)sh.colors[(size_t)fv[2] * 3 + k] / 255.0f);
+    float lin = alb * v;
+    lin = lin > 0.f ? lin : 0.f;
+    lin = lin < 1.f ? lin : 1.f;
+    rgb[i * 3 + k] = sh.lut[(int)(lin * 4095.0f + 0.5f)];
+  }
+}
+
+extern "C" size_t sam6d_render_views_workspace_bytes(int T, int H, int W) {
+  if (T < 1 || T > RS_MAX_T || H < 1 || H > RS_MAX_HW || W < 1 || W > RS_MAX_HW) return 0;
+  return (size_t)T * H * W * sizeof(unsigned long long);
+}
+
+extern "C" int sam6d_render_views(const float* vertices, int V, const int* faces, int F, const float* normals, const unsigned char* colors,
+                                  const float* view, const float* light, int T, float fx, float fy, float cx, float cy, int H, int W,
+                                  float near, float base_color, int colorize, const unsigned char* srgb_lut, int wave_area,
+                                  unsigned char* mask, int* face, float* depth, float* xyz, unsigned char* rgb, int* n_dropped,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+  SAM6D_REQUIRE(H >= 1 && H <= RS_MAX_HW && W >= 1 && W <= RS_MAX_HW, "render_views: H x W = %d x %d is not in 1 .. %d", H, W, RS_MAX_HW);
+  SAM6D_REQUIRE(T >= 1 && T <= RS_MAX_T, "render_views: T = %d is not in 1 .. %d", T, RS_MAX_T);
+  SAM6D_REQUIRE(F >= 1 && F <= RS_MAX_F, "render_views: F = %d is not in 1 .. %d", F, RS_MAX_F);
+  SAM6D_REQUIRE(V >= 1, "render_views: V = %d is not positive", V);
+  SAM6D_REQUIRE(near > 0.f, "render_views: near = %g is not positive", (double)near);
+  SAM6D_REQUIRE(wave_area >= 0, "render_views: wave_area = %d is negative", wave_area);
+  SAM6D_REQUIRE(vertices && faces && view && light && srgb_lut && mask && face && depth && xyz && rgb && n_dropped && workspace,
+                "render_views: null pointer");
+  const size_t need = sam6d_render_views_workspace_bytes(T, H, W);
+  SAM6D_REQUIRE(workspace_bytes >= need, "render_views: workspace of %zu bytes is below sam6d_render_views_workspace_bytes = %zu",
+                workspace_bytes, need);
+  SAM6D_REQUIRE(((uintptr_t)workspace & 7) == 0, "render_views: workspace is not 8-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t e = hipMemsetAsync(workspace, 0xff, need, s);
+  if (e == hipSuccess) e = hipMemsetAsync(n_dropped, 0, (size_t)T * sizeof(int), s);
+  if (e != hipSuccess) {
+    sam6d_set_error("render_views: memset failed: %s", hipGetErrorString(e));
+    return (int)e;
+  }
+  const RsCam cam = {fx, fy, cx, cy, near, H, W};
+  const RsShade sh = {normals, colors, light, srgb_lut, base_color, colorize};
+  unsigned long long* zbuf = (unsigned long long*)workspace;
+  hipLaunchKernelGGL(raster_faces_kernel, dim3((F + 63) / 64, T), dim3(64), 0, s, vertices, V, faces, F, view, cam,
+                     wave_area ? wave_area : RS_WAVE_AREA, zbuf, n_dropped);
+  SAM6D_LAUNCH_CHECK_CONT("render_views (faces)");
+  const size_t px = (size_t)T * H * W;  // at most 2^32: 2^24 blocks
+  hipLaunchKernelGGL(raster_resolve_kernel, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, s, vertices, V, faces, view, cam, sh, T, zbuf,
+                     mask, face, depth, xyz, rgb);
+  SAM6D_LAUNCH_CHECK("render_views (resolve)");
+}

@@ -11,7 +11,7 @@ LIB_PATH = os.environ.get("SAM6D_LIB") or os.path.join(os.path.dirname(_HERE), "
 
 c_f = ctypes.c_float
 c_i = ctypes.c_int
-ABI_VERSION = 5  # include/sam6d_hip.h SAM6D_ABI_VERSION (tests/test_abi.py keeps the two equal)
+ABI_VERSION = 6  # include/sam6d_hip.h SAM6D_ABI_VERSION (tests/test_abi.py keeps the two equal)
 c_l = ctypes.c_long
 c_p = ctypes.c_void_p
 
@@ -157,6 +157,11 @@ SIGNATURES = {
     "sam6d_sam_global_attention": [c_p] * 4 + [c_i, c_i, c_p],
     "sam6d_sam_neck_gather": [c_p, c_p, c_i, c_p],
     "sam6d_sam_front": [c_p, c_l, c_l] + [c_i] * 4 + [c_p, c_i, c_p, c_i] + [c_f] * 6 + [c_i, c_p, c_i, c_p],
+    "sam6d_render_views_workspace_bytes": [c_i] * 3,
+    "sam6d_render_views": [c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_i] + [c_f] * 4 + [c_i, c_i, c_f, c_f, c_i, c_p, c_i] + [c_p] * 7
+                          + [ctypes.c_size_t, c_p],
+    "sam6d_mesh_sample_workspace_bytes": [c_i],
+    "sam6d_mesh_sample": [c_p, c_i, c_p, c_i, c_i, ctypes.c_uint, ctypes.c_uint, c_p, c_p, c_p, ctypes.c_size_t, c_p],
 }
 
 _lib = None

@@ -1,8 +1,8 @@
 """The six input tensors of Net.forward built from device-resident data: the reference's get_test_data and get_templates
 (PEM/run_inference_custom_pytorch.py:226-367) without their per-detection host loops or cv2.
 
-File I/O (PNG, JSON, PLY), RLE decoding (ism.rle_to_mask), trimesh surface sampling and the detection-score threshold stay with the
-caller.  By default the random choices are drawn on the host with exactly the reference's np.random calls in the reference's order,
+File I/O (PNG, JSON), RLE decoding (ism.rle_to_mask) and the detection-score threshold stay with the caller; the PLY reader and the
+surface samples behind `model_points` are in sam6d_hip.onboard.  By default the random choices are drawn on the host with exactly the reference's np.random calls in the reference's order,
 so a seeded numpy state gives the reference's points; everything else runs in the library's kernels (proposal_geometry /
 proposal_choose / proposal_rgb, template_geometry / template_inputs: the tensor-level builders below, over csrc/testdata.hip, next.hip
 and rgbprep.hip; `test_data` and `templates` at the end put them together).
