@@ -873,6 +873,45 @@ size_t sam6d_mesh_sample_workspace_bytes(int F);
 int sam6d_mesh_sample(const float* vertices, int V, const int* faces, int F, int n, unsigned seed, unsigned row, float* points, int* face,
                       void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * The result pictures of the two inference scripts (vis_ism.png, vis_pem.png), built on the device
+ * ------------------------------------------------------------------------------------------------------------ */
+/* `draw_detections` of PEM/utils/draw_utils.py:75-97 as PEM/run_inference_custom.py:110-134 (`visualize`) uses it, for N poses in one
+ * call, with the side-by-side paste of :128-133.  rgb (H,W,3) u8, pixel (y, x) at rgb + y row_stride + 3 x (row_stride in bytes, at
+ * least 3 W: a crop view works); R (N,3,3), t (N,3), K (N,3,3) f32 row-major; box (8,3) f32, the corners in the order of
+ * draw_utils.py:20-49, and pts (P,3) f32, both in model units; colors (N,3) u8; thickness T of the box edges and radius r of the
+ * points in pixels (the reference draws with 3 and 1).  canvas (H, 2W, 3) u8: the left half is rgb, the right half rgb with the
+ * detections painted over it; n_skipped (N) i32: the primitives of an instance that were not drawn.
+ * Contract (the recipe at the top of csrc/overlay.hip, restated in tests/overlay_ref.py; bitwise reproducible): projection in fp32,
+ * P = ((R0 x + R1 y) + R2 z) + t per row, q = K P in the same association, u = (int)(q0 / q2), v = (int)(q1 / q2) truncating like the
+ * reference's int32 cast (draw_utils.py:13-16).  A point is skipped when q2 > 0 is false or a quotient is outside -8192 .. 8191
+ * (compared in fp32); an edge when either corner is; each adds one to n_skipped[i] (the reference has no rule and divides by zero).
+ * Paint order per instance as draw_utils.py:51-97: ground edges (4,5) (5,7) (6,4) (7,6) in int(0.3 c), pillars (k, k+4) in int(0.6 c),
+ * top edges (0,1) (1,3) (2,0) (3,2) in c, the P points in c; later paint wins, a later instance over an earlier one.  The thick line
+ * (round caps, integer distance predicate) and the disc (dx^2 + dy^2 <= r^2) are the package's own shapes, NOT cv2.line / cv2.circle:
+ * equal in kind only.  The painter keeps the largest key 4 i + stage + 1 per pixel with 32-bit atomic maxima on the workspace, and a
+ * second kernel is the only writer of the canvas: a function of the inputs alone.
+ * H, W 1 .. 8192, N 0 .. 65535, P 0 .. 65536, T 1 .. 15, r 0 .. 15; workspace 4-byte aligned and at least
+ * sam6d_draw_detections_workspace_bytes(H, W) (0 for sizes outside the limits); anything else returns non-zero without a launch or a
+ * write.  (New entries only, so SAM6D_ABI_VERSION stays.) */
+size_t sam6d_draw_detections_workspace_bytes(int H, int W);
+int sam6d_draw_detections(const unsigned char* rgb, long row_stride, int H, int W, const float* R, const float* t, const float* K, int N,
+                          const float* box, const float* pts, int P, const unsigned char* colors, int thickness, int radius,
+                          unsigned char* canvas, int* n_skipped, void* workspace, size_t workspace_bytes, void* stream);
+/* The picture of ISM/run_inference_custom.py:48-84 (`visualize`) for M masks in one call (M = 1 is the reference), with the
+ * side-by-side paste of :79-84.  rgb as above; masks (M,H,W) u8 or bool, non-zero = inside, drawn in the order given (later over
+ * earlier); lut (M,3,256) u8, the blend of :70-72 tabulated on the host per mask, channel and grey value; canvas (H, 2W, 3) u8: the
+ * left half is rgb, the right half the picture.
+ * Contract (csrc/overlay.hip, tests/overlay_ref.py; bitwise reproducible): grey = (4899 R + 9617 G + 1868 B + 8192) >> 14 (OpenCV's
+ * published 8-bit RGB2GRAY fixed point, restated, not pinned against cv2); a pixel covered by masks shows lut[m][c][grey] of the last
+ * such m, another pixel grey in all channels; with draw_edge != 0 a pixel in the edge of any mask is 255.  The edge is the package's
+ * own, NOT skimage's canny (:62), equal in kind only: mask pixels with a 4-neighbour inside the image that is not mask, dilated by
+ * the reference's binary_dilation(edge, np.ones((2, 2))) (:63) exactly.  A gather with one writer per byte, no atomics, no workspace.
+ * H, W 1 .. 8192, M 0 .. 4096 (M = 0: the grey picture; masks and lut may be NULL); anything else returns non-zero without a launch
+ * or a write.  (New entries only, so SAM6D_ABI_VERSION stays.) */
+int sam6d_overlay_masks(const unsigned char* rgb, long row_stride, int H, int W, const unsigned char* masks, int M,
+                        const unsigned char* lut, int draw_edge, unsigned char* canvas, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

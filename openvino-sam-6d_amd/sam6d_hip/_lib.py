@@ -162,6 +162,9 @@ SIGNATURES = {
                           + [ctypes.c_size_t, c_p],
     "sam6d_mesh_sample_workspace_bytes": [c_i],
     "sam6d_mesh_sample": [c_p, c_i, c_p, c_i, c_i, ctypes.c_uint, ctypes.c_uint, c_p, c_p, c_p, ctypes.c_size_t, c_p],
+    "sam6d_draw_detections_workspace_bytes": [c_i, c_i],
+    "sam6d_draw_detections": [c_p, c_l, c_i, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_p, ctypes.c_size_t, c_p],
+    "sam6d_overlay_masks": [c_p, c_l, c_i, c_i, c_p, c_i, c_p, c_i, c_p, c_p],
 }
 
 _lib = None
