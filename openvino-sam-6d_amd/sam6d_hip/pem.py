@@ -698,9 +698,28 @@ def linear_attention_forward(xq, xk, xv, lq, lk, lv, scale, heads=H):
     _lib.call("sam6d_linattn_kv", _p(kv), _p(kv, C), B, J, 2 * C, 2 * C, J * 2 * C, J * 2 * C, _p(kvT), _p(ksum), _s())
     _lib.call("sam6d_linattn_focus_q", _p(q), _p(scale), _p(ksum), B, I, C, _s())
     hid = _empty((B * I, C), xq)
-    for h in range(H):
-        gemm(q, kvT, None, hid, I, 64, 64, C, 64, C, a_off=h * 64, w_off=h * 4096, c_off=h * 64, batch=B, sA=I * C, sW=H * 4096, sC=I * C)
+    _linattn_contract(q, kvT, hid, B, I)
     return hid.reshape(B, I, C)
+
+
+def _linattn_contract(q, kvT, hid, Bn, I):
+    """hid[:, h] = (phi(q)_h z_h) @ kv_h for the four heads, batched over the Bn clouds: the last step of the launch-per-op linear
+    attention.  In matmul mode 1 these four GEMMs run on the exact fp32 loop of mode 0.  Cubing spreads a row of phi(q) z over twenty
+    orders of magnitude under a maximum near 2^-6, the lower end of the range in which sam6d_gemm_nt keeps the fp16 split: the lo halves
+    are fp16 subnormals there, every element carries 2^-25 absolute, and kv^T holds entries of a few hundred -- the split product was
+    off by 1.4e-5 of the largest output at (B, I, J) = (2, 300, 197), the exact loop by 1e-6.  (The fused layer scales every row by a
+    power of two instead.)  64 x 64 weights: the loop's rate does not matter."""
+    exact = _flags().mode == 1
+    if exact:
+        prev = int(_lib.load().sam6d_get_thread_matmul_mode())
+        _lib.call("sam6d_set_thread_matmul_mode", 0)
+    try:
+        for h in range(H):  # x_h = (phi(q)_h z) @ kv_h
+            gemm(q, kvT, None, hid, I, 64, 64, C, 64, C, a_off=h * 64, w_off=h * 4096, c_off=h * 64, batch=Bn, sA=I * C, sW=H * 4096,
+                 sC=I * C)
+    finally:
+        if exact:
+            _lib.call("sam6d_set_thread_matmul_mode", prev)
 
 
 def geometric_transformer(S, E, T):
@@ -754,9 +773,7 @@ def linear_transformer_layer(D, S, L):
     q = linear(D2, L["q"])
     _lib.call("sam6d_linattn_focus_q", _p(q), _p(L["scale"]), _p(ksum), Bp, I, C, _s())
     hid = _empty((rows, C), D)
-    for h in range(H):  # x_h = (phi(q)_h z) @ kv_h : batched over B'
-        gemm(q, kvT, None, hid, I, 64, 64, C, 64, C, a_off=h * 64, w_off=h * 4096, c_off=h * 64, batch=Bp, sA=I * C,
-             sW=H * 4096, sC=I * C)
+    _linattn_contract(q, kvT, hid, Bp, I)
     return _post_attention(hid, D2, L).reshape(Bp, I, C)
 
 
