@@ -912,6 +912,35 @@ int sam6d_draw_detections(const unsigned char* rgb, long row_stride, int H, int 
 int sam6d_overlay_masks(const unsigned char* rgb, long row_stride, int H, int W, const unsigned char* masks, int M,
                         const unsigned char* lut, int draw_edge, unsigned char* canvas, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * ISM's reference data from a template set: boxes and 224 x 224 crops of T templates, each on its own image
+ * (csrc/refdata.hip).  (New entries only, so SAM6D_ABI_VERSION stays.)
+ * ------------------------------------------------------------------------------------------------------------ */
+#define SAM6D_TEMPLATE_CUSTOM 0 /* ISM/run_inference_custom.py:138-140: rgb / 255 times mask / 255, no Normalize */
+#define SAM6D_TEMPLATE_BOP 1    /* ISM/provider/bop.py:68-81: rgb / 255, T.Normalize after the padding, no mask product */
+/* `mask.getbbox()` of ISM/run_inference_custom.py:136 (`image.getbbox()` of an RGBA template, ISM/provider/bop.py:66, with the alpha
+ * band given) for T single-band u8 images in one launch: boxes (T,4) i64 on the device = (left, upper, right + 1, lower + 1) over the
+ * pixels != 0, and (0,0,0,0) for an image without one (PIL returns None there).  Pixel (y, x) of image t is the byte
+ * band + t image_stride + (y W + x) pixel_stride (strides in bytes), so the alpha band of an interleaved (T,H,W,4) tensor is read in
+ * place with band = rgba + 3, pixel_stride 4.  No atomics and no workspace: the result does not depend on any order.
+ * T <= 65535, H W <= 2^29, pixel_stride 1 .. 64, image_stride >= 0; anything else returns non-zero without a launch. */
+int sam6d_template_boxes(const unsigned char* band, int T, int H, int W, long pixel_stride, long image_stride, long long* boxes,
+                         void* stream);
+/* The template crops of ISM/run_inference_custom.py:138-155 (flavour SAM6D_TEMPLATE_CUSTOM) and ISM/provider/bop.py:68-83
+ * (SAM6D_TEMPLATE_BOP) through CropResizePad(224) (ISM/utils/bbox_utils.py:89-126) for T templates in one launch, template t reading
+ * its own image through boxes[t] = (x1, y1, x2, y2) i64 on the device (exclusive ends; no read-back).  Channel c of pixel (y, x) of
+ * template t is the byte rgb + t rgb_image_stride + (y W + x) rgb_pixel_stride + c (3 for an RGB tensor, 4 for the colours of an RGBA
+ * one), its mask the byte mask + t mask_image_stride + (y W + x) mask_pixel_stride.  out_rgb (T,3,224,224) f32: custom
+ * fl32(u8 / 255) * fl32(mask / 255) with padding 0; bop (fl32(u8 / 255) - mean) / std in fp32 with padding (0 - mean) / std (mean
+ * 0.485/0.456/0.406, std 0.229/0.224/0.225).  out_mask (T,224,224) f32 = fl32(mask / 255), padding 0.  Either output may be NULL,
+ * rgb too when out_rgb is, and mask when neither out_mask nor the custom product needs it.  The gather is the one of
+ * sam6d_dino_crop_proposals (one index recipe, csrc/crop_index.h): bit-exact; a box with side <= 0 or an empty resized crop is all
+ * padding.  T <= 65535, H W <= 2^29, rgb_pixel_stride 3 .. 64, mask_pixel_stride 1 .. 64, image strides >= 0; anything else returns
+ * non-zero without a launch. */
+int sam6d_template_crops(const unsigned char* rgb, long rgb_pixel_stride, long rgb_image_stride, const unsigned char* mask,
+                         long mask_pixel_stride, long mask_image_stride, const long long* boxes, int T, int H, int W, int flavour,
+                         float* out_rgb, float* out_mask, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

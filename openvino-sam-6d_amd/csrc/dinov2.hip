@@ -10,19 +10,14 @@
 // The dense projections are sam6d_gemm_nt / _w16 (fc1 with the erf-GELU epilogue, proj / fc2 with the in-place residual; LayerScale is
 // folded into their weights at pack time).
 #include "common.h"
+#include "crop_index.h"
 #include "../../include/sam6d_hip.h"
 
 #define DN_C 1024
-#define DN_IMG 224
+#define DN_IMG CROP_IMG
 
 // ---- proposal crops -------------------------------------------------------------------------------------------------------------
-// F.interpolate(x, scale_factor = s) in the default nearest mode: output size floor(in * s) in double, source index
-// min((int) floorf(dst * (float)(1 / s)), in - 1) (ATen upsample_nearest with the scale it was given).
-__device__ __forceinline__ int dn_nearest(int dst, float scale, int in) {
-  const int s = (int)floorf((float)dst * scale);
-  return s < in - 1 ? s : in - 1;
-}
-
+// which image pixel an output pixel reads: crop_source of crop_index.h, the recipe csrc/refdata.hip shares
 __global__ __launch_bounds__(256) void dino_crop_kernel(const unsigned char* __restrict__ img, const float* __restrict__ masks,
                                                         const long long* __restrict__ boxes, int H, int W,
                                                         float* __restrict__ out_rgb, float* __restrict__ out_mask) {
@@ -30,49 +25,17 @@ __global__ __launch_bounds__(256) void dino_crop_kernel(const unsigned char* __r
   const int pix = blockIdx.x * 256 + threadIdx.x;
   if (pix >= DN_IMG * DN_IMG) return;
   const int Y = pix / DN_IMG, X = pix % DN_IMG;
-  const long long bx1 = boxes[4 * i], by1 = boxes[4 * i + 1], bx2 = boxes[4 * i + 2], by2 = boxes[4 * i + 3];
-  // scale_factor = 224 / max(box side) of the (unclamped) box sizes, bbox_utils.py:99-100: a Python number over a tensor, which torch
-  // evaluates as tensor.reciprocal() * 224 in fp32 -- two roundings, not one division (for side 3: 74.66667175, not 74.66666412)
-  const long long side = (bx2 - bx1) > (by2 - by1) ? (bx2 - bx1) : (by2 - by1);
-  const float sf = (1.0f / (float)side) * 224.0f;
-  // the slice image[:, y1:y2, x1:x2] (bbox_utils.py:104) ends at the image border
-  const int x1 = (int)(bx1 < 0 ? 0 : (bx1 > W ? W : bx1)), x2 = (int)(bx2 < 0 ? 0 : (bx2 > W ? W : bx2));
-  const int y1 = (int)(by1 < 0 ? 0 : (by1 > H ? H : by1)), y2 = (int)(by2 < 0 ? 0 : (by2 > H ? H : by2));
-  const int cw = x2 - x1, ch = y2 - y1;
-  int rw = 0, rh = 0;
-  if (side > 0 && cw > 0 && ch > 0) {
-    rw = (int)floor((double)cw * (double)sf);
-    rh = (int)floor((double)ch * (double)sf);
-  }
   float r = 0.f, g = 0.f, b = 0.f, m = 0.f;
-  if (rw > 0 && rh > 0 && rw <= DN_IMG && rh <= DN_IMG) {  // (an empty resized crop raises in the reference: all padding here)
-    const float scale1 = (float)(1.0 / (double)sf);
-    int py = Y, px = X, pad_t = 0, pad_l = 0;
-    if (rw == rh) {
-      // square after the resize: no padding (bbox_utils.py:111); the second interpolate maps side rw -> 224.  rw is 223 or 224 for
-      // every box side (224 / side is good to 2 ulp), and torch sizes the second output as floor(223 * (224.0 / 223)) = 224, so the
-      // 224 pixels written here are the reference's (tests/test_dinov2_host.py checks both statements)
-      if (rw != DN_IMG) {
-        const float scale2 = (float)(1.0 / (224.0 / (double)rw));
-        py = dn_nearest(Y, scale2, rw);
-        px = dn_nearest(X, scale2, rw);
-      }
-    } else {
-      pad_t = (DN_IMG - rh) / 2;
-      pad_l = (DN_IMG - rw) / 2;
-    }
-    const int ry = py - pad_t, rx = px - pad_l;
-    if (ry >= 0 && ry < rh && rx >= 0 && rx < rw) {
-      const int sy = y1 + dn_nearest(ry, scale1, ch), sx = x1 + dn_nearest(rx, scale1, cw);
-      const size_t at = (size_t)sy * W + sx;
-      m = masks[(size_t)i * H * W + at];
-      if (out_rgb) {
-        const unsigned char* p = img + 3 * at;
-        // ToTensor (u8 / 255), Normalize ((x - mean) / std), times the mask: fp32, in torch's order (dinov2.py:144-149, 167-169)
-        r = (((float)p[0] / 255.0f) - 0.485f) / 0.229f * m;
-        g = (((float)p[1] / 255.0f) - 0.456f) / 0.224f * m;
-        b = (((float)p[2] / 255.0f) - 0.406f) / 0.225f * m;
-      }
+  int sy, sx;
+  if (crop_source(boxes + 4 * i, H, W, Y, X, sy, sx)) {
+    const size_t at = (size_t)sy * W + sx;
+    m = masks[(size_t)i * H * W + at];
+    if (out_rgb) {
+      const unsigned char* p = img + 3 * at;
+      // ToTensor (u8 / 255), Normalize ((x - mean) / std), times the mask: fp32, in torch's order (dinov2.py:144-149, 167-169)
+      r = (((float)p[0] / 255.0f) - 0.485f) / 0.229f * m;
+      g = (((float)p[1] / 255.0f) - 0.456f) / 0.224f * m;
+      b = (((float)p[2] / 255.0f) - 0.406f) / 0.225f * m;
     }
   }
   if (out_rgb) {

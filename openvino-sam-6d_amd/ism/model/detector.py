@@ -2,7 +2,9 @@
 
 Constructor arguments, attribute names (`ref_data`, `matching_config`, `visible_thred`, ...) and method signatures are
 the reference's.  The proposal generators and the DINOv2 descriptor model are outside the hot path: they are accepted
-and stored, never touched here.  Lightning is optional (plain nn.Module when pytorch_lightning is absent)."""
+and stored, never touched here.  Lightning is optional (plain nn.Module when pytorch_lightning is absent).
+`ref_data` is the caller's to fill (ISM/run_inference_custom.py:157-163, 226-234); sam6d_hip.refdata.build makes it from a template
+set on the device."""
 import torch
 import torch.nn as nn
 

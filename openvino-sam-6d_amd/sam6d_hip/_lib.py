@@ -165,6 +165,8 @@ SIGNATURES = {
     "sam6d_draw_detections_workspace_bytes": [c_i, c_i],
     "sam6d_draw_detections": [c_p, c_l, c_i, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_p, ctypes.c_size_t, c_p],
     "sam6d_overlay_masks": [c_p, c_l, c_i, c_i, c_p, c_i, c_p, c_i, c_p, c_p],
+    "sam6d_template_boxes": [c_p, c_i, c_i, c_i, c_l, c_l, c_p, c_p],
+    "sam6d_template_crops": [c_p, c_l, c_l, c_p, c_l, c_l, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p],
 }
 
 _lib = None
