@@ -860,6 +860,22 @@ int sam6d_render_views(const float* vertices, int V, const int* faces, int F, co
                        float base_color, int colorize, const unsigned char* srgb_lut, int wave_area, unsigned char* mask, int* face,
                        float* depth, float* xyz, unsigned char* rgb, int* n_dropped, void* workspace, size_t workspace_bytes,
                        void* stream);
+/* The same renderer for a textured model: Render/render_custom_templates.py:60 loads its --cad_path with bproc.loader.load_obj, which
+ * takes an OBJ with its MTL and diffuse image (and a PLY that names a texture file) as well as a vertex-coloured PLY.  The arguments,
+ * the workspace, the outputs and the geometry are sam6d_render_views's; visibility is the same pass.  Only the albedo of rgb differs: it
+ * is the bilinear, repeat-wrapped lookup of `texture` at the perspective-correct attribute of face_uv (the TEXTURE recipe at the top of
+ * csrc/texture.hip, restated in tests/texture_ref.py).  face_uv (F,3,2) f32: (u, v) of each face's three corners in stored order,
+ * v = 0 at the bottom edge of the image.  texture (Ht,Wt,4) u8 on the device, 4-byte aligned, row 0 the top row, bytes R G B and one
+ * ignored byte.  texel_lut 256 f32 on the device: the albedo of a byte (k / 255 in fp32 gives the vertex-colour path's values; the
+ * host may pass the sRGB-to-linear table instead).  There is no colorize and no colors here: a caller that wants the grey render calls
+ * sam6d_render_views; base_color keeps its place in the argument list and is not used.  Ht, Wt 1 .. 8192; every limit of sam6d_render_views holds; anything else returns non-zero without a launch or
+ * a write.  (New entry only, so SAM6D_ABI_VERSION stays.) */
+int sam6d_render_views_textured(const float* vertices, int V, const int* faces, int F, const float* normals, const float* view,
+                                const float* light, int T, float fx, float fy, float cx, float cy, int H, int W, float near,
+                                float base_color, const unsigned char* srgb_lut, int wave_area, const float* face_uv,
+                                const unsigned char* texture, int Ht, int Wt, const float* texel_lut, unsigned char* mask, int* face,
+                                float* depth, float* xyz, unsigned char* rgb, int* n_dropped, void* workspace, size_t workspace_bytes,
+                                void* stream);
 /* trimesh.sample.sample_surface as the reference calls it (Render/render_custom_templates.py:35, ISM/run_inference_custom.py:232-234,
  * PEM/run_inference_custom_pytorch.py:298-300): n area-weighted points of the surface.  NOT trimesh's or numpy's stream: an integer
  * definition of its own (csrc/meshsample.hip, restated in tests/meshsample_ref.py), equal to the reference in distribution only:

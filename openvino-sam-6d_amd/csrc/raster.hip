@@ -41,117 +41,11 @@
 // than wave_area pixels is walked by its lane (the thread path: a dense scan is mostly triangles of a few pixels); the rest are
 // taken one after the other by the whole wave, 64 pixels of the box at a time (the wave path: a low-poly mesh is a few triangles of
 // tens of thousands of pixels).  Both paths call rs_offer() on a face set up by rs_setup(): the arithmetic is one piece of code.
-#include "common.h"
+//
+// FILES.  The face setup, coverage and weights are device functions in raster.h, shared with texture.hip, whose resolve kernel takes
+// the albedo from a texture image instead; visibility (rs_visibility below) is this file's for both entries.
+#include "raster.h"
 #include "../../include/sam6d_hip.h"
-
-#define RS_MAX_HW 2048
-#define RS_MAX_T 1024
-#define RS_MAX_F (1 << 24)
-#define RS_WAVE_AREA 256
-#define RS_GAIN 25.330296f
-#define RS_SNAP_LIMIT 16777216.0f
-
-struct RsCam {
-  float fx, fy, cx, cy, near;
-  int H, W;
-};
-
-struct RsFace {
-  int X[3], Y[3];  // snapped screen coordinates, vertices 1 and 2 swapped where the winding asked for it
-  float z[3];      // camera depth in that order
-  long long area2;
-  int b0, b1, b2;  // 0 where the edge opposite the vertex owns its points (top-left), else -1
-  int x0, x1, y0, y1;  // pixel bounding box clamped to the image; empty when x0 > x1 or y0 > y1
-  bool live;       // not dropped and area2 != 0
-  bool dropped;
-  bool swapped;
-};
-
-__device__ __forceinline__ float rs_row(const float* m, float x, float y, float z) { return ((m[0] * x + m[1] * y) + m[2] * z) + m[3]; }
-
-__device__ __forceinline__ int rs_snap(float f, float a, float z, float c) {
-  float u = (f * (a / z) + c) * 256.0f;
-  u = u >= -RS_SNAP_LIMIT ? u : -RS_SNAP_LIMIT;
-  u = u <= RS_SNAP_LIMIT ? u : RS_SNAP_LIMIT;
-  return (int)floorf(u + 0.5f);
-}
-
-__device__ __forceinline__ int rs_owner(int ax, int ay, int bx, int by) { return (by < ay || (by == ay && bx > ax)) ? 0 : -1; }
-
-__device__ __forceinline__ void rs_setup(RsFace& f, const float* __restrict__ vert, int V, const int* __restrict__ faces, int face,
-                                         const float* __restrict__ M, const RsCam& cam) {
-  f.live = false;
-  f.dropped = false;
-  f.swapped = false;
-  f.x0 = f.y0 = 0;
-  f.x1 = f.y1 = -1;
-  int id[3];
-  bool ok = true;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    id[k] = faces[(size_t)face * 3 + k];
-    ok = ok && (unsigned)id[k] < (unsigned)V;
-  }
-  if (ok) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const float x = vert[(size_t)id[k] * 3], y = vert[(size_t)id[k] * 3 + 1], z = vert[(size_t)id[k] * 3 + 2];
-      const float px = rs_row(M, x, y, z), py = rs_row(M + 4, x, y, z), pz = rs_row(M + 8, x, y, z);
-      ok = ok && (pz >= cam.near);
-      f.z[k] = pz;
-      f.X[k] = rs_snap(cam.fx, px, pz, cam.cx);
-      f.Y[k] = rs_snap(cam.fy, py, pz, cam.cy);
-    }
-  }
-  if (!ok) {
-    f.dropped = true;
-    return;
-  }
-  long long a2 = (long long)(f.X[1] - f.X[0]) * (f.Y[2] - f.Y[0]) - (long long)(f.X[2] - f.X[0]) * (f.Y[1] - f.Y[0]);
-  if (a2 == 0) return;
-  if (a2 < 0) {
-    int t = f.X[1]; f.X[1] = f.X[2]; f.X[2] = t;
-    t = f.Y[1]; f.Y[1] = f.Y[2]; f.Y[2] = t;
-    const float s = f.z[1]; f.z[1] = f.z[2]; f.z[2] = s;
-    a2 = -a2;
-    f.swapped = true;
-  }
-  f.area2 = a2;
-  f.b0 = rs_owner(f.X[1], f.Y[1], f.X[2], f.Y[2]);
-  f.b1 = rs_owner(f.X[2], f.Y[2], f.X[0], f.Y[0]);
-  f.b2 = rs_owner(f.X[0], f.Y[0], f.X[1], f.Y[1]);
-  const int xmin = min(f.X[0], min(f.X[1], f.X[2])), xmax = max(f.X[0], max(f.X[1], f.X[2]));
-  const int ymin = min(f.Y[0], min(f.Y[1], f.Y[2])), ymax = max(f.Y[0], max(f.Y[1], f.Y[2]));
-  // the pixels whose centre 256 j + 128 lies in [min, max], clamped to the image before anything is addressed
-  f.x0 = max((xmin + 127) >> 8, 0);
-  f.x1 = min((xmax - 128) >> 8, cam.W - 1);
-  f.y0 = max((ymin + 127) >> 8, 0);
-  f.y1 = min((ymax - 128) >> 8, cam.H - 1);
-  f.live = true;
-}
-
-__device__ __forceinline__ long long rs_edge(int ax, int ay, int bx, int by, int px, int py) {
-  return (long long)(bx - ax) * (py - ay) - (long long)(by - ay) * (px - ax);
-}
-
-// the edge values of pixel (x, y); true when the centre is covered
-__device__ __forceinline__ bool rs_cover(const RsFace& f, int x, int y, long long& w0, long long& w1, long long& w2) {
-  const int px = 256 * x + 128, py = 256 * y + 128;
-  w0 = rs_edge(f.X[1], f.Y[1], f.X[2], f.Y[2], px, py);
-  w1 = rs_edge(f.X[2], f.Y[2], f.X[0], f.Y[0], px, py);
-  w2 = rs_edge(f.X[0], f.Y[0], f.X[1], f.Y[1], px, py);
-  return (w0 + f.b0 >= 0) && (w1 + f.b1 >= 0) && (w2 + f.b2 >= 0);
-}
-
-// perspective-correct weights l and the depth from the edge values
-__device__ __forceinline__ float rs_weights(const RsFace& f, long long w0, long long w1, long long w2, float& l0, float& l1, float& l2) {
-  const float q0 = (float)w0 / f.z[0], q1 = (float)w1 / f.z[1], q2 = (float)w2 / f.z[2];
-  const float qs = (q0 + q1) + q2;
-  l0 = q0 / qs;
-  l1 = q1 / qs;
-  l2 = q2 / qs;
-  return (float)f.area2 / qs;
-}
 
 __device__ __forceinline__ void rs_offer(const RsFace& f, int face, int x, int y, unsigned long long* __restrict__ zrow0, int W) {
   long long w0, w1, w2;
@@ -203,8 +97,6 @@ struct RsShade {
   float base_color;
   int colorize;
 };
-
-__device__ __forceinline__ float rs_mix(float l0, float l1, float l2, float a0, float a1, float a2) { return (l0 * a0 + l1 * a1) + l2 * a2; }
 
 // one thread per pixel of every view: the only writer of the outputs
 __global__ __launch_bounds__(256) void raster_resolve_kernel(const float* __restrict__ vert, int V, const int* __restrict__ faces,
@@ -301,36 +193,52 @@ extern "C" size_t sam6d_render_views_workspace_bytes(int T, int H, int W) {
   return (size_t)T * H * W * sizeof(unsigned long long);
 }
 
+int rs_check(const char* who, int V, int F, int T, int H, int W, float near, int wave_area, bool pointers, const void* workspace,
+             size_t workspace_bytes) {
+  SAM6D_REQUIRE(H >= 1 && H <= RS_MAX_HW && W >= 1 && W <= RS_MAX_HW, "%s: H x W = %d x %d is not in 1 .. %d", who, H, W, RS_MAX_HW);
+  SAM6D_REQUIRE(T >= 1 && T <= RS_MAX_T, "%s: T = %d is not in 1 .. %d", who, T, RS_MAX_T);
+  SAM6D_REQUIRE(F >= 1 && F <= RS_MAX_F, "%s: F = %d is not in 1 .. %d", who, F, RS_MAX_F);
+  SAM6D_REQUIRE(V >= 1, "%s: V = %d is not positive", who, V);
+  SAM6D_REQUIRE(near > 0.f, "%s: near = %g is not positive", who, (double)near);
+  SAM6D_REQUIRE(wave_area >= 0, "%s: wave_area = %d is negative", who, wave_area);
+  SAM6D_REQUIRE(pointers && workspace, "%s: null pointer", who);
+  const size_t need = sam6d_render_views_workspace_bytes(T, H, W);
+  SAM6D_REQUIRE(workspace_bytes >= need, "%s: workspace of %zu bytes is below sam6d_render_views_workspace_bytes = %zu", who, workspace_bytes,
+                need);
+  SAM6D_REQUIRE(((uintptr_t)workspace & 7) == 0, "%s: workspace is not 8-byte aligned", who);
+  return 0;
+}
+
+int rs_visibility(const char* who, const float* vertices, int V, const int* faces, int F, const float* view, int T, const RsCam& cam,
+                  int wave_area, unsigned long long* zbuf, int* n_dropped, hipStream_t s) {
+  hipError_t e = hipMemsetAsync(zbuf, 0xff, (size_t)T * cam.H * cam.W * sizeof(unsigned long long), s);
+  if (e == hipSuccess) e = hipMemsetAsync(n_dropped, 0, (size_t)T * sizeof(int), s);
+  if (e != hipSuccess) {
+    sam6d_set_error("%s: memset failed: %s", who, hipGetErrorString(e));
+    return (int)e;
+  }
+  hipLaunchKernelGGL(raster_faces_kernel, dim3((F + 63) / 64, T), dim3(64), 0, s, vertices, V, faces, F, view, cam,
+                     wave_area ? wave_area : RS_WAVE_AREA, zbuf, n_dropped);
+  e = hipGetLastError();
+  if (e != hipSuccess) sam6d_set_error("%s (faces): launch failed: %s", who, hipGetErrorString(e));
+  return (int)e;
+}
+
 extern "C" int sam6d_render_views(const float* vertices, int V, const int* faces, int F, const float* normals, const unsigned char* colors,
                                   const float* view, const float* light, int T, float fx, float fy, float cx, float cy, int H, int W,
                                   float near, float base_color, int colorize, const unsigned char* srgb_lut, int wave_area,
                                   unsigned char* mask, int* face, float* depth, float* xyz, unsigned char* rgb, int* n_dropped,
                                   void* workspace, size_t workspace_bytes, void* stream) {
-  SAM6D_REQUIRE(H >= 1 && H <= RS_MAX_HW && W >= 1 && W <= RS_MAX_HW, "render_views: H x W = %d x %d is not in 1 .. %d", H, W, RS_MAX_HW);
-  SAM6D_REQUIRE(T >= 1 && T <= RS_MAX_T, "render_views: T = %d is not in 1 .. %d", T, RS_MAX_T);
-  SAM6D_REQUIRE(F >= 1 && F <= RS_MAX_F, "render_views: F = %d is not in 1 .. %d", F, RS_MAX_F);
-  SAM6D_REQUIRE(V >= 1, "render_views: V = %d is not positive", V);
-  SAM6D_REQUIRE(near > 0.f, "render_views: near = %g is not positive", (double)near);
-  SAM6D_REQUIRE(wave_area >= 0, "render_views: wave_area = %d is negative", wave_area);
-  SAM6D_REQUIRE(vertices && faces && view && light && srgb_lut && mask && face && depth && xyz && rgb && n_dropped && workspace,
-                "render_views: null pointer");
-  const size_t need = sam6d_render_views_workspace_bytes(T, H, W);
-  SAM6D_REQUIRE(workspace_bytes >= need, "render_views: workspace of %zu bytes is below sam6d_render_views_workspace_bytes = %zu",
-                workspace_bytes, need);
-  SAM6D_REQUIRE(((uintptr_t)workspace & 7) == 0, "render_views: workspace is not 8-byte aligned");
+  const int bad = rs_check("render_views", V, F, T, H, W, near, wave_area,
+                           vertices && faces && view && light && srgb_lut && mask && face && depth && xyz && rgb && n_dropped, workspace,
+                           workspace_bytes);
+  if (bad) return bad;
   hipStream_t s = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(workspace, 0xff, need, s);
-  if (e == hipSuccess) e = hipMemsetAsync(n_dropped, 0, (size_t)T * sizeof(int), s);
-  if (e != hipSuccess) {
-    sam6d_set_error("render_views: memset failed: %s", hipGetErrorString(e));
-    return (int)e;
-  }
   const RsCam cam = {fx, fy, cx, cy, near, H, W};
   const RsShade sh = {normals, colors, light, srgb_lut, base_color, colorize};
   unsigned long long* zbuf = (unsigned long long*)workspace;
-  hipLaunchKernelGGL(raster_faces_kernel, dim3((F + 63) / 64, T), dim3(64), 0, s, vertices, V, faces, F, view, cam,
-                     wave_area ? wave_area : RS_WAVE_AREA, zbuf, n_dropped);
-  SAM6D_LAUNCH_CHECK_CONT("render_views (faces)");
+  const int err = rs_visibility("render_views", vertices, V, faces, F, view, T, cam, wave_area, zbuf, n_dropped, s);
+  if (err) return err;
   const size_t px = (size_t)T * H * W;  // at most 2^32: 2^24 blocks
   hipLaunchKernelGGL(raster_resolve_kernel, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, s, vertices, V, faces, view, cam, sh, T, zbuf,
                      mask, face, depth, xyz, rgb);

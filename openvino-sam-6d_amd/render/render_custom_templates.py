@@ -4,7 +4,8 @@ sampler instead of trimesh and PIL instead of cv2.  The reference script's argum
 Instance_Segmentation_Model/utils/poses/predefined_poses/cam_poses_level0.npy (this package ships no copy of it).
 
 The geometry of the output (mask, xyz) is bitwise reproducible; the shading of rgb is the package's own and is not pinned against
-Cycles.  --size and --fov default to what BlenderProc's default configuration is believed to use.  PLY models only.
+Cycles.  --size and --fov default to what BlenderProc's default configuration is believed to use.  --cad_path: a PLY, or an OBJ with
+its MTL; a model that names a texture image (map_Kd, or a PLY's `comment TextureFile`) is rendered with it.
 """
 import argparse
 import os
@@ -28,7 +29,7 @@ def _flag(v):
 
 def main(argv=None):
     parser = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    parser.add_argument("--cad_path", required=True, help="The path of CAD model (PLY)")
+    parser.add_argument("--cad_path", required=True, help="The path of CAD model (PLY or OBJ)")
     parser.add_argument("--output_dir", required=True, help="The path to save CAD templates")
     parser.add_argument("--normalize", default=True, type=_flag, help="Whether to normalize CAD model or not")
     parser.add_argument("--colorize", default=False, type=_flag, help="Whether to colorize CAD model or not")
@@ -38,10 +39,10 @@ def main(argv=None):
     parser.add_argument("--fov", default=0.691111, type=float, help="horizontal field of view in radians")
     parser.add_argument("--seed", default=0, type=int, help="seed of the surface samples behind --normalize")
     args = parser.parse_args(argv)
-    if not args.cad_path.lower().endswith(".ply"):
-        parser.error("--cad_path: only PLY models are read (got %s)" % args.cad_path)
+    if not args.cad_path.lower().endswith((".ply", ".obj")):
+        parser.error("--cad_path: PLY and OBJ models are read (got %s)" % args.cad_path)
     from sam6d_hip import onboard
-    mesh = onboard.load_ply(args.cad_path)
+    mesh = onboard.load_mesh(args.cad_path)
     out = onboard.render_templates(mesh, np.load(args.cam_poses), normalize=args.normalize, colorize=args.colorize,
                                    base_color=args.base_color, size=args.size, fov=args.fov, seed=args.seed)
     save_fpath = onboard.save_templates(out, os.path.join(args.output_dir, "templates"))

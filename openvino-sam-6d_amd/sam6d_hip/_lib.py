@@ -160,6 +160,8 @@ SIGNATURES = {
     "sam6d_render_views_workspace_bytes": [c_i] * 3,
     "sam6d_render_views": [c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_i] + [c_f] * 4 + [c_i, c_i, c_f, c_f, c_i, c_p, c_i] + [c_p] * 7
                           + [ctypes.c_size_t, c_p],
+    "sam6d_render_views_textured": [c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_i] + [c_f] * 4 + [c_i, c_i, c_f, c_f, c_p, c_i, c_p, c_p, c_i, c_i, c_p]
+                                   + [c_p] * 7 + [ctypes.c_size_t, c_p],
     "sam6d_mesh_sample_workspace_bytes": [c_i],
     "sam6d_mesh_sample": [c_p, c_i, c_p, c_i, c_i, ctypes.c_uint, ctypes.c_uint, c_p, c_p, c_p, ctypes.c_size_t, c_p],
     "sam6d_draw_detections_workspace_bytes": [c_i, c_i],
