@@ -417,7 +417,12 @@ int sam6d_score_select_hypotheses_ws(const int* sel, const float* Rs, const floa
  * small kernels merge the chunks in ascending column order) -- rc < 0 otherwise: use sam6d_gemm_nt + sam6d_soft_assign +
  * sam6d_fine_assign.  pts2 (B, n-1, 3) template points.
  * -> label1, label2 (B, n-1) i32, pred (B, n-1, 3), weight (B, n-1).  ws: sam6d_fine_match_workspace_bytes_n(B, n) bytes
- * (sam6d_fine_match_workspace_bytes(B): the n = 2049 size). */
+ * (sam6d_fine_match_workspace_bytes(B): the n = 2049 size).
+ * temp >= sam6d_fine_match_min_temp() = 2 log2(e) / 125 = 0.0231 -- rc < 0 below it: the pipeline replaces the softmax's running maximum
+ * (torch.softmax, PEM/utils/model_utils.py:320-321) by the fixed shift 1 / temp, which |cos| <= 1 allows, and exp(-2 / temp) must stay a
+ * normal float32; smaller temperatures take sam6d_gemm_nt + sam6d_soft_assign + sam6d_fine_assign.  (New entry and a refusal of
+ * inputs whose results were not finite, so SAM6D_ABI_VERSION stays.) */
+float sam6d_fine_match_min_temp(void);
 size_t sam6d_fine_match_workspace_bytes(int B);
 size_t sam6d_fine_match_workspace_bytes_n(int B, int n);
 int sam6d_fine_match(const float* f, int B, int n, float temp, const float* pts2, int* label1, int* label2, float* pred,

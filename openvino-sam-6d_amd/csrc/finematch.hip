@@ -11,7 +11,8 @@
 //   * |att| <= 1 / temp because both sides are L2-normalised, so softmax needs no running maximum: with the fixed shift c = 1 / temp,
 //     E = exp(att - c) is in [e^-2c, 1] and softmax(att, 2)[n][m] = E[n][m] / sum_m E[n][m] (same for columns).  The similarity GEMM
 //     stores E and accumulates the row / column sums of its own tile in the epilogue (per-tile partials, merged in a fixed order: the
-//     result does not depend on the launch's timing or on the other proposals of the batch).
+//     result does not depend on the launch's timing or on the other proposals of the batch).  The shift bounds the temperature from
+//     below: temp >= FM_MIN_TEMP = 2 log2e / 125 = 0.0231, so that e^-2c stays a normal float (refused otherwise).
 //   * one pass finds both label vectors (row arg-max complete per wave, column arg-max per 64-row slab + a small merge),
 //   * one pass forms weight and pred.
 // E is stored with a row stride of 2052 floats and logical column m at physical column m + 3, so that column 1 -- where the 128-wide
@@ -25,6 +26,11 @@
 #define FM_COL0 3         // physical column of logical column 0
 #define FM_CHUNK 2048     // columns one label / assignment workgroup covers (32 per lane); np = 2048 (config 2) or 4096 (config 5)
 #define FM_OPSCALE 1024.0f
+// The smallest temperature the fixed shift serves: E = exp2((cos - 1) log2e / temp) has its smallest exponent, -2 log2e / temp, at
+// cos = -1, and v_exp_f32 flushes results below 2^-126 to zero -- a row of zeros has the sum 0, its reciprocal is inf and the labels
+// and weights are NaN.  2 log2e / temp <= 125 keeps every E a normal number with one unit of margin for the fmaf's rounding and a
+// cosine of 1 + 1e-6.  Smaller temperatures belong to sam6d_soft_assign + sam6d_fine_assign, which keep a running maximum.
+#define FM_MIN_TEMP ((float)(2.0 * 1.4426950408889634 / 125.0))
 // np = points per cloud (n - 1), a multiple of 2048.  Row stride of E: np + 4 floats; partial sums per row / column: 2 per 128-wide tile
 // + the bg column / row; 64-row slabs in the label pass.
 #define FM_LDE(np) ((np) + 4)
@@ -470,6 +476,7 @@ static size_t fm_workspace_bytes(int B, int np) {
   return s;
 }
 
+extern "C" float sam6d_fine_match_min_temp(void) { return FM_MIN_TEMP; }
 extern "C" size_t sam6d_fine_match_workspace_bytes(int B) { return fm_workspace_bytes(B, 2048); }
 extern "C" size_t sam6d_fine_match_workspace_bytes_n(int B, int n) {
   return (n > 1 && (n - 1) % FM_CHUNK == 0) ? fm_workspace_bytes(B, n - 1) : 0;
@@ -494,10 +501,16 @@ static int fm_run(const float* f, const _Float16* fh_in, const _Float16* fl_in, 
                   int* label1, int* label2, float* pred, float* weight, void* ws, size_t ws_bytes, void* stream) {
   SAM6D_REQUIRE(pts2 && label1 && label2 && pred && weight && ws, "fine_match: null pointer");
   SAM6D_REQUIRE(n == 2049 || n == 4097, "fine_match: built for n = 2049 or 4097 tokens per cloud (got %d)", n);
-  SAM6D_REQUIRE(B >= 0 && B <= 4096 && temp > 0.f, "fine_match: bad sizes");
+  SAM6D_REQUIRE(B >= 0 && B <= 4096, "fine_match: B = %d outside 0 .. 4096", B);
+  SAM6D_REQUIRE(temp >= FM_MIN_TEMP, "fine_match: temp = %g is below sam6d_fine_match_min_temp() = %g (the fixed softmax shift 1 / temp would underflow; "
+                "use sam6d_gemm_nt + sam6d_soft_assign + sam6d_fine_assign)", (double)temp, (double)FM_MIN_TEMP);
   const int np = n - 1, chunks = np / FM_CHUNK, lde = FM_LDE(np), slots = FM_SLOTS(np), slabs = FM_SLABS(np), nt = np / 128;
-  SAM6D_REQUIRE(ws_bytes >= fm_workspace_bytes(B, np), "fine_match: workspace too small");
-  SAM6D_REQUIRE((((size_t)ws | (size_t)f | (size_t)pts2 | (size_t)label2) & 15) == 0, "fine_match: pointers must be 16-byte aligned");
+  SAM6D_REQUIRE(ws_bytes >= fm_workspace_bytes(B, np), "fine_match: ws_bytes = %zu is below sam6d_fine_match_workspace_bytes_n(B, n) = %zu",
+                ws_bytes, fm_workspace_bytes(B, np));
+  SAM6D_REQUIRE(((size_t)ws & 15) == 0, "fine_match: ws must be 16-byte aligned");
+  SAM6D_REQUIRE(((size_t)f & 15) == 0, "fine_match: f must be 16-byte aligned");
+  SAM6D_REQUIRE(((size_t)pts2 & 15) == 0, "fine_match: pts2 must be 16-byte aligned");
+  SAM6D_REQUIRE(((size_t)label2 & 15) == 0, "fine_match: label2 must be 16-byte aligned");
   SAM6D_REQUIRE(f || (fh_in && fl_in), "fine_match: no features");
   SAM6D_REQUIRE((long)cdiv(B, 8) * 8 * nt * nt < 2147483647L, "fine_match: too many tiles for one launch");
   if (B == 0) return 0;

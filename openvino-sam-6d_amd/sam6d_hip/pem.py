@@ -961,11 +961,19 @@ def compute_fine_Rt(att, pts1, pts2, model, radius, dis_thres=0.15):
     return _fine_pose_tail(pred, wgt, st["l1"], pts1, model, radius, dis_thres)
 
 
+def fine_match_min_temp():
+    """the smallest temperature the fused fine-match pipeline serves (its fixed softmax shift 1 / temp: csrc/finematch.hip FM_MIN_TEMP)"""
+    return float(_lib.load().sam6d_fine_match_min_temp())
+
+
 @on_tensor_device
 def fine_match(f, B, n, temp, pts2):
     """f (2B*n, 256) out_proj outputs [scene clouds; template clouds] -- or the pair (fh, fl) of sam6d_linear_norm_split -- -> label1,
     label2 (B,n-1) i32, pred (B,n-1,3), weight (B,n-1)
-    (compute_feature_similarity + the soft-assignment head of compute_fine_Rt, PEM/utils/model_utils.py:131-153, 308-331)."""
+    (compute_feature_similarity + the soft-assignment head of compute_fine_Rt, PEM/utils/model_utils.py:131-153, 308-331).
+    temp >= fine_match_min_temp(); smaller temperatures take feature_similarity + compute_fine_Rt."""
+    if not float(temp) >= fine_match_min_temp():
+        raise ValueError("fine_match: temp = %g is below fine_match_min_temp() = %g" % (temp, fine_match_min_temp()))
     l1 = _empty((B, n - 1), pts2, torch.int32)
     l2 = _empty((B, n - 1), pts2, torch.int32)
     pred = _empty((B, n - 1, 3), pts2)
@@ -1132,7 +1140,8 @@ def fine_point_matching(dp, df, E, fps_idx, radius, model, init_R, init_t, W, cf
     """dp (2B,N,3) stacked [scene; template], df the dense features: (2B,N,256) stacked the same way, or the pair (scene (B,N,256),
     template (B,N,256)) left where the caller holds them  (PEM/model/fine_point_matching.py:42-79, eval).
     D: the result of fine_static() when the caller has already produced it.  fused_fine=False: the (B,N+1,N+1) attention matrix is
-    materialised (launch-per-op path; aux then carries it as `atten`), otherwise aux carries the pipeline's labels / weights."""
+    materialised (launch-per-op path; aux then carries it as `atten`), otherwise aux carries the pipeline's labels / weights.  The
+    launch-per-op path, which keeps a running maximum, also serves cfg["temp"] below fine_match_min_temp()."""
     Bp, N, _ = dp.shape
     B = Bp // 2
     if D is None:
@@ -1145,7 +1154,7 @@ def fine_point_matching(dp, df, E, fps_idx, radius, model, init_R, init_t, W, cf
     lead = None
     for k, blk in enumerate(blocks):
         D, lead = sparse_to_dense_transformer(D, E, fps_idx, blk, lead=lead, write_bg=(k == len(blocks) - 1), return_sparse=True)
-    if fused_fine and N in (2048, 4096) and _fused_block():
+    if fused_fine and N in (2048, 4096) and _fused_block() and cfg["temp"] >= fine_match_min_temp():
         # similarity + soft assignment as one pipeline: the (B, 2049, 2049) matrix is written once and read twice (finematch.hip)
         if "out_img" not in W.fine:
             W.fine["out_img"] = pack_cross_query(W.fine["out_proj"])
@@ -1211,14 +1220,16 @@ def resolve_routes(W, cfg, options):
     """The pipeline shape pem_match takes for this weight set, cfg and Options (a cfg key wins over the Options field of its name):
       fused_rpe        RPE attention without the embedding tensor: asked for, a split-precision mode, and the weight set's guard passed
       fused_rpe_guard  that guard (fused_rpe_in_range at cfg's sigma_a, which sets the range of the angular indices); None in mode 0
-      fused_fine       the fine similarity + soft-assignment pipeline of finematch.hip (it runs on the fused block kernels)
+      fused_fine       the fine similarity + soft-assignment pipeline of finematch.hip (it runs on the fused block kernels, and its fixed
+                       softmax shift serves cfg["temp"] >= fine_match_min_temp())
       overlap          the pose-independent fine work on a side stream
       microbatch       slices of the batch on concurrent streams"""
     split = options.mode >= 1
     guard = bool(fused_rpe_in_range(W, cfg.get("sigma_a", 15))) if split else None
     return dict(fused_rpe=bool(cfg.get("fused_rpe", options.fused_rpe)) and split and guard,
                 fused_rpe_guard=guard,
-                fused_fine=bool(cfg.get("fused_fine", options.fused_fine)) and options.fused_block,
+                fused_fine=(bool(cfg.get("fused_fine", options.fused_fine)) and options.fused_block
+                            and cfg.get("temp", DEFAULT_CFG["temp"]) >= fine_match_min_temp()),
                 overlap=bool(cfg.get("overlap", options.overlap)),
                 microbatch=int(cfg.get("microbatch", options.microbatch)))
 
