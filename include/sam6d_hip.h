@@ -934,6 +934,54 @@ int sam6d_overlay_masks(const unsigned char* rgb, long row_stride, int H, int W,
                         const unsigned char* lut, int draw_edge, unsigned char* canvas, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Checking poses against the depth image: the CAD model rendered at each pose (csrc/verify.hip, restated in
+ * tests/verify_ref.py).  (New entries only, so SAM6D_ABI_VERSION stays.)
+ * ------------------------------------------------------------------------------------------------------------ */
+/* The window of each of N poses: what a pose's render covers, before anything is rendered.  The reference has no check of a pose
+ * against the depth image -- it multiplies the detection score by the PEM score (PEM/run_inference_custom_pytorch.py:460-482) -- so the
+ * check and its thresholds are the package's own; the geometry is the template renderer's (Render/render_custom_templates.py:55-106 as
+ * sam6d_render_views restates it: the same device functions, unchanged).  vertices (V,3) f32, faces (F,3) i32, view (N,3,4) f32
+ * row-major object -> camera, one per pose; fx fy cx cy, H, W, near as sam6d_render_views has them.
+ * box (N,4) i32 = [x0, y0, x1, y1], inclusive: over the pose's live faces (not dropped, not of zero area) whose pixel box clamped to
+ * the image is not empty, the minimum x0, y0 and the maximum x1, y1 of those boxes; [0, 0, -1, -1] when there are none.  n_dropped (N)
+ * i32 with the meaning it has in sam6d_render_views.  Integer atomic min / max / add: a function of the inputs alone.
+ * H, W 1 .. 2048, N 1 .. 1024, F 1 .. 2^24, V >= 1, near > 0; anything else, or a null pointer, returns non-zero without a launch or a
+ * write. */
+int sam6d_pose_windows(const float* vertices, int V, const int* faces, int F, const float* view, int N, float fx, float fy, float cx,
+                       float cy, int H, int W, float near, int* box, int* n_dropped, void* stream);
+/* Renders the model at each of N poses into the pose's own window, classifies every rendered pixel against the observed depth and
+ * composites all poses into one instance map.  Beside PEM/run_inference_custom_pytorch.py:460-482, which has no such check: the check
+ * and its thresholds are the package's own (the renderer: Render/render_custom_templates.py:55-106 as sam6d_render_views restates it).
+ * Mesh, view, camera and wave_area as above and as in sam6d_render_views.  box (N,4) i32 from sam6d_pose_windows; offset (N+1) i64 on
+ * the device: the exclusive prefix sums of the windows' areas (x1 - x0 + 1) * (y1 - y0 + 1), 0 for an empty window; total: the host's
+ * copy of offset[N].  depth_obs (H,W) f32 in the unit of camera z; masks (N,H,W) u8 or NULL; tau >= 0, finite.
+ * Per rendered pixel of pose n with r its rendered depth and o = depth_obs[y][x]: unknown when o > 0 is false (also a NaN); else with
+ * e = o - r behind when e > tau, occluded when e < -tau, inlier otherwise; inter when masks[n][y][x] != 0.
+ * counts (N,8) i32 = n_render, n_inlier, n_occluded, n_behind, n_unknown, n_mask (the non-zero bytes of masks[n] over the whole
+ * image), n_inter, n_dropped; columns 1 .. 4 sum to column 0, columns 5 and 6 are 0 without masks.  ids (H,W) i32 or NULL: the pose
+ * whose render is nearest at the pixel, on a tie the lower index, -1 = background; depth_out (H,W) f32 or NULL: that depth, 0 =
+ * background.  total == 0: counts all 0 (column 7 too: it is counted by the raster pass, which is not launched), ids -1, depth_out 0.
+ * The recipe is at the top of csrc/verify.hip; 64-bit atomic minima and 32-bit atomic adds only: a function of the inputs alone.  The
+ * kernels clamp every box to the image and address no word at or beyond `total`, whatever box and offset hold.
+ * Limits of sam6d_pose_windows, wave_area >= 0, total 0 .. N H W, workspace 8-byte aligned and at least
+ * sam6d_pose_verify_workspace_bytes(total, H, W) = 8 (total + H W) (0 for sizes outside the limits); anything else, a null pointer
+ * or a negative or non-finite tau returns non-zero without a launch or a write. */
+size_t sam6d_pose_verify_workspace_bytes(long total, int H, int W);
+int sam6d_pose_verify(const float* vertices, int V, const int* faces, int F, const float* view, int N, float fx, float fy, float cx,
+                      float cy, int H, int W, float near, int wave_area, const int* box, const long long* offset, long total,
+                      const float* depth_obs, const unsigned char* masks, float tau, int* counts, int* ids, float* depth_out,
+                      void* workspace, size_t workspace_bytes, void* stream);
+/* The picture of an instance map: the rendered silhouettes where PEM/utils/draw_utils.py:75-97 draws a box and points
+ * (PEM/run_inference_custom_pytorch.py:480-482), the package's own.  rgb (H,W,3) u8 with a byte row_stride >= 3 W, ids (H,W) i32 (an id
+ * outside [0, N) counts as -1), colors (N,3) u8, alpha an integer in 0 .. 256.  canvas (H, 2W, 3) u8: the left half is rgb; on the
+ * right a pixel with id >= 0 shows (rgb_c * (256 - alpha) + color_c * alpha + 128) >> 8, or color_c unblended when one of its four
+ * neighbours inside the image has another id (the silhouette and the line between two instances; the image border is no edge), and a
+ * background pixel shows rgb.  A gather with one writer per byte, no atomics, no workspace.  H, W 1 .. 2048, N 1 .. 1024; anything
+ * else or a null pointer returns non-zero without a launch or a write. */
+int sam6d_overlay_instances(const unsigned char* rgb, long row_stride, int H, int W, const int* ids, const unsigned char* colors, int N,
+                            int alpha, unsigned char* canvas, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * ISM's reference data from a template set: boxes and 224 x 224 crops of T templates, each on its own image
  * (csrc/refdata.hip).  (New entries only, so SAM6D_ABI_VERSION stays.)
  * ------------------------------------------------------------------------------------------------------------ */

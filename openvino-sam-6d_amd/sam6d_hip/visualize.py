@@ -11,6 +11,9 @@ package's own, equal in kind only: the edge of a mask (not skimage's canny), the
 cv2.circle), the palette (distinctipy draws its colours at random, so there is nothing to match) and the rule that a point at or behind
 the camera plane is skipped and counted (the reference divides by zero).
 
+A third picture is the package's own altogether: vis_pem_render paints the instance map of verify.render_compare -- the CAD model's
+rendered silhouette at every pose -- beside the input (the recipe at the top of csrc/verify.hip, restated in tests/verify_ref.py).
+
 Imports runtime, _lib, torch and numpy; PIL only where an image is returned or saved.  There is no CPU route.
 """
 import numpy as np
@@ -311,4 +314,54 @@ def vis_pem(rgb, R, t, model_points, K, save_path=None):
     if K.shape[0] == 1 and R.shape[0] != 1:  # one camera for all instances
         K = K.expand(R.shape[0], 3, 3).contiguous()
     canvas, _ = draw_detections(img, R, put(t, (-1, 3)), model_points, K, colors=(255, 0, 0))
+    return _finish(canvas, save_path)
+
+
+# ------------------------------------------------------------------------------------------------------------ rendered silhouettes
+MAX_RENDER_SIZE = 2048    # H, W of sam6d_overlay_instances
+MAX_RENDER_INSTANCES = 1024
+
+
+@on_tensor_device
+def _overlay_instances(rgb, H, W, stride, ids, colors, alpha):
+    canvas = _empty((H, 2 * W, 3), rgb, torch.uint8)
+    _lib.call("sam6d_overlay_instances", rgb.data_ptr(), stride, H, W, _p(ids), colors.data_ptr(), int(colors.shape[0]), alpha,
+              canvas.data_ptr(), _s())
+    return canvas
+
+
+def overlay_instances(rgb, ids, colors, alpha=128):
+    """sam6d_overlay_instances: rgb (H,W,3) u8 and ids (H,W) i32 HIP tensors (verify.render_compare's instance map; an id outside
+    [0, N) is background), colors (N,3), alpha an integer in 0 .. 256 -> canvas (H, 2W, 3) u8 on the device: rgb on the left; on the
+    right every instance blended in its colour, its silhouette and the line to another instance in the colour unblended.  The recipe
+    is at the top of csrc/verify.hip."""
+    name = "overlay_instances"
+    H, W, stride = _image(rgb, name)
+    if not (H <= MAX_RENDER_SIZE and W <= MAX_RENDER_SIZE):
+        raise ValueError("%s: H x W = %d x %d is not in 1 .. %d" % (name, H, W, MAX_RENDER_SIZE))
+    _device_tensor(ids, name, "ids", torch.int32, (H, W))
+    c = np.asarray(colors)
+    if c.ndim != 2 or not 1 <= c.shape[0] <= MAX_RENDER_INSTANCES:
+        raise ValueError("%s: colors must be (N,3) with N in 1 .. %d, got %s" % (name, MAX_RENDER_INSTANCES, c.shape))
+    cols = _colors(c, c.shape[0], name)
+    if int(alpha) != alpha or not 0 <= int(alpha) <= 256:
+        raise ValueError("%s: alpha = %r is not an integer in 0 .. 256" % (name, alpha))
+    _on_device(name, rgb=rgb, ids=ids)
+    return _overlay_instances(rgb, H, W, stride, ids, torch.from_numpy(cols).to(rgb.device), int(alpha))
+
+
+def vis_pem_render(rgb, ids, colors=None, alpha=0.5, save_path=None):
+    """The picture vis_pem leaves out: the CAD model's rendered silhouette at every pose, beside the input.  rgb a PIL image, array or
+    HIP tensor; ids (H,W) i32 HIP tensor, the instance map of verify.render_compare (-1 = background); colors (N,3) or None =
+    palette(n) with n = the largest id + 1 (one read-back); alpha: the weight of the colour, rounded to 1 / 256.  -> the (2W, H) PIL
+    image, also written to save_path as PNG when given.  The package's own picture: the reference draws a box and points
+    (PEM/utils/draw_utils.py:75-97)."""
+    if not torch.is_tensor(ids):
+        raise ValueError("vis_pem_render: ids must be an (H,W) int32 torch tensor on a HIP device, got %s" % type(ids).__name__)
+    img = _to_device_image(rgb, ids.device if ids.is_cuda else None)
+    if colors is None:
+        colors = palette(max(int(ids.max()) + 1, 1) if ids.numel() else 1)
+    if not 0.0 <= float(alpha) <= 1.0:
+        raise ValueError("vis_pem_render: alpha = %r is not in 0 .. 1" % (alpha,))
+    canvas = overlay_instances(img, ids, colors, alpha=int(np.floor(float(alpha) * 256.0 + 0.5)))
     return _finish(canvas, save_path)
