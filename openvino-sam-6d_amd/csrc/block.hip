@@ -1439,7 +1439,9 @@ extern "C" int sam6d_linattn_layer(const float* D, const void* wimage, const flo
                                    const float* ksum, float* Dout, int B, int I, int row0, float eps, void* stream) {
   SAM6D_REQUIRE(D && wimage && consts && kvimage && kvinv && ksum && Dout && B >= 0 && I > 0 && row0 >= 0 && row0 < I,
                 "linattn_layer: bad arguments");
-  SAM6D_REQUIRE(((((size_t)D) | ((size_t)Dout) | ((size_t)wimage) | ((size_t)kvimage)) & 15) == 0, "linattn_layer: pointers must be 16-byte aligned");
+  // (kvinv: the kernel reads a cloud's four head scales as one 16-byte load)
+  SAM6D_REQUIRE(((((size_t)D) | ((size_t)Dout) | ((size_t)wimage) | ((size_t)kvimage) | ((size_t)kvinv)) & 15) == 0,
+                "linattn_layer: pointers must be 16-byte aligned");
   if (B == 0) return 0;
   if (int rc = tb_reserve_lds("linattn_layer")) return rc;
   const int tiles = (I - row0 + 16 * TB_WAVES - 1) / (16 * TB_WAVES);  // 64-token workgroups
