@@ -983,6 +983,37 @@ int sam6d_overlay_instances(const unsigned char* rgb, long row_stride, int H, in
                             int alpha, unsigned char* canvas, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Refining poses against the depth image: projective point-to-plane steps on the renders of csrc/verify.hip
+ * (csrc/refine.hip, restated in tests/refine_ref.py).  (New entries only, so SAM6D_ABI_VERSION stays.)
+ * ------------------------------------------------------------------------------------------------------------ */
+/* One Gauss-Newton iteration of a projective point-to-plane refinement for N poses at once.  The reference has no refinement: its
+ * poses leave PEM's weighted SVD as they are (PEM/run_inference_custom_pytorch.py:460-471); the method, its gates and its status codes
+ * are the package's own.  Mesh, camera, near, wave_area, box, offset, total, depth_obs and masks as in sam6d_pose_verify; box and
+ * offset are the caller's and stay the same for every iteration (sam6d_hip.refine: sam6d_pose_windows of the initial poses, grown by a
+ * margin).  state (N,12) f64, in and out: R row-major, then t.  scale: CAD units into the unit of t, non-zero and finite.
+ * The step (the recipe is at the top of csrc/refine.hip): view = [fl32(R * scale) | fl32(t)] is rastered into the windows with the
+ * raster pass of sam6d_pose_verify (one copy of the kernel: the same keys).  A rendered pixel with depth r on face f and observed
+ * depth o is a pair when o > 0, |o - r| <= gate and, with masks, masks[n][y][x] != 0; its residual e = nrm . (q - p) and its row
+ * J = [(q - t) x nrm, nrm] (q, p the observed and rendered points on the pixel's ray, nrm the face's unit normal towards the camera)
+ * are fp32, lengths times inv_unit (1 / the model's radius in the unit of t), and a pixel with |q - t| inv_unit > 16 or |e| > 16 is no
+ * pair.  The 28 products J_i J_j, J_i e, e e are formed exactly in float64, times 2^30, rounded to the nearest even integer and added
+ * with 64-bit integer atomics: acc (N,32) i64 = the upper triangle of [J e]^T [J e] row-major (words 0 .. 27; word 27 is sum e e),
+ * the pair count (28), zeros (29 .. 31) -- a function of the inputs alone.  Then per pose: A_ii += damping * A_ii, Cholesky,
+ * xi = (omega, v); R <- C(omega) R with the Cayley map C, t <- t + v / inv_unit, float64 with + - * / sqrt only.
+ * stats (N,4) i32 = pairs, status, the low and the high 32 bits of acc[n][27].  status: 0 stepped, 1 fewer than min_pairs pairs,
+ * 2 a pivot not positive, 3 |xi| > max_step (also a NaN), 4 the window is empty; with any but 0 state[n] keeps its bits.
+ * Limits of sam6d_pose_verify; gate >= 0, inv_unit > 0 and damping >= 0 finite, min_pairs >= 1, max_step > 0 (infinity: no bound);
+ * workspace, state and acc 8-byte aligned, the workspace at least sam6d_pose_refine_workspace_bytes(total, N) = 8 total + 80 N
+ * (0 for N outside 1 .. 1024 or total outside 0 .. 2^22 N); anything else or a null pointer returns non-zero without a launch or a
+ * write.  The kernels clamp every box to the image and address no word at or beyond `total`, whatever box and offset hold. */
+size_t sam6d_pose_refine_workspace_bytes(long total, int N);
+int sam6d_pose_refine_step(const float* vertices, int V, const int* faces, int F, float scale, int N, float fx, float fy, float cx,
+                           float cy, int H, int W, float near, int wave_area, const int* box, const long long* offset, long total,
+                           const float* depth_obs, const unsigned char* masks, float gate, float inv_unit, double damping,
+                           int min_pairs, double max_step, double* state, long long* acc, int* stats, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * ISM's reference data from a template set: boxes and 224 x 224 crops of T templates, each on its own image
  * (csrc/refdata.hip).  (New entries only, so SAM6D_ABI_VERSION stays.)
  * ------------------------------------------------------------------------------------------------------------ */

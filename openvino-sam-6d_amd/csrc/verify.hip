@@ -59,11 +59,8 @@
 // image, a face's box is clamped to the window, a word at or beyond `total` (or below 0) is never addressed, and a window word whose
 // index within its pose is at or beyond bw * bh is skipped.  Inconsistent boxes and offsets give meaningless counts, never an access
 // outside the buffers.
-#include "raster.h"
+#include "verify_raster.h"  // the window and the raster pass of b, shared with refine.hip
 #include "../../include/sam6d_hip.h"
-
-#define VF_MAX_N 1024
-#define VF_EMPTY (~0ull)
 
 __device__ __forceinline__ int vf_wave_min(int v) {
 #pragma unroll
@@ -80,7 +77,6 @@ __device__ __forceinline__ int vf_wave_sum(int v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
-__device__ __forceinline__ void vf_add(int* p, int v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // ---------------------------------------------------------------------------------------------------------- a. windows
 #define VF_WG 1024  // sixteen waves: what meets at a pose's few words is one offer per workgroup, not one per wave
@@ -142,15 +138,7 @@ __global__ __launch_bounds__(256) void windows_finish_kernel(int* __restrict__ b
   }
 }
 
-// the limits every entry of this file shares, by name and before a launch or a write
-static int vf_check(const char* who, int V, int F, int N, int H, int W, float near) {
-  SAM6D_REQUIRE(H >= 1 && H <= RS_MAX_HW && W >= 1 && W <= RS_MAX_HW, "%s: H x W = %d x %d is not in 1 .. %d", who, H, W, RS_MAX_HW);
-  SAM6D_REQUIRE(N >= 1 && N <= VF_MAX_N, "%s: N = %d is not in 1 .. %d", who, N, VF_MAX_N);
-  SAM6D_REQUIRE(F >= 1 && F <= RS_MAX_F, "%s: F = %d is not in 1 .. %d", who, F, RS_MAX_F);
-  SAM6D_REQUIRE(V >= 1, "%s: V = %d is not positive", who, V);
-  SAM6D_REQUIRE(near > 0.f, "%s: near = %g is not positive", who, (double)near);
-  return 0;
-}
+// vf_check, the limits every entry of this file shares: verify_raster.h
 
 extern "C" int sam6d_pose_windows(const float* vertices, int V, const int* faces, int F, const float* view, int N, float fx, float fy,
                                   float cx, float cy, int H, int W, float near, int* box, int* n_dropped, void* stream) {
@@ -172,82 +160,7 @@ extern "C" int sam6d_pose_windows(const float* vertices, int V, const int* faces
 }
 
 // ---------------------------------------------------------------------------------------------------------- b. verify
-struct VfWin {
-  int x0, y0, bw, bh;  // the box clamped to the image; 0 x 0 when empty
-  long long off;       // its first word
-};
-
-__device__ __forceinline__ VfWin vf_window(const int* __restrict__ box, const long long* __restrict__ offset, int n, int H, int W) {
-  const int* b = box + (size_t)n * 4;
-  VfWin w;
-  w.x0 = max(b[0], 0);
-  w.y0 = max(b[1], 0);
-  const int x1 = min(b[2], W - 1), y1 = min(b[3], H - 1);
-  w.bw = x1 >= w.x0 ? x1 - w.x0 + 1 : 0;  // x0 >= 0 and x1 <= W - 1: no overflow
-  w.bh = y1 >= w.y0 ? y1 - w.y0 + 1 : 0;
-  if (w.bw == 0 || w.bh == 0) w.bw = w.bh = 0;
-  w.off = offset[n];
-  return w;
-}
-
-// the face's pixel box clamped to the window
-__device__ __forceinline__ void vf_clamp(RsFace& f, const VfWin& w) {
-  f.x0 = max(f.x0, w.x0);
-  f.y0 = max(f.y0, w.y0);
-  f.x1 = min(f.x1, w.x0 + w.bw - 1);
-  f.y1 = min(f.y1, w.y0 + w.bh - 1);
-}
-
-__device__ __forceinline__ void vf_offer(const RsFace& f, int face, int x, int y, const VfWin& w, unsigned long long* __restrict__ zbuf,
-                                         long long total) {
-  long long w0, w1, w2;
-  if (!rs_cover(f, x, y, w0, w1, w2)) return;
-  float l0, l1, l2;
-  const float d = rs_weights(f, w0, w1, w2, l0, l1, l2);
-  const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)face;
-  const long long word = w.off + (long long)(y - w.y0) * w.bw + (x - w.x0);
-  if ((unsigned long long)word >= (unsigned long long)total) return;  // also a negative offset
-  __hip_atomic_fetch_min(zbuf + word, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// grid (ceil(F / 64), N), one wave each: raster_faces_kernel into the pose's window
-__global__ __launch_bounds__(64) void verify_faces_kernel(const float* __restrict__ vert, int V, const int* __restrict__ faces, int F,
-                                                          const float* __restrict__ view, RsCam cam, int wave_area,
-                                                          const int* __restrict__ box, const long long* __restrict__ offset,
-                                                          long long total, unsigned long long* __restrict__ zbuf,
-                                                          int* __restrict__ counts) {
-  const int n = blockIdx.y, lane = threadIdx.x;
-  const int face = blockIdx.x * 64 + lane;
-  const float* M = view + (size_t)n * 12;
-  const VfWin w = vf_window(box, offset, n, cam.H, cam.W);
-  RsFace f;
-  f.live = false;
-  f.dropped = false;
-  f.x0 = f.y0 = 0;
-  f.x1 = f.y1 = -1;
-  if (face < F) rs_setup(f, vert, V, faces, face, M, cam);
-  const int dropped = __popcll(__ballot(f.dropped));
-  if (lane == 0 && dropped) vf_add(counts + (size_t)n * 8 + 7, dropped);
-  if (w.bw == 0) return;  // (uniform over the wave)
-  vf_clamp(f, w);
-  const bool boxed = f.live && f.x0 <= f.x1 && f.y0 <= f.y1;
-  const int bw = f.x1 - f.x0 + 1, bh = f.y1 - f.y0 + 1;  // at most 2048 each: the product fits an int
-  const bool big = boxed && bw * bh >= wave_area;
-  if (boxed && !big)
-    for (int y = f.y0; y <= f.y1; ++y)
-      for (int x = f.x0; x <= f.x1; ++x) vf_offer(f, face, x, y, w, zbuf, total);
-  unsigned long long todo = __ballot(big);
-  while (todo) {
-    const int src = __ffsll((long long)todo) - 1;
-    todo &= todo - 1;
-    const int gface = blockIdx.x * 64 + src;
-    RsFace g;
-    rs_setup(g, vert, V, faces, gface, M, cam);  // the same code on the same inputs as the owner lane ran: the same face
-    vf_clamp(g, w);
-    const int gw = g.x1 - g.x0 + 1, cnt = gw * (g.y1 - g.y0 + 1);
-    for (int i = lane; i < cnt; i += 64) vf_offer(g, gface, g.x0 + i % gw, g.y0 + i / gw, w, zbuf, total);
-  }
-}
+// the window, the clamp, the offer and verify_faces_kernel (the raster pass): verify_raster.h
 
 // one thread per window word of all poses, sixteen waves in a workgroup.  Most workgroups lie inside one window: the counts of the
 // pose of the workgroup's first word are gathered in LDS and leave as one atomic per counter and workgroup; a wave's counts for

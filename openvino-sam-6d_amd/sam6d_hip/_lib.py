@@ -173,6 +173,9 @@ SIGNATURES = {
     "sam6d_pose_verify": [c_p, c_i, c_p, c_i, c_p, c_i] + [c_f] * 4 + [c_i, c_i, c_f, c_i, c_p, c_p, c_l, c_p, c_p, c_f, c_p, c_p, c_p, c_p,
                           ctypes.c_size_t, c_p],
     "sam6d_overlay_instances": [c_p, c_l, c_i, c_i, c_p, c_p, c_i, c_i, c_p, c_p],
+    "sam6d_pose_refine_workspace_bytes": [c_l, c_i],
+    "sam6d_pose_refine_step": [c_p, c_i, c_p, c_i, c_f, c_i] + [c_f] * 4 + [c_i, c_i, c_f, c_i, c_p, c_p, c_l, c_p, c_p, c_f, c_f,
+                               ctypes.c_double, c_i, ctypes.c_double, c_p, c_p, c_p, c_p, ctypes.c_size_t, c_p],
     "sam6d_template_boxes": [c_p, c_i, c_i, c_i, c_l, c_l, c_p, c_p],
     "sam6d_template_crops": [c_p, c_l, c_l, c_p, c_l, c_l, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p],
 }

@@ -135,29 +135,9 @@ def _verify(vertices, faces, view, intr, H, W, near, wave_area, box, depth, mask
     return counts, ids, out
 
 
-def render_compare(mesh, R, t, K, depth, masks=None, tol=TOL, scale=1.0, near=NEAR, wave_area=0, want_map=True):
-    """Renders the model at each of N poses and compares every rendered pixel with the observed depth.
-
-    mesh: what onboard.load_mesh returns (a dict with vertices and faces, numpy or tensors; uploaded when it is not on the device), or
-    a (vertices (V,3) f32, faces (F,3) i32) pair of HIP tensors.  R (N,3,3), t (N,3) f32 HIP tensors: the poses (pose_views).  K: one
-    3 x 3 matrix or (fx, fy, cx, cy).  depth (H,W) f32 HIP tensor in the unit of t (metres, as get_test_data forms it: depth *
-    depth_scale / 1000).  masks (N,H,W) u8 or bool HIP tensor, mask n beside pose n, or None.  tol: the depth tolerance in the unit of
-    t.  scale: CAD units into the unit of t (0.001 for a millimetre model).  near: faces with a vertex nearer than this are dropped
-    whole and counted (there is no clipper).  wave_area: as onboard.render_views.  want_map: also composite all poses into ids / depth.
-
-    -> PoseCheck.  Per pose, over the pixels its render covers (n_render):
-      inlier_ratio    the observed depth is within tol of the rendered one: the surface is where the pose says
-      behind_ratio    the observed depth is farther by more than tol: the camera sees THROUGH where the model should be -- evidence
-                      against the pose
-      occluded_ratio  the observed depth is nearer by more than tol: something stands in front -- an occluder, or a pose too deep
-      unknown_ratio   the sensor has no depth there (0, negative or NaN)
-      mask_iou        n_inter / (n_render + n_mask - n_inter) of the render against masks[n]; None without masks
-    each float32 true division, 0 where the denominator is 0; counts holds the integers, boxes the windows, and ids / depth the
-    instance map (the nearest pose per pixel, on a tie the lower index; -1 / 0 = background).  Nothing is thresholded or combined
-    into one score here: which ratios matter, and how much, is the caller's decision.
-
-    A CPU tensor raises RuntimeError; a wrong shape or dtype ValueError naming the argument."""
-    name = "render_compare"
+def _pose_args(name, mesh, R, t, K, depth, masks, near):
+    """The arguments render_compare and refine.refine_poses share, checked and made contiguous
+    -> vertices, faces, R, t, depth, masks, intr, H, W.  A wrong shape or dtype raises ValueError naming the argument."""
     if isinstance(mesh, dict):
         from .onboard import _mesh_tensors
         v = mesh["vertices"]
@@ -181,11 +161,6 @@ def render_compare(mesh, R, t, K, depth, masks=None, tol=TOL, scale=1.0, near=NE
             raise ValueError("%s: masks must be an (N,H,W) uint8 or bool tensor" % name)
         masks = _tensor(masks, name, "masks", masks.dtype, (N, H, W))
     intr = _intrinsics(K)
-    tol = float(tol)
-    if not (tol >= 0.0 and math.isfinite(tol)):
-        raise ValueError("%s: tol = %r is not a finite number >= 0" % (name, tol))
-    if int(wave_area) < 0:
-        raise ValueError("%s: wave_area = %d is negative" % (name, int(wave_area)))
     if not float(near) > 0.0:
         raise ValueError("%s: near = %r is not positive" % (name, near))
     for what, x in (("faces", faces), ("R", R), ("t", t), ("depth", depth), ("masks", masks)):
@@ -194,6 +169,39 @@ def render_compare(mesh, R, t, K, depth, masks=None, tol=TOL, scale=1.0, near=NE
                 raise RuntimeError("%s: needs HIP device tensors (%s is on %s, vertices on %s; this build has no CPU path)"
                                    % (name, what, x.device, vertices.device))
             raise ValueError("%s: %s is on %s and vertices on %s" % (name, what, x.device, vertices.device))
+    return vertices, faces, R, t, depth, masks, intr, H, W
+
+
+def render_compare(mesh, R, t, K, depth, masks=None, tol=TOL, scale=1.0, near=NEAR, wave_area=0, want_map=True):
+    """Renders the model at each of N poses and compares every rendered pixel with the observed depth.
+
+    mesh: what onboard.load_mesh returns (a dict with vertices and faces, numpy or tensors; uploaded when it is not on the device), or
+    a (vertices (V,3) f32, faces (F,3) i32) pair of HIP tensors.  R (N,3,3), t (N,3) f32 HIP tensors: the poses (pose_views).  K: one
+    3 x 3 matrix or (fx, fy, cx, cy).  depth (H,W) f32 HIP tensor in the unit of t (metres, as get_test_data forms it: depth *
+    depth_scale / 1000).  masks (N,H,W) u8 or bool HIP tensor, mask n beside pose n, or None.  tol: the depth tolerance in the unit of
+    t.  scale: CAD units into the unit of t (0.001 for a millimetre model).  near: faces with a vertex nearer than this are dropped
+    whole and counted (there is no clipper).  wave_area: as onboard.render_views.  want_map: also composite all poses into ids / depth.
+
+    -> PoseCheck.  Per pose, over the pixels its render covers (n_render):
+      inlier_ratio    the observed depth is within tol of the rendered one: the surface is where the pose says
+      behind_ratio    the observed depth is farther by more than tol: the camera sees THROUGH where the model should be -- evidence
+                      against the pose
+      occluded_ratio  the observed depth is nearer by more than tol: something stands in front -- an occluder, or a pose too deep
+      unknown_ratio   the sensor has no depth there (0, negative or NaN)
+      mask_iou        n_inter / (n_render + n_mask - n_inter) of the render against masks[n]; None without masks
+    each float32 true division, 0 where the denominator is 0; counts holds the integers, boxes the windows, and ids / depth the
+    instance map (the nearest pose per pixel, on a tie the lower index; -1 / 0 = background).  Nothing is thresholded or combined
+    into one score here: which ratios matter, and how much, is the caller's decision.
+
+    A CPU tensor raises RuntimeError; a wrong shape or dtype ValueError naming the argument."""
+    name = "render_compare"
+    vertices, faces, R, t, depth, masks, intr, H, W = _pose_args(name, mesh, R, t, K, depth, masks, near)
+    N = int(R.shape[0])
+    tol = float(tol)
+    if not (tol >= 0.0 and math.isfinite(tol)):
+        raise ValueError("%s: tol = %r is not a finite number >= 0" % (name, tol))
+    if int(wave_area) < 0:
+        raise ValueError("%s: wave_area = %d is negative" % (name, int(wave_area)))
     view = pose_views(R, t, scale)
     box, dropped = _windows(vertices, faces, view, intr, H, W, float(near))
     counts, ids, out = _verify(vertices, faces, view, intr, H, W, float(near), int(wave_area), box, depth, masks, tol, bool(want_map))
