@@ -621,12 +621,6 @@ extern "C" int sam6d_ball_query2(const float* new_xyz, const float* xyz, int B, 
 #define BQG_QPW 4            // queries per wave
 __host__ __device__ inline size_t bqg_cloud_bytes(int N) { return (size_t)N * 16 + (size_t)(BQG_CELLS + 1) * 4 + 12 + 16; }
 
-__device__ __forceinline__ int wave_min_i32(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 __device__ __forceinline__ int bqg_cell1(float v, float o, float inv_c) {
   const float u = fminf(fmaxf((v - o) * inv_c, 0.0f), (float)(BQG_G - 1));  // (NaN -> 0)
   return (int)u;

@@ -42,19 +42,23 @@
 // taken one after the other by the whole wave, 64 pixels of the box at a time (the wave path: a low-poly mesh is a few triangles of
 // tens of thousands of pixels).  Both paths call rs_offer() on a face set up by rs_setup(): the arithmetic is one piece of code.
 //
-// FILES.  The face setup, coverage and weights are device functions in raster.h, shared with texture.hip, whose resolve kernel takes
-// the albedo from a texture image instead; visibility (rs_visibility below) is this file's for both entries.
+// FILES.  Every step of the RECIPE is a device function in raster.h: setup, coverage and weights; the pass of the WORK paragraph
+// (rs_faces_pass, which verify_raster.h runs into a pose's window as well); the resolve of a pixel up to the lighting term and the tone
+// step (rs_resolve_pixel, rs_tone), shared with texture.hip, whose resolve kernel takes the albedo from a texture image instead.  This
+// file keeps the image sink, the two kernels' own lines (the drop count; the vertex-colour / grey albedo) and the host side:
+// rs_limits, rs_check and visibility (rs_visibility) for both render entries.
 #include "raster.h"
 #include "../../include/sam6d_hip.h"
 
-__device__ __forceinline__ void rs_offer(const RsFace& f, int face, int x, int y, unsigned long long* __restrict__ zrow0, int W) {
-  long long w0, w1, w2;
-  if (!rs_cover(f, x, y, w0, w1, w2)) return;
-  float l0, l1, l2;
-  const float d = rs_weights(f, w0, w1, w2, l0, l1, l2);
-  const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)face;
-  __hip_atomic_fetch_min(zrow0 + (size_t)y * W + x, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+// the z-buffer of one view: word y * W + x, every pixel of the face's box (rs_setup clamped it to the image)
+struct RsImageSink {
+  unsigned long long* z;
+  int W;
+  __device__ __forceinline__ void clamp(RsFace&) const {}
+  __device__ __forceinline__ void put(int x, int y, unsigned long long key) const {
+    __hip_atomic_fetch_min(z + (size_t)y * W + x, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+};
 
 // grid (ceil(F / 64), T), one wave each
 __global__ __launch_bounds__(64) void raster_faces_kernel(const float* __restrict__ vert, int V, const int* __restrict__ faces, int F,
@@ -63,7 +67,6 @@ __global__ __launch_bounds__(64) void raster_faces_kernel(const float* __restric
   const int t = blockIdx.y, lane = threadIdx.x;
   const int face = blockIdx.x * 64 + lane;
   const float* M = view + (size_t)t * 12;
-  unsigned long long* z = zbuf + (size_t)t * cam.H * cam.W;
   RsFace f;
   f.live = false;
   f.dropped = false;
@@ -71,22 +74,7 @@ __global__ __launch_bounds__(64) void raster_faces_kernel(const float* __restric
   f.x1 = f.y1 = -1;
   if (face < F) rs_setup(f, vert, V, faces, face, M, cam);
   if (f.dropped) atomicAdd(n_dropped + t, 1);
-  const bool boxed = f.live && f.x0 <= f.x1 && f.y0 <= f.y1;
-  const int bw = f.x1 - f.x0 + 1, bh = f.y1 - f.y0 + 1;  // at most 2048 each: the product fits an int
-  const bool big = boxed && bw * bh >= wave_area;
-  if (boxed && !big)
-    for (int y = f.y0; y <= f.y1; ++y)
-      for (int x = f.x0; x <= f.x1; ++x) rs_offer(f, face, x, y, z, cam.W);
-  unsigned long long todo = __ballot(big);
-  while (todo) {
-    const int src = __ffsll((long long)todo) - 1;
-    todo &= todo - 1;
-    const int gface = blockIdx.x * 64 + src;
-    RsFace g;
-    rs_setup(g, vert, V, faces, gface, M, cam);  // the same code on the same inputs as the owner lane ran: the same face
-    const int gw = g.x1 - g.x0 + 1, n = gw * (g.y1 - g.y0 + 1);
-    for (int i = lane; i < n; i += 64) rs_offer(g, gface, g.x0 + i % gw, g.y0 + i / gw, z, cam.W);
-  }
+  rs_faces_pass(f, face, vert, V, faces, M, cam, wave_area, RsImageSink{zbuf + (size_t)t * cam.H * cam.W, cam.W});
 }
 
 struct RsShade {
@@ -106,85 +94,17 @@ __global__ __launch_bounds__(256) void raster_resolve_kernel(const float* __rest
                                                              unsigned char* __restrict__ rgb) {
   const size_t hw = (size_t)cam.H * cam.W, i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= hw * (size_t)T) return;
-  const int t = (int)(i / hw), p = (int)(i % hw), y = p / cam.W, x = p % cam.W;
-  const unsigned long long key = zbuf[i];
-  if (key == ~0ull) {
-    mask[i] = 0;
-    face_out[i] = -1;
-    depth[i] = 0.f;
-    xyz[i * 3] = xyz[i * 3 + 1] = xyz[i * 3 + 2] = 0.f;
-    rgb[i * 3] = rgb[i * 3 + 1] = rgb[i * 3 + 2] = 0;
-    return;
-  }
-  const int face = (int)(unsigned)(key & 0xffffffffull);
-  const float* M = view + (size_t)t * 12;
-  RsFace f;
-  rs_setup(f, vert, V, faces, face, M, cam);
-  long long w0, w1, w2;
-  rs_cover(f, x, y, w0, w1, w2);
-  float l0, l1, l2;
-  const float d = rs_weights(f, w0, w1, w2, l0, l1, l2);
-  // the weights in the face's stored order (a winding swap exchanged vertices 1 and 2): every attribute is mixed in that order
-  const float m1 = f.swapped ? l2 : l1, m2 = f.swapped ? l1 : l2;
-  const int* fv = faces + (size_t)face * 3;
-  const float* a = vert + (size_t)fv[0] * 3;
-  const float* b = vert + (size_t)fv[1] * 3;
-  const float* c = vert + (size_t)fv[2] * 3;
-  mask[i] = 255;
-  face_out[i] = face;
-  depth[i] = d;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) xyz[i * 3 + k] = rs_mix(l0, m1, m2, a[k], b[k], c[k]);
-  // ---- shading (the package's own)
-  float P[3][3];  // camera-space vertices, stored order
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float* v = vert + (size_t)fv[k] * 3;
-    P[k][0] = rs_row(M, v[0], v[1], v[2]);
-    P[k][1] = rs_row(M + 4, v[0], v[1], v[2]);
-    P[k][2] = rs_row(M + 8, v[0], v[1], v[2]);
-  }
-  float Pc[3], n[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) Pc[k] = rs_mix(l0, m1, m2, P[0][k], P[1][k], P[2][k]);
-  if (sh.normals) {
-    float no[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) no[k] = rs_mix(l0, m1, m2, sh.normals[(size_t)fv[0] * 3 + k], sh.normals[(size_t)fv[1] * 3 + k], sh.normals[(size_t)fv[2] * 3 + k]);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) n[k] = (M[4 * k] * no[0] + M[4 * k + 1] * no[1]) + M[4 * k + 2] * no[2];
-  } else {
-    const float e1x = P[1][0] - P[0][0], e1y = P[1][1] - P[0][1], e1z = P[1][2] - P[0][2];
-    const float e2x = P[2][0] - P[0][0], e2y = P[2][1] - P[0][1], e2z = P[2][2] - P[0][2];
-    n[0] = e1y * e2z - e1z * e2y;
-    n[1] = e1z * e2x - e1x * e2z;
-    n[2] = e1x * e2y - e1y * e2x;
-  }
-  const float facing = (n[0] * Pc[0] + n[1] * Pc[1]) + n[2] * Pc[2];
-  if (facing > 0.f) {
-    n[0] = -n[0];
-    n[1] = -n[1];
-    n[2] = -n[2];
-  }
-  const float* lp = sh.light + (size_t)t * 3;
-  const float Lx = lp[0] - Pc[0], Ly = lp[1] - Pc[1], Lz = lp[2] - Pc[2];
-  const float d2 = (Lx * Lx + Ly * Ly) + Lz * Lz;
-  const float nn = (n[0] * n[0] + n[1] * n[1]) + n[2] * n[2];
-  const float ndl = (n[0] * Lx + n[1] * Ly) + n[2] * Lz;
-  float cs = ndl / (sqrtf(nn) * sqrtf(d2));
-  cs = cs > 0.f ? cs : 0.f;
-  const float v = RS_GAIN * cs / d2;
+  RsHit h;
+  if (!rs_resolve_pixel(i, vert, V, faces, view, cam, sh.normals, sh.light, zbuf, RsOut{mask, face_out, depth, xyz, rgb}, h)) return;
+  const int* fv = faces + (size_t)h.face * 3;
   const bool grey = sh.colorize || !sh.colors;
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     float alb = sh.base_color;
     if (!grey)
-      alb = rs_mix(l0, m1, m2, (float)sh.colors[(size_t)fv[0] * 3 + k] / 255.0f, (float)sh.colors[(size_t)fv[1] * 3 + k] / 255.0f,
+      alb = rs_mix(h.l0, h.m1, h.m2, (float)sh.colors[(size_t)fv[0] * 3 + k] / 255.0f, (float)sh.colors[(size_t)fv[1] * 3 + k] / 255.0f,
                    (float)sh.colors[(size_t)fv[2] * 3 + k] / 255.0f);
-    float lin = alb * v;
-    lin = lin > 0.f ? lin : 0.f;
-    lin = lin < 1.f ? lin : 1.f;
-    rgb[i * 3 + k] = sh.lut[(int)(lin * 4095.0f + 0.5f)];
+    rgb[i * 3 + k] = rs_tone(alb * h.v, sh.lut);
   }
 }
 
@@ -193,13 +113,19 @@ extern "C" size_t sam6d_render_views_workspace_bytes(int T, int H, int W) {
   return (size_t)T * H * W * sizeof(unsigned long long);
 }
 
-int rs_check(const char* who, int V, int F, int T, int H, int W, float near, int wave_area, bool pointers, const void* workspace,
-             size_t workspace_bytes) {
+int rs_limits(const char* who, int V, int F, const char* count_name, int count, int count_max, int H, int W, float near) {
   SAM6D_REQUIRE(H >= 1 && H <= RS_MAX_HW && W >= 1 && W <= RS_MAX_HW, "%s: H x W = %d x %d is not in 1 .. %d", who, H, W, RS_MAX_HW);
-  SAM6D_REQUIRE(T >= 1 && T <= RS_MAX_T, "%s: T = %d is not in 1 .. %d", who, T, RS_MAX_T);
+  SAM6D_REQUIRE(count >= 1 && count <= count_max, "%s: %s = %d is not in 1 .. %d", who, count_name, count, count_max);
   SAM6D_REQUIRE(F >= 1 && F <= RS_MAX_F, "%s: F = %d is not in 1 .. %d", who, F, RS_MAX_F);
   SAM6D_REQUIRE(V >= 1, "%s: V = %d is not positive", who, V);
   SAM6D_REQUIRE(near > 0.f, "%s: near = %g is not positive", who, (double)near);
+  return 0;
+}
+
+int rs_check(const char* who, int V, int F, int T, int H, int W, float near, int wave_area, bool pointers, const void* workspace,
+             size_t workspace_bytes) {
+  const int bad = rs_limits(who, V, F, "T", T, RS_MAX_T, H, W, near);
+  if (bad) return bad;
   SAM6D_REQUIRE(wave_area >= 0, "%s: wave_area = %d is negative", who, wave_area);
   SAM6D_REQUIRE(pointers && workspace, "%s: null pointer", who);
   const size_t need = sam6d_render_views_workspace_bytes(T, H, W);

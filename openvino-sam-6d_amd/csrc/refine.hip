@@ -1,5 +1,5 @@
 // Refining poses against the depth image the scene was measured with: projective point-to-plane Gauss-Newton steps, batched over N
-// poses.  Each pose is rendered into a window of its own (verify.hip's raster pass: verify_raster.h, unchanged), every rendered pixel
+// poses.  Each pose is rendered into a window of its own (verify.hip's raster pass: verify_raster.h), every rendered pixel
 // with an observed depth near the rendered one is a pair, the pairs' normal equations are summed as integers, and one thread per pose
 // solves them and moves the pose.  The reference has no refinement: its poses leave the weighted SVD of 2048 sampled points as they are
 // (PEM/run_inference_custom_pytorch.py:460-471).  The method, its gates and its status codes are the package's own, as the check of
@@ -18,8 +18,9 @@
 //             when o > 0, |o - r| <= gate and, with masks, masks[n][y][x] != 0, and when none of the tests below drops it.
 //     ray     rx = (((float)x + 0.5) - cx) / fx, ry = (((float)y + 0.5) - cy) / fy, 1: raster.hip's pixel centre.
 //     points  q = (rx o, ry o, o) observed, p = (rx r, ry r, r) rendered.
-//     normal  P0 P1 P2 = the face's stored vertices through view[n] (rs_row); a = P1 - P0, b = P2 - P0; m = a x b with
-//             m0 = a1 b2 - a2 b1, m1 = a2 b0 - a0 b2, m2 = a0 b1 - a1 b0; l = sqrt((m0 m0 + m1 m1) + m2 m2), dropped unless l > 0;
+//     normal  P0 P1 P2 = the face's stored vertices through view[n] (rs_to_camera); a = P1 - P0, b = P2 - P0; m = a x b with
+//             m0 = a1 b2 - a2 b1, m1 = a2 b0 - a0 b2, m2 = a0 b1 - a1 b0 (rs_face_normal: the resolve kernels' flat normal);
+//             l = sqrt((m0 m0 + m1 m1) + m2 m2), dropped unless l > 0;
 //             nrm = m / l, negated when (nrm0 p0 + nrm1 p1) + nrm2 p2 > 0: towards the camera.
 //     e       ((nrm0 d0 + nrm1 d1) + nrm2 d2) * inv_unit with d = q - p.
 //     c       (q - t) * inv_unit per component, t the view's fourth column; dropped unless (c0 c0 + c1 c1) + c2 c2 <= 16^2 and
@@ -58,8 +59,9 @@
 // reads a buffer in the launch that reduces into it, and state and stats have one writer, refine_solve_kernel's thread of the pose.
 //
 // WORK.  refine_view: one thread per matrix element.  raster: verify_faces_kernel, its thread path and wave path.  accumulate: one
-// thread per window word of all poses, sixteen waves to a workgroup, the grid sized by the sum of the windows, the pose found as
-// classify finds it.  The 29 sums are reduced inside the wave (shuffles), then in LDS for the pose of the workgroup's first word, and
+// thread per window word of all poses, sixteen waves to a workgroup, the grid sized by the sum of the windows, the pose and pixel
+// found by the code classify finds them with (verify_raster.h: vf_first_pose, vf_word, and vf_each_pose for the poses present in a
+// wave).  The 29 sums are reduced inside the wave (shuffles), then in LDS for the pose of the workgroup's first word, and
 // leave as one atomic per sum and workgroup -- verify.hip's WORK paragraph has what one atomic per wave cost there.  A wave without a
 // pair reduces nothing.  solve: one thread per pose.
 //
@@ -74,12 +76,6 @@
 #define RF_SCALE 1073741824.0        // 2^30
 #define RF_INV_SCALE (1.0 / 1073741824.0)
 #define RF_BOUND 16.0f
-
-__device__ __forceinline__ long long rf_wave_sum(long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // ---------------------------------------------------------------------------------------------------------- b. view
 __global__ __launch_bounds__(256) void refine_view_kernel(const double* __restrict__ state, int N, float scale, float* __restrict__ view) {
@@ -101,20 +97,16 @@ __device__ __forceinline__ bool rf_pair(const float* __restrict__ vert, int V, c
   for (int k = 0; k < 3; ++k) {
     const int id = faces[(size_t)face * 3 + k];
     if ((unsigned)id >= (unsigned)V) return false;
-    const float vx = vert[(size_t)id * 3], vy = vert[(size_t)id * 3 + 1], vz = vert[(size_t)id * 3 + 2];
-    P[k][0] = rs_row(M, vx, vy, vz);
-    P[k][1] = rs_row(M + 4, vx, vy, vz);
-    P[k][2] = rs_row(M + 8, vx, vy, vz);
+    rs_to_camera(M, vert + (size_t)id * 3, P[k]);
   }
   const float rx = (((float)x + 0.5f) - cam.cx) / cam.fx, ry = (((float)y + 0.5f) - cam.cy) / cam.fy;
   const float q0 = rx * o, q1 = ry * o, q2 = o;
   const float p0 = rx * r, p1 = ry * r, p2 = r;
-  const float a0 = P[1][0] - P[0][0], a1 = P[1][1] - P[0][1], a2 = P[1][2] - P[0][2];
-  const float b0 = P[2][0] - P[0][0], b1 = P[2][1] - P[0][1], b2 = P[2][2] - P[0][2];
-  const float m0 = a1 * b2 - a2 * b1, m1 = a2 * b0 - a0 * b2, m2 = a0 * b1 - a1 * b0;
-  const float l = sqrtf((m0 * m0 + m1 * m1) + m2 * m2);
+  float m[3];
+  rs_face_normal(P, m);
+  const float l = sqrtf((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]);
   if (!(l > 0.f)) return false;
-  float n0 = m0 / l, n1 = m1 / l, n2 = m2 / l;
+  float n0 = m[0] / l, n1 = m[1] / l, n2 = m[2] / l;
   if ((n0 * p0 + n1 * p1) + n2 * p2 > 0.f) {
     n0 = -n0;
     n1 = -n1;
@@ -155,39 +147,19 @@ __global__ __launch_bounds__(RF_WG) void refine_accumulate_kernel(const unsigned
   const long long base = (long long)blockIdx.x * RF_WG, i = base + threadIdx.x;
   const int lane = threadIdx.x & 63;
   if (threadIdx.x < RF_SUMS) wg[threadIdx.x] = 0;
-  // the last pose whose window starts at or before the workgroup's first word (uniform: every thread searches the same)
-  int lo = 0, hi = N - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (offset[mid] <= base) lo = mid; else hi = mid - 1;
-  }
-  const int nb = lo;
-  int n = nb;
+  const int nb = vf_first_pose(offset, N, base);
   bool pair = false;
   float u[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  if (i < total) {
-    while (n + 1 < N && offset[n + 1] <= i) ++n;
-    const VfWin w = vf_window(box, offset, n, H, W);
-    const long long local = i - w.off;
-    const unsigned long long key = zbuf[i];
-    if (key != VF_EMPTY && local >= 0 && local < (long long)w.bw * w.bh) {
-      const int y = w.y0 + (int)(local / w.bw), x = w.x0 + (int)(local % w.bw);
-      const size_t p = (size_t)y * W + x;
-      const float r = __uint_as_float((unsigned)(key >> 32));
-      const float o = depth_obs[p];
-      pair = o > 0.f && fabsf(o - r) <= gate;
-      if (pair && masks) pair = masks[(size_t)n * H * W + p] != 0;
-      if (pair) pair = rf_pair(vert, V, faces, F, (unsigned)(key & 0xffffffffull), view + (size_t)n * 12, cam, x, y, r, o, inv_unit, u);
-    }
+  VfPixel px;
+  if (vf_word(zbuf, total, box, offset, N, H, W, i, nb, px)) {
+    const float r = px.r(), o = depth_obs[px.p];
+    pair = o > 0.f && fabsf(o - r) <= gate;
+    if (pair && masks) pair = masks[(size_t)px.n * H * W + px.p] != 0;
+    if (pair) pair = rf_pair(vert, V, faces, F, px.face(), view + (size_t)px.n * 12, cam, px.x, px.y, r, o, inv_unit, u);
   }
   __syncthreads();  // wg is zero
-  unsigned long long pending = __ballot(pair);
-  while (pending) {  // per pose present in the wave (uniform)
-    const int lead = __ffsll((long long)pending) - 1;
-    const int pn = __shfl(n, lead, 64);
-    const bool mine = pair && n == pn;
-    const unsigned long long m = __ballot(mine);
-    pending &= ~m;
+  unsigned long long* const wg_of_nb = wg;
+  vf_each_pose(pair, px.n, [=](int lead, int pn, bool mine, unsigned long long m) {
     const bool local = pn == nb;
     unsigned long long* dst = acc + (size_t)pn * RF_WORDS;
     int k = 0;
@@ -196,12 +168,12 @@ __global__ __launch_bounds__(RF_WG) void refine_accumulate_kernel(const unsigned
 #pragma unroll
       for (int b = a; b < 7; ++b) {
         const long long term = mine ? (long long)rint((double)u[a] * (double)u[b] * RF_SCALE) : 0ll;
-        const long long sum = rf_wave_sum(term);
-        if (lane == lead) rf_put(sum, k, local, wg, dst);
+        const long long sum = wave_sum(term);
+        if (lane == lead) rf_put(sum, k, local, wg_of_nb, dst);
         ++k;
       }
-    if (lane == lead) rf_put((long long)__popcll(m), 28, local, wg, dst);
-  }
+    if (lane == lead) rf_put((long long)__popcll(m), 28, local, wg_of_nb, dst);
+  });
   __syncthreads();
   if (threadIdx.x < RF_SUMS && wg[threadIdx.x])
     __hip_atomic_fetch_add(acc + (size_t)nb * RF_WORDS + threadIdx.x, wg[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

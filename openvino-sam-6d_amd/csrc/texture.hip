@@ -1,10 +1,10 @@
 // Template rendering of a TEXTURED model (Render/render_custom_templates.py:60: bproc.loader.load_obj takes an OBJ with its MTL and
 // diffuse image, or a PLY that names a texture file): raster.hip's renderer with the albedo of rgb taken from one texture image.
-// Visibility is raster.hip's pass (rs_visibility), and the setup, coverage and weights are raster.h's device functions.  The resolve
-// kernel below writes mask, face, depth, xyz and computes the lighting term v with raster_resolve_kernel's lines, repeated here and
-// not called through a shared function: raster.hip's two kernels are pinned as built (tests/test_onboard_host.py), and moving those
-// lines behind a wrapper both kernels call changed raster_resolve_kernel's code (50 -> 54 VGPRs).  The recipe below is restated in
-// numpy, float32 operation by operation, in tests/texture_ref.py; like the rest of the shading it is the package's own.
+// Visibility is raster.hip's pass (rs_visibility).  The resolve kernel below calls raster.h's rs_resolve_pixel, the function
+// raster_resolve_kernel calls: it writes the background pixel, or mask, face, depth and xyz, and gives back the winner's weights and
+// the lighting term v.  What is this file's own is the albedo; the tone step after it is raster.h's rs_tone again.  So a texture of one
+// colour renders what the grey resolve renders with that albedo, bit for bit (tests/test_texture_gpu.py).  The recipe below is restated
+// in numpy, float32 operation by operation, in tests/texture_ref.py; like the rest of the shading it is the package's own.
 //
 // TEXTURE.  All float arithmetic is IEEE fp32 in the order written (the library is built with -ffp-contract=off and this file has no
 // fused multiply-add); only + - * /, floorf and comparisons run on the device.
@@ -22,7 +22,7 @@
 //           computes; or the sRGB-to-linear table).
 //   filter  top = a00 + fx * (a10 - a00);  bot = a01 + fx * (a11 - a01);  albedo = top + fy * (bot - top), per channel (a_ij: column
 //           x_i, row y_j).
-//   then    raster.hip's lines: lin = albedo * v clamped to [0, 1] by comparisons, rgb = srgb_lut[(int)(lin * 4095 + 0.5)].
+//   then    raster.hip's tone step (rs_tone): lin = albedo * v clamped to [0, 1] by comparisons, rgb = srgb_lut[(int)(lin * 4095 + 0.5)].
 // There is no mip chain: a texture much finer than the rendered surface aliases (the host offers an exact box reduction at load).
 //
 // WORK.  One thread per pixel of every view, as raster_resolve_kernel; a covered pixel adds six loads of face_uv, four 4-byte loads of
@@ -70,78 +70,12 @@ __global__ __launch_bounds__(256) void textured_resolve_kernel(const float* __re
   __syncthreads();
   const size_t hw = (size_t)cam.H * cam.W, i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= hw * (size_t)T) return;
-  const int t = (int)(i / hw), p = (int)(i % hw), y = p / cam.W, x = p % cam.W;
-  const unsigned long long key = zbuf[i];
-  if (key == ~0ull) {
-    mask[i] = 0;
-    face_out[i] = -1;
-    depth[i] = 0.f;
-    xyz[i * 3] = xyz[i * 3 + 1] = xyz[i * 3 + 2] = 0.f;
-    rgb[i * 3] = rgb[i * 3 + 1] = rgb[i * 3 + 2] = 0;
-    return;
-  }
-  const int face = (int)(unsigned)(key & 0xffffffffull);
-  const float* M = view + (size_t)t * 12;
-  RsFace f;
-  rs_setup(f, vert, V, faces, face, M, cam);
-  long long w0, w1, w2;
-  rs_cover(f, x, y, w0, w1, w2);
-  float l0, l1, l2;
-  const float d = rs_weights(f, w0, w1, w2, l0, l1, l2);
-  // the weights in the face's stored order (a winding swap exchanged vertices 1 and 2): every attribute is mixed in that order
-  const float m1 = f.swapped ? l2 : l1, m2 = f.swapped ? l1 : l2;
-  const int* fv = faces + (size_t)face * 3;
-  const float* a = vert + (size_t)fv[0] * 3;
-  const float* b = vert + (size_t)fv[1] * 3;
-  const float* c = vert + (size_t)fv[2] * 3;
-  mask[i] = 255;
-  face_out[i] = face;
-  depth[i] = d;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) xyz[i * 3 + k] = rs_mix(l0, m1, m2, a[k], b[k], c[k]);
-  // ---- the lighting term v: raster_resolve_kernel's lines
-  float P[3][3];  // camera-space vertices, stored order
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float* v = vert + (size_t)fv[k] * 3;
-    P[k][0] = rs_row(M, v[0], v[1], v[2]);
-    P[k][1] = rs_row(M + 4, v[0], v[1], v[2]);
-    P[k][2] = rs_row(M + 8, v[0], v[1], v[2]);
-  }
-  float Pc[3], n[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) Pc[k] = rs_mix(l0, m1, m2, P[0][k], P[1][k], P[2][k]);
-  if (normals) {
-    float no[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) no[k] = rs_mix(l0, m1, m2, normals[(size_t)fv[0] * 3 + k], normals[(size_t)fv[1] * 3 + k], normals[(size_t)fv[2] * 3 + k]);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) n[k] = (M[4 * k] * no[0] + M[4 * k + 1] * no[1]) + M[4 * k + 2] * no[2];
-  } else {
-    const float e1x = P[1][0] - P[0][0], e1y = P[1][1] - P[0][1], e1z = P[1][2] - P[0][2];
-    const float e2x = P[2][0] - P[0][0], e2y = P[2][1] - P[0][1], e2z = P[2][2] - P[0][2];
-    n[0] = e1y * e2z - e1z * e2y;
-    n[1] = e1z * e2x - e1x * e2z;
-    n[2] = e1x * e2y - e1y * e2x;
-  }
-  const float facing = (n[0] * Pc[0] + n[1] * Pc[1]) + n[2] * Pc[2];
-  if (facing > 0.f) {
-    n[0] = -n[0];
-    n[1] = -n[1];
-    n[2] = -n[2];
-  }
-  const float* lp = light + (size_t)t * 3;
-  const float Lx = lp[0] - Pc[0], Ly = lp[1] - Pc[1], Lz = lp[2] - Pc[2];
-  const float d2 = (Lx * Lx + Ly * Ly) + Lz * Lz;
-  const float nn = (n[0] * n[0] + n[1] * n[1]) + n[2] * n[2];
-  const float ndl = (n[0] * Lx + n[1] * Ly) + n[2] * Lz;
-  float cs = ndl / (sqrtf(nn) * sqrtf(d2));
-  cs = cs > 0.f ? cs : 0.f;
-  const float v = RS_GAIN * cs / d2;
+  RsHit h;
+  if (!rs_resolve_pixel(i, vert, V, faces, view, cam, normals, light, zbuf, RsOut{mask, face_out, depth, xyz, rgb}, h)) return;
   // ---- the albedo (TEXTURE)
-  const float* uv = tex.face_uv + (size_t)face * 6;
-  const float ru = tx_wrap(rs_mix(l0, m1, m2, uv[0], uv[2], uv[4]));
-  const float rv = tx_wrap(rs_mix(l0, m1, m2, uv[1], uv[3], uv[5]));
+  const float* uv = tex.face_uv + (size_t)h.face * 6;
+  const float ru = tx_wrap(rs_mix(h.l0, h.m1, h.m2, uv[0], uv[2], uv[4]));
+  const float rv = tx_wrap(rs_mix(h.l0, h.m1, h.m2, uv[1], uv[3], uv[5]));
   int x0, x1, y0, y1;
   float fx, fy;
   tx_taps(ru * (float)tex.Wt - 0.5f, tex.Wt, x0, x1, fx);
@@ -155,10 +89,7 @@ __global__ __launch_bounds__(256) void textured_resolve_kernel(const float* __re
     const float a01 = albedo_of[(t01 >> (8 * k)) & 255u], a11 = albedo_of[(t11 >> (8 * k)) & 255u];
     const float top = a00 + fx * (a10 - a00);
     const float bot = a01 + fx * (a11 - a01);
-    float lin = (top + fy * (bot - top)) * v;
-    lin = lin > 0.f ? lin : 0.f;
-    lin = lin < 1.f ? lin : 1.f;
-    rgb[i * 3 + k] = srgb_lut[(int)(lin * 4095.0f + 0.5f)];
+    rgb[i * 3 + k] = rs_tone((top + fy * (bot - top)) * h.v, srgb_lut);
   }
 }
 

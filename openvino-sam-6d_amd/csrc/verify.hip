@@ -3,9 +3,9 @@
 // picture is painted from that map.  The reference has no such check: it multiplies the detection score by the PEM score
 // (PEM/run_inference_custom_pytorch.py:460-471) and draws the top pose as a box and 512 points (:480-482 over
 // PEM/utils/draw_utils.py:75-97).  The check, its classes and its threshold are the package's own.  The geometry is the template
-// renderer's (Render/render_custom_templates.py:55-106 as csrc/raster.hip restates it): rs_setup, rs_cover and rs_weights of raster.h,
-// unchanged, so a pixel's coverage and depth are what sam6d_render_views gives for the same view, bit for bit.  Restated in numpy in
-// tests/verify_ref.py; every comparison is bit for bit.
+// renderer's (Render/render_custom_templates.py:55-106 as csrc/raster.hip restates it): the raster pass is raster.h's rs_faces_pass,
+// the one sam6d_render_views runs, writing into a window instead of an image, so a pixel's coverage and depth are that entry's for
+// the same view, bit for bit.  Restated in numpy in tests/verify_ref.py; every comparison is bit for bit.
 //
 // RECIPE.  All float arithmetic is IEEE fp32 in the order written (the library is built with -ffp-contract=off and this file has no
 // fused multiply-add), everything else is integer.  Camera, near plane, snap, coverage and depth are raster.hip's RECIPE.
@@ -55,28 +55,16 @@
 // grid is sized by the sum of the windows, never by the largest; a workgroup finds the pose of its first word in `offset` by
 // bisection and its threads step forward from there.  area: 16 bytes per thread and step.
 //
+// FILES.  raster.h: setup, coverage, weights and the raster pass.  verify_raster.h, shared with refine.hip: the window, its sink and
+// verify_faces_kernel; the walk from a window word to its pose and pixel (vf_first_pose, vf_word) and the loop over the poses present
+// in a wave (vf_each_pose) that classify runs.  common.h: the integer wave reductions.  The limits are raster.hip's rs_limits.
+//
 // WHAT THE HOST CANNOT SEE.  box and offset are on the device, so the kernels guard themselves: the window is the box clamped to the
 // image, a face's box is clamped to the window, a word at or beyond `total` (or below 0) is never addressed, and a window word whose
 // index within its pose is at or beyond bw * bh is skipped.  Inconsistent boxes and offsets give meaningless counts, never an access
 // outside the buffers.
 #include "verify_raster.h"  // the window and the raster pass of b, shared with refine.hip
 #include "../../include/sam6d_hip.h"
-
-__device__ __forceinline__ int vf_wave_min(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ int vf_wave_max(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ int vf_wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // ---------------------------------------------------------------------------------------------------------- a. windows
 #define VF_WG 1024  // sixteen waves: what meets at a pose's few words is one offer per workgroup, not one per wave
@@ -99,8 +87,8 @@ __global__ __launch_bounds__(VF_WG) void windows_faces_kernel(const float* __res
   const bool boxed = f.live && f.x0 <= f.x1 && f.y0 <= f.y1;
   // inside the wave first: ballot and popcount for the counter, shuffles for the box (no boxed face: x0 = y0 = INT_MAX, x1 = y1 = -1)
   const int w_dropped = __popcll(__ballot(f.dropped));
-  const int w_x0 = vf_wave_min(boxed ? f.x0 : 0x7fffffff), w_y0 = vf_wave_min(boxed ? f.y0 : 0x7fffffff);
-  const int w_x1 = vf_wave_max(boxed ? f.x1 : -1), w_y1 = vf_wave_max(boxed ? f.y1 : -1);
+  const int w_x0 = wave_min(boxed ? f.x0 : 0x7fffffff), w_y0 = wave_min(boxed ? f.y0 : 0x7fffffff);
+  const int w_x1 = wave_max(boxed ? f.x1 : -1), w_y1 = wave_max(boxed ? f.y1 : -1);
   if (lane == 0) {
     red[wave][0] = w_dropped;
     red[wave][1] = w_x0;
@@ -160,7 +148,7 @@ extern "C" int sam6d_pose_windows(const float* vertices, int V, const int* faces
 }
 
 // ---------------------------------------------------------------------------------------------------------- b. verify
-// the window, the clamp, the offer and verify_faces_kernel (the raster pass): verify_raster.h
+// the window, its sink and verify_faces_kernel (the raster pass), the word walk and the per-pose loop: verify_raster.h
 
 // one thread per window word of all poses, sixteen waves in a workgroup.  Most workgroups lie inside one window: the counts of the
 // pose of the workgroup's first word are gathered in LDS and leave as one atomic per counter and workgroup; a wave's counts for
@@ -174,57 +162,38 @@ __global__ __launch_bounds__(VF_WG) void verify_classify_kernel(const unsigned l
   const long long base = (long long)blockIdx.x * VF_WG, i = base + threadIdx.x;
   const int lane = threadIdx.x & 63;
   if (threadIdx.x < 6) wg[threadIdx.x] = 0;
-  // the last pose whose window starts at or before the workgroup's first word (uniform: every thread searches the same)
-  int lo = 0, hi = N - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (offset[mid] <= base) lo = mid; else hi = mid - 1;
-  }
-  const int nb = lo;
-  int n = nb, cls = 0, inter = 0;  // cls: 0 nothing to count, 1 inlier, 2 occluded, 3 behind, 4 unknown
-  if (i < total) {
-    while (n + 1 < N && offset[n + 1] <= i) ++n;
-    const VfWin w = vf_window(box, offset, n, H, W);
-    const long long local = i - w.off;
-    const unsigned long long key = zbuf[i];
-    if (key != VF_EMPTY && local >= 0 && local < (long long)w.bw * w.bh) {
-      const int y = w.y0 + (int)(local / w.bw), x = w.x0 + (int)(local % w.bw);
-      const size_t p = (size_t)y * W + x;
-      const float r = __uint_as_float((unsigned)(key >> 32));
-      const float o = depth_obs[p];
-      if (!(o > 0.f)) cls = 4;
-      else {
-        const float e = o - r;
-        cls = e > tau ? 3 : (e < -tau ? 2 : 1);
-      }
-      if (masks) inter = masks[(size_t)n * H * W + p] != 0;
-      if (composite)
-        __hip_atomic_fetch_min(comp + p, (key & 0xffffffff00000000ull) | (unsigned)n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const int nb = vf_first_pose(offset, N, base);
+  int cls = 0, inter = 0;  // cls: 0 nothing to count, 1 inlier, 2 occluded, 3 behind, 4 unknown
+  VfPixel px;
+  if (vf_word(zbuf, total, box, offset, N, H, W, i, nb, px)) {
+    const float o = depth_obs[px.p];
+    if (!(o > 0.f)) cls = 4;
+    else {
+      const float e = o - px.r();
+      cls = e > tau ? 3 : (e < -tau ? 2 : 1);
     }
+    if (masks) inter = masks[(size_t)px.n * H * W + px.p] != 0;
+    if (composite)
+      __hip_atomic_fetch_min(comp + px.p, (px.key & 0xffffffff00000000ull) | (unsigned)px.n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   __syncthreads();  // wg is zero
   // per pose present in the wave: ballot and popcount, then one add per counter
-  unsigned long long pending = __ballot(cls != 0);
-  while (pending) {
-    const int lead = __ffsll((long long)pending) - 1;
-    const int pn = __shfl(n, lead, 64);
-    const bool mine = cls != 0 && n == pn;
-    const unsigned long long m = __ballot(mine);
-    pending &= ~m;
+  int* const wg_of_nb = wg;
+  vf_each_pose(cls != 0, px.n, [=](int lead, int pn, bool mine, unsigned long long m) {
     const int c[6] = {(int)__popcll(m),
                       (int)__popcll(__ballot(mine && cls == 1)),
                       (int)__popcll(__ballot(mine && cls == 2)),
                       (int)__popcll(__ballot(mine && cls == 3)),
                       (int)__popcll(__ballot(mine && cls == 4)),
                       (int)__popcll(__ballot(mine && inter))};
-    if (lane != lead) continue;
+    if (lane != lead) return;
 #pragma unroll
     for (int k = 0; k < 6; ++k) {
       if (!c[k]) continue;
-      if (pn == nb) atomicAdd(&wg[k], c[k]);
+      if (pn == nb) atomicAdd(&wg_of_nb[k], c[k]);
       else vf_add(counts + (size_t)pn * 8 + (k < 5 ? k : 6), c[k]);
     }
-  }
+  });
   __syncthreads();
   if (threadIdx.x < 6 && wg[threadIdx.x]) vf_add(counts + (size_t)nb * 8 + (threadIdx.x < 5 ? threadIdx.x : 6), wg[threadIdx.x]);
 }
@@ -255,7 +224,7 @@ __global__ __launch_bounds__(256) void verify_mask_area_kernel(const unsigned ch
       for (long long b = e0; b < e1; ++b) cnt += m[b] != 0;
     }
   }
-  cnt = vf_wave_sum(cnt);
+  cnt = wave_sum(cnt);
   if (lane == 0 && cnt) vf_add(counts + (size_t)n * 8 + 5, cnt);
 }
 

@@ -68,12 +68,9 @@ def _refine(vertices, faces, R, t, intr, H, W, near, depth, masks, scale, iters,
     N = int(R.shape[0])
     box, _ = verify._windows(vertices, faces, verify.pose_views(R, t, scale), intr, H, W, near)
     box = grow_boxes(box, margin, H, W)
-    bw = (box[:, 2] - box[:, 0] + 1).clamp_(min=0).to(torch.int64)
-    bh = (box[:, 3] - box[:, 1] + 1).clamp_(min=0).to(torch.int64)
-    offset = torch.zeros((N + 1,), dtype=torch.int64, device=box.device)
-    torch.cumsum(bw * bh, dim=0, out=offset[1:])
+    offset, total = verify.window_offsets(box)
     # the one read-back, two numbers in one copy: the window total (it sizes the workspace) and the mesh radius (the unit of length)
-    both = torch.stack([offset[N].to(torch.float64), mesh_radius2(vertices).to(torch.float64)]).cpu()
+    both = torch.stack([total.to(torch.float64), mesh_radius2(vertices).to(torch.float64)]).cpu()
     total, radius2 = int(both[0]), float(both[1])
     if not (radius2 > 0.0 and math.isfinite(radius2)):
         raise ValueError("refine_poses: the mesh has no extent (max |vertex|^2 = %r)" % radius2)

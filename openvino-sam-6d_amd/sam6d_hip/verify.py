@@ -116,14 +116,22 @@ def _size(name, size, N, F, V):
     return H, W
 
 
-@on_tensor_device
-def _verify(vertices, faces, view, intr, H, W, near, wave_area, box, depth, masks, tau, want_map):
-    N = int(view.shape[0])
+def window_offsets(box):
+    """box (N,4) i32 [x0, y0, x1, y1] inclusive -> offset (N+1) i64 on the device: the first z-buffer word of each pose's window, and
+    in offset[N] the words of all windows together (still on the device: reading it back is the caller's)"""
+    N = int(box.shape[0])
     bw = (box[:, 2] - box[:, 0] + 1).clamp_(min=0).to(torch.int64)
     bh = (box[:, 3] - box[:, 1] + 1).clamp_(min=0).to(torch.int64)
     offset = torch.zeros((N + 1,), dtype=torch.int64, device=box.device)
     torch.cumsum(bw * bh, dim=0, out=offset[1:])
-    total = int(offset[N])  # the one read-back: 8 bytes, to size the workspace
+    return offset, offset[N]
+
+
+@on_tensor_device
+def _verify(vertices, faces, view, intr, H, W, near, wave_area, box, depth, masks, tau, want_map):
+    N = int(view.shape[0])
+    offset, total = window_offsets(box)
+    total = int(total)  # the one read-back: 8 bytes, to size the workspace
     need = int(_lib.load().sam6d_pose_verify_workspace_bytes(total, H, W))
     ws = _empty((need // 8,), vertices, torch.int64)
     counts = _empty((N, 8), vertices, torch.int32)

@@ -93,30 +93,8 @@ def test_package_crop_resize_pad_matches_fixture_and_refuses():
 def test_attention_kernel_resources():
     """DESIGN section 8 row f5 states the attention kernel's budget: at most 128 VGPRs (two workgroups' worth of waves per SIMD would
     fit the register file; LDS allows one) and no scratch.  Read from the code object's metadata."""
-    import os
-    import re
-    import subprocess
-    from sam6d_hip import _lib
-    from tests.test_abi import _gfx950_code_objects
-    readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    if not os.path.exists(readelf):
-        pytest.skip("llvm-readelf not available")
-    found = None
-    for blob in _gfx950_code_objects(_lib.LIB_PATH):
-        if b"dino_attention_kernel" not in blob:
-            continue
-        p = os.path.join(os.environ.get("TMPDIR", "/tmp"), "dino_co_%d.elf" % os.getpid())
-        with open(p, "wb") as f:
-            f.write(blob)
-        try:
-            notes = subprocess.run([readelf, "--notes", p], capture_output=True, text=True, check=True).stdout
-        finally:
-            os.remove(p)
-        for entry in re.split(r"\n\s*- \.agpr_count", notes):
-            if re.search(r"\.name:\s+_Z21dino_attention_kernel", entry):
-                found = (int(re.search(r"\.vgpr_count:\s+(\d+)", entry).group(1)),
-                         int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", entry).group(1)),
-                         int(re.search(r"\.vgpr_spill_count:\s+(\d+)", entry).group(1)))
+    from tests._util import kernel_resources
+    found = kernel_resources(b"dino_attention_kernel", r"(dino_attention_kernel)").get("dino_attention_kernel")
     assert found is not None, "dino_attention_kernel not found in the library"
     print("\n[dinov2] attention kernel: %d VGPRs, %d B scratch, %d spilled" % found)
     assert found[0] <= 128 and found[1] == 0 and found[2] == 0, found

@@ -13,7 +13,7 @@ import torch
 
 from tests import meshsample_ref as MS
 from tests import raster_ref as RR
-from tests._util import PKG, ROOT
+from tests._util import PKG, ROOT, kernel_resources
 
 POSES = np.load(os.path.join(ROOT, "tests", "golden", "template_cam_poses.npz"))["cam_poses"]
 NEAR = 1.0e-3
@@ -428,34 +428,11 @@ def test_c_entries_refuse_by_name_before_a_launch():
 # ------------------------------------------------------------------------------------------------------------ kernels
 def test_kernel_resources():
     """none of the new kernels uses scratch or spills, and each keeps within its built VGPR count rounded up
-    to the next step of 8 (built: raster_faces 62, raster_resolve 50, ms_area 18, ms_block_sum 9, ms_scan_blocks 14, ms_start 14,
+    to the next step of 8 (built: raster_faces 62, raster_resolve 52, ms_area 18, ms_block_sum 9, ms_scan_blocks 14, ms_start 14,
     ms_sample 22).  The vector atomics are the 64-bit unsigned min of the z-buffer, the drop counter's add and area_max's unsigned max."""
-    from sam6d_hip import _lib
-    from tests.test_abi import _gfx950_code_objects
-    readelf, objdump = "/opt/rocm/lib/llvm/bin/llvm-readelf", "/opt/rocm/lib/llvm/bin/llvm-objdump"
-    if not (os.path.exists(readelf) and os.path.exists(objdump)):
-        pytest.skip("llvm-readelf / llvm-objdump not available")
     limits = dict(raster_faces_kernel=64, raster_resolve_kernel=56, ms_area_kernel=24, ms_block_sum_kernel=16, ms_scan_blocks_kernel=16,
                   ms_start_kernel=16, ms_sample_kernel=24)
-    found, atomics = {}, set()
-    for blob in _gfx950_code_objects(_lib.LIB_PATH):
-        if b"raster_faces_kernel" not in blob and b"ms_sample_kernel" not in blob:
-            continue
-        p = os.path.join(os.environ.get("TMPDIR", "/tmp"), "onboard_co_%d.elf" % os.getpid())
-        with open(p, "wb") as fh:
-            fh.write(blob)
-        try:
-            notes = subprocess.run([readelf, "--notes", p], capture_output=True, text=True, check=True).stdout
-            asm = subprocess.run([objdump, "-d", "--mcpu=gfx950", p], capture_output=True, text=True, check=True).stdout
-        finally:
-            os.remove(p)
-        atomics |= set(re.findall(r"\b(global_atomic_\w+|flat_atomic_\w+)", asm))
-        for entry in re.split(r"\n\s*- \.agpr_count", notes):
-            name = re.search(r"\.name:\s+_Z\d+((?:raster|ms)_[a-z_]+_kernel)", entry)
-            if name:
-                found[name.group(1)] = (int(re.search(r"\.vgpr_count:\s+(\d+)", entry).group(1)),
-                                        int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", entry).group(1)),
-                                        int(re.search(r"\.vgpr_spill_count:\s+(\d+)", entry).group(1)))
+    found, atomics = kernel_resources((b"raster_faces_kernel", b"ms_sample_kernel"), r"((?:raster|ms)_[a-z_]+_kernel)", disassemble=True)
     print("\n[onboard] (VGPRs, scratch bytes, spilled): %s; atomics %s" % (found, sorted(atomics)))
     assert set(found) == set(limits), found
     for name, cap in limits.items():

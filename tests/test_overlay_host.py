@@ -245,34 +245,9 @@ def test_kernel_resources():
     """none of the three kernels uses scratch or spills, each keeps within its built VGPR count rounded up
     to the next step of 8 (built: overlay_masks 20, draw_paint 46, draw_resolve 11), and the only vector atomics of the file are the
     painter's 32-bit unsigned max and the skip counter's add."""
-    import os
-    import re
-    import subprocess
-    from sam6d_hip import _lib
-    from tests.test_abi import _gfx950_code_objects
-    readelf, objdump = "/opt/rocm/lib/llvm/bin/llvm-readelf", "/opt/rocm/lib/llvm/bin/llvm-objdump"
-    if not (os.path.exists(readelf) and os.path.exists(objdump)):
-        pytest.skip("llvm-readelf / llvm-objdump not available")
+    from tests._util import kernel_resources
     limits = dict(overlay_masks_kernel=24, draw_paint_kernel=48, draw_resolve_kernel=16)
-    found, atomics = {}, set()
-    for blob in _gfx950_code_objects(_lib.LIB_PATH):
-        if b"draw_paint_kernel" not in blob:
-            continue
-        p = os.path.join(os.environ.get("TMPDIR", "/tmp"), "overlay_co_%d.elf" % os.getpid())
-        with open(p, "wb") as fh:
-            fh.write(blob)
-        try:
-            notes = subprocess.run([readelf, "--notes", p], capture_output=True, text=True, check=True).stdout
-            asm = subprocess.run([objdump, "-d", "--mcpu=gfx950", p], capture_output=True, text=True, check=True).stdout
-        finally:
-            os.remove(p)
-        atomics |= set(re.findall(r"\b(global_atomic_\w+|flat_atomic_\w+)", asm))
-        for entry in re.split(r"\n\s*- \.agpr_count", notes):
-            name = re.search(r"\.name:\s+_Z\d+((?:overlay|draw)_[a-z_]+_kernel)", entry)
-            if name:
-                found[name.group(1)] = (int(re.search(r"\.vgpr_count:\s+(\d+)", entry).group(1)),
-                                        int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", entry).group(1)),
-                                        int(re.search(r"\.vgpr_spill_count:\s+(\d+)", entry).group(1)))
+    found, atomics = kernel_resources(b"draw_paint_kernel", r"((?:overlay|draw)_[a-z_]+_kernel)", disassemble=True)
     print("\n[overlay] (VGPRs, scratch bytes, spilled): %s; atomics %s" % (found, sorted(atomics)))
     assert set(found) == set(limits), found
     for name, cap in limits.items():

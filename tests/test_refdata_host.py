@@ -2,7 +2,6 @@
 (tests/refdata_ref.py) against the installed Pillow and against the composition of parts already pinned to the reference, the plain-torch
 partner against the restatement, the pose recipe, what is refused, the import layer and the kernels' registers."""
 import os
-import re
 import subprocess
 import sys
 
@@ -249,29 +248,9 @@ def test_load_templates_round_trip(tmp_path):
 def test_kernel_resources():
     """neither new kernel uses scratch or spills, and each keeps within its built VGPR count rounded up to
     the next step of 8 (built: tpl_bbox 22, tpl_crop<custom> 20, tpl_crop<bop> 20).  The code object holds these kernels alone."""
-    from sam6d_hip import _lib
-    from tests.test_abi import _gfx950_code_objects
-    readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    if not os.path.exists(readelf):
-        pytest.skip("llvm-readelf not available")
+    from tests._util import kernel_resources
     limits = {"tpl_bbox_kernel": 24, "tpl_crop_kernelILb0EE": 24, "tpl_crop_kernelILb1EE": 24}
-    found = {}
-    for blob in _gfx950_code_objects(_lib.LIB_PATH):
-        if b"tpl_bbox_kernel" not in blob:
-            continue
-        p = os.path.join(os.environ.get("TMPDIR", "/tmp"), "refdata_co_%d.elf" % os.getpid())
-        with open(p, "wb") as fh:
-            fh.write(blob)
-        try:
-            notes = subprocess.run([readelf, "--notes", p], capture_output=True, text=True, check=True).stdout
-        finally:
-            os.remove(p)
-        for entry in re.split(r"\n\s*- \.agpr_count", notes):
-            name = re.search(r"\.name:\s+_Z\d+(\w+?_kernel(?:ILb[01]EE)?)", entry)
-            if name:
-                found[name.group(1)] = (int(re.search(r"\.vgpr_count:\s+(\d+)", entry).group(1)),
-                                        int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", entry).group(1)),
-                                        int(re.search(r"\.vgpr_spill_count:\s+(\d+)", entry).group(1)))
+    found = kernel_resources(b"tpl_bbox_kernel", r"(\w+?_kernel(?:ILb[01]EE)?)")
     print("\n[refdata] (VGPRs, scratch bytes, spilled): %s" % found)
     assert set(found) == set(limits), found
     for name, cap in limits.items():

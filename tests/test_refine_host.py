@@ -182,32 +182,11 @@ def test_refine_poses_refusals():
 
 def test_kernel_resources():
     """no kernel of refine.hip uses scratch or spills, and each keeps within its built VGPR count rounded up
-    to the next step of 8 (built: refine_view 8, refine_accumulate 76, refine_solve 70, and its copy of verify_faces 63, the figure of
+    to the next step of 8 (built: refine_view 8, refine_accumulate 78, refine_solve 70, and its copy of verify_faces 63, the figure of
     verify.hip's).  Read from the code object's metadata: the compiler's figures, not a GPU's."""
-    import re
-    import subprocess
-    from tests.test_abi import _gfx950_code_objects
-    readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    if not os.path.exists(readelf):
-        pytest.skip("llvm-readelf not available")
+    from tests._util import kernel_resources
     limits = dict(refine_view_kernel=8, refine_accumulate_kernel=80, refine_solve_kernel=72, verify_faces_kernel=64)
-    found = {}
-    for blob in _gfx950_code_objects(_lib.LIB_PATH):
-        if b"refine_accumulate_kernel" not in blob:
-            continue
-        p = os.path.join(os.environ.get("TMPDIR", "/tmp"), "refine_co_%d.elf" % os.getpid())
-        with open(p, "wb") as fh:
-            fh.write(blob)
-        try:
-            notes = subprocess.run([readelf, "--notes", p], capture_output=True, text=True, check=True).stdout
-        finally:
-            os.remove(p)
-        for entry in re.split(r"\n\s*- \.agpr_count", notes):
-            name = re.search(r"\.name:\s+_Z\d+([a-z_]+_kernel)", entry)
-            if name:
-                found[name.group(1)] = (int(re.search(r"\.vgpr_count:\s+(\d+)", entry).group(1)),
-                                        int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", entry).group(1)),
-                                        int(re.search(r"\.vgpr_spill_count:\s+(\d+)", entry).group(1)))
+    found = kernel_resources(b"refine_accumulate_kernel")
     print("\n[refine] (VGPRs, scratch bytes, spilled): %s" % found)
     assert set(found) == set(limits), found
     for name, cap in limits.items():

@@ -4,7 +4,6 @@ kernel's resources.  No GPU."""
 import importlib
 import inspect
 import os
-import re
 import subprocess
 import sys
 
@@ -159,27 +158,8 @@ def test_dropin_generate_masks_cpu_contract():
 
 def test_mask_stats_kernel_resources():
     """the statistics kernel keeps within 64 VGPRs (eight waves per SIMD) and uses no scratch."""
-    from sam6d_hip import _lib
-    from tests.test_abi import _gfx950_code_objects
-    readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    if not os.path.exists(readelf):
-        pytest.skip("llvm-readelf not available")
-    found = None
-    for blob in _gfx950_code_objects(_lib.LIB_PATH):
-        if b"amg_stats_kernel" not in blob:
-            continue
-        p = os.path.join(os.environ.get("TMPDIR", "/tmp"), "amg_co_%d.elf" % os.getpid())
-        with open(p, "wb") as f:
-            f.write(blob)
-        try:
-            notes = subprocess.run([readelf, "--notes", p], capture_output=True, text=True, check=True).stdout
-        finally:
-            os.remove(p)
-        for entry in re.split(r"\n\s*- \.agpr_count", notes):
-            if re.search(r"\.name:\s+_Z16amg_stats_kernel", entry):
-                found = (int(re.search(r"\.vgpr_count:\s+(\d+)", entry).group(1)),
-                         int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", entry).group(1)),
-                         int(re.search(r"\.vgpr_spill_count:\s+(\d+)", entry).group(1)))
+    from tests._util import kernel_resources
+    found = kernel_resources(b"amg_stats_kernel", r"(amg_stats_kernel)").get("amg_stats_kernel")
     assert found is not None, "amg_stats_kernel not found in the library"
     print("\n[sam_amg] statistics kernel: %d VGPRs, %d B scratch, %d spilled" % found)
     assert found[0] <= 64 and found[1] == 0 and found[2] == 0, found

@@ -245,32 +245,9 @@ def test_kernel_resources():
     """DESIGN section 8 row f7 states the budgets: the image->token kernel keeps a 56-float table column per thread (<= 160 VGPRs), the
     token->image kernel <= 96, the upscaling kernel keeps a sub-pixel's 64 channels per thread (<= 200: two waves per SIMD); none
     may use scratch.  Read from the code object's metadata."""
-    import os
-    import re
-    import subprocess
-    from sam6d_hip import _lib
-    from tests.test_abi import _gfx950_code_objects
-    readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    if not os.path.exists(readelf):
-        pytest.skip("llvm-readelf not available")
+    from tests._util import kernel_resources
     budget = {"samdec_i2t_kernel": 160, "samdec_t2i_kernel": 96, "samdec_upscale_kernel": 200}
-    found = {}
-    for blob in _gfx950_code_objects(_lib.LIB_PATH):
-        if b"samdec_i2t_kernel" not in blob:
-            continue
-        p = os.path.join(os.environ.get("TMPDIR", "/tmp"), "samdec_co_%d.elf" % os.getpid())
-        with open(p, "wb") as f:
-            f.write(blob)
-        try:
-            notes = subprocess.run([readelf, "--notes", p], capture_output=True, text=True, check=True).stdout
-        finally:
-            os.remove(p)
-        for entry in re.split(r"\n\s*- \.agpr_count", notes):
-            m = re.search(r"\.name:\s+_Z\d+(samdec_[a-z0-9_]+_kernel)", entry)
-            if m:
-                found[m.group(1)] = (int(re.search(r"\.vgpr_count:\s+(\d+)", entry).group(1)),
-                                     int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", entry).group(1)),
-                                     int(re.search(r"\.vgpr_spill_count:\s+(\d+)", entry).group(1)))
+    found = kernel_resources(b"samdec_i2t_kernel", r"(samdec_[a-z0-9_]+_kernel)")
     for name, cap in budget.items():
         assert name in found, "%s not found in the library" % name
         print("\n[sam_decoder] %s: %d VGPRs, %d B scratch, %d spilled" % ((name,) + found[name]))

@@ -200,32 +200,9 @@ def test_kernel_resources():
     """DESIGN section 8 row f8 states the budgets: built values rounded up to the next allocation step of 8 registers -- the windowed
     kernel 124 -> 128 VGPRs (two waves per SIMD fit beside its 159 KB of LDS either way), the global kernel 162 -> 168 (three waves per
     SIMD), the gather 16; none may use scratch.  Read from the code object's metadata."""
-    import os
-    import re
-    import subprocess
-    from sam6d_hip import _lib
-    from tests.test_abi import _gfx950_code_objects
-    readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    if not os.path.exists(readelf):
-        pytest.skip("llvm-readelf not available")
+    from tests._util import kernel_resources
     budget = {"sam_window_attention_kernel": 128, "sam_global_attention_kernel": 168, "sam_neck_gather_kernel": 16}
-    found = {}
-    for blob in _gfx950_code_objects(_lib.LIB_PATH):
-        if b"sam_window_attention_kernel" not in blob:
-            continue
-        p = os.path.join(os.environ.get("TMPDIR", "/tmp"), "samenc_co_%d.elf" % os.getpid())
-        with open(p, "wb") as f:
-            f.write(blob)
-        try:
-            notes = subprocess.run([readelf, "--notes", p], capture_output=True, text=True, check=True).stdout
-        finally:
-            os.remove(p)
-        for entry in re.split(r"\n\s*- \.agpr_count", notes):
-            m = re.search(r"\.name:\s+_Z\d+(sam_[a-z0-9_]+_kernel)", entry)
-            if m:
-                found[m.group(1)] = (int(re.search(r"\.vgpr_count:\s+(\d+)", entry).group(1)),
-                                     int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", entry).group(1)),
-                                     int(re.search(r"\.vgpr_spill_count:\s+(\d+)", entry).group(1)))
+    found = kernel_resources(b"sam_window_attention_kernel", r"(sam_[a-z0-9_]+_kernel)")
     for name, cap in budget.items():
         assert name in found, "%s not found in the library" % name
         print("\n[sam_encoder] %s: %d VGPRs, %d B scratch, %d spilled" % ((name,) + found[name]))

@@ -209,32 +209,9 @@ def test_encoder_embed_split_keeps_the_launches(monkeypatch):
 def test_kernel_resources():
     """DESIGN section 8 row f9 states the budget: sam_front_kernel builds at VGPRS_BUILT registers, held to the next allocation step of 8,
     and may not use scratch.  Read from the code object's metadata."""
-    import os
-    import re
-    import subprocess
-    from sam6d_hip import _lib
-    from tests.test_abi import _gfx950_code_objects
-    readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    if not os.path.exists(readelf):
-        pytest.skip("llvm-readelf not available")
+    from tests._util import kernel_resources
     budget = {"sam_front_kernel": VGPR_BUDGET}
-    found = {}
-    for blob in _gfx950_code_objects(_lib.LIB_PATH):
-        if b"sam_front_kernel" not in blob:
-            continue
-        p = os.path.join(os.environ.get("TMPDIR", "/tmp"), "samfront_co_%d.elf" % os.getpid())
-        with open(p, "wb") as f:
-            f.write(blob)
-        try:
-            notes = subprocess.run([readelf, "--notes", p], capture_output=True, text=True, check=True).stdout
-        finally:
-            os.remove(p)
-        for entry in re.split(r"\n\s*- \.agpr_count", notes):
-            m = re.search(r"\.name:\s+_Z\d+(sam_front_kernel)", entry)
-            if m:
-                found[m.group(1)] = (int(re.search(r"\.vgpr_count:\s+(\d+)", entry).group(1)),
-                                     int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", entry).group(1)),
-                                     int(re.search(r"\.vgpr_spill_count:\s+(\d+)", entry).group(1)))
+    found = kernel_resources(b"sam_front_kernel", r"(sam_front_kernel)")
     for name, cap in budget.items():
         assert name in found, "%s not found in the library's code objects" % name
         vgprs, scratch, spills = found[name]

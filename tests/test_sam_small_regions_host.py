@@ -5,7 +5,6 @@ import importlib
 import inspect
 import os
 import re
-import subprocess
 import sys
 import types
 
@@ -169,28 +168,8 @@ def test_ops_refuse_cpu_tensors():
 def test_region_kernels_resources():
     """no kernel of csrc/regions.hip uses scratch; the tile labeller keeps within 64 VGPRs (eight waves per
     SIMD; the build reports 62), the others within 32 (they report 10 to 18)."""
-    from sam6d_hip import _lib
-    from tests.test_abi import _gfx950_code_objects
-    readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    if not os.path.exists(readelf):
-        pytest.skip("llvm-readelf not available")
-    found = {}
-    for blob in _gfx950_code_objects(_lib.LIB_PATH):
-        if b"rg_init_kernel" not in blob:
-            continue
-        p = os.path.join(os.environ.get("TMPDIR", "/tmp"), "regions_co_%d.elf" % os.getpid())
-        with open(p, "wb") as f:
-            f.write(blob)
-        try:
-            notes = subprocess.run([readelf, "--notes", p], capture_output=True, text=True, check=True).stdout
-        finally:
-            os.remove(p)
-        for entry in re.split(r"\n\s*- \.agpr_count", notes):
-            name = re.search(r"\.name:\s+_Z\d+(rg_[a-z_]+_kernel)", entry)
-            if name:
-                found[name.group(1)] = (int(re.search(r"\.vgpr_count:\s+(\d+)", entry).group(1)),
-                                        int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", entry).group(1)),
-                                        int(re.search(r"\.vgpr_spill_count:\s+(\d+)", entry).group(1)))
+    from tests._util import kernel_resources
+    found = kernel_resources(b"rg_init_kernel", r"(rg_[a-z_]+_kernel)")
     print("\n[sam_small_regions] VGPRs, scratch bytes, spills: %s" % found)
     want = {"rg_init_kernel", "rg_merge_kernel", "rg_flatten_kernel", "rg_emit_kernel", "rg_state_init_kernel", "rg_roots_kernel",
             "rg_fill_kernel", "rg_keep_kernel", "rg_finish_kernel"}

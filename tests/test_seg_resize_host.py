@@ -7,8 +7,6 @@ images, so test_restatement_matches_cv2 runs only where cv2 imports."""
 import importlib
 import inspect
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -167,28 +165,8 @@ def test_dropin_switch():
 def test_kernel_resources():
     """the mask kernel keeps within 64 VGPRs (eight waves per SIMD) and uses no scratch; the image kernel
     uses no scratch and keeps within 48 VGPRs (built: 43)."""
-    from sam6d_hip import _lib
-    from tests.test_abi import _gfx950_code_objects
-    readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    if not os.path.exists(readelf):
-        pytest.skip("llvm-readelf not available")
-    found = {}
-    for blob in _gfx950_code_objects(_lib.LIB_PATH):
-        if b"seg_masks_resize_kernel" not in blob:
-            continue
-        p = os.path.join(os.environ.get("TMPDIR", "/tmp"), "segresize_co_%d.elf" % os.getpid())
-        with open(p, "wb") as f:
-            f.write(blob)
-        try:
-            notes = subprocess.run([readelf, "--notes", p], capture_output=True, text=True, check=True).stdout
-        finally:
-            os.remove(p)
-        for entry in re.split(r"\n\s*- \.agpr_count", notes):
-            name = re.search(r"\.name:\s+_Z\d+(seg_(?:masks|image)_resize_kernel)", entry)
-            if name:
-                found[name.group(1)] = (int(re.search(r"\.vgpr_count:\s+(\d+)", entry).group(1)),
-                                        int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", entry).group(1)),
-                                        int(re.search(r"\.vgpr_spill_count:\s+(\d+)", entry).group(1)))
+    from tests._util import kernel_resources
+    found = kernel_resources(b"seg_masks_resize_kernel", r"(seg_(?:masks|image)_resize_kernel)")
     assert set(found) == {"seg_masks_resize_kernel", "seg_image_resize_kernel"}, found
     print("\n[seg_resize] (VGPRs, scratch bytes, spilled): %s" % (found,))
     assert found["seg_masks_resize_kernel"][0] <= 64 and found["seg_masks_resize_kernel"][1:] == (0, 0), found

@@ -174,6 +174,22 @@ def test_views_and_attributes(dev, T, with_normals, decode_srgb):
             assert np.array_equal(grey[k].cpu().numpy(), want[k]), k
 
 
+@pytest.mark.parametrize("with_normals", [False, True])
+@pytest.mark.parametrize("b", [0, 77, 255])
+def test_one_texel_equals_the_grey_render(dev, b, with_normals):
+    """device against device: a 1 x 1 texture of bytes (b, b, b) filters to a + fx * (a - a) = a = texel_table()[b] exactly, so the
+    textured resolve writes what the grey resolve (colorize) writes with that base_color, on all six outputs, bit for bit -- the two
+    kernels share raster.h's resolve core and tone step"""
+    v, f, view, light, intr = _ico_scene(1, (17, 33), (0, 41))
+    normals = (v / np.linalg.norm(v, axis=1, keepdims=True)).astype(np.float32) if with_normals else None
+    face_uv = (np.random.default_rng(b).random((len(f), 3, 2)) * 3 - 1).astype(np.float32)
+    got = _render(dev, v, f, face_uv, np.full((1, 1, 3), b, np.uint8), view, light, intr, (17, 33), normals=normals)
+    grey = _render(dev, v, f, None, None, view, light, intr, (17, 33), normals=normals, colorize=True, base_color=float(onboard.texel_table()[b]))
+    assert int((got["mask"] == 255).sum()) > 80
+    for k in KEYS:
+        assert got[k].dtype == grey[k].dtype and torch.equal(got[k], grey[k]), (k, int((got[k] != grey[k]).sum()))
+
+
 def test_untextured_route_is_unchanged(dev):
     """render_views without the new keywords == sam6d_render_views called directly on the same inputs, byte for byte"""
     v, f, view, light, intr = _ico_scene(2, (64, 64), (6, 10, 36))

@@ -3,7 +3,6 @@ and read back, what the readers refuse, the numpy restatement of the TEXTURE rec
 restatement, to a float64 lookup and to the image's orientation, what the C entry refuses before a launch, and the kernel's registers."""
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -288,6 +287,26 @@ def test_constant_texture_equals_constant_vertex_colours(name):
     assert np.array_equal(got["rgb"], want["rgb"])
 
 
+@pytest.mark.parametrize("with_normals", [False, True])
+@pytest.mark.parametrize("b", [0, 77, 255])
+def test_one_texel_equals_the_grey_render(b, with_normals):
+    """The two resolve kernels share one core, so the restatements must agree where the albedos do: a 1 x 1 texture of bytes (b, b, b)
+    filters to a + fx * (a - a) = a = texel_table()[b] exactly, and the textured render is the grey render (colorize) with that
+    base_color on all six outputs, bit for bit.  tests/test_texture_gpu.py holds the device to the same, device against device."""
+    from sam6d_hip import onboard
+    v, f = RR.icosphere(1, 50.0)
+    view, light = onboard.view_matrices(POSES[[0, 41]], 0.5 / 50.0)
+    intr = (0.5 * 33 / np.tan(0.5 * 0.691111), 0.5 * 33 / np.tan(0.5 * 0.691111), 0.5 * 33, 0.5 * 17)
+    lut, table = onboard.srgb_table(), onboard.texel_table()
+    normals = (v / np.linalg.norm(v, axis=1, keepdims=True)).astype(np.float32) if with_normals else None
+    face_uv = (np.random.default_rng(b).random((len(f), 3, 2)) * 3 - 1).astype(np.float32)
+    got = TR.render(v, f, normals, face_uv, np.full((1, 1, 3), b, np.uint8), table, view, light, intr, (17, 33), NEAR, lut)
+    want = RR.render(v, f, normals, None, view, light, intr, (17, 33), NEAR, float(table[b]), True, lut)
+    assert (got["mask"] == 255).sum() > 80
+    for k in ("mask", "face", "depth", "xyz", "rgb", "n_dropped"):
+        assert np.array_equal(got[k], want[k]), k
+
+
 def _px(points, z=1.0):
     p = np.asarray(points, np.float64)
     z = np.broadcast_to(np.asarray(z, np.float64), (len(p),))
@@ -413,30 +432,10 @@ def test_c_entry_refuses_by_name_before_a_launch():
 
 # ------------------------------------------------------------------------------------------------------------ the kernel
 def test_kernel_resources():
-    """textured_resolve_kernel uses no scratch and spills nothing, and keeps within its built VGPR count (49)
-    rounded up to the next step of 8.  Only the .vgpr_count, scratch and spill notes of the code object are read."""
-    from sam6d_hip import _lib
-    from tests.test_abi import _gfx950_code_objects
-    readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    if not os.path.exists(readelf):
-        pytest.skip("llvm-readelf not available")
-    found = {}
-    for blob in _gfx950_code_objects(_lib.LIB_PATH):
-        if b"textured_resolve_kernel" not in blob:
-            continue
-        p = os.path.join(os.environ.get("TMPDIR", "/tmp"), "texture_co_%d.elf" % os.getpid())
-        with open(p, "wb") as fh:
-            fh.write(blob)
-        try:
-            notes = subprocess.run([readelf, "--notes", p], capture_output=True, text=True, check=True).stdout
-        finally:
-            os.remove(p)
-        for entry in re.split(r"\n\s*- \.agpr_count", notes):
-            name = re.search(r"\.name:\s+_Z\d+([a-z_]+_kernel)", entry)
-            if name:
-                found[name.group(1)] = (int(re.search(r"\.vgpr_count:\s+(\d+)", entry).group(1)),
-                                        int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", entry).group(1)),
-                                        int(re.search(r"\.vgpr_spill_count:\s+(\d+)", entry).group(1)))
+    """textured_resolve_kernel uses no scratch and spills nothing, and keeps within its built VGPR count (52)
+    rounded up to the next step of 8.  Only the register, scratch and spill notes of the code object are read."""
+    from tests._util import kernel_resources
+    found = kernel_resources(b"textured_resolve_kernel")
     print("\n[texture] (VGPRs, scratch bytes, spilled): %s" % found)
     assert set(found) == {"textured_resolve_kernel"}, found  # the visibility kernel stays in raster.hip's code object
     assert found["textured_resolve_kernel"][0] <= 56 and found["textured_resolve_kernel"][1:] == (0, 0), found

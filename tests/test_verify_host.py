@@ -150,34 +150,12 @@ def test_render_compare_refusals():
 
 def test_kernel_resources():
     """no kernel of verify.hip uses scratch or spills, and each keeps within its built VGPR count rounded
-    up to the next step of 8 (built: windows_faces 80, windows_finish 6, verify_faces 63, verify_classify 24, verify_mask_area 12,
+    up to the next step of 8 (built: windows_faces 80, windows_finish 6, verify_faces 63, verify_classify 22, verify_mask_area 12,
     verify_resolve 6, overlay_instances 14).  Read from the code object's metadata: the compiler's figures, not a GPU's."""
-    import os
-    import re
-    import subprocess
-    from tests.test_abi import _gfx950_code_objects
-    readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    if not os.path.exists(readelf):
-        pytest.skip("llvm-readelf not available")
+    from tests._util import kernel_resources
     limits = dict(windows_faces_kernel=80, windows_finish_kernel=8, verify_faces_kernel=64, verify_classify_kernel=24,
                   verify_mask_area_kernel=16, verify_resolve_kernel=8, overlay_instances_kernel=16)
-    found = {}
-    for blob in _gfx950_code_objects(_lib.LIB_PATH):
-        if b"verify_classify_kernel" not in blob:
-            continue
-        p = os.path.join(os.environ.get("TMPDIR", "/tmp"), "verify_co_%d.elf" % os.getpid())
-        with open(p, "wb") as fh:
-            fh.write(blob)
-        try:
-            notes = subprocess.run([readelf, "--notes", p], capture_output=True, text=True, check=True).stdout
-        finally:
-            os.remove(p)
-        for entry in re.split(r"\n\s*- \.agpr_count", notes):
-            name = re.search(r"\.name:\s+_Z\d+([a-z_]+_kernel)", entry)
-            if name:
-                found[name.group(1)] = (int(re.search(r"\.vgpr_count:\s+(\d+)", entry).group(1)),
-                                        int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", entry).group(1)),
-                                        int(re.search(r"\.vgpr_spill_count:\s+(\d+)", entry).group(1)))
+    found = kernel_resources(b"verify_classify_kernel")
     print("\n[verify] (VGPRs, scratch bytes, spilled): %s" % found)
     assert set(found) == set(limits), found
     for name, cap in limits.items():
