@@ -1042,6 +1042,52 @@ int sam6d_template_crops(const unsigned char* rgb, long rgb_pixel_stride, long r
                          long mask_pixel_stride, long mask_image_stride, const long long* boxes, int T, int H, int W, int flavour,
                          float* out_rgb, float* out_mask, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Scoring poses against ground truth: MSSD, MSPD, ADD and VSD (csrc/poseerr.hip, restated in tests/poseerr_ref.py).
+ * (New entries only, so SAM6D_ABI_VERSION stays.)
+ * ------------------------------------------------------------------------------------------------------------ */
+/* The point errors of N estimated poses against their ground truths.  Beside PEM/run_inference_custom_pytorch.py:460-471, which
+ * writes its poses and has no evaluation: the errors are the published ones (Hodan et al., BOP Challenge 2020; ADD: Hinterstoisser
+ * et al. 2012), restated by the package and pinned against its numpy restatement, not against bop_toolkit.
+ * points (V,3) f32 model vertices in CAD units; est, gt (N,3,4) f32 row-major object -> camera; syms (S,3,4) f32 the object's symmetry
+ * transforms in CAD units (row 0 the identity by convention, not enforced); fx fy cx cy the camera; inv_unit > 0, finite.
+ * Per pose n and symmetry s, G = fl32(gt[n] o syms[s]) (formed in float64); per point e = est[n] x, g = G x, d2 = |e - g|^2, and
+ * p2 = the squared pixel distance of their projections u = fx * (x / z) + cx, v = fy * (y / z) + cy, all fp32 in the order of the
+ * recipe at the top of csrc/poseerr.hip.  A point with e_z > 0 or g_z > 0 false takes no part in the pair's p2 maximum; n_skipped[n]
+ * counts such points for s = 0.
+ * mssd[n] = sqrtf(min_s max_x d2), mspd[n] = sqrtf(min_s max_x p2) f32; mssd_sym[n], mspd_sym[n] i32 the lowest s that attains the
+ * minimum; add_sum[n] i64 = sum_x rint((double)sqrtf(d2 at s = 0) * inv_unit * 2^30), a term above 2^42 (4096 units; a NaN too)
+ * counted as 2^42: ADD = add_sum / 2^30 / inv_unit / V.  Integer atomic maxima and adds only: a function of the inputs alone.
+ * V 1 .. 2^20, N 1 .. 1024, S 1 .. 1024; workspace and add_sum 8-byte aligned, the workspace at least
+ * sam6d_pose_point_errors_workspace_bytes(N, S) = 8 N S (0 for sizes outside the limits); anything else, a null pointer or a
+ * non-finite inv_unit returns non-zero without a launch or a write, the argument named in sam6d_last_error(). */
+size_t sam6d_pose_point_errors_workspace_bytes(int N, int S);
+int sam6d_pose_point_errors(const float* points, int V, const float* est, const float* gt, int N, const float* syms, int S, float fx,
+                            float fy, float cx, float cy, float inv_unit, float* mssd, float* mspd, int* mssd_sym, int* mspd_sym,
+                            int* n_skipped, long long* add_sum, void* workspace, size_t workspace_bytes, void* stream);
+/* The counts of BOP's Visible Surface Discrepancy for N pose pairs.  Beside PEM/run_inference_custom_pytorch.py:460-471, as above; the
+ * renderer is the package's own (Render/render_custom_templates.py:55-106 as sam6d_render_views restates it), so the figure is BOP's
+ * in kind and not pixel for pixel.  Mesh, camera, near, wave_area as in sam6d_pose_verify.  view (2N,3,4) f32: views 0 .. N-1 the
+ * estimates, N .. 2N-1 the ground truths; box (2N,4) i32 and offset (2N+1) i64 on the device as in sam6d_pose_verify, both views of a
+ * pair with the same box (the union of their sam6d_pose_windows boxes), so that the ground-truth word of word i is i + offset[N];
+ * total: the host's copy of offset[2N].  depth_obs (H,W) f32; delta >= 0 finite, in the unit of camera z; taus: T numbers >= 0 ON THE
+ * HOST, T 1 .. 16; inv_norm > 0 finite (1, or 1 / the model's diameter).
+ * Per window pixel, with the rendered depths r_e, r_g (or absent), o = depth_obs[y][x] a reading when o > 0, and distances D = z * c,
+ * c = sqrtf((ax ax + ay ay) + 1), ax = ((float)x - cx) / fx: visib_gt = has_g && (!reading || D_g - D_o <= delta),
+ * visib_est = has_e && (!reading || D_e - D_o <= delta || visib_gt) (BOP's `bop19` visibility); cost_k counts the pixels visible in
+ * both with fabsf(D_g - D_e) * inv_norm >= taus[k] (BOP's `step` cost).
+ * counts (N, 4+T) i32 = n_union, n_inter, n_visib_est, n_visib_gt, cost_0 .. cost_{T-1}; VSD_k = (cost_k + n_union - n_inter) /
+ * n_union, 1 where n_union is 0.  total == 0: all 0.  64-bit atomic minima and 32-bit atomic adds only: a function of the inputs
+ * alone.  The kernels clamp every box to the image and address no word at or beyond `total`, whatever box and offset hold.
+ * Limits of sam6d_pose_windows with N 1 .. 512, wave_area >= 0, fx and fy not 0, total 0 .. 2 N H W, workspace 8-byte aligned and at
+ * least sam6d_pose_vsd_workspace_bytes(total, N) = 8 total + 64 N (the z-buffer words, and the raster pass's counter words; 0 for
+ * sizes outside the limits); anything else or a null pointer returns non-zero without a launch or a write. */
+size_t sam6d_pose_vsd_workspace_bytes(long total, int N);
+int sam6d_pose_vsd(const float* vertices, int V, const int* faces, int F, const float* view, int N, float fx, float fy, float cx,
+                   float cy, int H, int W, float near, int wave_area, const int* box, const long long* offset, long total,
+                   const float* depth_obs, float delta, const float* taus, int T, float inv_norm, int* counts, void* workspace,
+                   size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,395 @@
+// Scoring poses against ground truth: the BOP pose errors MSSD, MSPD and VSD (Hodan et al., "BOP Challenge 2020 on 6D Object
+// Localization", section 2.2) and ADD (Hinterstoisser et al. 2012), batched over N pose pairs.  The reference has no evaluation code:
+// it writes its poses (PEM/run_inference_custom_pytorch.py:460-471) and leaves the scoring to bop_toolkit.  The definitions are the
+// published ones, restated here and pinned against the numpy restatement tests/poseerr_ref.py -- NOT against bop_toolkit, which the
+// suite does not have.  VSD renders with the package's own rasteriser (verify.hip's raster pass: verify_raster.h), so it is BOP's in
+// kind and not pixel for pixel.  Every comparison with the restatement is bit for bit.
+//
+// RECIPE.  All float arithmetic is IEEE fp32 in the order written unless float64 is named (the library is built with
+// -ffp-contract=off and this file has no fused multiply-add), everything else is integer.
+//
+//  a. point errors (sam6d_pose_point_errors), per pose n, symmetry s and model point x:
+//   G        = gt[n] o syms[s] in float64 from the fp32 factors: G_rc = (gt_r0 S_0c + gt_r1 S_1c) + gt_r2 S_2c, and for c = 3
+//            ... + gt_r3 (the products are exact, the sums run left to right), rounded once to fp32.
+//   points   e = E x and g = G x with E = est[n]: ((M_r0 x0 + M_r1 x1) + M_r2 x2) + M_r3 (raster.h's rs_to_camera).
+//   d2       = (dx dx + dy dy) + dz dz with d = e - g.
+//   pixels   u_e = fx * (e0 / e2) + cx, v_e = fy * (e1 / e2) + cy, the same for g; p2 = du du + dv dv with du = u_e - u_g.
+//   skipped  a point with e2 > 0 false or g2 > 0 false takes no part in the pair's p2 maximum (it does in the d2 maximum);
+//            n_skipped[n] counts such points for s = 0 only.  The package's own rule, as draw_detections' behind-camera rule; BOP
+//            divides regardless.  A pair all of whose points are skipped has the p2 maximum 0.
+//   maxima   over the points, of the bit patterns: a value > 0 orders as its bits, 0 is 0, and anything else (a NaN) counts as
+//            0x7fc00000, above every number.
+//   MSSD     mssd[n] = sqrtf(min_s max_x d2), mssd_sym[n] = the lowest s that attains the minimum.  MSPD: the same with p2.
+//   ADD      add_sum[n] = sum_x rint(w) with w = ((double)sqrtf(d2 at s = 0) * (double)inv_unit) * 2^30, and w = 2^42 where
+//            w <= 2^42 is false (4096 units; also a NaN): a 64-bit integer sum, at most 2^20 * 2^42 = 2^62.
+//
+//  b. VSD (sam6d_pose_vsd).  2N views: 0 .. N-1 the estimates, N .. 2N-1 the ground truths, rastered into their windows by
+//     verify_faces_kernel unchanged (verify.hip RECIPE b).  Both views of a pair have the same window (the caller's: the union of their
+//     boxes), so the halves have the same layout and the ground-truth word of word i < offset[N] is i + offset[N].  Per word i of pair
+//     n at pixel (x, y), with r_e and r_g the depths in the two keys or absent (has_e, has_g):
+//   reading  o = depth_obs[y][x] is one when o > 0 (false also for a NaN, as in verify.hip).
+//   distance c = sqrtf((ax ax + ay ay) + 1) with ax = ((float)x - cx) / fx, ay = ((float)y - cy) / fy; D = z * c for r_e, r_g and o.
+//   visible  visib_gt = has_g && (!reading || D_g - D_o <= delta);
+//            visib_est = has_e && (!reading || D_e - D_o <= delta || visib_gt)           (BOP's visibility mode `bop19`)
+//   sets     inter = visib_est && visib_gt, union = visib_est || visib_gt.
+//   cost     cost_k = the inter pixels with fabsf(D_g - D_e) * inv_norm >= taus[k]          (BOP's cost type `step`)
+//   counts   (N, 4 + T) i32 = n_union, n_inter, n_visib_est, n_visib_gt, cost_0 .. cost_{T-1}.  total == 0: all 0, no pass runs.
+//     The caller forms vsd[n][k] = (cost_k + n_union - n_inter) / n_union, and 1 where n_union is 0, as BOP does.
+//
+// WHY THE RESULT IS A FUNCTION OF THE INPUTS ALONE.  Where workgroups meet it is an integer atomic at agent scope: 32-bit maxima (the
+// d2 and p2 bit patterns), 32-bit adds (the counters), 64-bit adds (add_sum), 64-bit minima (the z-buffer), all commutative and
+// associative.  The buffers are set by memsets that precede the kernels in stream order, nothing reads a buffer in the launch that
+// reduces into it, and mssd, mspd and their indices have one writer, point_errors_finish_kernel's wave of the pose.
+//
+// WORK.  point errors: N S V point transforms.  A workgroup of four waves takes 1024 points of one pose, four per thread, and keeps
+// their x, e and (u_e, v_e) in registers across the loop over s; the G of 128 symmetries at a time are formed once per workgroup into
+// LDS and read from there as broadcasts; per s the wave's two maxima are reduced on the DPP path (no LDS round trip), meet the other
+// waves' in LDS, and leave as one atomic per word, workgroup and tile.  finish: one wave per pose takes the minima over s as 64-bit
+// keys (bits << 32 | s: the lowest s wins a tie).  VSD: verify_faces_kernel, then one thread per window word of the estimates' half,
+// sixteen waves to a workgroup, the counters reduced per pose inside the wave and then in LDS as verify_classify_kernel does.
+//
+// WHAT THE HOST CANNOT SEE.  box and offset are on the device: the window is the box clamped to the image, no word at or beyond
+// `total` (or below 0) is addressed whatever they hold, and counts is addressed by a pose index in [0, N) alone.  Inconsistent boxes
+// and offsets give meaningless counts, never an access outside the buffers.
+#include "verify_raster.h"
+#include "../../include/sam6d_hip.h"
+
+#define PE_MAX_V (1 << 20)
+#define PE_MAX_N 1024
+#define PE_MAX_S 1024
+#define PE_MAX_PAIRS 512
+#define PE_MAX_T 16
+#define PE_WG 256
+#define PE_PTS 4                    // points per thread
+#define PE_CHUNK (PE_WG * PE_PTS)   // points per workgroup
+#define PE_ST 128                   // symmetries per LDS tile
+#define PE_VSD_WG 1024              // sixteen waves, as verify.hip's classify: one offer per workgroup at a pose's counters
+#define PE_NAN 0x7fc00000u
+#define PE_SCALE 1073741824.0       // 2^30
+#define PE_TERM_MAX 4398046511104.0 // 2^42
+
+struct PeCam {
+  float fx, fy, cx, cy;
+};
+struct PeTaus {
+  float v[PE_MAX_T];
+};
+
+// ---------------------------------------------------------------------------------------------------------- a. point errors
+// RECIPE maxima: the word a value offers
+__device__ __forceinline__ unsigned pe_bits(float v) { return v > 0.f ? __float_as_uint(v) : (v == 0.f ? 0u : PE_NAN); }
+
+template <int CTRL>
+__device__ __forceinline__ unsigned pe_dpp(unsigned x) {
+  return (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xf, 0xf, false);
+}
+// the maximum over the wave in every lane, on the DPP path as common.h's wave_max_dpp: rotations inside each row of 16, then the
+// exchanges with the lanes 16 and 32 away
+__device__ __forceinline__ unsigned pe_wave_max(unsigned v) {
+  typedef unsigned u2_ __attribute__((ext_vector_type(2)));
+  v = max(v, pe_dpp<0x128>(v));  // row_ror:8
+  v = max(v, pe_dpp<0x124>(v));  // row_ror:4
+  v = max(v, pe_dpp<0x122>(v));  // row_ror:2
+  v = max(v, pe_dpp<0x121>(v));  // row_ror:1
+  const u2_ a = __builtin_amdgcn_permlane16_swap(v, v, false, false);
+  v = max(v, (threadIdx.x & 16) ? a[0] : a[1]);
+  const u2_ b = __builtin_amdgcn_permlane32_swap(v, v, false, false);
+  return max(v, (threadIdx.x & 32) ? b[0] : b[1]);
+}
+
+// grid (ceil(V / 1024), N), four waves: point blockIdx.x * 1024 + j * 256 + tid for j = 0 .. 3.  ws (N,S,2) u32 arrives zeroed:
+// word 0 the d2 maximum of the pair, word 1 the p2 maximum
+__global__ __launch_bounds__(PE_WG) void point_errors_kernel(const float* __restrict__ points, int V, const float* __restrict__ est,
+                                                             const float* __restrict__ gt, const float* __restrict__ syms, int S, PeCam cam,
+                                                             float inv_unit, unsigned* __restrict__ ws, int* __restrict__ n_skipped,
+                                                             unsigned long long* __restrict__ add_sum) {
+  __shared__ float G[PE_ST][12];
+  __shared__ unsigned mx[PE_ST * 2];
+  const int n = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
+  const float* E = est + (size_t)n * 12;
+  const float* Gt = gt + (size_t)n * 12;
+  float x[PE_PTS][3], e[PE_PTS][3], ue[PE_PTS], ve[PE_PTS];
+  bool live[PE_PTS], front[PE_PTS];
+#pragma unroll
+  for (int j = 0; j < PE_PTS; ++j) {
+    const int idx = blockIdx.x * PE_CHUNK + j * PE_WG + tid;  // below 2^20 + 1024
+    live[j] = idx < V;
+    x[j][0] = x[j][1] = x[j][2] = 0.f;
+    if (live[j]) {
+      x[j][0] = points[(size_t)idx * 3];
+      x[j][1] = points[(size_t)idx * 3 + 1];
+      x[j][2] = points[(size_t)idx * 3 + 2];
+    }
+    rs_to_camera(E, x[j], e[j]);
+    front[j] = e[j][2] > 0.f;
+    ue[j] = cam.fx * (e[j][0] / e[j][2]) + cam.cx;
+    ve[j] = cam.fy * (e[j][1] / e[j][2]) + cam.cy;
+  }
+  for (int s0 = 0; s0 < S; s0 += PE_ST) {
+    const int cnt = min(PE_ST, S - s0);
+    __syncthreads();  // the tile before is flushed
+    for (int t = tid; t < cnt * 12; t += PE_WG) {
+      const int sl = t / 12, k = t % 12, r = k >> 2, c = k & 3;
+      const float* Sm = syms + (size_t)(s0 + sl) * 12;
+      double a = (double)Gt[r * 4] * (double)Sm[c];
+      a = a + (double)Gt[r * 4 + 1] * (double)Sm[4 + c];
+      a = a + (double)Gt[r * 4 + 2] * (double)Sm[8 + c];
+      if (c == 3) a = a + (double)Gt[r * 4 + 3];
+      G[sl][k] = (float)a;
+    }
+    for (int t = tid; t < cnt * 2; t += PE_WG) mx[t] = 0u;
+    __syncthreads();
+    for (int sl = 0; sl < cnt; ++sl) {
+      float M[12];
+#pragma unroll
+      for (int k = 0; k < 12; ++k) M[k] = G[sl][k];
+      unsigned m2 = 0u, mp = 0u;
+      float d2s[PE_PTS];
+      bool skip[PE_PTS];
+#pragma unroll
+      for (int j = 0; j < PE_PTS; ++j) {
+        float g[3];
+        rs_to_camera(M, x[j], g);
+        const float dx = e[j][0] - g[0], dy = e[j][1] - g[1], dz = e[j][2] - g[2];
+        const float d2 = (dx * dx + dy * dy) + dz * dz;
+        const float ug = cam.fx * (g[0] / g[2]) + cam.cx, vg = cam.fy * (g[1] / g[2]) + cam.cy;
+        const float du = ue[j] - ug, dv = ve[j] - vg;
+        const float p2 = du * du + dv * dv;
+        skip[j] = !(front[j] && g[2] > 0.f);
+        d2s[j] = d2;
+        if (live[j]) {
+          m2 = max(m2, pe_bits(d2));
+          if (!skip[j]) mp = max(mp, pe_bits(p2));
+        }
+      }
+      if (s0 + sl == 0) {  // (uniform) ADD and the skipped points, of the first symmetry alone
+        long long term = 0;
+        int skipped = 0;
+#pragma unroll
+        for (int j = 0; j < PE_PTS; ++j) {
+          if (!live[j]) continue;
+          double w = ((double)sqrtf(d2s[j]) * (double)inv_unit) * PE_SCALE;
+          if (!(w <= PE_TERM_MAX)) w = PE_TERM_MAX;
+          term += (long long)rint(w);
+          skipped += skip[j] ? 1 : 0;
+        }
+        term = wave_sum(term);
+        skipped = wave_sum(skipped);
+        if (lane == 0) {
+          if (term) __hip_atomic_fetch_add(add_sum + n, (unsigned long long)term, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          if (skipped) vf_add(n_skipped + n, skipped);
+        }
+      }
+      m2 = pe_wave_max(m2);
+      mp = pe_wave_max(mp);
+      if (lane == 0) {
+        if (m2) atomicMax(&mx[sl * 2], m2);
+        if (mp) atomicMax(&mx[sl * 2 + 1], mp);
+      }
+    }
+    __syncthreads();
+    for (int t = tid; t < cnt * 2; t += PE_WG) {
+      const unsigned v = mx[t];
+      if (v) __hip_atomic_fetch_max(ws + ((size_t)n * S + s0) * 2 + t, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
+__device__ __forceinline__ unsigned long long pe_wave_min_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long w = __shfl_xor(v, o, 64);
+    v = w < v ? w : v;
+  }
+  return v;
+}
+
+// one wave per pose: the only writer of mssd, mspd and their indices
+__global__ __launch_bounds__(64) void point_errors_finish_kernel(const unsigned* __restrict__ ws, int S, float* __restrict__ mssd,
+                                                                 float* __restrict__ mspd, int* __restrict__ mssd_sym,
+                                                                 int* __restrict__ mspd_sym) {
+  const int n = blockIdx.x, lane = threadIdx.x;
+  unsigned long long k2 = ~0ull, kp = ~0ull;
+  for (int s = lane; s < S; s += 64) {
+    const unsigned* w = ws + ((size_t)n * S + s) * 2;
+    const unsigned long long a = ((unsigned long long)w[0] << 32) | (unsigned)s, b = ((unsigned long long)w[1] << 32) | (unsigned)s;
+    k2 = a < k2 ? a : k2;
+    kp = b < kp ? b : kp;
+  }
+  k2 = pe_wave_min_u64(k2);
+  kp = pe_wave_min_u64(kp);
+  if (lane != 0) return;
+  mssd[n] = sqrtf(__uint_as_float((unsigned)(k2 >> 32)));
+  mssd_sym[n] = (int)(unsigned)(k2 & 0xffffffffull);
+  mspd[n] = sqrtf(__uint_as_float((unsigned)(kp >> 32)));
+  mspd_sym[n] = (int)(unsigned)(kp & 0xffffffffull);
+}
+
+extern "C" size_t sam6d_pose_point_errors_workspace_bytes(int N, int S) {
+  if (N < 1 || N > PE_MAX_N || S < 1 || S > PE_MAX_S) return 0;
+  return (size_t)N * S * 2 * sizeof(unsigned);
+}
+
+#define PE_POINTER(who, p) SAM6D_REQUIRE((p) != nullptr, who ": " #p " is a null pointer")
+
+extern "C" int sam6d_pose_point_errors(const float* points, int V, const float* est, const float* gt, int N, const float* syms, int S,
+                                       float fx, float fy, float cx, float cy, float inv_unit, float* mssd, float* mspd, int* mssd_sym,
+                                       int* mspd_sym, int* n_skipped, long long* add_sum, void* workspace, size_t workspace_bytes,
+                                       void* stream) {
+  SAM6D_REQUIRE(V >= 1 && V <= PE_MAX_V, "pose_point_errors: V = %d is not in 1 .. %d", V, PE_MAX_V);
+  SAM6D_REQUIRE(N >= 1 && N <= PE_MAX_N, "pose_point_errors: N = %d is not in 1 .. %d", N, PE_MAX_N);
+  SAM6D_REQUIRE(S >= 1 && S <= PE_MAX_S, "pose_point_errors: S = %d is not in 1 .. %d", S, PE_MAX_S);
+  SAM6D_REQUIRE(inv_unit > 0.f && inv_unit <= 3.4028234e38f, "pose_point_errors: inv_unit = %g is not a finite number > 0", (double)inv_unit);
+  PE_POINTER("pose_point_errors", points);
+  PE_POINTER("pose_point_errors", est);
+  PE_POINTER("pose_point_errors", gt);
+  PE_POINTER("pose_point_errors", syms);
+  PE_POINTER("pose_point_errors", mssd);
+  PE_POINTER("pose_point_errors", mspd);
+  PE_POINTER("pose_point_errors", mssd_sym);
+  PE_POINTER("pose_point_errors", mspd_sym);
+  PE_POINTER("pose_point_errors", n_skipped);
+  PE_POINTER("pose_point_errors", add_sum);
+  PE_POINTER("pose_point_errors", workspace);
+  const size_t need = sam6d_pose_point_errors_workspace_bytes(N, S);
+  SAM6D_REQUIRE(workspace_bytes >= need, "pose_point_errors: workspace of %zu bytes is below sam6d_pose_point_errors_workspace_bytes = %zu",
+                workspace_bytes, need);
+  SAM6D_REQUIRE(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)add_sum & 7) == 0, "pose_point_errors: workspace or add_sum is not 8-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t e = hipMemsetAsync(workspace, 0, need, s);
+  if (e == hipSuccess) e = hipMemsetAsync(n_skipped, 0, (size_t)N * sizeof(int), s);
+  if (e == hipSuccess) e = hipMemsetAsync(add_sum, 0, (size_t)N * sizeof(long long), s);
+  if (e != hipSuccess) {
+    sam6d_set_error("pose_point_errors: memset failed: %s", hipGetErrorString(e));
+    return (int)e;
+  }
+  const PeCam cam = {fx, fy, cx, cy};
+  hipLaunchKernelGGL(point_errors_kernel, dim3((V + PE_CHUNK - 1) / PE_CHUNK, N), dim3(PE_WG), 0, s, points, V, est, gt, syms, S, cam, inv_unit,
+                     (unsigned*)workspace, n_skipped, (unsigned long long*)add_sum);
+  SAM6D_LAUNCH_CHECK_CONT("pose_point_errors (points)");
+  hipLaunchKernelGGL(point_errors_finish_kernel, dim3(N), dim3(64), 0, s, (const unsigned*)workspace, S, mssd, mspd, mssd_sym, mspd_sym);
+  SAM6D_LAUNCH_CHECK("pose_point_errors (finish)");
+}
+
+// ---------------------------------------------------------------------------------------------------------- b. VSD
+// One thread per window word of the estimates' half (the grid is sized by `total`, the host's figure; a workgroup beyond the half
+// leaves at once), sixteen waves in a workgroup.  The walk from word i to its pair and pixel is vf_word's, without its test of the
+// key: a pixel counts when either key of the pair is there.  The counts of the pair of the workgroup's first word are gathered in
+// LDS and leave as one atomic per counter and workgroup, a wave's counts for another pair as one atomic per counter and wave.
+__global__ __launch_bounds__(PE_VSD_WG) void vsd_compare_kernel(const unsigned long long* __restrict__ zbuf, long long total,
+                                                            const int* __restrict__ box, const long long* __restrict__ offset, int N, int H,
+                                                            int W, const float* __restrict__ depth_obs, PeCam cam, float delta, PeTaus taus,
+                                                            int T, float inv_norm, int* __restrict__ counts) {
+  __shared__ int wg[4 + PE_MAX_T];
+  const long long half = offset[N];
+  const long long lim = half < total ? half : total;  // words of the estimates' half that exist
+  const long long base = (long long)blockIdx.x * PE_VSD_WG, i = base + threadIdx.x;
+  if (base >= lim) return;  // (uniform over the workgroup; also a negative half)
+  const int lane = threadIdx.x & 63, C = 4 + T;
+  if (threadIdx.x < C) wg[threadIdx.x] = 0;
+  const int nb = vf_first_pose(offset, N, base);
+  int n = nb;
+  bool uni = false, inter = false, v_e = false, v_g = false;
+  float err = 0.f;
+  if (i < lim) {
+    while (n + 1 < N && offset[n + 1] <= i) ++n;
+    const VfWin w = vf_window(box, offset, n, H, W);
+    const long long local = i - w.off;
+    const unsigned long long j = (unsigned long long)i + (unsigned long long)half;  // (unsigned: whatever offset[N] holds, no overflow)
+    if (local >= 0 && local < (long long)w.bw * w.bh) {
+      const unsigned long long ke = zbuf[i];
+      const unsigned long long kg = j < (unsigned long long)total ? zbuf[j] : VF_EMPTY;
+      const bool has_e = ke != VF_EMPTY, has_g = kg != VF_EMPTY;
+      if (has_e || has_g) {
+        const int y = w.y0 + (int)(local / w.bw), x = w.x0 + (int)(local % w.bw);
+        const float o = depth_obs[(size_t)y * W + x];
+        const bool reading = o > 0.f;
+        const float ax = ((float)x - cam.cx) / cam.fx, ay = ((float)y - cam.cy) / cam.fy;
+        const float c = sqrtf((ax * ax + ay * ay) + 1.f);
+        const float De = __uint_as_float((unsigned)(ke >> 32)) * c, Dg = __uint_as_float((unsigned)(kg >> 32)) * c, Do = o * c;
+        v_g = has_g && (!reading || Dg - Do <= delta);
+        v_e = has_e && (!reading || De - Do <= delta || v_g);
+        inter = v_e && v_g;
+        uni = v_e || v_g;
+        err = fabsf(Dg - De) * inv_norm;
+      }
+    }
+  }
+  __syncthreads();  // wg is zero
+  int* const wg_of_nb = wg;
+  vf_each_pose(uni, n, [=](int lead, int pn, bool mine, unsigned long long m) {
+    int c[4 + PE_MAX_T];
+    c[0] = (int)__popcll(m);
+    c[1] = (int)__popcll(__ballot(mine && inter));
+    c[2] = (int)__popcll(__ballot(mine && v_e));
+    c[3] = (int)__popcll(__ballot(mine && v_g));
+#pragma unroll
+    for (int k = 0; k < PE_MAX_T; ++k) c[4 + k] = k < T ? (int)__popcll(__ballot(mine && inter && err >= taus.v[k])) : 0;
+    if (lane != lead) return;
+#pragma unroll
+    for (int k = 0; k < 4 + PE_MAX_T; ++k) {
+      if (k >= C || !c[k]) continue;
+      if (pn == nb) atomicAdd(&wg_of_nb[k], c[k]);
+      else vf_add(counts + (size_t)pn * C + k, c[k]);
+    }
+  });
+  __syncthreads();
+  if (threadIdx.x < C && wg[threadIdx.x]) vf_add(counts + (size_t)nb * C + threadIdx.x, wg[threadIdx.x]);
+}
+
+extern "C" size_t sam6d_pose_vsd_workspace_bytes(long total, int N) {
+  if (N < 1 || N > PE_MAX_PAIRS || total < 0 || total > 2L * N * RS_MAX_HW * RS_MAX_HW) return 0;
+  return (size_t)total * sizeof(unsigned long long) + (size_t)N * 2 * 8 * sizeof(int);
+}
+
+extern "C" int sam6d_pose_vsd(const float* vertices, int V, const int* faces, int F, const float* view, int N, float fx, float fy, float cx,
+                              float cy, int H, int W, float near, int wave_area, const int* box, const long long* offset, long total,
+                              const float* depth_obs, float delta, const float* taus, int T, float inv_norm, int* counts, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+  const int bad = rs_limits("pose_vsd", V, F, "N", N, PE_MAX_PAIRS, H, W, near);
+  if (bad) return bad;
+  SAM6D_REQUIRE(wave_area >= 0, "pose_vsd: wave_area = %d is negative", wave_area);
+  SAM6D_REQUIRE(delta >= 0.f && delta <= 3.4028234e38f, "pose_vsd: delta = %g is not a finite number >= 0", (double)delta);
+  SAM6D_REQUIRE(inv_norm > 0.f && inv_norm <= 3.4028234e38f, "pose_vsd: inv_norm = %g is not a finite number > 0", (double)inv_norm);
+  SAM6D_REQUIRE(fx != 0.f && fy != 0.f && fx == fx && fy == fy, "pose_vsd: fx, fy = %g, %g: zero or not a number", (double)fx, (double)fy);
+  SAM6D_REQUIRE(T >= 1 && T <= PE_MAX_T, "pose_vsd: T = %d is not in 1 .. %d", T, PE_MAX_T);
+  SAM6D_REQUIRE(total >= 0 && total <= 2L * N * H * W, "pose_vsd: total = %ld is not in 0 .. 2 N H W = %ld", total, 2L * N * H * W);
+  PE_POINTER("pose_vsd", vertices);
+  PE_POINTER("pose_vsd", faces);
+  PE_POINTER("pose_vsd", view);
+  PE_POINTER("pose_vsd", box);
+  PE_POINTER("pose_vsd", offset);
+  PE_POINTER("pose_vsd", depth_obs);
+  PE_POINTER("pose_vsd", taus);
+  PE_POINTER("pose_vsd", counts);
+  PE_POINTER("pose_vsd", workspace);
+  PeTaus tv;
+  for (int k = 0; k < PE_MAX_T; ++k) {
+    tv.v[k] = k < T ? taus[k] : 0.f;
+    SAM6D_REQUIRE(tv.v[k] >= 0.f && tv.v[k] <= 3.4028234e38f, "pose_vsd: taus[%d] = %g is not a finite number >= 0", k, (double)tv.v[k]);
+  }
+  const size_t need = sam6d_pose_vsd_workspace_bytes(total, N);
+  SAM6D_REQUIRE(workspace_bytes >= need, "pose_vsd: workspace of %zu bytes is below sam6d_pose_vsd_workspace_bytes = %zu", workspace_bytes,
+                need);
+  SAM6D_REQUIRE(((uintptr_t)workspace & 7) == 0, "pose_vsd: workspace is not 8-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  const RsCam cam = {fx, fy, cx, cy, near, H, W};
+  unsigned long long* zbuf = (unsigned long long*)workspace;
+  int* dropped = (int*)(zbuf + total);  // the raster pass's dropped-face counter lives in column 7 of (2N,8); nothing reads it
+  hipError_t e = hipMemsetAsync(counts, 0, (size_t)N * (4 + T) * sizeof(int), s);
+  if (e == hipSuccess && total > 0) e = hipMemsetAsync(zbuf, 0xff, (size_t)total * 8, s);
+  if (e == hipSuccess && total > 0) e = hipMemsetAsync(dropped, 0, (size_t)N * 2 * 8 * sizeof(int), s);
+  if (e != hipSuccess) {
+    sam6d_set_error("pose_vsd: memset failed: %s", hipGetErrorString(e));
+    return (int)e;
+  }
+  if (total == 0) return 0;
+  hipLaunchKernelGGL(verify_faces_kernel, dim3((F + 63) / 64, 2 * N), dim3(64), 0, s, vertices, V, faces, F, view, cam,
+                     wave_area ? wave_area : RS_WAVE_AREA, box, offset, (long long)total, zbuf, dropped);
+  SAM6D_LAUNCH_CHECK_CONT("pose_vsd (faces)");
+  // total <= 2^32: at most 2^22 blocks
+  const PeCam pc = {fx, fy, cx, cy};
+  hipLaunchKernelGGL(vsd_compare_kernel, dim3((unsigned)((total + PE_VSD_WG - 1) / PE_VSD_WG)), dim3(PE_VSD_WG), 0, s, zbuf, (long long)total, box, offset, N, H,
+                     W, depth_obs, pc, delta, tv, T, inv_norm, counts);
+  SAM6D_LAUNCH_CHECK("pose_vsd (compare)");
+}

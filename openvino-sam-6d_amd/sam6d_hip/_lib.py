@@ -178,6 +178,11 @@ SIGNATURES = {
                                ctypes.c_double, c_i, ctypes.c_double, c_p, c_p, c_p, c_p, ctypes.c_size_t, c_p],
     "sam6d_template_boxes": [c_p, c_i, c_i, c_i, c_l, c_l, c_p, c_p],
     "sam6d_template_crops": [c_p, c_l, c_l, c_p, c_l, c_l, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p],
+    "sam6d_pose_point_errors_workspace_bytes": [c_i, c_i],
+    "sam6d_pose_point_errors": [c_p, c_i, c_p, c_p, c_i, c_p, c_i] + [c_f] * 5 + [c_p] * 7 + [ctypes.c_size_t, c_p],
+    "sam6d_pose_vsd_workspace_bytes": [c_l, c_i],
+    "sam6d_pose_vsd": [c_p, c_i, c_p, c_i, c_p, c_i] + [c_f] * 4 + [c_i, c_i, c_f, c_i, c_p, c_p, c_l, c_p, c_f, c_p, c_i, c_f, c_p, c_p,
+                       ctypes.c_size_t, c_p],
 }
 
 _lib = None
