@@ -19,11 +19,60 @@
 // NW wave slots.
 //
 // Selection rule: max distance, lowest index on ties == the reference's strict `d2 > best` scan in increasing k (sampling.cpp:105-111).
-// (fps_big_kernel / fps_grid_kernel pack it into one 64-bit key: d2 >= +0 so its bit pattern is monotone; key = bits(d2) << 32 | ~idx.)
-// Points inside the origin ball (mag <= 1e-3, compared in double like the reference, sampling.cpp:102-103) never
-// compete and keep temp = FLT_MAX (key 0 / candidate distance -1).  If every point is skipped the result is index 0, as in the
-// reference (besti initialised to 0).
+// Points inside the origin ball never compete and keep temp = FLT_MAX (key 0 / candidate distance -1).  If every point is skipped
+// the result is index 0, as in the reference (besti initialised to 0).
 // =========================================================================================================
+// The steps the three kernels share, each written once.
+// A point inside the origin ball is not live: mag <= 1e-3, compared in double like the reference (sampling.cpp:102-103).
+__device__ __forceinline__ bool fps_live(float x, float y, float z) {
+  const float mag = x * x + y * y + z * z;
+  return !((double)mag <= 1e-3);
+}
+// the running min-distance `td` of the point (x, y, z) after (x1, y1, z1) was selected: std::min(d, td) (sampling.cpp:105-107)
+__device__ __forceinline__ float fps_min_dist(float td, float x, float y, float z, float x1, float y1, float z1) {
+  const float dx = x - x1, dy = y - y1, dz = z - z1;
+  const float d = dx * dx + dy * dy + dz * dz;
+  return (td < d) ? td : d;
+}
+// one of the points a lane keeps in registers: point k of the cloud p (in LDS or global memory); a lane slot past the cloud is not live
+struct FpsPoint {
+  float x, y, z, td;
+  bool live;
+};
+__device__ __forceinline__ FpsPoint fps_load_point(const float* p, int k, int N) {
+  FpsPoint q = {0.f, 0.f, 0.f, FLT_MAX, false};
+  if (k < N) {
+    q.x = p[(size_t)k * 3 + 0];
+    q.y = p[(size_t)k * 3 + 1];
+    q.z = p[(size_t)k * 3 + 2];
+    q.live = fps_live(q.x, q.y, q.z);
+  }
+  return q;
+}
+// fps_big_kernel / fps_grid_kernel pack the selection rule into one 64-bit key whose maximum is the winner: d2 >= +0 so its bit pattern
+// is monotone, and ~k makes the lower index the larger key on a tie; key = bits(d2) << 32 | ~k.  Key 0: no live point, index 0.
+__device__ __forceinline__ unsigned long long fps_key(float d2, unsigned k) {
+  return ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned long long)(~k);
+}
+__device__ __forceinline__ int fps_key_index(unsigned long long key) {
+  return (key == 0ull) ? 0 : (int)(~(unsigned int)(key & 0xffffffffull));
+}
+// the workgroup's maximum key, in every thread: wave maximum -> one LDS slot per wave -> one barrier -> the maximum of the NW slots
+// (`slots`: NW words, not reused before the next barrier -- the callers alternate between two sets)
+template <int NW>
+__device__ __forceinline__ unsigned long long fps_block_max_key(unsigned long long key, unsigned long long* slots, int t) {
+  key = wave_max_u64(key);
+  if ((t & 63) == 0) slots[t >> 6] = key;
+  __syncthreads();
+  unsigned long long best = slots[0];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) {
+    const unsigned long long v = slots[w];
+    best = v > best ? v : best;
+  }
+  return best;
+}
+
 // max reductions for the sampling rounds as single instructions (v_max_f32_dpp; the compiler's form of the same DPP step is a
 // v_mov 0, the DPP move, a canonicalising v_max and the v_max: the rounds are bound by instructions issued per round)
 template <int ROR>
@@ -80,23 +129,9 @@ __global__ __launch_bounds__(THREADS) void fps_reg_kernel(const float* __restric
   for (int i = t; i < N * 3; i += THREADS) sp[i] = p[i];
   __syncthreads();
 
-  float px[PPT], py[PPT], pz[PPT], td[PPT];
-  bool live[PPT];
+  FpsPoint pt[PPT];
 #pragma unroll
-  for (int i = 0; i < PPT; ++i) {
-    const int k = t * PPT + i;
-    if (k < N) {
-      px[i] = sp[k * 3 + 0];
-      py[i] = sp[k * 3 + 1];
-      pz[i] = sp[k * 3 + 2];
-      const float mag = px[i] * px[i] + py[i] * py[i] + pz[i] * pz[i];
-      live[i] = !((double)mag <= 1e-3);
-    } else {
-      px[i] = py[i] = pz[i] = 0.f;
-      live[i] = false;
-    }
-    td[i] = FLT_MAX;
-  }
+  for (int i = 0; i < PPT; ++i) pt[i] = fps_load_point(sp, t * PPT + i, N);
   if (t == 0) o[0] = 0;
   const float x0 = fps_uniform(sp[0]), y0 = fps_uniform(sp[1]), z0 = fps_uniform(sp[2]);
   float x1 = x0, y1 = y0, z1 = z0;  // the last selected point (wave-uniform: scalar registers)
@@ -106,16 +141,14 @@ __global__ __launch_bounds__(THREADS) void fps_reg_kernel(const float* __restric
     int bk = 0;
 #pragma unroll
     for (int i = 0; i < PPT; ++i) {
-      const float dx = px[i] - x1, dy = py[i] - y1, dz = pz[i] - z1;
-      const float d = dx * dx + dy * dy + dz * dz;
-      const float d2 = (td[i] < d) ? td[i] : d;
-      td[i] = live[i] ? d2 : td[i];
-      const bool take = live[i] & (d2 > bd);
+      const float d2 = fps_min_dist(pt[i].td, pt[i].x, pt[i].y, pt[i].z, x1, y1, z1);
+      pt[i].td = pt[i].live ? d2 : pt[i].td;
+      const bool take = pt[i].live & (d2 > bd);
       bd = take ? d2 : bd;
       bk = take ? t * PPT + i : bk;
-      bx = take ? px[i] : bx;
-      by = take ? py[i] : by;
-      bz = take ? pz[i] : bz;
+      bx = take ? pt[i].x : bx;
+      by = take ? pt[i].y : by;
+      bz = take ? pt[i].z : bz;
     }
     const float wm = fps_wave_max(bd);
     const int wl = __ffsll((long long)__ballot(bd == wm)) - 1;  // lowest lane with the wave maximum = lowest index
@@ -176,27 +209,13 @@ __global__ __launch_bounds__(THREADS) void fps_big_kernel(const float* __restric
     unsigned long long key = 0ull;
     for (int k = t; k < N; k += THREADS) {
       const float x2 = p[k * 3 + 0], y2 = p[k * 3 + 1], z2 = p[k * 3 + 2];
-      const float mag = x2 * x2 + y2 * y2 + z2 * z2;
-      if ((double)mag <= 1e-3) continue;
-      const float dx = x2 - x1, dy = y2 - y1, dz = z2 - z1;
-      const float d = dx * dx + dy * dy + dz * dz;
-      const float old = td[k];
-      const float d2 = (old < d) ? old : d;
+      if (!fps_live(x2, y2, z2)) continue;
+      const float d2 = fps_min_dist(td[k], x2, y2, z2, x1, y1, z1);
       td[k] = d2;
-      const unsigned long long kk =
-          ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned long long)(~(unsigned int)k);
+      const unsigned long long kk = fps_key(d2, (unsigned int)k);
       key = kk > key ? kk : key;
     }
-    key = wave_max_u64(key);
-    if ((t & 63) == 0) slots[j & 1][t >> 6] = key;
-    __syncthreads();
-    unsigned long long best = slots[j & 1][0];
-#pragma unroll
-    for (int w = 1; w < NW; ++w) {
-      const unsigned long long v = slots[j & 1][w];
-      best = v > best ? v : best;
-    }
-    last = (best == 0ull) ? 0 : (int)(~(unsigned int)(best & 0xffffffffull));
+    last = fps_key_index(fps_block_max_key<NW>(key, slots[j & 1], t));
     if (t == 0) o[j] = last;
   }
 }
@@ -225,23 +244,10 @@ __global__ __launch_bounds__(256) void fps_grid_kernel(const float* __restrict__
   unsigned long long* abort_flag = fps_grid_ws(temp, b, N);  // [abort | arrived | best[0 .. m)]: zeroed by fps_grid_zero_kernel
   unsigned long long* arrived = abort_flag + 1;
   unsigned long long* best = abort_flag + 2;
-  float px[PPT], py[PPT], pz[PPT], td[PPT];
-  bool live[PPT];
+  const int k0 = g * (256 * PPT) + t;  // lane t owns the STRIDED points k0 + 256 i of the workgroup's 256 x PPT
+  FpsPoint pt[PPT];
 #pragma unroll
-  for (int i = 0; i < PPT; ++i) {
-    const int k = g * (256 * PPT) + i * 256 + t;
-    if (k < N) {
-      px[i] = p[(size_t)k * 3 + 0];
-      py[i] = p[(size_t)k * 3 + 1];
-      pz[i] = p[(size_t)k * 3 + 2];
-      const float mag = px[i] * px[i] + py[i] * py[i] + pz[i] * pz[i];
-      live[i] = !((double)mag <= 1e-3);
-    } else {
-      px[i] = py[i] = pz[i] = 0.f;
-      live[i] = false;
-    }
-    td[i] = FLT_MAX;
-  }
+  for (int i = 0; i < PPT; ++i) pt[i] = fps_load_point(p, k0 + i * 256, N);
   if (g == 0 && t == 0) o[0] = 0;
   int last = 0;
   for (int j = 1; j < m; ++j) {
@@ -249,23 +255,14 @@ __global__ __launch_bounds__(256) void fps_grid_kernel(const float* __restrict__
     unsigned long long key = 0ull;
 #pragma unroll
     for (int i = 0; i < PPT; ++i) {
-      if (live[i]) {
-        const float dx = px[i] - x1, dy = py[i] - y1, dz = pz[i] - z1;
-        const float d = dx * dx + dy * dy + dz * dz;
-        const float d2 = (td[i] < d) ? td[i] : d;
-        td[i] = d2;
-        const unsigned int k = (unsigned int)(g * (256 * PPT) + i * 256 + t);
-        const unsigned long long kk = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned long long)(~k);
+      if (pt[i].live) {
+        pt[i].td = fps_min_dist(pt[i].td, pt[i].x, pt[i].y, pt[i].z, x1, y1, z1);
+        const unsigned long long kk = fps_key(pt[i].td, (unsigned int)(k0 + i * 256));
         key = kk > key ? kk : key;
       }
     }
-    key = wave_max_u64(key);
-    if ((t & 63) == 0) slots[j & 1][t >> 6] = key;
-    __syncthreads();
+    const unsigned long long mine = fps_block_max_key<4>(key, slots[j & 1], t);
     if (t == 0) {
-      unsigned long long mine = slots[j & 1][0];
-#pragma unroll
-      for (int w = 1; w < 4; ++w) mine = slots[j & 1][w] > mine ? slots[j & 1][w] : mine;
       if (mine) __hip_atomic_fetch_max(&best[j], mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_fetch_add(arrived, 1ull, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
       const unsigned long long target = (unsigned long long)j * (unsigned long long)G;
@@ -285,7 +282,7 @@ __global__ __launch_bounds__(256) void fps_grid_kernel(const float* __restrict__
     const unsigned long long win = s_best;
     if (win == ~0ull) return;  // aborted (~0 is no valid key: the distance field would be a NaN pattern); the gated fps_big_kernel
                                // launched right behind this kernel recomputes the cloud
-    last = (win == 0ull) ? 0 : (int)(~(unsigned int)(win & 0xffffffffull));
+    last = fps_key_index(win);
     if (g == 0 && t == 0) o[j] = last;
   }
 }
@@ -372,6 +369,13 @@ extern "C" int sam6d_gather_points(const float* points, const int* idx, int B, i
 
 // Row gather on the (B,N,C) layout the pipeline keeps its features in: out[b,j,:] = feats[b,idx[b,j]+off,:].
 // One wave per output row, 16-byte lanes when C % 4 == 0.  Out-of-range index -> zeros (same rule as gather_points).
+// The wave's copy of one row of C % 4 == 0 floats on 16-byte lanes; zeros when the row is not `ok` (srow is then not read).
+__device__ __forceinline__ void wave_copy_row4(const float* srow, float* drow, int C, bool ok) {
+  const float4* src = reinterpret_cast<const float4*>(srow);
+  float4* dst = reinterpret_cast<float4*>(drow);
+  for (int c = (threadIdx.x & 63); c < C / 4; c += 64) dst[c] = ok ? src[c] : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
 __global__ void gather_rows_kernel(const float* __restrict__ feats, const int* __restrict__ idx, int N, int M, int C,
                                    long in_stride_b, long out_stride_b, int idx_off, float* __restrict__ out) {
   const int b = blockIdx.y;
@@ -382,9 +386,7 @@ __global__ void gather_rows_kernel(const float* __restrict__ feats, const int* _
   const float* srow = feats + (size_t)b * in_stride_b + (size_t)(ok ? a : 0) * C;
   float* drow = out + (size_t)b * out_stride_b + (size_t)j * C;
   if ((C & 3) == 0) {
-    const float4* src = reinterpret_cast<const float4*>(srow);
-    float4* dst = reinterpret_cast<float4*>(drow);
-    for (int c = (threadIdx.x & 63); c < C / 4; c += 64) dst[c] = ok ? src[c] : make_float4(0.f, 0.f, 0.f, 0.f);
+    wave_copy_row4(srow, drow, C, ok);
   } else {
     for (int c = (threadIdx.x & 63); c < C; c += 64) drow[c] = ok ? srow[c] : 0.f;
   }
@@ -423,10 +425,7 @@ __global__ void gather_rows_lead_kernel(const float* __restrict__ feats, const i
     // without the + 1 (the reference's quirk, transformer.py:667-705), and FPS always starts at index 0
     srow = (ok && a > 0) ? feats + (size_t)b * in_stride_b + (size_t)a * C : lead + (size_t)b * lead_stride_b;
   }
-  float* drow = out + (size_t)b * out_stride_b + (size_t)j * C;
-  const float4* src = reinterpret_cast<const float4*>(srow);
-  float4* dst = reinterpret_cast<float4*>(drow);
-  for (int c = (threadIdx.x & 63); c < C / 4; c += 64) dst[c] = ok ? src[c] : make_float4(0.f, 0.f, 0.f, 0.f);
+  wave_copy_row4(srow, out + (size_t)b * out_stride_b + (size_t)j * C, C, ok);
 }
 
 extern "C" int sam6d_gather_rows_lead(const float* feats, const int* idx, int B, int N, int M, int C, long in_stride_b,
@@ -451,21 +450,49 @@ extern "C" int sam6d_gather_rows_lead(const float* feats, const int* idx, int B,
 // =========================================================================================================
 #define BQ_CH 2048
 #define BQ_QPB 64
-__global__ __launch_bounds__(256) void ball_query_kernel(const float* __restrict__ new_xyz, const float* __restrict__ xyz,
-                                                         int N, int M, float radius2, int nsample,
-                                                         int* __restrict__ idx) {
+// The hits of one 64-candidate step (lane l tests candidate k_lane0 + l) join the query's index list `row` in lane order = index order
+// while slots are free; the very first hit is kept for the tail.
+__device__ __forceinline__ void bq_append(bool hit, int k_lane0, int lane, int ns, int* row, int& cnt, int& first) {
+  const unsigned long long mask = __ballot(hit);
+  if (mask) {
+    if (cnt == 0) first = k_lane0 + (__ffsll((long long)mask) - 1);
+    const int pos = cnt + __popcll(mask & ((1ull << lane) - 1ull));
+    if (hit && pos < ns) row[pos] = k_lane0 + lane;
+    cnt += __popcll(mask);
+  }
+}
+// tail fill: slots [cnt, ns) of a query's index list hold the first hit (or 0 when the ball is empty)
+__device__ __forceinline__ void bq_tail_fill(int* row, int cnt, int ns, int first, int lane) {
+  for (int l = min(cnt, ns) + lane; l < ns; l += 64) row[l] = first;
+}
+
+// NR radii in one pass over the candidates (PositionalEncoding queries the same cloud with r1 < r2: fine_point_matching.py
+// :108-131): the distance of a (query, candidate) pair is computed once, each radius keeps its own hit counter and index list.
+// Same semantics for every radius (index order, first hit pre-fills, empty ball -> zeros).
+template <int NR>
+struct BqRadii {
+  float r2[NR];  // squared radius: the fp32 product, as the reference (ball_query.cpp:20)
+  int ns[NR];    // nsample
+  int* idx[NR];  // (B, M, ns)
+};
+
+template <int NR>
+__global__ __launch_bounds__(256) void ball_query_kernel(const float* __restrict__ new_xyz, const float* __restrict__ xyz, int N, int M,
+                                                         BqRadii<NR> a) {
   __shared__ float sp[BQ_CH * 3];
-  __shared__ int s_cnt[BQ_QPB];
-  __shared__ int s_first[BQ_QPB];
+  __shared__ int s_cnt[NR][BQ_QPB];
+  __shared__ int s_first[NR][BQ_QPB];
   const int b = blockIdx.y;
   const int q0 = blockIdx.x * BQ_QPB;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const float* cx = xyz + (size_t)b * N * 3;
   const float* cq = new_xyz + (size_t)b * M * 3;
-  int* ci = idx + (size_t)b * M * nsample;
+  int* ci[NR];  // this cloud's index lists
+#pragma unroll
+  for (int r = 0; r < NR; ++r) ci[r] = a.idx[r] + (size_t)b * M * a.ns[r];
   if (threadIdx.x < BQ_QPB) {
-    s_cnt[threadIdx.x] = 0;
-    s_first[threadIdx.x] = 0;
+#pragma unroll
+    for (int r = 0; r < NR; ++r) s_cnt[r][threadIdx.x] = s_first[r][threadIdx.x] = 0;
   }
   for (int base = 0; base < N; base += BQ_CH) {
     const int cn = min(BQ_CH, N - base);
@@ -475,118 +502,61 @@ __global__ __launch_bounds__(256) void ball_query_kernel(const float* __restrict
     for (int ql = wave; ql < BQ_QPB; ql += 4) {
       const int q = q0 + ql;
       if (q >= M) break;
-      int cnt = s_cnt[ql];
-      if (cnt >= nsample) continue;
+      int cnt[NR], first[NR];
+#pragma unroll
+      for (int r = 0; r < NR; ++r) {
+        cnt[r] = s_cnt[r][ql];
+        first[r] = s_first[r][ql];
+      }
+      auto open = [&] {  // some radius has free slots left
+        bool o = false;
+#pragma unroll
+        for (int r = 0; r < NR; ++r) o = o || cnt[r] < a.ns[r];
+        return o;
+      };
+      if (!open()) continue;
       const float qx = cq[q * 3 + 0], qy = cq[q * 3 + 1], qz = cq[q * 3 + 2];
-      int first = s_first[ql];
-      for (int k0 = 0; k0 < cn && cnt < nsample; k0 += 64) {
-        const int k = k0 + lane;
-        bool hit = false;
-        if (k < cn) {
-          const float x = sp[k * 3 + 0], y = sp[k * 3 + 1], z = sp[k * 3 + 2];
-          const float d2 = (qx - x) * (qx - x) + (qy - y) * (qy - y) + (qz - z) * (qz - z);
-          hit = d2 < radius2;
+      for (int k0 = 0; k0 < cn && open(); k0 += 64) {
+        const int k = base + k0 + lane;  // this lane's candidate as an index into the cloud: the value bq_append stores
+        float d2 = INFINITY;             // a lane past the chunk: no hit
+        if (k < base + cn) {
+          const float* c = sp + (k - base) * 3;
+          const float x = c[0], y = c[1], z = c[2];
+          d2 = (qx - x) * (qx - x) + (qy - y) * (qy - y) + (qz - z) * (qz - z);
         }
-        const unsigned long long mask = __ballot(hit);
-        if (mask) {
-          if (cnt == 0) first = base + k0 + (__ffsll((long long)mask) - 1);
-          const int pos = cnt + __popcll(mask & ((1ull << lane) - 1ull));
-          if (hit && pos < nsample) ci[(size_t)q * nsample + pos] = base + k;
-          cnt += __popcll(mask);
-        }
+#pragma unroll
+        for (int r = 0; r < NR; ++r)  // (a single radius is open here: the loop's condition)
+          if (NR == 1 || cnt[r] < a.ns[r]) bq_append(d2 < a.r2[r], base + k0, lane, a.ns[r], ci[r] + (size_t)q * a.ns[r], cnt[r], first[r]);
       }
       if (lane == 0) {
-        s_cnt[ql] = cnt;
-        s_first[ql] = first;
+#pragma unroll
+        for (int r = 0; r < NR; ++r) {
+          s_cnt[r][ql] = cnt[r];
+          s_first[r][ql] = first[r];
+        }
       }
     }
   }
   __syncthreads();
-  // tail fill: slots [cnt, nsample) hold the first hit (or 0 when the ball is empty)
   for (int ql = wave; ql < BQ_QPB; ql += 4) {
     const int q = q0 + ql;
     if (q >= M) break;
-    const int cnt = min(s_cnt[ql], nsample), first = s_first[ql];
-    for (int l = cnt + lane; l < nsample; l += 64) ci[(size_t)q * nsample + l] = first;
+    int cnt[NR], first[NR];  // (all LDS reads issued before the first store)
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+      cnt[r] = s_cnt[r][ql];
+      first[r] = s_first[r][ql];
+    }
+#pragma unroll
+    for (int r = 0; r < NR; ++r) bq_tail_fill(ci[r] + (size_t)q * a.ns[r], cnt[r], a.ns[r], first[r], lane);
   }
 }
 
-// Two radii in one pass over the candidates (PositionalEncoding queries the same cloud with r1 < r2: fine_point_matching.py
-// :108-131): the distance of a (query, candidate) pair is computed once, each radius keeps its own hit counter and index list.
-// Same per-radius semantics as ball_query_kernel (index order, first hit pre-fills, empty ball -> zeros).
-__global__ __launch_bounds__(256) void ball_query2_kernel(const float* __restrict__ new_xyz, const float* __restrict__ xyz, int N,
-                                                          int M, float r2a, int nsa, int* __restrict__ idxa, float r2b, int nsb,
-                                                          int* __restrict__ idxb) {
-  __shared__ float sp[BQ_CH * 3];
-  __shared__ int s_cnt[2][BQ_QPB];
-  __shared__ int s_first[2][BQ_QPB];
-  const int b = blockIdx.y;
-  const int q0 = blockIdx.x * BQ_QPB;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const float* cx = xyz + (size_t)b * N * 3;
-  const float* cq = new_xyz + (size_t)b * M * 3;
-  int* cia = idxa + (size_t)b * M * nsa;
-  int* cib = idxb + (size_t)b * M * nsb;
-  if (threadIdx.x < BQ_QPB) {
-    s_cnt[0][threadIdx.x] = s_cnt[1][threadIdx.x] = 0;
-    s_first[0][threadIdx.x] = s_first[1][threadIdx.x] = 0;
-  }
-  for (int base = 0; base < N; base += BQ_CH) {
-    const int cn = min(BQ_CH, N - base);
-    __syncthreads();
-    for (int i = threadIdx.x; i < cn * 3; i += 256) sp[i] = cx[(size_t)base * 3 + i];
-    __syncthreads();
-    for (int ql = wave; ql < BQ_QPB; ql += 4) {
-      const int q = q0 + ql;
-      if (q >= M) break;
-      int ca = s_cnt[0][ql], cb = s_cnt[1][ql];
-      if (ca >= nsa && cb >= nsb) continue;
-      const float qx = cq[q * 3 + 0], qy = cq[q * 3 + 1], qz = cq[q * 3 + 2];
-      int fa = s_first[0][ql], fb = s_first[1][ql];
-      for (int k0 = 0; k0 < cn && (ca < nsa || cb < nsb); k0 += 64) {
-        const int k = k0 + lane;
-        float d2 = INFINITY;
-        if (k < cn) {
-          const float x = sp[k * 3 + 0], y = sp[k * 3 + 1], z = sp[k * 3 + 2];
-          d2 = (qx - x) * (qx - x) + (qy - y) * (qy - y) + (qz - z) * (qz - z);
-        }
-        if (ca < nsa) {
-          const bool hit = d2 < r2a;
-          const unsigned long long mask = __ballot(hit);
-          if (mask) {
-            if (ca == 0) fa = base + k0 + (__ffsll((long long)mask) - 1);
-            const int pos = ca + __popcll(mask & ((1ull << lane) - 1ull));
-            if (hit && pos < nsa) cia[(size_t)q * nsa + pos] = base + k;
-            ca += __popcll(mask);
-          }
-        }
-        if (cb < nsb) {
-          const bool hit = d2 < r2b;
-          const unsigned long long mask = __ballot(hit);
-          if (mask) {
-            if (cb == 0) fb = base + k0 + (__ffsll((long long)mask) - 1);
-            const int pos = cb + __popcll(mask & ((1ull << lane) - 1ull));
-            if (hit && pos < nsb) cib[(size_t)q * nsb + pos] = base + k;
-            cb += __popcll(mask);
-          }
-        }
-      }
-      if (lane == 0) {
-        s_cnt[0][ql] = ca;
-        s_cnt[1][ql] = cb;
-        s_first[0][ql] = fa;
-        s_first[1][ql] = fb;
-      }
-    }
-  }
-  __syncthreads();
-  for (int ql = wave; ql < BQ_QPB; ql += 4) {  // tail fill: slots [cnt, nsample) hold the first hit (or 0 when the ball is empty)
-    const int q = q0 + ql;
-    if (q >= M) break;
-    const int ca = min(s_cnt[0][ql], nsa), cb = min(s_cnt[1][ql], nsb), fa = s_first[0][ql], fb = s_first[1][ql];
-    for (int l = ca + lane; l < nsa; l += 64) cia[(size_t)q * nsa + l] = fa;
-    for (int l = cb + lane; l < nsb; l += 64) cib[(size_t)q * nsb + l] = fb;
-  }
+// the one launch of the all-pairs scan behind sam6d_ball_query (NR = 1) and sam6d_ball_query2 (NR = 2)
+template <int NR>
+static void ball_query_launch(const float* new_xyz, const float* xyz, int B, int N, int M, const BqRadii<NR>& a, void* stream) {
+  dim3 grid(cdiv(M, BQ_QPB), B);
+  hipLaunchKernelGGL((ball_query_kernel<NR>), grid, dim3(256), 0, (hipStream_t)stream, new_xyz, xyz, N, M, a);
 }
 
 extern "C" int sam6d_ball_query2(const float* new_xyz, const float* xyz, int B, int N, int M, float radius1, int nsample1, int* idx1,
@@ -595,9 +565,7 @@ extern "C" int sam6d_ball_query2(const float* new_xyz, const float* xyz, int B, 
   SAM6D_REQUIRE(B >= 0 && N > 0 && M >= 0 && nsample1 > 0 && nsample2 > 0, "ball_query2: bad sizes");
   SAM6D_REQUIRE(B <= 65535, "ball_query2: B must be <= 65535");
   if (B == 0 || M == 0) return 0;
-  dim3 grid(cdiv(M, BQ_QPB), B);
-  hipLaunchKernelGGL(ball_query2_kernel, grid, dim3(256), 0, (hipStream_t)stream, new_xyz, xyz, N, M, radius1 * radius1, nsample1,
-                     idx1, radius2 * radius2, nsample2, idx2);
+  ball_query_launch<2>(new_xyz, xyz, B, N, M, {{radius1 * radius1, radius2 * radius2}, {nsample1, nsample2}, {idx1, idx2}}, stream);
   SAM6D_LAUNCH_CHECK("ball_query2");
 }
 
@@ -621,9 +589,36 @@ extern "C" int sam6d_ball_query2(const float* new_xyz, const float* xyz, int B, 
 #define BQG_QPW 4            // queries per wave
 __host__ __device__ inline size_t bqg_cloud_bytes(int N) { return (size_t)N * 16 + (size_t)(BQG_CELLS + 1) * 4 + 12 + 16; }
 
+// One cloud's workspace: what bqg_build_kernel writes and bqg_query_kernel reads.
+struct BqgView {
+  float4* sorted;           // [N] (x, y, z, index), sorted by cell
+  int* start;               // [G^3 + 1] cell starts in `sorted`
+  float* org;               // the grid's origin x, y, z and 1 / c as stored ...
+  float ox, oy, oz, inv_c;  // ... and in registers (bqg_load_origin, or the build kernel that computes them)
+};
+__device__ __forceinline__ BqgView bqg_view(unsigned char* ws, int b, int N) {
+  unsigned char* wb = ws + (size_t)b * ((bqg_cloud_bytes(N) + 15) & ~(size_t)15);
+  BqgView v;
+  v.sorted = reinterpret_cast<float4*>(wb);
+  v.start = reinterpret_cast<int*>(wb + (size_t)N * 16);
+  v.org = reinterpret_cast<float*>(wb + (size_t)N * 16 + (size_t)(BQG_CELLS + 1) * 4);
+  return v;
+}
+__device__ __forceinline__ void bqg_load_origin(BqgView& v) {
+  v.ox = v.org[0]; v.oy = v.org[1]; v.oz = v.org[2]; v.inv_c = v.org[3];
+}
+
 __device__ __forceinline__ int bqg_cell1(float v, float o, float inv_c) {
   const float u = fminf(fmaxf((v - o) * inv_c, 0.0f), (float)(BQG_G - 1));  // (NaN -> 0)
   return (int)u;
+}
+// the cell of a point: clamped coordinates per axis, and their place in the cell-start table (x runs fastest)
+struct BqgCell {
+  int x, y, z;
+  __device__ __forceinline__ int index() const { return (z * BQG_G + y) * BQG_G + x; }
+};
+__device__ __forceinline__ BqgCell bqg_cell(float x, float y, float z, const BqgView& v) {
+  return {bqg_cell1(x, v.ox, v.inv_c), bqg_cell1(y, v.oy, v.inv_c), bqg_cell1(z, v.oz, v.inv_c)};
 }
 
 __global__ __launch_bounds__(1024) void bqg_build_kernel(const float* __restrict__ xyz, int N, float cell, unsigned char* __restrict__ ws) {
@@ -632,10 +627,7 @@ __global__ __launch_bounds__(1024) void bqg_build_kernel(const float* __restrict
   __shared__ int wsum[16];
   const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const float* p = xyz + (size_t)b * N * 3;
-  unsigned char* wb = ws + (size_t)b * ((bqg_cloud_bytes(N) + 15) & ~(size_t)15);
-  float4* sorted = reinterpret_cast<float4*>(wb);
-  int* start = reinterpret_cast<int*>(wb + (size_t)N * 16);
-  float* org = reinterpret_cast<float*>(wb + (size_t)N * 16 + (size_t)(BQG_CELLS + 1) * 4);
+  BqgView cloud = bqg_view(ws, b, N);
   float mx = INFINITY, my = INFINITY, mz = INFINITY;
   for (int i = t; i < N; i += 1024) {
     const float x = p[i * 3], y = p[i * 3 + 1], z = p[i * 3 + 2];
@@ -651,23 +643,15 @@ __global__ __launch_bounds__(1024) void bqg_build_kernel(const float* __restrict
   if (!(ox > -3.0e38f && ox < 3.0e38f)) ox = 0.f;
   if (!(oy > -3.0e38f && oy < 3.0e38f)) oy = 0.f;
   if (!(oz > -3.0e38f && oz < 3.0e38f)) oz = 0.f;
-  const float inv_c = 1.0f / cell;
-  if (t == 0) { org[0] = ox; org[1] = oy; org[2] = oz; org[3] = inv_c; }
-  for (int i = t; i < N; i += 1024) {
-    const int c = (bqg_cell1(p[i * 3 + 2], oz, inv_c) * BQG_G + bqg_cell1(p[i * 3 + 1], oy, inv_c)) * BQG_G + bqg_cell1(p[i * 3], ox, inv_c);
-    atomicAdd(&hist[c], 1);
-  }
+  cloud.ox = ox; cloud.oy = oy; cloud.oz = oz; cloud.inv_c = 1.0f / cell;
+  if (t == 0) { cloud.org[0] = ox; cloud.org[1] = oy; cloud.org[2] = oz; cloud.org[3] = cloud.inv_c; }
+  for (int i = t; i < N; i += 1024) atomicAdd(&hist[bqg_cell(p[i * 3], p[i * 3 + 1], p[i * 3 + 2], cloud).index()], 1);
   __syncthreads();
-  // exclusive scan of the 4096 counts: 4 per thread, wave scan, wave totals
+  // exclusive scan of the 4096 counts: 4 per thread, wave scan (integer sums: exact in any order), wave totals
   int v[4], sum = 0;
 #pragma unroll
   for (int u = 0; u < 4; ++u) { v[u] = hist[t * 4 + u]; sum += v[u]; }
-  int inc = sum;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int nb = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += nb;
-  }
+  const int inc = wave_incl_scan_i32_dpp(sum);
   if (lane == 63) wsum[wave] = inc;
   __syncthreads();
   int base = 0;
@@ -675,33 +659,29 @@ __global__ __launch_bounds__(1024) void bqg_build_kernel(const float* __restrict
   int run = base + inc - sum;
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
-    start[t * 4 + u] = run;
+    cloud.start[t * 4 + u] = run;
     hist[t * 4 + u] = run;   // becomes the scatter cursor
     run += v[u];
   }
-  if (t == 1023) start[BQG_CELLS] = run;
+  if (t == 1023) cloud.start[BQG_CELLS] = run;
   __syncthreads();
   for (int i = t; i < N; i += 1024) {
     const float x = p[i * 3], y = p[i * 3 + 1], z = p[i * 3 + 2];
-    const int c = (bqg_cell1(z, oz, inv_c) * BQG_G + bqg_cell1(y, oy, inv_c)) * BQG_G + bqg_cell1(x, ox, inv_c);
-    const int slot = atomicAdd(&hist[c], 1);
-    sorted[slot] = make_float4(x, y, z, __int_as_float(i));
+    const int slot = atomicAdd(&hist[bqg_cell(x, y, z, cloud).index()], 1);
+    cloud.sorted[slot] = make_float4(x, y, z, __int_as_float(i));
   }
 }
 
 template <int WPL>  // mask words per lane: N <= 2048 * WPL
 __global__ __launch_bounds__(256) void bqg_query_kernel(const float* __restrict__ new_xyz, int N, int M, float r2a, int nsa,
                                                         int* __restrict__ idxa, float r2b, int nsb, int* __restrict__ idxb,
-                                                        const unsigned char* __restrict__ ws, int* __restrict__ cnta,
-                                                        int* __restrict__ cntb) {
+                                                        unsigned char* __restrict__ ws, int* __restrict__ cnta,
+                                                        int* __restrict__ cntb) {  // (ws is only read here)
   __shared__ unsigned maskA[4][64 * WPL];
   __shared__ unsigned maskB[4][64 * WPL];
   const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned char* wb = ws + (size_t)b * ((bqg_cloud_bytes(N) + 15) & ~(size_t)15);
-  const float4* sorted = reinterpret_cast<const float4*>(wb);
-  const int* start = reinterpret_cast<const int*>(wb + (size_t)N * 16);
-  const float* org = reinterpret_cast<const float*>(wb + (size_t)N * 16 + (size_t)(BQG_CELLS + 1) * 4);
-  const float ox = org[0], oy = org[1], oz = org[2], inv_c = org[3];
+  BqgView cloud = bqg_view(ws, b, N);
+  bqg_load_origin(cloud);
   unsigned* mA = maskA[wave];
   unsigned* mB = maskB[wave];
   for (int qi = 0; qi < BQG_QPW; ++qi) {
@@ -711,18 +691,17 @@ __global__ __launch_bounds__(256) void bqg_query_kernel(const float* __restrict_
     const float qx = qp[0], qy = qp[1], qz = qp[2];
 #pragma unroll
     for (int j = 0; j < WPL; ++j) { mA[lane * WPL + j] = 0u; mB[lane * WPL + j] = 0u; }
-    const int cx = bqg_cell1(qx, ox, inv_c), cy = bqg_cell1(qy, oy, inv_c), cz = bqg_cell1(qz, oz, inv_c);
-    const int x0 = max(cx - 1, 0), x1 = min(cx + 1, BQG_G - 1);
+    const BqgCell qc = bqg_cell(qx, qy, qz, cloud);
+    const int x0 = max(qc.x - 1, 0), x1 = min(qc.x + 1, BQG_G - 1);
     for (int dz = -1; dz <= 1; ++dz) {
-      const int z = cz + dz;
+      const int z = qc.z + dz;
       if (z < 0 || z >= BQG_G) continue;
       for (int dy = -1; dy <= 1; ++dy) {
-        const int y = cy + dy;
+        const int y = qc.y + dy;
         if (y < 0 || y >= BQG_G) continue;
-        const int row = (z * BQG_G + y) * BQG_G;
-        const int lo = start[row + x0], hi = start[row + x1 + 1];
+        const int lo = cloud.start[BqgCell{x0, y, z}.index()], hi = cloud.start[BqgCell{x1, y, z}.index() + 1];
         for (int k = lo + lane; k < hi; k += 64) {
-          const float4 c = sorted[k];
+          const float4 c = cloud.sorted[k];
           const float d2 = (qx - c.x) * (qx - c.x) + (qy - c.y) * (qy - c.y) + (qz - c.z) * (qz - c.z);
           const int id = __float_as_int(c.w);
           if (d2 < r2b) atomicOr(&mB[id >> 5], 1u << (id & 31));
@@ -755,7 +734,7 @@ __global__ __launch_bounds__(256) void bqg_query_kernel(const float* __restrict_
           x &= x - 1;
         }
       }
-      for (int l = min(total, ns) + lane; l < ns; l += 64) out[l] = first;
+      bq_tail_fill(out, total, ns, first, lane);
       // slots filled with hits; an empty ball counts 1: its slots all hold index 0, one row for whoever evaluates the ball
       if (nhit && lane == 0) *nhit = max(min(total, ns), 1);
     };
@@ -794,8 +773,11 @@ static int ball_query2_grid_impl(const float* new_xyz, const float* xyz, int B, 
     if (int rc = sam6d_ball_query2(new_xyz, xyz, B, N, M, radius1, nsample1, idx1, radius2, nsample2, idx2, stream)) return rc;
     const long total = (long)B * M;
     if (!cnt1 || total == 0) return 0;
-    hipLaunchKernelGGL(bq_count_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, idx1, nsample1, total, cnt1);
-    hipLaunchKernelGGL(bq_count_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, idx2, nsample2, total, cnt2);
+    const int* idxs[2] = {idx1, idx2};
+    const int nss[2] = {nsample1, nsample2};
+    int* cnts[2] = {cnt1, cnt2};
+    for (int r = 0; r < 2; ++r)
+      hipLaunchKernelGGL(bq_count_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, idxs[r], nss[r], total, cnts[r]);
     SAM6D_LAUNCH_CHECK("ball_query2_grid_counts(count)");
   }
   if (B == 0 || M == 0) return 0;
@@ -803,13 +785,8 @@ static int ball_query2_grid_impl(const float* new_xyz, const float* xyz, int B, 
   SAM6D_LAUNCH_CHECK_CONT("ball_query2_grid(build)");
   const dim3 grid(cdiv(M, 4 * BQG_QPW), B);
   const float r2a = radius1 * radius1, r2b = radius2 * radius2;  // fp32 products, as the reference (ball_query.cpp:20)
-  const unsigned char* wsc = (const unsigned char*)ws;
-  if (N <= 2048)
-    hipLaunchKernelGGL((bqg_query_kernel<1>), grid, dim3(256), 0, s, new_xyz, N, M, r2a, nsample1, idx1, r2b, nsample2, idx2, wsc, cnt1, cnt2);
-  else if (N <= 4096)
-    hipLaunchKernelGGL((bqg_query_kernel<2>), grid, dim3(256), 0, s, new_xyz, N, M, r2a, nsample1, idx1, r2b, nsample2, idx2, wsc, cnt1, cnt2);
-  else
-    hipLaunchKernelGGL((bqg_query_kernel<4>), grid, dim3(256), 0, s, new_xyz, N, M, r2a, nsample1, idx1, r2b, nsample2, idx2, wsc, cnt1, cnt2);
+  const auto query = N <= 2048 ? bqg_query_kernel<1> : N <= 4096 ? bqg_query_kernel<2> : bqg_query_kernel<4>;  // mask words for N bits
+  hipLaunchKernelGGL(query, grid, dim3(256), 0, s, new_xyz, N, M, r2a, nsample1, idx1, r2b, nsample2, idx2, (unsigned char*)ws, cnt1, cnt2);
   SAM6D_LAUNCH_CHECK("ball_query2_grid");
 }
 
@@ -832,9 +809,7 @@ extern "C" int sam6d_ball_query(const float* new_xyz, const float* xyz, int B, i
   SAM6D_REQUIRE(B >= 0 && N > 0 && M >= 0 && nsample > 0, "ball_query: bad sizes");
   SAM6D_REQUIRE(B <= 65535, "ball_query: B must be <= 65535");
   if (B == 0 || M == 0) return 0;
-  const float r2 = radius * radius;  // fp32 product, as the reference (ball_query.cpp:20)
-  dim3 grid(cdiv(M, BQ_QPB), B);
-  hipLaunchKernelGGL(ball_query_kernel, grid, dim3(256), 0, (hipStream_t)stream, new_xyz, xyz, N, M, r2, nsample, idx);
+  ball_query_launch<1>(new_xyz, xyz, B, N, M, {{radius * radius}, {nsample}, {idx}}, stream);
   SAM6D_LAUNCH_CHECK("ball_query");
 }
 

@@ -37,8 +37,11 @@ def test_fps_reference_test_shape(dev, ext):
     assert np.array_equal(idx.cpu().numpy(), g["fps_big_idx"])
 
 
-@pytest.mark.parametrize("B,N,m", [(3, 2048, 196), (2, 1000, 64), (1, 4096, 300), (2, 5000, 128), (1, 64, 64), (2, 7, 3)])
+@pytest.mark.parametrize("B,N,m", [(3, 2048, 196), (2, 1000, 64), (1, 4096, 300), (2, 5000, 128), (1, 64, 64), (2, 7, 3),
+                                   (1, 2049, 8), (2, 4097, 8), (1, 1, 3)])
 def test_fps_vs_oracle(dev, ext, B, N, m):
+    """Also the dispatch edges: 2049 is the first N on the 1024-thread register kernel, 4097 the first on the multi-workgroup kernel and
+    its one-workgroup fallback, and a one-point cloud repeats its point in every round.  A fifth of cloud 0 lies in the origin ball."""
     from oracle import pointops as P
     g = torch.Generator().manual_seed(B * 1000 + N)
     xyz = torch.rand(B, N, 3, generator=g) - 0.5
@@ -197,6 +200,103 @@ def test_gather_rows(dev):
     got = ops.gather_rows(f.to(dev), idx.to(dev))
     want = torch.gather(f, 1, idx.long().unsqueeze(2).expand(3, 50, 256))
     assert torch.equal(got.cpu(), want)
+
+
+@pytest.mark.parametrize("idx_off", [0, 1, -1])
+@pytest.mark.parametrize("C", [3, 8])
+def test_gather_rows_both_paths_offset_and_padding(dev, C, idx_off):
+    """sam6d_gather_rows on its scalar path (C = 3: the points of sample_pts_feats) and its 16-byte path (C = 8): idx + idx_off addresses
+    the row, a row below 0 or at N gives zeros, and the padding between the clouds of a wider output stays as it was."""
+    from sam6d_hip import _lib
+    B, N, M, pad = 2, 17, 9, 8 - C % 4
+    gen = torch.Generator().manual_seed(17 + C)
+    feats = torch.randn(B, N, C, generator=gen)
+    row = torch.randint(0, N, (B, M), generator=gen)  # the row that idx + idx_off addresses
+    row[0, 0], row[0, 1], row[0, 2], row[1, 5] = 0, N - 1, -1, N
+    idx = (row - idx_off).to(torch.int32)
+    stride = M * C + pad
+    want = torch.full((B, stride), -7.0)
+    for b in range(B):
+        for j in range(M):
+            a = int(row[b, j])
+            want[b, j * C:(j + 1) * C] = feats[b, a] if 0 <= a < N else 0.0
+    out = torch.full((B, stride), -7.0, device=dev)
+    fd, idd = feats.to(dev), idx.to(dev)
+    _lib.call("sam6d_gather_rows", fd.data_ptr(), idd.data_ptr(), B, N, M, C, N * C, stride, idx_off, out.data_ptr(),
+              torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    assert torch.equal(out.cpu(), want)
+
+
+def _bq_call(dev, new, xyz, radii):
+    """sam6d_ball_query (one (radius, nsample) pair) or sam6d_ball_query2 (two) into sentinel-filled lists."""
+    from sam6d_hip import _lib
+    B, M, N = new.shape[0], new.shape[1], xyz.shape[1]
+    nd, xd = new.to(dev).contiguous(), xyz.to(dev).contiguous()
+    out = [torch.full((B, M, ns), -7, dtype=torch.int32, device=dev) for _, ns in radii]
+    args = [v for (r, ns), o in zip(radii, out) for v in (float(r), ns, o.data_ptr())]
+    _lib.call("sam6d_ball_query" if len(radii) == 1 else "sam6d_ball_query2", nd.data_ptr(), xd.data_ptr(), B, N, M, *args, None)
+    torch.cuda.synchronize()
+    return [o.cpu() for o in out]
+
+
+@pytest.mark.parametrize("radii", [((0.3, 8),), ((0.2, 4), (0.4, 8))])
+def test_ball_query_first_hit_in_one_candidate_chunk(dev, radii):
+    """N = 2049 is one candidate past the 2048-point chunk of the all-pairs scan: the only point inside any ball is point 2048, so the
+    first hit -- the value every slot is pre-filled with -- comes from the second chunk.  One query's ball is empty."""
+    from oracle import pointops as P
+    g = torch.Generator().manual_seed(2049)
+    xyz = torch.rand(1, 2049, 3, generator=g) + 10.0
+    xyz[0, 2048] = torch.tensor([0.05, -0.02, 0.01])
+    new = torch.tensor([[[0.0, 0.0, 0.0], [-40.0, 3.0, 0.0], [0.1, 0.05, 0.0]]])
+    want = [P.ball_query(new, xyz, r, ns) for r, ns in radii]
+    for w in want:
+        assert w[0, 0].eq(2048).all() and w[0, 1].eq(0).all() and w[0, 2].eq(2048).all()
+    got = _bq_call(dev, new, xyz, radii)
+    for gi, w in zip(got, want):
+        assert torch.equal(gi, w)
+
+
+def test_ball_query_nsample_above_one_wave_step(dev):
+    """nsample = 70: the tail fill of a nearly empty list takes a second 64-lane stride, and a ball with 90 hits in the first two
+    64-candidate steps is cut at slot 70 inside the second step."""
+    from oracle import pointops as P
+    N, r, ns = 130, 0.5, 70
+    xyz = torch.zeros(1, N, 3)
+    xyz[0, :, 0] = torch.arange(N) * 0.01  # a line: the hits of a query are a run of consecutive indices
+    new = torch.tensor([[[0.40, 0.0, 0.0], [-0.495, 0.0, 0.0], [-0.30, 0.0, 0.0], [0.65, 0.45, 0.0], [0.185, 0.0, 0.0]]])
+    hits = (((new[:, :, None] - xyz[:, None]) ** 2).sum(-1) < r * r).sum(-1)[0]
+    assert hits[0] > ns and int(torch.nonzero(((new[0, 0] - xyz[0]) ** 2).sum(-1) < r * r).max()) < 128
+    assert 1 <= hits[1:].min() < 6 and hits[1:].max() == 69  # (fewer than 6 hits: slots 64 .. 69 belong to the tail)
+    want = P.ball_query(new, xyz, r, ns)
+    assert torch.equal(1 + (want[..., 1:] != want[..., :1]).sum(-1)[0], hits.clamp(max=ns))
+    got, = _bq_call(dev, new, xyz, ((r, ns),))
+    assert torch.equal(got, want)
+
+
+@pytest.mark.parametrize("B,N,M,r1,ns1,r2,ns2", [(2, 8193, 70, 0.05, 32, 0.1, 64), (1, 40, 5, 0.0, 4, 0.0, 8)])
+def test_ball_query2_grid_counts_on_the_all_pairs_fallback(dev, B, N, M, r1, ns1, r2, ns2):
+    """sam6d_ball_query2_grid_counts outside the pruned kernel's range (N above 8192; no positive radius): the indices of the all-pairs
+    scan, and counts recounted from them on the device, equal to the host recount."""
+    from oracle import pointops as P
+    from sam6d_hip import _lib
+    g = torch.Generator().manual_seed(N + M)
+    xyz = torch.rand(B, N, 3, generator=g) - 0.5
+    new = (torch.rand(B, M, 3, generator=g) - 0.5) * 1.3  # some queries have empty balls
+    want = [P.ball_query(new, xyz, r, ns) for r, ns in ((r1, ns1), (r2, ns2))]
+    scan = _bq_call(dev, new, xyz, ((r1, ns1), (r2, ns2)))
+    nd, xd = new.to(dev), xyz.to(dev)
+    idx = [torch.full((B, M, ns), -9, dtype=torch.int32, device=dev) for ns in (ns1, ns2)]
+    cnt = [torch.full((B, M), -9, dtype=torch.int32, device=dev) for _ in range(2)]
+    nbytes = int(_lib.load().sam6d_ball_query2_grid_workspace_bytes(B, N))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    _lib.call("sam6d_ball_query2_grid_counts", nd.data_ptr(), xd.data_ptr(), B, N, M, float(r1), ns1, idx[0].data_ptr(), float(r2), ns2,
+              idx[1].data_ptr(), ws.data_ptr(), nbytes, cnt[0].data_ptr(), cnt[1].data_ptr(), None)
+    torch.cuda.synchronize()
+    for k in range(2):
+        i = idx[k].cpu()
+        assert torch.equal(i, scan[k]) and torch.equal(i, want[k])
+        assert torch.equal(cnt[k].cpu(), (1 + (i[..., 1:] != i[..., :1]).sum(-1)).to(torch.int32))
 
 
 def test_error_contract(dev, ext):
