@@ -1088,6 +1088,41 @@ int sam6d_pose_vsd(const float* vertices, int V, const int* faces, int F, const 
                    const float* depth_obs, float delta, const float* taus, int T, float inv_norm, int* counts, void* workspace,
                    size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * ADD-S / ADI and the model diameter: exact pruned searches over all pairs of vertices (csrc/nearest.hip, restated in
+ * tests/nearest_ref.py).  (New entries only, so SAM6D_ABI_VERSION stays.)
+ * ------------------------------------------------------------------------------------------------------------ */
+/* ADI (ADD-S: Hinterstoisser et al. 2012; Hodan et al. 2016) of N estimated poses against their ground truths, over the model's
+ * vertices.  Beside PEM/run_inference_custom_pytorch.py:460-471, which writes its poses: the reference has no evaluation code.  The
+ * definition is the published one, restated by the package and pinned against its numpy restatement, not against bop_toolkit.
+ * points (V,3) f32 model vertices in CAD units; est, gt (N,3,4) f32 row-major object -> camera; inv_unit > 0, finite; no symmetries.
+ * Per pose n and point i: e_i = est[n] x_i, g_j = gt[n] x_j, m_i = the least d2_ij = |e_i - g_j|^2 over all j (fp32 in the order of
+ * the recipe at the top of csrc/nearest.hip; a NaN never wins, m_i = +inf where no d2 is a number), and
+ * adi_sum[n] i64 = sum_i rint((double)sqrtf(m_i) * inv_unit * 2^30), a term above 2^42 (4096 units; a NaN too) counted as 2^42:
+ * ADI = adi_sum / 2^30 / inv_unit / V.  Tiles of 256 points whose box cannot hold a nearer point are skipped; the bound holds in fp32
+ * without a margin, so the sum has the bits of the full search.  flags: bit 0 = skip nothing (the full V x V walk), other bits 0.
+ * The order of the points does not change the sum; tiles of neighbouring points (a sort along a space-filling curve) skip more.
+ * Integer atomic adds only: a function of the inputs alone.
+ * V 1 .. 2^20, N 1 .. 1024; workspace and adi_sum 8-byte aligned, the workspace at least sam6d_pose_adi_workspace_bytes(V, N) =
+ * 24 N ceil(V / 256) (the boxes; 0 for sizes outside the limits); anything else, a null pointer or a non-finite inv_unit returns
+ * non-zero without a launch or a write, the argument named in sam6d_last_error(). */
+size_t sam6d_pose_adi_workspace_bytes(int V, int N);
+int sam6d_pose_adi(const float* points, int V, const float* est, const float* gt, int N, float inv_unit, int flags, long long* adi_sum,
+                   void* workspace, size_t workspace_bytes, void* stream);
+/* The diameter of a point set as bop_toolkit defines a model's: the largest distance between two of its points.  Beside
+ * PEM/run_inference_custom_pytorch.py:460-471, as above: the reference has no evaluation code and reads no diameter.
+ * points (V,3) f32; seeds (n_seeds) i32 ON THE DEVICE, point indices whose distances to all points give the first lower bound (the
+ * extreme point of each axis is a good choice); a seed outside [0, V) is ignored, never dereferenced.  diameter: one f32 =
+ * sqrtf(max_ij d2_ij), d2_ij = |x_i - x_j|^2 in fp32 in the order of the recipe at the top of csrc/nearest.hip, the maximum taken as
+ * sam6d_pose_point_errors takes its maxima (a NaN is above every number: a coordinate that is not finite gives NaN).  V = 1 gives 0.
+ * Tile pairs whose boxes cannot hold a pair farther apart than the seeds' bound are skipped; the bound holds in fp32 without a margin,
+ * so the result has the bits of the full search.  flags: bit 0 = skip nothing, other bits 0.  Integer atomic maxima only.
+ * V 1 .. 2^20, n_seeds 1 .. 8; workspace 8-byte aligned and at least sam6d_points_diameter_workspace_bytes(V) = 8 + 24 ceil(V / 256)
+ * (0 for a V outside the limits); anything else or a null pointer returns non-zero without a launch or a write. */
+size_t sam6d_points_diameter_workspace_bytes(int V);
+int sam6d_points_diameter(const float* points, int V, const int* seeds, int n_seeds, int flags, float* diameter, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,8 +5,15 @@ published ones, restated by the package: the recipe is at the top of csrc/poseer
 comparison with that restatement is bit for bit.  Nothing here is pinned against bop_toolkit itself.  VSD renders with the package's
 own rasteriser (sam6d_hip.verify's raster pass), so it is BOP's in kind and not pixel for pixel.
 
-Left to the caller: ADD-S / ADI, the model diameter (pass models_info's), the `tlinear` cost, other visibility modes, several meshes in
-one call, BOP's file formats, the matching of estimates to ground-truth instances, and the BOP threshold lists (recall takes any).
+The two quantities that need a search over all pairs of vertices are here too (csrc/nearest.hip, restated in tests/nearest_ref.py):
+ADD-S / ADI without symmetries (adi; Hinterstoisser et al. 2012, Hodan et al. 2016) and the model diameter as bop_toolkit defines it,
+the largest distance between two vertices (model_diameter, models_info).  Both are exact searches that skip tiles of points whose
+bounding box cannot change the result; the bound holds in fp32 without a margin, so the pruned and the full search give the same bits.
+ADI is evaluated over the vertices, as pose_errors is.
+
+Left to the caller: symmetry-aware ADI, the index of the nearest vertex and of the diametral pair, ADI over surface samples, the
+`tlinear` cost, other visibility modes, several meshes in one call, BOP's file formats, the matching of estimates to ground-truth
+instances, and the BOP threshold lists (recall and auc take any).
 
 Imports verify, runtime, _lib, torch and numpy only.  There is no CPU route: a CPU tensor raises RuntimeError.
 """
@@ -101,6 +108,18 @@ def recall(err, thresholds):
     return (err[None, :] < thr[:, None]).to(torch.float32).mean(dim=1)
 
 
+def auc(err, max_err):
+    """The area under the recall-over-threshold curve on [0, max_err], as a fraction of max_err (YCB-V's AUC of ADD(-S) with
+    max_err = 0.1 m): err (N) tensor -> a 0-dim f64 tensor on err's device, mean(clamp(max_err - err, min=0)) / max_err.  A NaN error
+    counts as a miss.  A plain torch op."""
+    if not torch.is_tensor(err) or err.dim() != 1 or err.numel() < 1:
+        raise ValueError("auc: err must be an (N) tensor with N >= 1")
+    max_err = float(max_err)
+    if not (max_err > 0.0 and math.isfinite(max_err)):
+        raise ValueError("auc: max_err = %r is not a finite number > 0" % max_err)
+    return torch.nan_to_num(torch.clamp(max_err - err.to(torch.float64), min=0.0), nan=0.0).mean() / max_err
+
+
 # ------------------------------------------------------------------------------------------------------------ point errors
 def _points(name, mesh_or_points, like):
     """(V,3) f32 contiguous: a tensor, a mesh dict (numpy or tensors; uploaded beside `like` when it is not a tensor) or a
@@ -147,6 +166,17 @@ def _same_device(name, first, rest):
             raise ValueError("%s: %s is on %s and the model on %s" % (name, what, x.device, first.device))
 
 
+def _inv_unit(name, unit):
+    """1 / unit as the float32 the kernels count in (None: 1)"""
+    unit = 1.0 if unit is None else float(unit)
+    if not (unit > 0.0 and math.isfinite(unit)):
+        raise ValueError("%s: unit = %r is not a finite number > 0" % (name, unit))
+    inv_unit = float(np.float32(1.0 / unit))
+    if not (inv_unit > 0.0 and math.isfinite(inv_unit)):
+        raise ValueError("%s: unit = %r: 1 / unit is not a finite float32 > 0" % (name, unit))
+    return inv_unit
+
+
 @on_tensor_device
 def _point_errors(points, est, gt, syms, intr, inv_unit):
     V, N, S = int(points.shape[0]), int(est.shape[0]), int(syms.shape[0])
@@ -179,12 +209,7 @@ def pose_errors(mesh_or_points, R_est, t_est, R_gt, t_gt, K, syms=None, scale=1.
     N, R_est, t_est, R_gt, t_gt = _pair(name, R_est, t_est, R_gt, t_gt, MAX_POSES)
     points = _points(name, mesh_or_points, R_est)
     intr = _intrinsics(name, K)
-    unit = 1.0 if unit is None else float(unit)
-    if not (unit > 0.0 and math.isfinite(unit)):
-        raise ValueError("%s: unit = %r is not a finite number > 0" % (name, unit))
-    inv_unit = float(np.float32(1.0 / unit))
-    if not (inv_unit > 0.0 and math.isfinite(inv_unit)):
-        raise ValueError("%s: unit = %r: 1 / unit is not a finite float32 > 0" % (name, unit))
+    inv_unit = _inv_unit(name, unit)
     if syms is None:
         syms = np.concatenate([np.eye(3), np.zeros((3, 1))], axis=1)[None].astype(np.float32)
     host = None if torch.is_tensor(syms) else np.asarray(syms)
@@ -197,6 +222,111 @@ def pose_errors(mesh_or_points, R_est, t_est, R_gt, t_gt, K, syms=None, scale=1.
         syms = syms.to(points.device)
     _same_device(name, points, (("R_est", R_est), ("t_est", t_est), ("R_gt", R_gt), ("t_gt", t_gt), ("syms", syms)))
     return _point_errors(points, verify.pose_views(R_est, t_est, scale), verify.pose_views(R_gt, t_gt, scale), syms, intr, inv_unit)
+
+
+# ------------------------------------------------------------------------------------------------------------ ADI, the diameter
+class AdiErrors:
+    """What adi returns; both tensors are on the device.  adi (N) f32 in the unit of t, adi_sum (N) i64 the integer it is formed
+    from."""
+
+    def __init__(self, adi, adi_sum):
+        self.adi, self.adi_sum = adi, adi_sum
+
+
+def _spread10(q):
+    """the 10 low bits of an i64 tensor to every third bit"""
+    q = (q | (q << 16)) & 0x30000FF
+    q = (q | (q << 8)) & 0x300F00F
+    q = (q | (q << 4)) & 0x30C30C3
+    return (q | (q << 2)) & 0x9249249
+
+
+def morton_order(points):
+    """(V,3) f32 -> (V) i64, the points' order along a Morton curve: 10 bits per axis over the bounding box (one step for all three
+    axes, the longest side's, so that the cells are cubes), interleaved, a stable argsort.  Plain torch ops.  Consecutive points are
+    then neighbours in space, so the kernels' tiles of 256 are compact and their boxes prune; the order is plumbing, no result depends
+    on it.  A coordinate that is not finite counts as 0."""
+    x = torch.nan_to_num(points, nan=0.0, posinf=0.0, neginf=0.0)
+    lo = x.min(dim=0).values
+    span = (x.max(dim=0).values - lo).max().clamp_min(1e-30)
+    q = ((x - lo) / span * 1023.0).clamp(0.0, 1023.0).to(torch.int64)
+    return torch.argsort(_spread10(q[:, 0]) | (_spread10(q[:, 1]) << 1) | (_spread10(q[:, 2]) << 2), stable=True)
+
+
+@on_tensor_device
+def _adi(points, est, gt, inv_unit, sort, prune):
+    V, N = int(points.shape[0]), int(est.shape[0])
+    if sort:
+        points = points[morton_order(points)].contiguous()
+    need = int(_lib.load().sam6d_pose_adi_workspace_bytes(V, N))
+    ws = _empty((need // 8,), points, torch.int64)
+    adi_sum = _empty((N,), points, torch.int64)
+    _lib.call("sam6d_pose_adi", _p(points), V, _p(est), _p(gt), N, inv_unit, 0 if prune else 1, adi_sum.data_ptr(), ws.data_ptr(), need, _s())
+    return AdiErrors((adi_sum.to(torch.float64) / ADD_SCALE / inv_unit / V).to(torch.float32), adi_sum)
+
+
+def adi(mesh_or_points, R_est, t_est, R_gt, t_gt, scale=1.0, unit=None, sort=True, prune=True):
+    """ADD-S / ADI of N estimated poses against their ground truths, over the model's vertices: the mean over the vertices of the
+    distance from a vertex under the estimate to the NEAREST vertex under the ground truth, the error for an object whose symmetries
+    make ADD meaningless.  No symmetry transforms are applied.
+
+    mesh_or_points, R_est, t_est, R_gt, t_gt, scale and unit as pose_errors has them (there is no K); a nearest distance above 4096
+    units counts as 4096, and so does a vertex with no nearest distance (a NaN in the pose).  sort: order the vertices along a Morton
+    curve first (morton_order), so that the search's tiles are compact; prune: skip the tiles whose box cannot hold a nearer vertex.
+    Neither changes a bit of the result; prune=False is the full V x V walk.
+    -> AdiErrors: adi (N) f32 in the unit of t, adi_sum (N) i64.
+    A CPU tensor raises RuntimeError; a wrong shape or dtype ValueError naming the argument."""
+    name = "adi"
+    N, R_est, t_est, R_gt, t_gt = _pair(name, R_est, t_est, R_gt, t_gt, MAX_POSES)
+    points = _points(name, mesh_or_points, R_est)
+    inv_unit = _inv_unit(name, unit)
+    _same_device(name, points, (("R_est", R_est), ("t_est", t_est), ("R_gt", R_gt), ("t_gt", t_gt)))
+    return _adi(points, verify.pose_views(R_est, t_est, scale), verify.pose_views(R_gt, t_gt, scale), inv_unit, bool(sort), bool(prune))
+
+
+@on_tensor_device
+def _diameter(points, sort, prune):
+    if sort:
+        points = points[morton_order(points)].contiguous()
+    V = int(points.shape[0])
+    seeds = torch.cat([points.argmin(dim=0), points.argmax(dim=0)]).to(torch.int32)  # the extreme vertex of each axis, both ends
+    need = int(_lib.load().sam6d_points_diameter_workspace_bytes(V))
+    ws = _empty((need // 8,), points, torch.int64)
+    out = _empty((1,), points)
+    _lib.call("sam6d_points_diameter", _p(points), V, _p(seeds), int(seeds.numel()), 0 if prune else 1, _p(out), ws.data_ptr(), need, _s())
+    return out.reshape(())
+
+
+def _model_points(name, mesh_or_points):
+    """_points for the calls without a pose: a numpy mesh goes to the current HIP device"""
+    like = torch.empty(0, device="cuda") if torch.cuda.is_available() else None
+    return _points(name, mesh_or_points, like)
+
+
+def model_diameter(mesh_or_points, sort=True, prune=True):
+    """The model's diameter as bop_toolkit defines it, the largest distance between two of its vertices, by an exact search over all
+    pairs: mesh_or_points as pose_errors has it -> a 0-dim f32 tensor on the device, in CAD units.  NaN where a coordinate is not
+    finite.  sort and prune as adi has them: neither changes a bit of the result.
+    A CPU tensor raises RuntimeError; a wrong shape or dtype ValueError naming the argument."""
+    return _diameter(_model_points("model_diameter", mesh_or_points), bool(sort), bool(prune))
+
+
+def _extent(points):
+    """(V,3) -> (6) min_x, min_y, min_z, size_x, size_y, size_z; plain torch ops"""
+    lo, hi = points.min(dim=0).values, points.max(dim=0).values
+    return torch.cat([lo, hi - lo])
+
+
+INFO_FIELDS = ("diameter", "min_x", "min_y", "min_z", "size_x", "size_y", "size_z")
+
+
+def models_info(mesh_or_points):
+    """The geometric fields of a BOP models_info.json entry for a model that has none (a CAD file onboard.load_mesh read): diameter
+    (model_diameter) and min_x, min_y, min_z, size_x, size_y, size_z (the bounding box; plain torch ops), a dict of Python floats in
+    CAD units.  One read-back of 28 bytes.  Symmetries are not detected."""
+    points = _model_points("models_info", mesh_or_points)
+    row = torch.cat([_diameter(points, True, True).reshape(1), _extent(points)]).cpu()
+    return dict(zip(INFO_FIELDS, (float(v) for v in row)))
 
 
 # ------------------------------------------------------------------------------------------------------------ VSD
