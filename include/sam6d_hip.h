@@ -1123,6 +1123,52 @@ size_t sam6d_points_diameter_workspace_bytes(int V);
 int sam6d_points_diameter(const float* points, int V, const int* seeds, int n_seeds, int flags, float* diameter, void* workspace,
                           size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * All-pairs pose errors, the matching of estimates to ground-truth instances and the removal of duplicate poses
+ * (csrc/posematch.hip, restated in tests/posematch_ref.py).  (New entries only, so SAM6D_ABI_VERSION stays.)
+ * ------------------------------------------------------------------------------------------------------------ */
+/* The point errors of every pose a[i] against every pose b[j] of one object.  Beside PEM/run_inference_custom_pytorch.py:460-471,
+ * which writes all its poses out unmatched and has no evaluation.  For every (i, j) the outputs are, bit for bit, what
+ * sam6d_pose_point_errors gives for est = a[i], gt = b[j] (the recipe at the top of csrc/poseerr.hip, one copy of its per-point step
+ * in csrc/poseerr_point.h): G = fl32(b[j] o syms[s]), mssd = sqrtf(min_s max_x d2), mspd the same in pixels, the lowest s on a tie,
+ * n_skipped the points behind the camera under either pose for s = 0, add_sum the 2^30-scaled integer ADD sum capped at 2^42 a term.
+ * points (V,3) f32; a (A,3,4), b (B,3,4), syms (S,3,4) f32 row-major; inv_unit > 0, finite.  flags: bit 0 = no MSPD: fx fy cx cy
+ * are ignored, the projections are not computed, and mspd, mspd_sym, n_skipped are not written (they may be null); other bits 0.
+ * mssd, mspd (A,B) f32; mssd_sym, mspd_sym, n_skipped (A,B) i32; add_sum (A,B) i64, 8-byte aligned.
+ * The B S matrices are split over the launch grid by the sizes alone (runs of 8 .. 256 matrices, at least about 2048 workgroups where there are that many runs); the
+ * partial results meet as integer atomic maxima and adds, so the outputs are a function of the inputs alone and not of the split.
+ * V 1 .. 2^20; A, B, S 1 .. 1024 each and A B S <= 2^22; workspace 8-byte aligned and at least
+ * sam6d_pose_pair_errors_workspace_bytes(A, B, S) = 8 A B S (0 for sizes outside the limits); anything else, a null pointer or a
+ * non-finite inv_unit returns non-zero without a launch or a write, the argument named in sam6d_last_error(). */
+size_t sam6d_pose_pair_errors_workspace_bytes(int A, int B, int S);
+int sam6d_pose_pair_errors(const float* points, int V, const float* a, int A, const float* b, int B, const float* syms, int S, float fx,
+                           float fy, float cx, float cy, float inv_unit, int flags, float* mssd, float* mspd, int* mssd_sym,
+                           int* mspd_sym, int* n_skipped, long long* add_sum, void* workspace, size_t workspace_bytes, void* stream);
+/* Greedy matching of A estimates to B targets from an error matrix, for each of T thresholds on its own.  Beside
+ * PEM/run_inference_custom_pytorch.py:460-471, which writes its poses out unmatched.  BOP's match_poses in kind; the recipe is the
+ * package's own (csrc/posematch.hip RECIPE b) and is pinned against its numpy restatement, not against bop_toolkit.
+ * err (A,B) f32; scores (A) f32; thr (T) f32 ON THE DEVICE; valid (B) bytes, non-zero = a target that may be taken, null = all.
+ * The estimates go by descending score, equal scores the lower index first, a NaN score last; with max_ests > 0 only the first
+ * max_ests of that order take part.  Per threshold k, in that order, estimate i takes the target j with the smallest err[i][j] among
+ * those valid, not yet taken and with err[i][j] < thr[k] (strict; false for a NaN), the lowest j among equal errors.
+ * est_match (T,A) i32 = j or -1; gt_match (T,B) i32 = i or -1; n_matched (T) i32.  One wave per threshold, no atomics.
+ * A, B 1 .. 1024, T 1 .. 64, max_ests >= 0; workspace 4-byte aligned and at least sam6d_pose_match_workspace_bytes(A) = 4 A rounded
+ * up to 16 (0 for an A outside the limits); anything else or a null pointer returns non-zero without a launch or a write. */
+size_t sam6d_pose_match_workspace_bytes(int A);
+int sam6d_pose_match(const float* err, int A, int B, const float* scores, const float* thr, int T, const unsigned char* valid,
+                     int max_ests, int* est_match, int* gt_match, int* n_matched, void* workspace, size_t workspace_bytes, void* stream);
+/* Greedy removal of duplicate poses from an (N,N) error matrix.  Beside PEM/run_inference_custom_pytorch.py:460-471, which writes
+ * every pose with its score.  The recipe is the package's own (csrc/posematch.hip RECIPE c), pinned against its numpy restatement.
+ * err (N,N) f32, need not be symmetric, the diagonal is never read; scores (N) f32, the order as in sam6d_pose_match.  Walking the
+ * order, pose i is kept unless a pose r kept before it has err[r][i] < thresh (strict; false for a NaN).
+ * keep_idx (N) i64, 8-byte aligned: the kept poses in order, then -1; count (1) i32; suppressed_by (N) i32: the first kept pose in
+ * order that suppresses i, i itself when it is kept.  No atomics.
+ * N 1 .. 1024; workspace 8-byte aligned and at least sam6d_pose_nms_workspace_bytes(N) = 4 N rounded up to 16, + 8 N ceil(N / 64)
+ * (0 for an N outside the limits); anything else or a null pointer returns non-zero without a launch or a write. */
+size_t sam6d_pose_nms_workspace_bytes(int N);
+int sam6d_pose_nms(const float* err, const float* scores, int N, float thresh, long long* keep_idx, int* count, int* suppressed_by,
+                   void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

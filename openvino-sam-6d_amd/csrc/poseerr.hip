@@ -52,6 +52,7 @@
 // `total` (or below 0) is addressed whatever they hold, and counts is addressed by a pose index in [0, N) alone.  Inconsistent boxes
 // and offsets give meaningless counts, never an access outside the buffers.
 #include "verify_raster.h"
+#include "poseerr_point.h"
 #include "../../include/sam6d_hip.h"
 
 #define PE_MAX_V (1 << 20)
@@ -59,44 +60,14 @@
 #define PE_MAX_S 1024
 #define PE_MAX_PAIRS 512
 #define PE_MAX_T 16
-#define PE_WG 256
-#define PE_PTS 4                    // points per thread
-#define PE_CHUNK (PE_WG * PE_PTS)   // points per workgroup
-#define PE_ST 128                   // symmetries per LDS tile
 #define PE_VSD_WG 1024              // sixteen waves, as verify.hip's classify: one offer per workgroup at a pose's counters
-#define PE_NAN 0x7fc00000u
-#define PE_SCALE 1073741824.0       // 2^30
-#define PE_TERM_MAX 4398046511104.0 // 2^42
 
-struct PeCam {
-  float fx, fy, cx, cy;
-};
 struct PeTaus {
   float v[PE_MAX_T];
 };
 
 // ---------------------------------------------------------------------------------------------------------- a. point errors
-// RECIPE maxima: the word a value offers
-__device__ __forceinline__ unsigned pe_bits(float v) { return v > 0.f ? __float_as_uint(v) : (v == 0.f ? 0u : PE_NAN); }
-
-template <int CTRL>
-__device__ __forceinline__ unsigned pe_dpp(unsigned x) {
-  return (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xf, 0xf, false);
-}
-// the maximum over the wave in every lane, on the DPP path as common.h's wave_max_dpp: rotations inside each row of 16, then the
-// exchanges with the lanes 16 and 32 away
-__device__ __forceinline__ unsigned pe_wave_max(unsigned v) {
-  typedef unsigned u2_ __attribute__((ext_vector_type(2)));
-  v = max(v, pe_dpp<0x128>(v));  // row_ror:8
-  v = max(v, pe_dpp<0x124>(v));  // row_ror:4
-  v = max(v, pe_dpp<0x122>(v));  // row_ror:2
-  v = max(v, pe_dpp<0x121>(v));  // row_ror:1
-  const u2_ a = __builtin_amdgcn_permlane16_swap(v, v, false, false);
-  v = max(v, (threadIdx.x & 16) ? a[0] : a[1]);
-  const u2_ b = __builtin_amdgcn_permlane32_swap(v, v, false, false);
-  return max(v, (threadIdx.x & 32) ? b[0] : b[1]);
-}
-
+// The per-point step, the word a value offers to a maximum and the wave reductions are poseerr_point.h's, shared with posematch.hip.
 // grid (ceil(V / 1024), N), four waves: point blockIdx.x * 1024 + j * 256 + tid for j = 0 .. 3.  ws (N,S,2) u32 arrives zeroed:
 // word 0 the d2 maximum of the pair, word 1 the p2 maximum
 __global__ __launch_bounds__(PE_WG) void point_errors_kernel(const float* __restrict__ points, int V, const float* __restrict__ est,
@@ -106,73 +77,27 @@ __global__ __launch_bounds__(PE_WG) void point_errors_kernel(const float* __rest
   __shared__ float G[PE_ST][12];
   __shared__ unsigned mx[PE_ST * 2];
   const int n = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
-  const float* E = est + (size_t)n * 12;
   const float* Gt = gt + (size_t)n * 12;
-  float x[PE_PTS][3], e[PE_PTS][3], ue[PE_PTS], ve[PE_PTS];
-  bool live[PE_PTS], front[PE_PTS];
-#pragma unroll
-  for (int j = 0; j < PE_PTS; ++j) {
-    const int idx = blockIdx.x * PE_CHUNK + j * PE_WG + tid;  // below 2^20 + 1024
-    live[j] = idx < V;
-    x[j][0] = x[j][1] = x[j][2] = 0.f;
-    if (live[j]) {
-      x[j][0] = points[(size_t)idx * 3];
-      x[j][1] = points[(size_t)idx * 3 + 1];
-      x[j][2] = points[(size_t)idx * 3 + 2];
-    }
-    rs_to_camera(E, x[j], e[j]);
-    front[j] = e[j][2] > 0.f;
-    ue[j] = cam.fx * (e[j][0] / e[j][2]) + cam.cx;
-    ve[j] = cam.fy * (e[j][1] / e[j][2]) + cam.cy;
-  }
+  PePoints<true> P;
+  P.load(points, V, blockIdx.x, tid, est + (size_t)n * 12, cam);
   for (int s0 = 0; s0 < S; s0 += PE_ST) {
     const int cnt = min(PE_ST, S - s0);
     __syncthreads();  // the tile before is flushed
-    for (int t = tid; t < cnt * 12; t += PE_WG) {
-      const int sl = t / 12, k = t % 12, r = k >> 2, c = k & 3;
-      const float* Sm = syms + (size_t)(s0 + sl) * 12;
-      double a = (double)Gt[r * 4] * (double)Sm[c];
-      a = a + (double)Gt[r * 4 + 1] * (double)Sm[4 + c];
-      a = a + (double)Gt[r * 4 + 2] * (double)Sm[8 + c];
-      if (c == 3) a = a + (double)Gt[r * 4 + 3];
-      G[sl][k] = (float)a;
-    }
+    for (int t = tid; t < cnt * 12; t += PE_WG) G[t / 12][t % 12] = pe_compose(Gt, syms + (size_t)(s0 + t / 12) * 12, t % 12);
     for (int t = tid; t < cnt * 2; t += PE_WG) mx[t] = 0u;
     __syncthreads();
     for (int sl = 0; sl < cnt; ++sl) {
       float M[12];
 #pragma unroll
       for (int k = 0; k < 12; ++k) M[k] = G[sl][k];
-      unsigned m2 = 0u, mp = 0u;
+      unsigned m2, mp;
       float d2s[PE_PTS];
       bool skip[PE_PTS];
-#pragma unroll
-      for (int j = 0; j < PE_PTS; ++j) {
-        float g[3];
-        rs_to_camera(M, x[j], g);
-        const float dx = e[j][0] - g[0], dy = e[j][1] - g[1], dz = e[j][2] - g[2];
-        const float d2 = (dx * dx + dy * dy) + dz * dz;
-        const float ug = cam.fx * (g[0] / g[2]) + cam.cx, vg = cam.fy * (g[1] / g[2]) + cam.cy;
-        const float du = ue[j] - ug, dv = ve[j] - vg;
-        const float p2 = du * du + dv * dv;
-        skip[j] = !(front[j] && g[2] > 0.f);
-        d2s[j] = d2;
-        if (live[j]) {
-          m2 = max(m2, pe_bits(d2));
-          if (!skip[j]) mp = max(mp, pe_bits(p2));
-        }
-      }
+      P.step(M, cam, m2, mp, d2s, skip);
       if (s0 + sl == 0) {  // (uniform) ADD and the skipped points, of the first symmetry alone
-        long long term = 0;
-        int skipped = 0;
-#pragma unroll
-        for (int j = 0; j < PE_PTS; ++j) {
-          if (!live[j]) continue;
-          double w = ((double)sqrtf(d2s[j]) * (double)inv_unit) * PE_SCALE;
-          if (!(w <= PE_TERM_MAX)) w = PE_TERM_MAX;
-          term += (long long)rint(w);
-          skipped += skip[j] ? 1 : 0;
-        }
+        long long term;
+        int skipped;
+        P.add_terms(d2s, skip, inv_unit, term, skipped);
         term = wave_sum(term);
         skipped = wave_sum(skipped);
         if (lane == 0) {
@@ -193,15 +118,6 @@ __global__ __launch_bounds__(PE_WG) void point_errors_kernel(const float* __rest
       if (v) __hip_atomic_fetch_max(ws + ((size_t)n * S + s0) * 2 + t, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
-}
-
-__device__ __forceinline__ unsigned long long pe_wave_min_u64(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long w = __shfl_xor(v, o, 64);
-    v = w < v ? w : v;
-  }
-  return v;
 }
 
 // one wave per pose: the only writer of mssd, mspd and their indices

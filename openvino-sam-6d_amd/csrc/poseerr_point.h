@@ -1,0 +1,124 @@
+// The per-point step of the point errors (poseerr.hip RECIPE a) and the bit-pattern helpers around it, in one copy for the two
+// kernels that walk model points under a pose and a list of composed matrices: point_errors_kernel (poseerr.hip: est[n] against
+// gt[n] o syms[s]) and pair_errors_kernel (posematch.hip: a[i] against b[j] o syms[s]).  The recipe is written out at the top of
+// poseerr.hip and nowhere else; every function here names the line of it that it is.
+#pragma once
+#include "raster.h"
+#include "common.h"
+
+#define PE_WG 256
+#define PE_PTS 4                    // points per thread
+#define PE_CHUNK (PE_WG * PE_PTS)   // points per workgroup
+#define PE_ST 128                   // composed matrices per LDS tile
+#define PE_NAN 0x7fc00000u
+#define PE_SCALE 1073741824.0       // 2^30
+#define PE_TERM_MAX 4398046511104.0 // 2^42
+
+struct PeCam {
+  float fx, fy, cx, cy;
+};
+
+// RECIPE maxima: the word a value offers
+__device__ __forceinline__ unsigned pe_bits(float v) { return v > 0.f ? __float_as_uint(v) : (v == 0.f ? 0u : PE_NAN); }
+
+template <int CTRL>
+__device__ __forceinline__ unsigned pe_dpp(unsigned x) {
+  return (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xf, 0xf, false);
+}
+// the maximum over the wave in every lane, on the DPP path as common.h's wave_max_dpp: rotations inside each row of 16, then the
+// exchanges with the lanes 16 and 32 away
+__device__ __forceinline__ unsigned pe_wave_max(unsigned v) {
+  typedef unsigned u2_ __attribute__((ext_vector_type(2)));
+  v = max(v, pe_dpp<0x128>(v));  // row_ror:8
+  v = max(v, pe_dpp<0x124>(v));  // row_ror:4
+  v = max(v, pe_dpp<0x122>(v));  // row_ror:2
+  v = max(v, pe_dpp<0x121>(v));  // row_ror:1
+  const u2_ a = __builtin_amdgcn_permlane16_swap(v, v, false, false);
+  v = max(v, (threadIdx.x & 16) ? a[0] : a[1]);
+  const u2_ b = __builtin_amdgcn_permlane32_swap(v, v, false, false);
+  return max(v, (threadIdx.x & 32) ? b[0] : b[1]);
+}
+
+__device__ __forceinline__ unsigned long long pe_wave_min_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long w = __shfl_xor(v, o, 64);
+    v = w < v ? w : v;
+  }
+  return v;
+}
+
+// RECIPE G: element k = 4 r + c of fl32(Gt o Sm), both (3,4) row-major
+__device__ __forceinline__ float pe_compose(const float* __restrict__ Gt, const float* __restrict__ Sm, int k) {
+  const int r = k >> 2, c = k & 3;
+  double a = (double)Gt[r * 4] * (double)Sm[c];
+  a = a + (double)Gt[r * 4 + 1] * (double)Sm[4 + c];
+  a = a + (double)Gt[r * 4 + 2] * (double)Sm[8 + c];
+  if (c == 3) a = a + (double)Gt[r * 4 + 3];
+  return (float)a;
+}
+
+// the points of one thread and what does not change over the matrices: x, e = E x, e's pixel (PIX), whether e lies in front
+template <bool PIX>
+struct PePoints {
+  float x[PE_PTS][3], e[PE_PTS][3], ue[PE_PTS], ve[PE_PTS];
+  bool live[PE_PTS], front[PE_PTS];
+
+  // points chunk * 1024 + j * 256 + tid for j = 0 .. 3 (below 2^20 + 1024); RECIPE points, pixels for E
+  __device__ __forceinline__ void load(const float* __restrict__ points, int V, int chunk, int tid, const float* __restrict__ E, const PeCam& cam) {
+#pragma unroll
+    for (int j = 0; j < PE_PTS; ++j) {
+      const int idx = chunk * PE_CHUNK + j * PE_WG + tid;
+      live[j] = idx < V;
+      x[j][0] = x[j][1] = x[j][2] = 0.f;
+      if (live[j]) {
+        x[j][0] = points[(size_t)idx * 3];
+        x[j][1] = points[(size_t)idx * 3 + 1];
+        x[j][2] = points[(size_t)idx * 3 + 2];
+      }
+      rs_to_camera(E, x[j], e[j]);
+      front[j] = e[j][2] > 0.f;
+      if (PIX) {
+        ue[j] = cam.fx * (e[j][0] / e[j][2]) + cam.cx;
+        ve[j] = cam.fy * (e[j][1] / e[j][2]) + cam.cy;
+      }
+    }
+  }
+
+  // RECIPE d2, pixels, skipped, maxima for the matrix M (12 floats in registers): the thread's words m2, mp over its live points;
+  // d2s and skip per point for the caller's ADD
+  __device__ __forceinline__ void step(const float (&M)[12], const PeCam& cam, unsigned& m2, unsigned& mp, float (&d2s)[PE_PTS], bool (&skip)[PE_PTS]) const {
+    m2 = 0u;
+    mp = 0u;
+#pragma unroll
+    for (int j = 0; j < PE_PTS; ++j) {
+      float g[3];
+      rs_to_camera(M, x[j], g);
+      const float dx = e[j][0] - g[0], dy = e[j][1] - g[1], dz = e[j][2] - g[2];
+      const float d2 = (dx * dx + dy * dy) + dz * dz;
+      d2s[j] = d2;
+      skip[j] = !(front[j] && g[2] > 0.f);
+      if (live[j]) m2 = max(m2, pe_bits(d2));
+      if (PIX) {
+        const float ug = cam.fx * (g[0] / g[2]) + cam.cx, vg = cam.fy * (g[1] / g[2]) + cam.cy;
+        const float du = ue[j] - ug, dv = ve[j] - vg;
+        const float p2 = du * du + dv * dv;
+        if (live[j] && !skip[j]) mp = max(mp, pe_bits(p2));
+      }
+    }
+  }
+
+  // RECIPE ADD, skipped: the thread's sum of terms and count of skipped points, of its live points
+  __device__ __forceinline__ void add_terms(const float (&d2s)[PE_PTS], const bool (&skip)[PE_PTS], float inv_unit, long long& term, int& skipped) const {
+    term = 0;
+    skipped = 0;
+#pragma unroll
+    for (int j = 0; j < PE_PTS; ++j) {
+      if (!live[j]) continue;
+      double w = ((double)sqrtf(d2s[j]) * (double)inv_unit) * PE_SCALE;
+      if (!(w <= PE_TERM_MAX)) w = PE_TERM_MAX;
+      term += (long long)rint(w);
+      skipped += skip[j] ? 1 : 0;
+    }
+  }
+};

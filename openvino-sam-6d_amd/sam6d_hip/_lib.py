@@ -187,6 +187,12 @@ SIGNATURES = {
     "sam6d_pose_adi": [c_p, c_i, c_p, c_p, c_i, c_f, c_i, c_p, c_p, ctypes.c_size_t, c_p],
     "sam6d_points_diameter_workspace_bytes": [c_i],
     "sam6d_points_diameter": [c_p, c_i, c_p, c_i, c_i, c_p, c_p, ctypes.c_size_t, c_p],
+    "sam6d_pose_pair_errors_workspace_bytes": [c_i, c_i, c_i],
+    "sam6d_pose_pair_errors": [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_i] + [c_f] * 5 + [c_i] + [c_p] * 7 + [ctypes.c_size_t, c_p],
+    "sam6d_pose_match_workspace_bytes": [c_i],
+    "sam6d_pose_match": [c_p, c_i, c_i, c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, ctypes.c_size_t, c_p],
+    "sam6d_pose_nms_workspace_bytes": [c_i],
+    "sam6d_pose_nms": [c_p, c_p, c_i, c_f, c_p, c_p, c_p, c_p, ctypes.c_size_t, c_p],
 }
 
 _lib = None

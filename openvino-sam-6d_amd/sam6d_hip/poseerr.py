@@ -12,8 +12,8 @@ bounding box cannot change the result; the bound holds in fp32 without a margin,
 ADI is evaluated over the vertices, as pose_errors is.
 
 Left to the caller: symmetry-aware ADI, the index of the nearest vertex and of the diametral pair, ADI over surface samples, the
-`tlinear` cost, other visibility modes, several meshes in one call, BOP's file formats, the matching of estimates to ground-truth
-instances, and the BOP threshold lists (recall and auc take any).
+`tlinear` cost, other visibility modes, several meshes in one call, BOP's file formats, and the BOP threshold lists (recall and auc
+take any).  The matching of estimates to ground-truth instances, which every function here takes as given, is sam6d_hip.posematch's.
 
 Imports verify, runtime, _lib, torch and numpy only.  There is no CPU route: a CPU tensor raises RuntimeError.
 """

@@ -1,0 +1,243 @@
+"""All-pairs pose errors on the device, and what is built on an error matrix: the matching of estimates to ground-truth instances
+and the removal of duplicate poses.  sam6d_hip.poseerr scores pose PAIRS (estimate n against ground truth n); with several proposals
+per instance, as SAM's over-segmentation gives them, somebody has to decide which ground truth an estimate belongs to and which
+estimates are the same instance, and both need the error of every pose against every other pose of the same object.
+
+The reference has none of this: it writes all its poses with their scores (PEM/run_inference_custom_pytorch.py:460-471) and leaves
+matching and scoring to bop_toolkit.  pair_errors is poseerr.pose_errors for every (i, j), bit for bit (csrc/posematch.hip over the
+per-point step of csrc/poseerr_point.h).  match_poses is BOP's match_poses IN KIND -- greedy, by descending score, each estimate
+taking the nearest free target under the threshold -- and pose_nms is a greedy suppression; both recipes are the package's own,
+written out at the top of csrc/posematch.hip and restated in tests/posematch_ref.py, and every comparison with that restatement is
+bit for bit.  Nothing here is pinned against bop_toolkit itself, which the suite does not have.
+
+Poses of different objects are separate calls, one mesh each (INTEGRATION.md has the loop over template_ids).  Left to the caller:
+symmetry-aware ADI and VSD as matrices, several meshes in one call, BOP's file formats and threshold lists.
+
+Imports poseerr, verify, runtime, _lib, torch and numpy only; the library is loaded at the first launch, not at import.  There is no
+CPU route: a CPU tensor raises RuntimeError.
+"""
+import numpy as np
+import torch
+
+from . import _lib, verify
+from .poseerr import ADD_SCALE, MAX_POINTS, _intrinsics, _inv_unit, _points, _same_device  # noqa: F401
+from .runtime import _empty, _p, _s, on_tensor_device
+from .verify import _tensor
+
+MAX_POSES = 1024             # A, B, S of pair_errors and match_poses, N of pose_nms
+MAX_TRIPLES = 1 << 22        # A B S: a workspace of 8 bytes per triple, 32 MiB at most
+MAX_THRESHOLDS = 64
+NO_MSPD = 1                  # sam6d_pose_pair_errors flags bit 0
+
+
+class PairErrors:
+    """What pair_errors returns; every tensor is on the device and (A,B): row i the pose a[i], column j the pose b[j].  mssd, add f32
+    in the unit of t, mssd_sym i32, add_sum i64 the integer ADD is formed from; with K also mspd f32 in pixels, mspd_sym i32 and
+    n_skipped i32, else None.  The fields are poseerr.PoseErrors' for est = a[i], gt = b[j]."""
+
+    def __init__(self, mssd, mspd, add, mssd_sym, mspd_sym, n_skipped, add_sum):
+        self.mssd, self.mspd, self.add, self.mssd_sym, self.mspd_sym = mssd, mspd, add, mssd_sym, mspd_sym
+        self.n_skipped, self.add_sum = n_skipped, add_sum
+
+
+class PoseMatches:
+    """What match_poses returns.  est_match (T,A) i32 the target of estimate i under threshold k or -1, gt_match (T,B) i32 the
+    estimate that took target j or -1, n_matched (T) i32, all on the device; n_targets a Python int, the targets that could be taken
+    (valid ones)."""
+
+    def __init__(self, est_match, gt_match, n_matched, n_targets):
+        self.est_match, self.gt_match, self.n_matched, self.n_targets = est_match, gt_match, n_matched, n_targets
+
+
+class PoseNms:
+    """What pose_nms returns, all on the device.  keep_idx (N) i64 the kept poses by descending score, then -1; count (1) i32 how many;
+    suppressed_by (N) i32 the first kept pose in order that suppresses i, i itself when it is kept.  kept() reads count back (4
+    bytes) and returns keep_idx[:count]."""
+
+    def __init__(self, keep_idx, count, suppressed_by):
+        self.keep_idx, self.count, self.suppressed_by = keep_idx, count, suppressed_by
+
+    def kept(self):
+        return self.keep_idx[:int(self.count)]
+
+
+# ------------------------------------------------------------------------------------------------------------ pair errors
+def _poses(name, what, R, t):
+    if not torch.is_tensor(R) or R.dim() != 3:
+        raise ValueError("%s: R_%s must be an (N,3,3) float32 tensor" % (name, what))
+    N = int(R.shape[0])
+    R, t = _tensor(R, name, "R_" + what, torch.float32, (N, 3, 3)), _tensor(t, name, "t_" + what, torch.float32, (N, 3))
+    if not 1 <= N <= MAX_POSES:
+        raise ValueError("%s: R_%s: %s = %d is not in 1 .. %d" % (name, what, what.upper(), N, MAX_POSES))
+    return R, t
+
+
+def _syms(name, syms, points):
+    """(S,3,4) f32 beside the points: None is the identity alone, a host array is uploaded"""
+    if syms is None:
+        syms = np.concatenate([np.eye(3), np.zeros((3, 1))], axis=1)[None].astype(np.float32)
+    host = None if torch.is_tensor(syms) else np.asarray(syms)
+    syms = _tensor(syms if host is None else torch.from_numpy(np.ascontiguousarray(host)), name, "syms", torch.float32, (None, 3, 4))
+    if not 1 <= int(syms.shape[0]) <= MAX_POSES:
+        raise ValueError("%s: syms: S = %d is not in 1 .. %d" % (name, int(syms.shape[0]), MAX_POSES))
+    if host is not None:
+        if not points.is_cuda:
+            raise RuntimeError("%s: needs HIP device tensors (this build has no CPU path)" % name)
+        syms = syms.to(points.device)
+    return syms
+
+
+@on_tensor_device
+def _pair_errors(points, a, b, syms, intr, inv_unit):
+    V, A, B, S = int(points.shape[0]), int(a.shape[0]), int(b.shape[0]), int(syms.shape[0])
+    need = int(_lib.load().sam6d_pose_pair_errors_workspace_bytes(A, B, S))
+    ws = _empty((need // 8,), points, torch.int64)
+    mssd, mssd_sym = _empty((A, B), points), _empty((A, B), points, torch.int32)
+    add_sum = _empty((A, B), points, torch.int64)
+    mspd = mspd_sym = skipped = None
+    if intr is not None:
+        mspd, mspd_sym, skipped = _empty((A, B), points), _empty((A, B), points, torch.int32), _empty((A, B), points, torch.int32)
+    _lib.call("sam6d_pose_pair_errors", _p(points), V, _p(a), A, _p(b), B, _p(syms), S, *(intr or (0.0, 0.0, 0.0, 0.0)), inv_unit,
+              0 if intr is not None else NO_MSPD, _p(mssd), _p(mspd), _p(mssd_sym), _p(mspd_sym), _p(skipped), add_sum.data_ptr(),
+              ws.data_ptr(), need, _s())
+    add = (add_sum.to(torch.float64) / ADD_SCALE / inv_unit / V).to(torch.float32)
+    return PairErrors(mssd, mspd, add, mssd_sym, mspd_sym, skipped, add_sum)
+
+
+def pair_errors(mesh_or_points, R_a, t_a, R_b, t_b, K=None, syms=None, scale=1.0, unit=None):
+    """MSSD, MSPD and ADD of every pose a[i] against every pose b[j] of one object, over the model's vertices: for every (i, j), bit
+    for bit, what poseerr.pose_errors gives for est = a[i], gt = b[j].
+
+    mesh_or_points, syms, scale and unit as poseerr.pose_errors has them.  R_a (A,3,3), t_a (A,3), R_b (B,3,3), t_b (B,3) f32 HIP
+    tensors; A, B and the number of symmetries S at most 1024 each, and A B S at most 2^22.  K: one 3 x 3 matrix or (fx, fy, cx, cy);
+    None leaves MSPD out: the projections are not computed and mspd, mspd_sym, n_skipped are None.
+    -> PairErrors, every field (A,B).  The symmetries are applied to b: where a symmetry other than the first attains the minimum,
+    mssd[i][j] and mssd[j][i] of a set against itself can differ in the last bits.
+    A CPU tensor raises RuntimeError; a wrong shape or dtype ValueError naming the argument."""
+    name = "pair_errors"
+    R_a, t_a = _poses(name, "a", R_a, t_a)
+    R_b, t_b = _poses(name, "b", R_b, t_b)
+    points = _points(name, mesh_or_points, R_a)
+    intr = None if K is None else _intrinsics(name, K)
+    inv_unit = _inv_unit(name, unit)
+    syms = _syms(name, syms, points)
+    A, B, S = int(R_a.shape[0]), int(R_b.shape[0]), int(syms.shape[0])
+    if A * B * S > MAX_TRIPLES:
+        raise ValueError("%s: A B S = %d x %d x %d = %d is above the cap of %d: split a or b" % (name, A, B, S, A * B * S, MAX_TRIPLES))
+    _same_device(name, points, (("R_a", R_a), ("t_a", t_a), ("R_b", R_b), ("t_b", t_b), ("syms", syms)))
+    return _pair_errors(points, verify.pose_views(R_a, t_a, scale), verify.pose_views(R_b, t_b, scale), syms, intr, inv_unit)
+
+
+# ------------------------------------------------------------------------------------------------------------ matching
+def _device_only(name, *tensors):
+    """after the shapes and dtypes: the host-side shortcuts (no targets, no poses) refuse a CPU tensor as a launch would"""
+    if any(torch.is_tensor(x) and not x.is_cuda for x in tensors):
+        raise RuntimeError("%s: needs HIP device tensors (this build has no CPU path)" % name)
+
+
+def _matrix(name, err, square=False):
+    err = _tensor(err, name, "err", torch.float32, (None, None))
+    if square and int(err.shape[0]) != int(err.shape[1]):
+        raise ValueError("%s: err must have shape (N,N), got %s" % (name, tuple(err.shape)))
+    return err
+
+
+@on_tensor_device
+def _match(err, scores, thr, valid, max_ests):
+    A, B, T = int(err.shape[0]), int(err.shape[1]), int(thr.shape[0])
+    need = int(_lib.load().sam6d_pose_match_workspace_bytes(A))
+    ws = _empty((need // 4,), err, torch.int32)
+    est_match, gt_match, n_matched = (_empty(s, err, torch.int32) for s in ((T, A), (T, B), (T,)))
+    _lib.call("sam6d_pose_match", _p(err), A, B, _p(scores), _p(thr), T, None if valid is None else valid.data_ptr(), max_ests, _p(est_match),
+              _p(gt_match), _p(n_matched), _p(ws), need, _s())
+    return est_match, gt_match, n_matched
+
+
+def match_poses(err, scores, thresholds, valid=None, max_ests=0):
+    """Greedy matching of A estimates to B ground-truth instances of one object from their error matrix, for each threshold on its
+    own: BOP's match_poses in kind, the package's own recipe (csrc/posematch.hip RECIPE b), not pinned against bop_toolkit.
+
+    err (A,B) f32 HIP tensor (pair_errors' mssd, mspd or add); scores (A) f32 HIP tensor; thresholds: 1 .. 64 numbers (a sequence or a
+    tensor), in err's unit; valid (B) bool HIP tensor, the targets that may be taken (None: all); max_ests > 0: only the max_ests
+    best-scored estimates take part (BOP: the number of instances of the object in the image).
+    The estimates go by descending score, equal scores the lower index first, a NaN score last.  In that order estimate i takes the
+    free valid target j with the smallest err[i][j] < threshold (strict; never a NaN), the lowest j among equal errors.
+    -> PoseMatches: est_match (T,A), gt_match (T,B), n_matched (T) i32 and n_targets.  B = 0, A = 0 or no valid target: everything is
+    -1 / 0, by torch fills without a launch.  One read-back of 8 bytes when valid is given.
+    A CPU tensor raises RuntimeError; a wrong shape or dtype ValueError naming the argument."""
+    name = "match_poses"
+    err = _matrix(name, err)
+    A, B = int(err.shape[0]), int(err.shape[1])
+    scores = _tensor(scores, name, "scores", torch.float32, (A,))
+    if not (A <= MAX_POSES and B <= MAX_POSES):
+        raise ValueError("%s: err: A, B = %d, %d: each must be at most %d" % (name, A, B, MAX_POSES))
+    thr = torch.as_tensor(thresholds, dtype=torch.float32).reshape(-1)
+    T = int(thr.shape[0])
+    if not 1 <= T <= MAX_THRESHOLDS:
+        raise ValueError("%s: thresholds: T = %d is not in 1 .. %d" % (name, T, MAX_THRESHOLDS))
+    max_ests = int(max_ests)
+    if max_ests < 0:
+        raise ValueError("%s: max_ests = %d is negative" % (name, max_ests))
+    n_targets = B
+    if valid is not None:
+        valid = _tensor(valid, name, "valid", torch.bool, (B,))
+    _device_only(name, err, scores, valid)
+    thr = thr.to(err.device).contiguous()
+    _same_device(name, err, (("scores", scores),) + ((("valid", valid),) if valid is not None else ()))
+    if valid is not None:
+        n_targets = int(valid.sum())
+    if A == 0 or n_targets == 0:
+        return PoseMatches(torch.full((T, A), -1, dtype=torch.int32, device=err.device), torch.full((T, B), -1, dtype=torch.int32, device=err.device),
+                           torch.zeros((T,), dtype=torch.int32, device=err.device), n_targets)
+    return PoseMatches(*_match(err, scores, thr, valid, max_ests), n_targets)
+
+
+def instance_recall(n_matched, n_targets):
+    """The recall over the INSTANCES: n_matched / n_targets as f32, NaN where n_targets is 0.  n_matched a tensor (match_poses'
+    (T), or sums of it over images and objects), n_targets a number or a tensor that broadcasts.  A plain torch op.
+    This is not poseerr.recall: that is the fraction of pose PAIRS under a threshold, where the caller already knows which ground
+    truth belongs to which estimate; this divides the matched instances by the instances there are, as every BOP recall does."""
+    if not torch.is_tensor(n_matched):
+        raise ValueError("instance_recall: n_matched must be a tensor")
+    n = torch.as_tensor(n_targets, device=n_matched.device).to(torch.float32)
+    return torch.where(n > 0, n_matched.to(torch.float32) / n, torch.full_like(n, float("nan")))
+
+
+# ------------------------------------------------------------------------------------------------------------ suppression
+@on_tensor_device
+def _nms(err, scores, thresh):
+    N = int(err.shape[0])
+    need = int(_lib.load().sam6d_pose_nms_workspace_bytes(N))
+    ws = _empty((need // 8,), err, torch.int64)
+    keep_idx, count, by = _empty((N,), err, torch.int64), _empty((1,), err, torch.int32), _empty((N,), err, torch.int32)
+    _lib.call("sam6d_pose_nms", _p(err), _p(scores), N, thresh, keep_idx.data_ptr(), _p(count), _p(by), ws.data_ptr(), need, _s())
+    return PoseNms(keep_idx, count, by)
+
+
+def pose_nms(err, scores, thresh):
+    """Greedy removal of duplicate poses of one object from their (N,N) error matrix (csrc/posematch.hip RECIPE c; the package's own
+    recipe).  err (N,N) f32 HIP tensor, err[r][i] the error of pose i against pose r; it need not be symmetric and its diagonal is not
+    read.  scores (N) f32 HIP tensor; the order is match_poses'.  Walking it, pose i is kept unless a pose r kept before it has
+    err[r][i] < thresh (strict).  A pose that only a suppressed pose would suppress is kept.
+    -> PoseNms: keep_idx (N) i64, count (1) i32, suppressed_by (N) i32.  N = 0: empty tensors, no launch.  N at most 1024.
+    A CPU tensor raises RuntimeError; a wrong shape or dtype ValueError naming the argument."""
+    name = "pose_nms"
+    err = _matrix(name, err, square=True)
+    N = int(err.shape[0])
+    scores = _tensor(scores, name, "scores", torch.float32, (N,))
+    if N > MAX_POSES:
+        raise ValueError("%s: err: N = %d is above %d" % (name, N, MAX_POSES))
+    _device_only(name, err, scores)
+    _same_device(name, err, (("scores", scores),))
+    if N == 0:
+        return PoseNms(torch.empty((0,), dtype=torch.int64, device=err.device), torch.zeros((1,), dtype=torch.int32, device=err.device),
+                       torch.empty((0,), dtype=torch.int32, device=err.device))
+    return _nms(err, scores, float(thresh))
+
+
+def nms_poses(mesh_or_points, R, t, scores, thresh, syms=None, scale=1.0):
+    """pose_nms on the MSSD of the poses against themselves: pair_errors(mesh, R, t, R, t, syms=syms, scale=scale).mssd, so thresh is
+    a length in the unit of t (a fraction of the model's diameter is a good one).  Arguments as pair_errors and pose_nms have them.
+    -> (PoseNms, the (N,N) mssd matrix)."""
+    mssd = pair_errors(mesh_or_points, R, t, R, t, K=None, syms=syms, scale=scale).mssd
+    return pose_nms(mssd, scores, thresh), mssd
