@@ -45,6 +45,18 @@ void sam6d_set_error(const char* fmt, ...);
     }                                                                                   \
   } while (0)
 
+// after the hipMemsetAsync calls of an entry `name`: e is the first error among them
+#define SAM6D_MEMSET_CHECK(name, e)                                                     \
+  do {                                                                                  \
+    if ((e) != hipSuccess) {                                                            \
+      sam6d_set_error("%s: memset failed: %s", name, hipGetErrorString(e));             \
+      return (int)(e);                                                                  \
+    }                                                                                   \
+  } while (0)
+
+// the refusal of a null argument, by the argument's own name
+#define SAM6D_POINTER(who, p) SAM6D_REQUIRE((p) != nullptr, who ": " #p " is a null pointer")
+
 // ---- device helpers ---------------------------------------------------------------------------------------
 typedef float f32x4 __attribute__((ext_vector_type(4)));     // one MFMA accumulator tile per lane
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));  // one fp16 MFMA operand (k = 32) per lane

@@ -53,16 +53,15 @@
 // nn_diameter_kernel, which reduces into a second word, and nn_diameter_finish_kernel, the only writer of `diameter`, reads both.
 //
 // WORK.  ADI: a workgroup of four waves takes 1024 points of one pose, four per thread, and keeps their e and m in registers, as
-// point_errors_kernel is laid out.  It walks the tiles beginning with the tiles of its own indices: with a small pose error the
-// nearest vertex is the point itself or a neighbour, so m is tight after the first tile and the bounds of the others decide.  Per
-// tile one __syncthreads_or takes the decision (and closes the reads of the tile before); the tile's g_j are formed once per
-// workgroup into LDS and read from there as broadcasts, nine vector instructions per pair.  At the end one wave_sum and one
-// atomic per wave.  Diameter: the same walk over the tile pairs (a, b) with b >= a, the column tiles of a row chunk dealt to
-// gridDim.y workgroups so that a small model still fills the chip; one atomic per wave.
+// pair_errors_kernel (posematch.hip) is laid out.  It walks the tiles beginning with the tiles of its own indices: with a small pose
+// error the nearest vertex is the point itself or a neighbour, so m is tight after the first tile and the bounds of the others decide.
+// The walk is nn_walk, the one copy of it: per tile one barrier with an OR takes the decision (and closes the reads of the tile
+// before); the tile's g_j are formed once per workgroup into LDS and read from there as broadcasts, nine vector instructions per
+// pair.  At the end one wave_sum and one atomic per wave.  Diameter: nn_walk over the tile pairs (a, b) with b >= a, the column
+// tiles of a row chunk dealt to gridDim.y workgroups so that a small model still fills the chip; one atomic per wave.
 //
 // WHAT THE HOST CANNOT SEE.  The seed indices are on the device: one outside [0, V) is ignored, never dereferenced.
-#include "raster.h"
-#include "common.h"
+#include "poseerr_point.h"
 #include "../../include/sam6d_hip.h"
 
 #define NN_MAX_V (1 << 20)
@@ -74,25 +73,22 @@
 #define NN_TILE 256                 // points per box and LDS tile
 #define NN_NO_PRUNE 1               // flags bit 0
 #define NN_INF 0x7f800000u
-#define NN_NAN 0x7fc00000u
-#define NN_SCALE 1073741824.0       // 2^30
-#define NN_TERM_MAX 4398046511104.0 // 2^42
 #define NN_DIAM_WGS 2048            // the diameter's main launch aims at this many workgroups
 
-// RECIPE d2
-__device__ __forceinline__ float nn_d2(const float (&a)[3], float bx, float by, float bz) {
-  const float dx = a[0] - bx, dy = a[1] - by, dz = a[2] - bz;
-  return (dx * dx + dy * dy) + dz * dz;
-}
+// The constants, the guarded point load (pe_load_point), d2 (pe_d2) and the ADD term (pe_add_term) are poseerr_point.h's.
 // RECIPE maximum: the word the unsigned maximum of raw d2 bits stands for
-__device__ __forceinline__ unsigned nn_word(unsigned raw) { return raw > NN_INF ? NN_NAN : raw; }
+__device__ __forceinline__ unsigned nn_word(unsigned raw) { return raw > NN_INF ? PE_NAN : raw; }
 
-__device__ __forceinline__ void nn_load(const float* __restrict__ points, int V, int idx, float (&x)[3]) {
-  x[0] = x[1] = x[2] = 0.f;
-  if (idx < V) {
-    x[0] = points[(size_t)idx * 3];
-    x[1] = points[(size_t)idx * 3 + 1];
-    x[2] = points[(size_t)idx * 3 + 2];
+// the point idx under the (3,4) matrix M, or the raw point where M is null; zeros go in beyond V
+__device__ __forceinline__ void nn_point(const float* __restrict__ points, int V, int idx, const float* __restrict__ M, float (&g)[3]) {
+  float x[3];
+  pe_load_point(points, V, idx, x);
+  if (M) {  // (uniform)
+    rs_to_camera(M, x, g);
+  } else {
+    g[0] = x[0];
+    g[1] = x[1];
+    g[2] = x[2];
   }
 }
 
@@ -103,15 +99,8 @@ __global__ __launch_bounds__(NN_TILE) void nn_boxes_kernel(const float* __restri
                                                            float* __restrict__ box) {
   __shared__ float red[NN_TILE / 64][6];
   const int t = blockIdx.x, n = blockIdx.y, tid = threadIdx.x, idx = t * NN_TILE + tid;
-  float x[3], g[3], b[6];
-  nn_load(points, V, idx, x);
-  if (gt) {
-    rs_to_camera(gt + (size_t)n * 12, x, g);
-  } else {
-    g[0] = x[0];
-    g[1] = x[1];
-    g[2] = x[2];
-  }
+  float g[3], b[6];
+  nn_point(points, V, idx, gt ? gt + (size_t)n * 12 : nullptr, g);
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     b[k] = idx < V ? fminf(INFINITY, g[k]) : INFINITY;       // a NaN leaves +inf
@@ -132,71 +121,77 @@ __global__ __launch_bounds__(NN_TILE) void nn_boxes_kernel(const float* __restri
   }
 }
 
-// ---------------------------------------------------------------------------------------------------------- a. ADI
-// grid (ceil(V / 1024), N), four waves: point blockIdx.x * 1024 + j * 256 + tid for j = 0 .. 3.  adi_sum (N) arrives zeroed
-__global__ __launch_bounds__(NN_WG) void nn_adi_kernel(const float* __restrict__ points, int V, const float* __restrict__ est,
-                                                       const float* __restrict__ gt, int T, const float* __restrict__ box, float inv_unit,
-                                                       int flags, unsigned long long* __restrict__ adi_sum) {
-  __shared__ float4 G[NN_TILE];
-  const int n = blockIdx.y, tid = threadIdx.x;
-  const float* E = est + (size_t)n * 12;
-  const float* Gt = gt + (size_t)n * 12;
-  const float* bx = box + (size_t)n * T * 6;
-  float e[NN_PTS][3], m[NN_PTS];
-  bool live[NN_PTS];
-#pragma unroll
-  for (int j = 0; j < NN_PTS; ++j) {
-    const int idx = blockIdx.x * NN_CHUNK + j * NN_WG + tid;  // below 2^20 + 1024
-    float x[3];
-    live[j] = idx < V;
-    nn_load(points, V, idx, x);
-    rs_to_camera(E, x, e[j]);
-    m[j] = INFINITY;
-  }
-  const int first = blockIdx.x * NN_PTS;  // the tile of the workgroup's first point: below T
-  for (int s = 0; s < T; ++s) {
-    const int t = first + s < T ? first + s : first + s - T;
+// ---------------------------------------------------------------------------------------------------------- the walk
+// THE SKIPPING's protocol for a workgroup of four waves, in one copy.  tiles(s) is the s-th tile of the workgroup's sequence, below 0
+// after the last.  A tile is walked when flags has NN_NO_PRUNE or skips(lo, hi) is false in any thread: whether all of the thread's
+// points can do without a tile whose box is lo, hi (box (T,6), read only then).  point(idx, g) is the tile's point idx as it is
+// staged, and fold(c) takes one staged point into the thread's points.  Every thread of the workgroup calls it, with the same tiles
+template <class Tiles, class Skips, class Point, class Fold>
+__device__ __forceinline__ void nn_walk(int V, const float* __restrict__ box, int flags, Tiles tiles, Skips skips, Point point, Fold fold) {
+  __shared__ float4 tile[NN_TILE];
+  const int tid = threadIdx.x;
+  for (int s = 0, t; (t = tiles(s)) >= 0; ++s) {
     bool walk = (flags & NN_NO_PRUNE) != 0;
     if (!walk) {  // (uniform)
       float lo[3], hi[3];
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
-        lo[k] = bx[(size_t)t * 6 + k];
-        hi[k] = bx[(size_t)t * 6 + 3 + k];
+        lo[k] = box[(size_t)t * 6 + k];
+        hi[k] = box[(size_t)t * 6 + 3 + k];
       }
-#pragma unroll
-      for (int j = 0; j < NN_PTS; ++j) {
-        float gap[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) gap[k] = fmaxf(fmaxf(e[j][k] - hi[k], lo[k] - e[j][k]), 0.f);  // the gap of the header, without a branch
-        const float lb = (gap[0] * gap[0] + gap[1] * gap[1]) + gap[2] * gap[2];
-        walk = walk || (live[j] && !(lb > m[j]));
-      }
+      walk = !skips(lo, hi);
     }
     if (!__syncthreads_or(walk)) continue;  // (uniform; the barrier also closes the reads of the tile before)
-    {
-      float x[3], g[3];
-      nn_load(points, V, t * NN_TILE + tid, x);
-      rs_to_camera(Gt, x, g);
-      G[tid] = make_float4(g[0], g[1], g[2], 0.f);
-    }
+    float g[3];
+    point(t * NN_TILE + tid, g);
+    tile[tid] = make_float4(g[0], g[1], g[2], 0.f);
     __syncthreads();
     const int cnt = min(NN_TILE, V - t * NN_TILE);
 #pragma unroll 4
-    for (int jj = 0; jj < cnt; ++jj) {
-      const float4 g = G[jj];
-#pragma unroll
-      for (int j = 0; j < NN_PTS; ++j) m[j] = fminf(m[j], nn_d2(e[j], g.x, g.y, g.z));  // m is never a NaN: d2 < m ? d2 : m
-    }
+    for (int jj = 0; jj < cnt; ++jj) fold(tile[jj]);
   }
-  long long term = 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------- a. ADI
+// grid (ceil(V / 1024), N), four waves: point blockIdx.x * 1024 + j * 256 + tid for j = 0 .. 3.  adi_sum (N) arrives zeroed
+__global__ __launch_bounds__(NN_WG) void nn_adi_kernel(const float* __restrict__ points, int V, const float* __restrict__ est,
+                                                       const float* __restrict__ gt, int T, const float* __restrict__ box, float inv_unit,
+                                                       int flags, unsigned long long* __restrict__ adi_sum) {
+  const int n = blockIdx.y, tid = threadIdx.x;
+  const float* Gt = gt + (size_t)n * 12;
+  float e[NN_PTS][3], m[NN_PTS];
+  bool live[NN_PTS];
 #pragma unroll
   for (int j = 0; j < NN_PTS; ++j) {
-    if (!live[j]) continue;
-    double w = ((double)sqrtf(m[j]) * (double)inv_unit) * NN_SCALE;
-    if (!(w <= NN_TERM_MAX)) w = NN_TERM_MAX;
-    term += (long long)rint(w);
+    const int idx = blockIdx.x * NN_CHUNK + j * NN_WG + tid;  // below 2^20 + 1024
+    live[j] = idx < V;
+    nn_point(points, V, idx, est + (size_t)n * 12, e[j]);
+    m[j] = INFINITY;
   }
+  const int first = blockIdx.x * NN_PTS;  // the tile of the workgroup's first point: below T
+  nn_walk(
+      V, box + (size_t)n * T * 6, flags, [&](int s) { return s < T ? (first + s < T ? first + s : first + s - T) : -1; },
+      [&](const float(&lo)[3], const float(&hi)[3]) {
+        bool all = true;
+#pragma unroll
+        for (int j = 0; j < NN_PTS; ++j) {
+          float gap[3];
+#pragma unroll
+          for (int k = 0; k < 3; ++k) gap[k] = fmaxf(fmaxf(e[j][k] - hi[k], lo[k] - e[j][k]), 0.f);  // the gap of the header, without a branch
+          const float lb = (gap[0] * gap[0] + gap[1] * gap[1]) + gap[2] * gap[2];
+          all = all && (!live[j] || lb > m[j]);
+        }
+        return all;
+      },
+      [&](int idx, float(&g)[3]) { nn_point(points, V, idx, Gt, g); },
+      [&](const float4 g) {
+#pragma unroll
+        for (int j = 0; j < NN_PTS; ++j) m[j] = fminf(m[j], pe_d2(e[j], g.x, g.y, g.z));  // m is never a NaN: d2 < m ? d2 : m
+      });
+  long long term = 0;
+#pragma unroll
+  for (int j = 0; j < NN_PTS; ++j)
+    if (live[j]) term += pe_add_term(m[j], inv_unit);
   term = wave_sum(term);
   if ((tid & 63) == 0 && term) __hip_atomic_fetch_add(adi_sum + n, (unsigned long long)term, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -206,28 +201,23 @@ extern "C" size_t sam6d_pose_adi_workspace_bytes(int V, int N) {
   return (size_t)N * ((V + NN_TILE - 1) / NN_TILE) * 6 * sizeof(float);
 }
 
-#define NN_POINTER(who, p) SAM6D_REQUIRE((p) != nullptr, who ": " #p " is a null pointer")
-
 extern "C" int sam6d_pose_adi(const float* points, int V, const float* est, const float* gt, int N, float inv_unit, int flags,
                               long long* adi_sum, void* workspace, size_t workspace_bytes, void* stream) {
   SAM6D_REQUIRE(V >= 1 && V <= NN_MAX_V, "pose_adi: V = %d is not in 1 .. %d", V, NN_MAX_V);
   SAM6D_REQUIRE(N >= 1 && N <= NN_MAX_N, "pose_adi: N = %d is not in 1 .. %d", N, NN_MAX_N);
-  SAM6D_REQUIRE(inv_unit > 0.f && inv_unit <= 3.4028234e38f, "pose_adi: inv_unit = %g is not a finite number > 0", (double)inv_unit);
+  if (const int bad = pe_check_inv_unit("pose_adi", inv_unit)) return bad;
   SAM6D_REQUIRE((flags & ~NN_NO_PRUNE) == 0, "pose_adi: flags = %d has bits beyond bit 0", flags);
-  NN_POINTER("pose_adi", points);
-  NN_POINTER("pose_adi", est);
-  NN_POINTER("pose_adi", gt);
-  NN_POINTER("pose_adi", adi_sum);
-  NN_POINTER("pose_adi", workspace);
+  SAM6D_POINTER("pose_adi", points);
+  SAM6D_POINTER("pose_adi", est);
+  SAM6D_POINTER("pose_adi", gt);
+  SAM6D_POINTER("pose_adi", adi_sum);
+  SAM6D_POINTER("pose_adi", workspace);
   const size_t need = sam6d_pose_adi_workspace_bytes(V, N);
   SAM6D_REQUIRE(workspace_bytes >= need, "pose_adi: workspace of %zu bytes is below sam6d_pose_adi_workspace_bytes = %zu", workspace_bytes, need);
   SAM6D_REQUIRE(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)adi_sum & 7) == 0, "pose_adi: workspace or adi_sum is not 8-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   const hipError_t e = hipMemsetAsync(adi_sum, 0, (size_t)N * sizeof(long long), s);
-  if (e != hipSuccess) {
-    sam6d_set_error("pose_adi: memset failed: %s", hipGetErrorString(e));
-    return (int)e;
-  }
+  SAM6D_MEMSET_CHECK("pose_adi", e);
   const int T = (V + NN_TILE - 1) / NN_TILE;
   float* box = (float*)workspace;
   hipLaunchKernelGGL(nn_boxes_kernel, dim3(T, N), dim3(NN_TILE), 0, s, points, V, gt, T, box);
@@ -248,12 +238,12 @@ __global__ __launch_bounds__(NN_WG) void nn_seed_kernel(const float* __restrict_
                                                         unsigned* __restrict__ seed_word) {
   const int idx = blockIdx.x * NN_WG + threadIdx.x;
   float x[3];
-  nn_load(points, V, idx, x);
+  pe_load_point(points, V, idx, x);
   unsigned raw = 0u;
   for (int k = 0; k < n_seeds; ++k) {
     const int sd = seeds[k];
     if ((unsigned)sd >= (unsigned)V) continue;  // (uniform) ignored, never dereferenced
-    const float d2 = nn_d2(x, points[(size_t)sd * 3], points[(size_t)sd * 3 + 1], points[(size_t)sd * 3 + 2]);
+    const float d2 = pe_d2(x, points[(size_t)sd * 3], points[(size_t)sd * 3 + 1], points[(size_t)sd * 3 + 2]);
     if (idx < V) raw = max(raw, __float_as_uint(d2));
   }
   nn_offer(seed_word, raw);
@@ -263,51 +253,37 @@ __global__ __launch_bounds__(NN_WG) void nn_seed_kernel(const float* __restrict_
 // + Y, + 2 Y ... below T.  seed_word is the earlier launch's, read only; best arrives zeroed
 __global__ __launch_bounds__(NN_WG) void nn_diameter_kernel(const float* __restrict__ points, int V, int T, const float* __restrict__ box,
                                                             const unsigned* __restrict__ seed_word, int flags, unsigned* __restrict__ best) {
-  __shared__ float4 X[NN_TILE];
   const int tid = threadIdx.x;
   float x[NN_PTS][3];
   bool fin[NN_PTS];
 #pragma unroll
   for (int j = 0; j < NN_PTS; ++j) {
     const int idx = blockIdx.x * NN_CHUNK + j * NN_WG + tid;
-    nn_load(points, V, min(idx, V - 1), x[j]);  // a thread beyond V holds a copy of the last point: a maximum does not count copies
+    pe_load_point(points, V, min(idx, V - 1), x[j]);  // a thread beyond V holds a copy of the last point: a maximum does not count copies
     fin[j] = fabsf(x[j][0]) < INFINITY && fabsf(x[j][1]) < INFINITY && fabsf(x[j][2]) < INFINITY;
   }
   const float L = __uint_as_float(*seed_word);  // a NaN (0x7fc00000) skips nothing
   unsigned raw = 0u;
-  for (int t = blockIdx.x * NN_PTS + blockIdx.y; t < T; t += gridDim.y) {
-    bool walk = (flags & NN_NO_PRUNE) != 0;
-    if (!walk) {  // (uniform)
-      float lo[3], hi[3];
+  const int first = blockIdx.x * NN_PTS + blockIdx.y, Y = gridDim.y;
+  nn_walk(
+      V, box, flags, [&](int s) { return first + s * Y < T ? first + s * Y : -1; },
+      [&](const float(&lo)[3], const float(&hi)[3]) {
+        bool all = true;
 #pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        lo[k] = box[(size_t)t * 6 + k];
-        hi[k] = box[(size_t)t * 6 + 3 + k];
-      }
+        for (int j = 0; j < NN_PTS; ++j) {
+          float u[3];
 #pragma unroll
-      for (int j = 0; j < NN_PTS; ++j) {
-        float u[3];
+          for (int k = 0; k < 3; ++k) u[k] = fmaxf(fabsf(x[j][k] - lo[k]), fabsf(x[j][k] - hi[k]));
+          const float ub = (u[0] * u[0] + u[1] * u[1]) + u[2] * u[2];
+          all = all && ub <= L && fin[j];
+        }
+        return all;
+      },
+      [&](int idx, float(&c)[3]) { nn_point(points, V, idx, nullptr, c); },
+      [&](const float4 c) {
 #pragma unroll
-        for (int k = 0; k < 3; ++k) u[k] = fmaxf(fabsf(x[j][k] - lo[k]), fabsf(x[j][k] - hi[k]));
-        const float ub = (u[0] * u[0] + u[1] * u[1]) + u[2] * u[2];
-        walk = walk || !(ub <= L) || !fin[j];
-      }
-    }
-    if (!__syncthreads_or(walk)) continue;  // (uniform; the barrier also closes the reads of the tile before)
-    {
-      float c[3];
-      nn_load(points, V, t * NN_TILE + tid, c);
-      X[tid] = make_float4(c[0], c[1], c[2], 0.f);
-    }
-    __syncthreads();
-    const int cnt = min(NN_TILE, V - t * NN_TILE);
-#pragma unroll 4
-    for (int jj = 0; jj < cnt; ++jj) {
-      const float4 c = X[jj];
-#pragma unroll
-      for (int j = 0; j < NN_PTS; ++j) raw = max(raw, __float_as_uint(nn_d2(x[j], c.x, c.y, c.z)));
-    }
-  }
+        for (int j = 0; j < NN_PTS; ++j) raw = max(raw, __float_as_uint(pe_d2(x[j], c.x, c.y, c.z)));
+      });
   nn_offer(best, raw);
 }
 
@@ -326,10 +302,10 @@ extern "C" int sam6d_points_diameter(const float* points, int V, const int* seed
   SAM6D_REQUIRE(V >= 1 && V <= NN_MAX_V, "points_diameter: V = %d is not in 1 .. %d", V, NN_MAX_V);
   SAM6D_REQUIRE(n_seeds >= 1 && n_seeds <= NN_MAX_SEEDS, "points_diameter: n_seeds = %d is not in 1 .. %d", n_seeds, NN_MAX_SEEDS);
   SAM6D_REQUIRE((flags & ~NN_NO_PRUNE) == 0, "points_diameter: flags = %d has bits beyond bit 0", flags);
-  NN_POINTER("points_diameter", points);
-  NN_POINTER("points_diameter", seeds);
-  NN_POINTER("points_diameter", diameter);
-  NN_POINTER("points_diameter", workspace);
+  SAM6D_POINTER("points_diameter", points);
+  SAM6D_POINTER("points_diameter", seeds);
+  SAM6D_POINTER("points_diameter", diameter);
+  SAM6D_POINTER("points_diameter", workspace);
   const size_t need = sam6d_points_diameter_workspace_bytes(V);
   SAM6D_REQUIRE(workspace_bytes >= need, "points_diameter: workspace of %zu bytes is below sam6d_points_diameter_workspace_bytes = %zu",
                 workspace_bytes, need);
@@ -338,10 +314,7 @@ extern "C" int sam6d_points_diameter(const float* points, int V, const int* seed
   unsigned* words = (unsigned*)workspace;
   float* box = (float*)(words + 2);
   const hipError_t e = hipMemsetAsync(words, 0, 2 * sizeof(unsigned), s);
-  if (e != hipSuccess) {
-    sam6d_set_error("points_diameter: memset failed: %s", hipGetErrorString(e));
-    return (int)e;
-  }
+  SAM6D_MEMSET_CHECK("points_diameter", e);
   const int T = (V + NN_TILE - 1) / NN_TILE, chunks = (V + NN_CHUNK - 1) / NN_CHUNK;
   hipLaunchKernelGGL(nn_boxes_kernel, dim3(T, 1), dim3(NN_TILE), 0, s, points, V, (const float*)nullptr, T, box);
   SAM6D_LAUNCH_CHECK_CONT("points_diameter (boxes)");

@@ -36,17 +36,14 @@
 //   counts   (N, 4 + T) i32 = n_union, n_inter, n_visib_est, n_visib_gt, cost_0 .. cost_{T-1}.  total == 0: all 0, no pass runs.
 //     The caller forms vsd[n][k] = (cost_k + n_union - n_inter) / n_union, and 1 where n_union is 0, as BOP does.
 //
-// WHY THE RESULT IS A FUNCTION OF THE INPUTS ALONE.  Where workgroups meet it is an integer atomic at agent scope: 32-bit maxima (the
-// d2 and p2 bit patterns), 32-bit adds (the counters), 64-bit adds (add_sum), 64-bit minima (the z-buffer), all commutative and
-// associative.  The buffers are set by memsets that precede the kernels in stream order, nothing reads a buffer in the launch that
-// reduces into it, and mssd, mspd and their indices have one writer, point_errors_finish_kernel's wave of the pose.
+// WHY THE RESULT IS A FUNCTION OF THE INPUTS ALONE.  a: posematch.hip's paragraph of that name, part a; the kernels are its.  b: where
+// workgroups meet it is an integer atomic at agent scope: 32-bit adds (the counters) and 64-bit minima (the z-buffer), commutative and
+// associative.  The buffers are set by memsets that precede the kernels in stream order, and nothing reads a buffer in the launch
+// that reduces into it.
 //
-// WORK.  point errors: N S V point transforms.  A workgroup of four waves takes 1024 points of one pose, four per thread, and keeps
-// their x, e and (u_e, v_e) in registers across the loop over s; the G of 128 symmetries at a time are formed once per workgroup into
-// LDS and read from there as broadcasts; per s the wave's two maxima are reduced on the DPP path (no LDS round trip), meet the other
-// waves' in LDS, and leave as one atomic per word, workgroup and tile.  finish: one wave per pose takes the minima over s as 64-bit
-// keys (bits << 32 | s: the lowest s wins a tie).  VSD: verify_faces_kernel, then one thread per window word of the estimates' half,
-// sixteen waves to a workgroup, the counters reduced per pose inside the wave and then in LDS as verify_classify_kernel does.
+// WORK.  point errors: N S V point transforms, by posematch.hip's pair kernels on the diagonal (its WORK a, with A = N, B = 1 and b's
+// row taken from i).  VSD: verify_faces_kernel, then one thread per window word of the estimates' half, sixteen waves to a workgroup,
+// the counters reduced per pose inside the wave and then in LDS as verify_classify_kernel does.
 //
 // WHAT THE HOST CANNOT SEE.  box and offset are on the device: the window is the box clamped to the image, no word at or beyond
 // `total` (or below 0) is addressed whatever they hold, and counts is addressed by a pose index in [0, N) alone.  Inconsistent boxes
@@ -67,86 +64,11 @@ struct PeTaus {
 };
 
 // ---------------------------------------------------------------------------------------------------------- a. point errors
-// The per-point step, the word a value offers to a maximum and the wave reductions are poseerr_point.h's, shared with posematch.hip.
-// grid (ceil(V / 1024), N), four waves: point blockIdx.x * 1024 + j * 256 + tid for j = 0 .. 3.  ws (N,S,2) u32 arrives zeroed:
-// word 0 the d2 maximum of the pair, word 1 the p2 maximum
-__global__ __launch_bounds__(PE_WG) void point_errors_kernel(const float* __restrict__ points, int V, const float* __restrict__ est,
-                                                             const float* __restrict__ gt, const float* __restrict__ syms, int S, PeCam cam,
-                                                             float inv_unit, unsigned* __restrict__ ws, int* __restrict__ n_skipped,
-                                                             unsigned long long* __restrict__ add_sum) {
-  __shared__ float G[PE_ST][12];
-  __shared__ unsigned mx[PE_ST * 2];
-  const int n = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
-  const float* Gt = gt + (size_t)n * 12;
-  PePoints<true> P;
-  P.load(points, V, blockIdx.x, tid, est + (size_t)n * 12, cam);
-  for (int s0 = 0; s0 < S; s0 += PE_ST) {
-    const int cnt = min(PE_ST, S - s0);
-    __syncthreads();  // the tile before is flushed
-    for (int t = tid; t < cnt * 12; t += PE_WG) G[t / 12][t % 12] = pe_compose(Gt, syms + (size_t)(s0 + t / 12) * 12, t % 12);
-    for (int t = tid; t < cnt * 2; t += PE_WG) mx[t] = 0u;
-    __syncthreads();
-    for (int sl = 0; sl < cnt; ++sl) {
-      float M[12];
-#pragma unroll
-      for (int k = 0; k < 12; ++k) M[k] = G[sl][k];
-      unsigned m2, mp;
-      float d2s[PE_PTS];
-      bool skip[PE_PTS];
-      P.step(M, cam, m2, mp, d2s, skip);
-      if (s0 + sl == 0) {  // (uniform) ADD and the skipped points, of the first symmetry alone
-        long long term;
-        int skipped;
-        P.add_terms(d2s, skip, inv_unit, term, skipped);
-        term = wave_sum(term);
-        skipped = wave_sum(skipped);
-        if (lane == 0) {
-          if (term) __hip_atomic_fetch_add(add_sum + n, (unsigned long long)term, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if (skipped) vf_add(n_skipped + n, skipped);
-        }
-      }
-      m2 = pe_wave_max(m2);
-      mp = pe_wave_max(mp);
-      if (lane == 0) {
-        if (m2) atomicMax(&mx[sl * 2], m2);
-        if (mp) atomicMax(&mx[sl * 2 + 1], mp);
-      }
-    }
-    __syncthreads();
-    for (int t = tid; t < cnt * 2; t += PE_WG) {
-      const unsigned v = mx[t];
-      if (v) __hip_atomic_fetch_max(ws + ((size_t)n * S + s0) * 2 + t, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-}
-
-// one wave per pose: the only writer of mssd, mspd and their indices
-__global__ __launch_bounds__(64) void point_errors_finish_kernel(const unsigned* __restrict__ ws, int S, float* __restrict__ mssd,
-                                                                 float* __restrict__ mspd, int* __restrict__ mssd_sym,
-                                                                 int* __restrict__ mspd_sym) {
-  const int n = blockIdx.x, lane = threadIdx.x;
-  unsigned long long k2 = ~0ull, kp = ~0ull;
-  for (int s = lane; s < S; s += 64) {
-    const unsigned* w = ws + ((size_t)n * S + s) * 2;
-    const unsigned long long a = ((unsigned long long)w[0] << 32) | (unsigned)s, b = ((unsigned long long)w[1] << 32) | (unsigned)s;
-    k2 = a < k2 ? a : k2;
-    kp = b < kp ? b : kp;
-  }
-  k2 = pe_wave_min_u64(k2);
-  kp = pe_wave_min_u64(kp);
-  if (lane != 0) return;
-  mssd[n] = sqrtf(__uint_as_float((unsigned)(k2 >> 32)));
-  mssd_sym[n] = (int)(unsigned)(k2 & 0xffffffffull);
-  mspd[n] = sqrtf(__uint_as_float((unsigned)(kp >> 32)));
-  mspd_sym[n] = (int)(unsigned)(kp & 0xffffffffull);
-}
-
+// The kernels are posematch.hip's: est[n] against gt[n] o syms[s] is the diagonal of its all-pairs walk (poseerr_point.h's pe_errors).
 extern "C" size_t sam6d_pose_point_errors_workspace_bytes(int N, int S) {
   if (N < 1 || N > PE_MAX_N || S < 1 || S > PE_MAX_S) return 0;
   return (size_t)N * S * 2 * sizeof(unsigned);
 }
-
-#define PE_POINTER(who, p) SAM6D_REQUIRE((p) != nullptr, who ": " #p " is a null pointer")
 
 extern "C" int sam6d_pose_point_errors(const float* points, int V, const float* est, const float* gt, int N, const float* syms, int S,
                                        float fx, float fy, float cx, float cy, float inv_unit, float* mssd, float* mspd, int* mssd_sym,
@@ -155,36 +77,24 @@ extern "C" int sam6d_pose_point_errors(const float* points, int V, const float* 
   SAM6D_REQUIRE(V >= 1 && V <= PE_MAX_V, "pose_point_errors: V = %d is not in 1 .. %d", V, PE_MAX_V);
   SAM6D_REQUIRE(N >= 1 && N <= PE_MAX_N, "pose_point_errors: N = %d is not in 1 .. %d", N, PE_MAX_N);
   SAM6D_REQUIRE(S >= 1 && S <= PE_MAX_S, "pose_point_errors: S = %d is not in 1 .. %d", S, PE_MAX_S);
-  SAM6D_REQUIRE(inv_unit > 0.f && inv_unit <= 3.4028234e38f, "pose_point_errors: inv_unit = %g is not a finite number > 0", (double)inv_unit);
-  PE_POINTER("pose_point_errors", points);
-  PE_POINTER("pose_point_errors", est);
-  PE_POINTER("pose_point_errors", gt);
-  PE_POINTER("pose_point_errors", syms);
-  PE_POINTER("pose_point_errors", mssd);
-  PE_POINTER("pose_point_errors", mspd);
-  PE_POINTER("pose_point_errors", mssd_sym);
-  PE_POINTER("pose_point_errors", mspd_sym);
-  PE_POINTER("pose_point_errors", n_skipped);
-  PE_POINTER("pose_point_errors", add_sum);
-  PE_POINTER("pose_point_errors", workspace);
+  if (const int bad = pe_check_inv_unit("pose_point_errors", inv_unit)) return bad;
+  SAM6D_POINTER("pose_point_errors", points);
+  SAM6D_POINTER("pose_point_errors", est);
+  SAM6D_POINTER("pose_point_errors", gt);
+  SAM6D_POINTER("pose_point_errors", syms);
+  SAM6D_POINTER("pose_point_errors", mssd);
+  SAM6D_POINTER("pose_point_errors", mspd);
+  SAM6D_POINTER("pose_point_errors", mssd_sym);
+  SAM6D_POINTER("pose_point_errors", mspd_sym);
+  SAM6D_POINTER("pose_point_errors", n_skipped);
+  SAM6D_POINTER("pose_point_errors", add_sum);
+  SAM6D_POINTER("pose_point_errors", workspace);
   const size_t need = sam6d_pose_point_errors_workspace_bytes(N, S);
   SAM6D_REQUIRE(workspace_bytes >= need, "pose_point_errors: workspace of %zu bytes is below sam6d_pose_point_errors_workspace_bytes = %zu",
                 workspace_bytes, need);
   SAM6D_REQUIRE(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)add_sum & 7) == 0, "pose_point_errors: workspace or add_sum is not 8-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(workspace, 0, need, s);
-  if (e == hipSuccess) e = hipMemsetAsync(n_skipped, 0, (size_t)N * sizeof(int), s);
-  if (e == hipSuccess) e = hipMemsetAsync(add_sum, 0, (size_t)N * sizeof(long long), s);
-  if (e != hipSuccess) {
-    sam6d_set_error("pose_point_errors: memset failed: %s", hipGetErrorString(e));
-    return (int)e;
-  }
-  const PeCam cam = {fx, fy, cx, cy};
-  hipLaunchKernelGGL(point_errors_kernel, dim3((V + PE_CHUNK - 1) / PE_CHUNK, N), dim3(PE_WG), 0, s, points, V, est, gt, syms, S, cam, inv_unit,
-                     (unsigned*)workspace, n_skipped, (unsigned long long*)add_sum);
-  SAM6D_LAUNCH_CHECK_CONT("pose_point_errors (points)");
-  hipLaunchKernelGGL(point_errors_finish_kernel, dim3(N), dim3(64), 0, s, (const unsigned*)workspace, S, mssd, mspd, mssd_sym, mspd_sym);
-  SAM6D_LAUNCH_CHECK("pose_point_errors (finish)");
+  return pe_errors("pose_point_errors", points, V, est, N, gt, 1, true, syms, S, PeCam{fx, fy, cx, cy}, inv_unit, true, mssd, mspd, mssd_sym, mspd_sym,
+                   n_skipped, add_sum, workspace, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------- b. VSD
@@ -270,15 +180,15 @@ extern "C" int sam6d_pose_vsd(const float* vertices, int V, const int* faces, in
   SAM6D_REQUIRE(fx != 0.f && fy != 0.f && fx == fx && fy == fy, "pose_vsd: fx, fy = %g, %g: zero or not a number", (double)fx, (double)fy);
   SAM6D_REQUIRE(T >= 1 && T <= PE_MAX_T, "pose_vsd: T = %d is not in 1 .. %d", T, PE_MAX_T);
   SAM6D_REQUIRE(total >= 0 && total <= 2L * N * H * W, "pose_vsd: total = %ld is not in 0 .. 2 N H W = %ld", total, 2L * N * H * W);
-  PE_POINTER("pose_vsd", vertices);
-  PE_POINTER("pose_vsd", faces);
-  PE_POINTER("pose_vsd", view);
-  PE_POINTER("pose_vsd", box);
-  PE_POINTER("pose_vsd", offset);
-  PE_POINTER("pose_vsd", depth_obs);
-  PE_POINTER("pose_vsd", taus);
-  PE_POINTER("pose_vsd", counts);
-  PE_POINTER("pose_vsd", workspace);
+  SAM6D_POINTER("pose_vsd", vertices);
+  SAM6D_POINTER("pose_vsd", faces);
+  SAM6D_POINTER("pose_vsd", view);
+  SAM6D_POINTER("pose_vsd", box);
+  SAM6D_POINTER("pose_vsd", offset);
+  SAM6D_POINTER("pose_vsd", depth_obs);
+  SAM6D_POINTER("pose_vsd", taus);
+  SAM6D_POINTER("pose_vsd", counts);
+  SAM6D_POINTER("pose_vsd", workspace);
   PeTaus tv;
   for (int k = 0; k < PE_MAX_T; ++k) {
     tv.v[k] = k < T ? taus[k] : 0.f;
@@ -295,10 +205,7 @@ extern "C" int sam6d_pose_vsd(const float* vertices, int V, const int* faces, in
   hipError_t e = hipMemsetAsync(counts, 0, (size_t)N * (4 + T) * sizeof(int), s);
   if (e == hipSuccess && total > 0) e = hipMemsetAsync(zbuf, 0xff, (size_t)total * 8, s);
   if (e == hipSuccess && total > 0) e = hipMemsetAsync(dropped, 0, (size_t)N * 2 * 8 * sizeof(int), s);
-  if (e != hipSuccess) {
-    sam6d_set_error("pose_vsd: memset failed: %s", hipGetErrorString(e));
-    return (int)e;
-  }
+  SAM6D_MEMSET_CHECK("pose_vsd", e);
   if (total == 0) return 0;
   hipLaunchKernelGGL(verify_faces_kernel, dim3((F + 63) / 64, 2 * N), dim3(64), 0, s, vertices, V, faces, F, view, cam,
                      wave_area ? wave_area : RS_WAVE_AREA, box, offset, (long long)total, zbuf, dropped);

@@ -1,7 +1,8 @@
-// The per-point step of the point errors (poseerr.hip RECIPE a) and the bit-pattern helpers around it, in one copy for the two
-// kernels that walk model points under a pose and a list of composed matrices: point_errors_kernel (poseerr.hip: est[n] against
-// gt[n] o syms[s]) and pair_errors_kernel (posematch.hip: a[i] against b[j] o syms[s]).  The recipe is written out at the top of
-// poseerr.hip and nowhere else; every function here names the line of it that it is.
+// The pieces of the distance recipe (poseerr.hip RECIPE a) in one copy for the scoring family: the constants, the guarded point
+// load, d2, the ADD term and the per-point step under a composed matrix, for pair_errors_kernel (posematch.hip: the one kernel that
+// walks model points under composed matrices, for sam6d_pose_pair_errors and, on the diagonal, sam6d_pose_point_errors) and for
+// nearest.hip's searches; the bit-pattern helpers around them; and the host pieces the entries share.  The recipe is written out at
+// the top of poseerr.hip and nowhere else; every function here names the line of it that it is.
 #pragma once
 #include "raster.h"
 #include "common.h"
@@ -17,6 +18,29 @@
 struct PeCam {
   float fx, fy, cx, cy;
 };
+
+// the point idx of (V,3), zeros beyond V
+__device__ __forceinline__ void pe_load_point(const float* __restrict__ points, int V, int idx, float (&x)[3]) {
+  x[0] = x[1] = x[2] = 0.f;
+  if (idx < V) {
+    x[0] = points[(size_t)idx * 3];
+    x[1] = points[(size_t)idx * 3 + 1];
+    x[2] = points[(size_t)idx * 3 + 2];
+  }
+}
+
+// RECIPE d2
+__device__ __forceinline__ float pe_d2(const float (&a)[3], float bx, float by, float bz) {
+  const float dx = a[0] - bx, dy = a[1] - by, dz = a[2] - bz;
+  return (dx * dx + dy * dy) + dz * dz;
+}
+
+// RECIPE ADD: one point's term
+__device__ __forceinline__ long long pe_add_term(float d2, float inv_unit) {
+  double w = ((double)sqrtf(d2) * (double)inv_unit) * PE_SCALE;
+  if (!(w <= PE_TERM_MAX)) w = PE_TERM_MAX;
+  return (long long)rint(w);
+}
 
 // RECIPE maxima: the word a value offers
 __device__ __forceinline__ unsigned pe_bits(float v) { return v > 0.f ? __float_as_uint(v) : (v == 0.f ? 0u : PE_NAN); }
@@ -70,12 +94,7 @@ struct PePoints {
     for (int j = 0; j < PE_PTS; ++j) {
       const int idx = chunk * PE_CHUNK + j * PE_WG + tid;
       live[j] = idx < V;
-      x[j][0] = x[j][1] = x[j][2] = 0.f;
-      if (live[j]) {
-        x[j][0] = points[(size_t)idx * 3];
-        x[j][1] = points[(size_t)idx * 3 + 1];
-        x[j][2] = points[(size_t)idx * 3 + 2];
-      }
+      pe_load_point(points, V, idx, x[j]);
       rs_to_camera(E, x[j], e[j]);
       front[j] = e[j][2] > 0.f;
       if (PIX) {
@@ -94,8 +113,7 @@ struct PePoints {
     for (int j = 0; j < PE_PTS; ++j) {
       float g[3];
       rs_to_camera(M, x[j], g);
-      const float dx = e[j][0] - g[0], dy = e[j][1] - g[1], dz = e[j][2] - g[2];
-      const float d2 = (dx * dx + dy * dy) + dz * dz;
+      const float d2 = pe_d2(e[j], g[0], g[1], g[2]);
       d2s[j] = d2;
       skip[j] = !(front[j] && g[2] > 0.f);
       if (live[j]) m2 = max(m2, pe_bits(d2));
@@ -115,10 +133,23 @@ struct PePoints {
 #pragma unroll
     for (int j = 0; j < PE_PTS; ++j) {
       if (!live[j]) continue;
-      double w = ((double)sqrtf(d2s[j]) * (double)inv_unit) * PE_SCALE;
-      if (!(w <= PE_TERM_MAX)) w = PE_TERM_MAX;
-      term += (long long)rint(w);
+      term += pe_add_term(d2s[j], inv_unit);
       skipped += skip[j] ? 1 : 0;
     }
   }
 };
+
+// ---- host side ----------------------------------------------------------------------------------------------------------
+// the refusal of an inv_unit that is not a finite number > 0 -> 0 or SAM6D_EINVAL with the error text set
+static inline int pe_check_inv_unit(const char* who, float inv_unit) {
+  SAM6D_REQUIRE(inv_unit > 0.f && inv_unit <= 3.4028234e38f, "%s: inv_unit = %g is not a finite number > 0", who, (double)inv_unit);
+  return 0;
+}
+
+// Host side of the point errors, one copy for both entries (defined in posematch.hip): zeroes ws (A B S pairs of words), n_skipped
+// (pix) and add_sum in stream order, picks the run of matrices per workgroup, launches pair_errors_kernel<pix, diag> and
+// pair_errors_finish_kernel.  diag (with pix and B = 1 alone): a[i] is scored against b[i].  !pix: mspd, mspd_sym and n_skipped are
+// not touched.  `who` names the entry in an error text.  -> 0, or the hipError_t with sam6d_set_error() called.
+int pe_errors(const char* who, const float* points, int V, const float* a, int A, const float* b, int B, bool diag, const float* syms, int S,
+              const PeCam& cam, float inv_unit, bool pix, float* mssd, float* mspd, int* mssd_sym, int* mspd_sym, int* n_skipped,
+              long long* add_sum, void* ws, hipStream_t st);

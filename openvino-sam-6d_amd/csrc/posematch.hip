@@ -41,7 +41,9 @@
 // the other waves' in LDS, and leave as one atomic per word, workgroup and tile; the ADD terms of a matrix with s = 0 meet in LDS in
 // the same way.  blockIdx.z splits the matrices into runs of 8 .. 256: a small A x V still fills the chip, and a large B S does not
 // make workgroups so long that the last round of them leaves most of the chip idle (measured: DESIGN section 8, f21).  finish: one
-// wave per pair, as point_errors_finish_kernel.  b: one wave per threshold; lane l holds the taken flags of the targets l, l + 64,
+// wave per pair takes the minima over s as 64-bit keys (bits << 32 | s: the lowest s wins a tie).  sam6d_pose_point_errors
+// (poseerr.hip) is the same launch on the diagonal: B = 1 and b's row taken from i, so A = N poses against their own ground truths
+// under the same split.  b: one wave per threshold; lane l holds the taken flags of the targets l, l + 64,
 // ..., sixteen per lane, in one register, and the next estimate's row is loaded while the present one is decided.  c: the bit mask
 // over the ordered poses (one thread per row and word, the upper triangle), then one wave whose lane w owns removed-word w.
 //
@@ -63,8 +65,9 @@
 
 // ---------------------------------------------------------------------------------------------------------- a. pair errors
 // grid (ceil(V / 1024), A, Z), four waves; the workgroup's matrices are m = blockIdx.z * run .. + run - 1 (below B S).
-// ws (A, B S, 2) u32 arrives zeroed: word 0 the d2 maximum of the triple, word 1 the p2 maximum
-template <bool PIX>
+// ws (A, B S, 2) u32 arrives zeroed: word 0 the d2 maximum of the triple, word 1 the p2 maximum.  DIAG (then B = 1): the pose
+// b[i] stands for b[0], the diagonal of A x A without the rest of it
+template <bool PIX, bool DIAG>
 __global__ __launch_bounds__(PE_WG) void pair_errors_kernel(const float* __restrict__ points, int V, const float* __restrict__ a,
                                                             const float* __restrict__ b, int B, const float* __restrict__ syms, int S, int run,
                                                             PeCam cam, float inv_unit, unsigned* __restrict__ ws, int* __restrict__ n_skipped,
@@ -75,6 +78,7 @@ __global__ __launch_bounds__(PE_WG) void pair_errors_kernel(const float* __restr
   __shared__ int skl[PE_ST];
   const int i = blockIdx.y, tid = threadIdx.x, lane = tid & 63, BS = B * S;  // B S <= 2^20
   const int m_lo = blockIdx.z * run, m_hi = min(BS, m_lo + run);
+  if (DIAG) b += (size_t)i * 12;
   PePoints<PIX> P;
   P.load(points, V, blockIdx.x, tid, a + (size_t)i * 12, cam);
   for (int m0 = m_lo; m0 < m_hi; m0 += PE_ST) {
@@ -156,6 +160,33 @@ __global__ __launch_bounds__(256) void pair_errors_finish_kernel(const unsigned*
   mspd_sym[n] = (int)(unsigned)(kp & 0xffffffffull);
 }
 
+// poseerr_point.h's pe_errors: the host side of both entries.  ws holds A B S pairs of words
+int pe_errors(const char* who, const float* points, int V, const float* a, int A, const float* b, int B, bool diag, const float* syms, int S,
+              const PeCam& cam, float inv_unit, bool pix, float* mssd, float* mspd, int* mssd_sym, int* mspd_sym, int* n_skipped,
+              long long* add_sum, void* ws, hipStream_t st) {
+  const size_t pairs = (size_t)A * B;
+  hipError_t e = hipMemsetAsync(ws, 0, pairs * S * 2 * sizeof(unsigned), st);
+  if (e == hipSuccess && pix) e = hipMemsetAsync(n_skipped, 0, pairs * sizeof(int), st);
+  if (e == hipSuccess) e = hipMemsetAsync(add_sum, 0, pairs * sizeof(long long), st);
+  SAM6D_MEMSET_CHECK(who, e);
+  // the split of the B S matrices over blockIdx.z: enough workgroups for the chip, runs of PM_MIN_RUN .. PM_MAX_RUN matrices
+  const int chunks = (V + PE_CHUNK - 1) / PE_CHUNK, BS = B * S;
+  const long long wgs = (long long)chunks * A;
+  const int zwant = (int)((PM_WGS + wgs - 1) / wgs);
+  const int per = (BS + zwant - 1) / zwant, run = per < PM_MIN_RUN ? PM_MIN_RUN : (per > PM_MAX_RUN ? PM_MAX_RUN : per);
+  const dim3 grid(chunks, A, (BS + run - 1) / run);  // z <= max(PM_WGS, 2^20 / PM_MAX_RUN) = 4096
+  const auto kernel = diag ? pair_errors_kernel<true, true> : (pix ? pair_errors_kernel<true, false> : pair_errors_kernel<false, false>);
+  hipLaunchKernelGGL(kernel, grid, dim3(PE_WG), 0, st, points, V, a, b, B, syms, S, run, cam, inv_unit, (unsigned*)ws,
+                     pix ? n_skipped : (int*)nullptr, (unsigned long long*)add_sum);
+  char step[64];
+  snprintf(step, sizeof step, "%s (points)", who);
+  SAM6D_LAUNCH_CHECK_CONT(step);
+  hipLaunchKernelGGL(pair_errors_finish_kernel, dim3((unsigned)((pairs + 3) / 4)), dim3(256), 0, st, (const unsigned*)ws, (int)pairs, S, mssd,
+                     pix ? mspd : (float*)nullptr, mssd_sym, mspd_sym);
+  snprintf(step, sizeof step, "%s (finish)", who);
+  SAM6D_LAUNCH_CHECK(step);
+}
+
 static bool pm_sizes_ok(int A, int B, int S) {
   return A >= 1 && A <= PM_MAX_N && B >= 1 && B <= PM_MAX_N && S >= 1 && S <= PM_MAX_N && (long long)A * B * S <= PM_MAX_TRIPLES;
 }
@@ -164,8 +195,6 @@ extern "C" size_t sam6d_pose_pair_errors_workspace_bytes(int A, int B, int S) {
   if (!pm_sizes_ok(A, B, S)) return 0;
   return (size_t)A * B * S * 2 * sizeof(unsigned);
 }
-
-#define PM_POINTER(who, p) SAM6D_REQUIRE((p) != nullptr, who ": " #p " is a null pointer")
 
 extern "C" int sam6d_pose_pair_errors(const float* points, int V, const float* a, int A, const float* b, int B, const float* syms, int S,
                                       float fx, float fy, float cx, float cy, float inv_unit, int flags, float* mssd, float* mspd,
@@ -176,52 +205,28 @@ extern "C" int sam6d_pose_pair_errors(const float* points, int V, const float* a
   SAM6D_REQUIRE(B >= 1 && B <= PM_MAX_N, "pose_pair_errors: B = %d is not in 1 .. %d", B, PM_MAX_N);
   SAM6D_REQUIRE(S >= 1 && S <= PM_MAX_N, "pose_pair_errors: S = %d is not in 1 .. %d", S, PM_MAX_N);
   SAM6D_REQUIRE(pm_sizes_ok(A, B, S), "pose_pair_errors: A B S = %lld is above the cap of %d", (long long)A * B * S, PM_MAX_TRIPLES);
-  SAM6D_REQUIRE(inv_unit > 0.f && inv_unit <= 3.4028234e38f, "pose_pair_errors: inv_unit = %g is not a finite number > 0", (double)inv_unit);
+  if (const int bad = pe_check_inv_unit("pose_pair_errors", inv_unit)) return bad;
   SAM6D_REQUIRE((flags & ~PM_NO_MSPD) == 0, "pose_pair_errors: flags = %d has bits beyond bit 0", flags);
   const bool pix = !(flags & PM_NO_MSPD);
-  PM_POINTER("pose_pair_errors", points);
-  PM_POINTER("pose_pair_errors", a);
-  PM_POINTER("pose_pair_errors", b);
-  PM_POINTER("pose_pair_errors", syms);
-  PM_POINTER("pose_pair_errors", mssd);
-  PM_POINTER("pose_pair_errors", mssd_sym);
+  SAM6D_POINTER("pose_pair_errors", points);
+  SAM6D_POINTER("pose_pair_errors", a);
+  SAM6D_POINTER("pose_pair_errors", b);
+  SAM6D_POINTER("pose_pair_errors", syms);
+  SAM6D_POINTER("pose_pair_errors", mssd);
+  SAM6D_POINTER("pose_pair_errors", mssd_sym);
   if (pix) {
-    PM_POINTER("pose_pair_errors", mspd);
-    PM_POINTER("pose_pair_errors", mspd_sym);
-    PM_POINTER("pose_pair_errors", n_skipped);
+    SAM6D_POINTER("pose_pair_errors", mspd);
+    SAM6D_POINTER("pose_pair_errors", mspd_sym);
+    SAM6D_POINTER("pose_pair_errors", n_skipped);
   }
-  PM_POINTER("pose_pair_errors", add_sum);
-  PM_POINTER("pose_pair_errors", workspace);
+  SAM6D_POINTER("pose_pair_errors", add_sum);
+  SAM6D_POINTER("pose_pair_errors", workspace);
   const size_t need = sam6d_pose_pair_errors_workspace_bytes(A, B, S);
   SAM6D_REQUIRE(workspace_bytes >= need, "pose_pair_errors: workspace of %zu bytes is below sam6d_pose_pair_errors_workspace_bytes = %zu",
                 workspace_bytes, need);
   SAM6D_REQUIRE(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)add_sum & 7) == 0, "pose_pair_errors: workspace or add_sum is not 8-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  const size_t pairs = (size_t)A * B;
-  hipError_t e = hipMemsetAsync(workspace, 0, need, st);
-  if (e == hipSuccess && pix) e = hipMemsetAsync(n_skipped, 0, pairs * sizeof(int), st);
-  if (e == hipSuccess) e = hipMemsetAsync(add_sum, 0, pairs * sizeof(long long), st);
-  if (e != hipSuccess) {
-    sam6d_set_error("pose_pair_errors: memset failed: %s", hipGetErrorString(e));
-    return (int)e;
-  }
-  // the split of the B S matrices over blockIdx.z: enough workgroups for the chip, runs of PM_MIN_RUN .. PM_MAX_RUN matrices
-  const int chunks = (V + PE_CHUNK - 1) / PE_CHUNK, BS = B * S;
-  const long long wgs = (long long)chunks * A;
-  const int zwant = (int)((PM_WGS + wgs - 1) / wgs);
-  const int per = (BS + zwant - 1) / zwant, run = per < PM_MIN_RUN ? PM_MIN_RUN : (per > PM_MAX_RUN ? PM_MAX_RUN : per);
-  const dim3 grid(chunks, A, (BS + run - 1) / run);  // z <= max(PM_WGS, 2^20 / PM_MAX_RUN) = 4096
-  const PeCam cam = {fx, fy, cx, cy};
-  if (pix)
-    hipLaunchKernelGGL(pair_errors_kernel<true>, grid, dim3(PE_WG), 0, st, points, V, a, b, B, syms, S, run, cam, inv_unit, (unsigned*)workspace,
-                       n_skipped, (unsigned long long*)add_sum);
-  else
-    hipLaunchKernelGGL(pair_errors_kernel<false>, grid, dim3(PE_WG), 0, st, points, V, a, b, B, syms, S, run, cam, inv_unit,
-                       (unsigned*)workspace, (int*)nullptr, (unsigned long long*)add_sum);
-  SAM6D_LAUNCH_CHECK_CONT("pose_pair_errors (points)");
-  hipLaunchKernelGGL(pair_errors_finish_kernel, dim3((unsigned)((pairs + 3) / 4)), dim3(256), 0, st, (const unsigned*)workspace, (int)pairs, S, mssd,
-                     pix ? mspd : (float*)nullptr, mssd_sym, mspd_sym);
-  SAM6D_LAUNCH_CHECK("pose_pair_errors (finish)");
+  return pe_errors("pose_pair_errors", points, V, a, A, b, B, false, syms, S, PeCam{fx, fy, cx, cy}, inv_unit, pix, mssd, mspd, mssd_sym, mspd_sym,
+                   n_skipped, add_sum, workspace, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------- the order
@@ -312,13 +317,13 @@ extern "C" int sam6d_pose_match(const float* err, int A, int B, const float* sco
   SAM6D_REQUIRE(B >= 1 && B <= PM_MAX_N, "pose_match: B = %d is not in 1 .. %d", B, PM_MAX_N);
   SAM6D_REQUIRE(T >= 1 && T <= PM_MAX_T, "pose_match: T = %d is not in 1 .. %d", T, PM_MAX_T);
   SAM6D_REQUIRE(max_ests >= 0, "pose_match: max_ests = %d is negative", max_ests);
-  PM_POINTER("pose_match", err);
-  PM_POINTER("pose_match", scores);
-  PM_POINTER("pose_match", thr);
-  PM_POINTER("pose_match", est_match);
-  PM_POINTER("pose_match", gt_match);
-  PM_POINTER("pose_match", n_matched);
-  PM_POINTER("pose_match", workspace);
+  SAM6D_POINTER("pose_match", err);
+  SAM6D_POINTER("pose_match", scores);
+  SAM6D_POINTER("pose_match", thr);
+  SAM6D_POINTER("pose_match", est_match);
+  SAM6D_POINTER("pose_match", gt_match);
+  SAM6D_POINTER("pose_match", n_matched);
+  SAM6D_POINTER("pose_match", workspace);
   const size_t need = sam6d_pose_match_workspace_bytes(A);
   SAM6D_REQUIRE(workspace_bytes >= need, "pose_match: workspace of %zu bytes is below sam6d_pose_match_workspace_bytes = %zu", workspace_bytes,
                 need);
@@ -326,10 +331,7 @@ extern "C" int sam6d_pose_match(const float* err, int A, int B, const float* sco
   hipStream_t st = (hipStream_t)stream;
   hipError_t e = hipMemsetAsync(est_match, 0xff, (size_t)T * A * sizeof(int), st);
   if (e == hipSuccess) e = hipMemsetAsync(gt_match, 0xff, (size_t)T * B * sizeof(int), st);
-  if (e != hipSuccess) {
-    sam6d_set_error("pose_match: memset failed: %s", hipGetErrorString(e));
-    return (int)e;
-  }
+  SAM6D_MEMSET_CHECK("pose_match", e);
   int* order = (int*)workspace;
   hipLaunchKernelGGL(pm_order_kernel, dim3((A + 255) / 256), dim3(256), 0, st, scores, A, order);
   SAM6D_LAUNCH_CHECK_CONT("pose_match (order)");
@@ -405,21 +407,18 @@ extern "C" size_t sam6d_pose_nms_workspace_bytes(int N) {
 extern "C" int sam6d_pose_nms(const float* err, const float* scores, int N, float thresh, long long* keep_idx, int* count, int* suppressed_by,
                               void* workspace, size_t workspace_bytes, void* stream) {
   SAM6D_REQUIRE(N >= 1 && N <= PM_MAX_N, "pose_nms: N = %d is not in 1 .. %d", N, PM_MAX_N);
-  PM_POINTER("pose_nms", err);
-  PM_POINTER("pose_nms", scores);
-  PM_POINTER("pose_nms", keep_idx);
-  PM_POINTER("pose_nms", count);
-  PM_POINTER("pose_nms", suppressed_by);
-  PM_POINTER("pose_nms", workspace);
+  SAM6D_POINTER("pose_nms", err);
+  SAM6D_POINTER("pose_nms", scores);
+  SAM6D_POINTER("pose_nms", keep_idx);
+  SAM6D_POINTER("pose_nms", count);
+  SAM6D_POINTER("pose_nms", suppressed_by);
+  SAM6D_POINTER("pose_nms", workspace);
   const size_t need = sam6d_pose_nms_workspace_bytes(N);
   SAM6D_REQUIRE(workspace_bytes >= need, "pose_nms: workspace of %zu bytes is below sam6d_pose_nms_workspace_bytes = %zu", workspace_bytes, need);
   SAM6D_REQUIRE(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)keep_idx & 7) == 0, "pose_nms: workspace or keep_idx is not 8-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   const hipError_t e = hipMemsetAsync(keep_idx, 0xff, (size_t)N * sizeof(long long), st);
-  if (e != hipSuccess) {
-    sam6d_set_error("pose_nms: memset failed: %s", hipGetErrorString(e));
-    return (int)e;
-  }
+  SAM6D_MEMSET_CHECK("pose_nms", e);
   const int nw = (N + 63) / 64;
   int* order = (int*)workspace;
   unsigned long long* mask = (unsigned long long*)((char*)workspace + pm_order_bytes(N));

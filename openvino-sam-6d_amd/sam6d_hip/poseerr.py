@@ -177,18 +177,42 @@ def _inv_unit(name, unit):
     return inv_unit
 
 
-@on_tensor_device
-def _point_errors(points, est, gt, syms, intr, inv_unit):
-    V, N, S = int(points.shape[0]), int(est.shape[0]), int(syms.shape[0])
-    need = int(_lib.load().sam6d_pose_point_errors_workspace_bytes(N, S))
+def _syms(name, syms, points, limit=MAX_SYMS):
+    """(S,3,4) f32 beside the points: None is the identity alone, a host array is uploaded"""
+    if syms is None:
+        syms = np.concatenate([np.eye(3), np.zeros((3, 1))], axis=1)[None].astype(np.float32)
+    host = None if torch.is_tensor(syms) else np.asarray(syms)
+    syms = _tensor(syms if host is None else torch.from_numpy(np.ascontiguousarray(host)), name, "syms", torch.float32, (None, 3, 4))
+    if not 1 <= int(syms.shape[0]) <= limit:
+        raise ValueError("%s: syms: S = %d is not in 1 .. %d" % (name, int(syms.shape[0]), limit))
+    if host is not None:
+        if not points.is_cuda:
+            raise RuntimeError("%s: needs HIP device tensors (this build has no CPU path)" % name)
+        syms = syms.to(points.device)
+    return syms
+
+
+def _errors(cls, entry, points, shape, poses, syms, intr, inv_unit, flags=()):
+    """One call of sam6d_pose_point_errors or sam6d_pose_pair_errors -> cls: the outputs have `shape` ((N) or (A,B)), `poses` are the
+    entry's pose arguments.  intr None (the pair entry alone): no mspd, mspd_sym, n_skipped"""
+    V, S = int(points.shape[0]), int(syms.shape[0])
+    need = int(getattr(_lib.load(), entry + "_workspace_bytes")(*shape, S))
     ws = _empty((need // 8,), points, torch.int64)
-    mssd, mspd = _empty((N,), points), _empty((N,), points)
-    mssd_sym, mspd_sym, skipped = (_empty((N,), points, torch.int32) for _ in range(3))
-    add_sum = _empty((N,), points, torch.int64)
-    _lib.call("sam6d_pose_point_errors", _p(points), V, _p(est), _p(gt), N, _p(syms), S, *intr, inv_unit, _p(mssd), _p(mspd), _p(mssd_sym),
+    mssd, mssd_sym = _empty(shape, points), _empty(shape, points, torch.int32)
+    add_sum = _empty(shape, points, torch.int64)
+    mspd = mspd_sym = skipped = None
+    if intr is not None:
+        mspd, mspd_sym, skipped = _empty(shape, points), _empty(shape, points, torch.int32), _empty(shape, points, torch.int32)
+    _lib.call(entry, _p(points), V, *poses, _p(syms), S, *(intr or (0.0, 0.0, 0.0, 0.0)), inv_unit, *flags, _p(mssd), _p(mspd), _p(mssd_sym),
               _p(mspd_sym), _p(skipped), add_sum.data_ptr(), ws.data_ptr(), need, _s())
     add = (add_sum.to(torch.float64) / ADD_SCALE / inv_unit / V).to(torch.float32)
-    return PoseErrors(mssd, mspd, add, mssd_sym, mspd_sym, skipped, add_sum)
+    return cls(mssd, mspd, add, mssd_sym, mspd_sym, skipped, add_sum)
+
+
+@on_tensor_device
+def _point_errors(points, est, gt, syms, intr, inv_unit):
+    N = int(est.shape[0])
+    return _errors(PoseErrors, "sam6d_pose_point_errors", points, (N,), (_p(est), _p(gt), N), syms, intr, inv_unit)
 
 
 def pose_errors(mesh_or_points, R_est, t_est, R_gt, t_gt, K, syms=None, scale=1.0, unit=None):
@@ -210,16 +234,7 @@ def pose_errors(mesh_or_points, R_est, t_est, R_gt, t_gt, K, syms=None, scale=1.
     points = _points(name, mesh_or_points, R_est)
     intr = _intrinsics(name, K)
     inv_unit = _inv_unit(name, unit)
-    if syms is None:
-        syms = np.concatenate([np.eye(3), np.zeros((3, 1))], axis=1)[None].astype(np.float32)
-    host = None if torch.is_tensor(syms) else np.asarray(syms)
-    syms = _tensor(syms if host is None else torch.from_numpy(np.ascontiguousarray(host)), name, "syms", torch.float32, (None, 3, 4))
-    if not 1 <= int(syms.shape[0]) <= MAX_SYMS:
-        raise ValueError("%s: syms: S = %d is not in 1 .. %d" % (name, int(syms.shape[0]), MAX_SYMS))
-    if host is not None:  # a host array goes beside the points
-        if not points.is_cuda:
-            raise RuntimeError("%s: needs HIP device tensors (this build has no CPU path)" % name)
-        syms = syms.to(points.device)
+    syms = _syms(name, syms, points)
     _same_device(name, points, (("R_est", R_est), ("t_est", t_est), ("R_gt", R_gt), ("t_gt", t_gt), ("syms", syms)))
     return _point_errors(points, verify.pose_views(R_est, t_est, scale), verify.pose_views(R_gt, t_gt, scale), syms, intr, inv_unit)
 

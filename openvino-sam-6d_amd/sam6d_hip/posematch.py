@@ -13,14 +13,13 @@ bit for bit.  Nothing here is pinned against bop_toolkit itself, which the suite
 Poses of different objects are separate calls, one mesh each (INTEGRATION.md has the loop over template_ids).  Left to the caller:
 symmetry-aware ADI and VSD as matrices, several meshes in one call, BOP's file formats and threshold lists.
 
-Imports poseerr, verify, runtime, _lib, torch and numpy only; the library is loaded at the first launch, not at import.  There is no
+Imports poseerr, verify, runtime, _lib and torch only; the library is loaded at the first launch, not at import.  There is no
 CPU route: a CPU tensor raises RuntimeError.
 """
-import numpy as np
 import torch
 
 from . import _lib, verify
-from .poseerr import ADD_SCALE, MAX_POINTS, _intrinsics, _inv_unit, _points, _same_device  # noqa: F401
+from .poseerr import ADD_SCALE, MAX_POINTS, PoseErrors, _errors, _intrinsics, _inv_unit, _points, _same_device, _syms  # noqa: F401
 from .runtime import _empty, _p, _s, on_tensor_device
 from .verify import _tensor
 
@@ -30,14 +29,10 @@ MAX_THRESHOLDS = 64
 NO_MSPD = 1                  # sam6d_pose_pair_errors flags bit 0
 
 
-class PairErrors:
+class PairErrors(PoseErrors):
     """What pair_errors returns; every tensor is on the device and (A,B): row i the pose a[i], column j the pose b[j].  mssd, add f32
     in the unit of t, mssd_sym i32, add_sum i64 the integer ADD is formed from; with K also mspd f32 in pixels, mspd_sym i32 and
     n_skipped i32, else None.  The fields are poseerr.PoseErrors' for est = a[i], gt = b[j]."""
-
-    def __init__(self, mssd, mspd, add, mssd_sym, mspd_sym, n_skipped, add_sum):
-        self.mssd, self.mspd, self.add, self.mssd_sym, self.mspd_sym = mssd, mspd, add, mssd_sym, mspd_sym
-        self.n_skipped, self.add_sum = n_skipped, add_sum
 
 
 class PoseMatches:
@@ -72,36 +67,11 @@ def _poses(name, what, R, t):
     return R, t
 
 
-def _syms(name, syms, points):
-    """(S,3,4) f32 beside the points: None is the identity alone, a host array is uploaded"""
-    if syms is None:
-        syms = np.concatenate([np.eye(3), np.zeros((3, 1))], axis=1)[None].astype(np.float32)
-    host = None if torch.is_tensor(syms) else np.asarray(syms)
-    syms = _tensor(syms if host is None else torch.from_numpy(np.ascontiguousarray(host)), name, "syms", torch.float32, (None, 3, 4))
-    if not 1 <= int(syms.shape[0]) <= MAX_POSES:
-        raise ValueError("%s: syms: S = %d is not in 1 .. %d" % (name, int(syms.shape[0]), MAX_POSES))
-    if host is not None:
-        if not points.is_cuda:
-            raise RuntimeError("%s: needs HIP device tensors (this build has no CPU path)" % name)
-        syms = syms.to(points.device)
-    return syms
-
-
 @on_tensor_device
 def _pair_errors(points, a, b, syms, intr, inv_unit):
-    V, A, B, S = int(points.shape[0]), int(a.shape[0]), int(b.shape[0]), int(syms.shape[0])
-    need = int(_lib.load().sam6d_pose_pair_errors_workspace_bytes(A, B, S))
-    ws = _empty((need // 8,), points, torch.int64)
-    mssd, mssd_sym = _empty((A, B), points), _empty((A, B), points, torch.int32)
-    add_sum = _empty((A, B), points, torch.int64)
-    mspd = mspd_sym = skipped = None
-    if intr is not None:
-        mspd, mspd_sym, skipped = _empty((A, B), points), _empty((A, B), points, torch.int32), _empty((A, B), points, torch.int32)
-    _lib.call("sam6d_pose_pair_errors", _p(points), V, _p(a), A, _p(b), B, _p(syms), S, *(intr or (0.0, 0.0, 0.0, 0.0)), inv_unit,
-              0 if intr is not None else NO_MSPD, _p(mssd), _p(mspd), _p(mssd_sym), _p(mspd_sym), _p(skipped), add_sum.data_ptr(),
-              ws.data_ptr(), need, _s())
-    add = (add_sum.to(torch.float64) / ADD_SCALE / inv_unit / V).to(torch.float32)
-    return PairErrors(mssd, mspd, add, mssd_sym, mspd_sym, skipped, add_sum)
+    A, B = int(a.shape[0]), int(b.shape[0])
+    return _errors(PairErrors, "sam6d_pose_pair_errors", points, (A, B), (_p(a), A, _p(b), B), syms, intr, inv_unit,
+                   (0 if intr is not None else NO_MSPD,))
 
 
 def pair_errors(mesh_or_points, R_a, t_a, R_b, t_b, K=None, syms=None, scale=1.0, unit=None):
@@ -120,7 +90,7 @@ def pair_errors(mesh_or_points, R_a, t_a, R_b, t_b, K=None, syms=None, scale=1.0
     points = _points(name, mesh_or_points, R_a)
     intr = None if K is None else _intrinsics(name, K)
     inv_unit = _inv_unit(name, unit)
-    syms = _syms(name, syms, points)
+    syms = _syms(name, syms, points, MAX_POSES)
     A, B, S = int(R_a.shape[0]), int(R_b.shape[0]), int(syms.shape[0])
     if A * B * S > MAX_TRIPLES:
         raise ValueError("%s: A B S = %d x %d x %d = %d is above the cap of %d: split a or b" % (name, A, B, S, A * B * S, MAX_TRIPLES))

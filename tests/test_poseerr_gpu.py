@@ -153,6 +153,25 @@ def test_a_point_behind_the_camera(dev):
     assert want["mspd"][1] == without["mspd"][1] and want["add_sum"][1] > without["add_sum"][1]  # left out of MSPD alone
 
 
+def test_point_errors_many_symmetries_through_the_c_entry(dev):
+    """sam6d_pose_point_errors itself at S = 1024 over two poses of 65 points: so few workgroups per symmetry that a launch which
+    splits the symmetries deals them out in many short runs, and the minimum lies in a later run than the first"""
+    pts, est, gt, syms = _scene(65, 2, 1024)
+    V, N, S = 65, 2, 1024
+    want = PR.point_errors(pts, est, gt, syms, INTR, 0.5)
+    assert want["mssd_sym"].max() >= 256 and not want["n_skipped"].any()
+    d = [_t(np.asarray(a, F32), dev) for a in (pts, est, gt, syms)]
+    out = dict(mssd=torch.float32, mspd=torch.float32, mssd_sym=torch.int32, mspd_sym=torch.int32, n_skipped=torch.int32, add_sum=torch.int64)
+    out = {k: torch.full((N,), 77, dtype=dt, device=dev) for k, dt in out.items()}
+    need = _lib.load().sam6d_pose_point_errors_workspace_bytes(N, S)
+    ws = torch.full((need // 8,), 77, dtype=torch.int64, device=dev)
+    _lib.call("sam6d_pose_point_errors", d[0].data_ptr(), V, d[1].data_ptr(), d[2].data_ptr(), N, d[3].data_ptr(), S, *INTR, 0.5,
+              *(out[k].data_ptr() for k in ("mssd", "mspd", "mssd_sym", "mspd_sym", "n_skipped", "add_sum")), ws.data_ptr(), need,
+              torch.cuda.current_stream().cuda_stream)
+    for k, b in out.items():
+        assert np.array_equal(b.cpu().numpy(), want[k]), (k, b.cpu().numpy(), want[k])
+
+
 def test_point_error_refusals_write_nothing(dev):
     pts, est, gt, syms = _scene(65, 3, 2)
     V, N, S, G = 65, 3, 2, 16

@@ -227,10 +227,11 @@ def test_refusals():
 # ------------------------------------------------------------------------------------------------------------ the kernels
 def test_kernel_resources():
     """no kernel of poseerr.hip uses scratch or spills a vector register, and each keeps within its built
-    VGPR count rounded up to the next step of 8 (built: point_errors 72, point_errors_finish 16, vsd_compare 25; verify_faces, the
-    shared raster pass, 63 as in its other two code objects).  Read from the code object's metadata: the compiler's figures."""
+    VGPR count rounded up to the next step of 8 (built: vsd_compare 25; verify_faces, the shared raster pass, 63 as in its other two
+    code objects).  The point errors have no kernel of their own here: they run posematch.hip's, which tests/test_posematch_host.py
+    holds to their counts.  Read from the code object's metadata: the compiler's figures."""
     from tests._util import kernel_resources
-    limits = dict(point_errors_kernel=72, point_errors_finish_kernel=16, vsd_compare_kernel=32, verify_faces_kernel=64)
+    limits = dict(vsd_compare_kernel=32, verify_faces_kernel=64)
     found = kernel_resources(b"vsd_compare_kernel")
     print("\n[poseerr] (VGPRs, scratch bytes, spilled): %s" % found)
     assert set(found) == set(limits), found

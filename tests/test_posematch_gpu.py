@@ -212,6 +212,29 @@ def test_pair_errors_python_entry(dev):
     assert all(np.array_equal(getattr(bare, k).cpu().numpy(), want[k]) for k in NO_K) and np.array_equal(bare.add.cpu().numpy(), add)
 
 
+def test_pose_errors_are_the_diagonal_of_pair_errors(dev):
+    """V = 1025 is two chunks, S = 129 two LDS tiles, and runs of 8 matrices end inside a tile: every field of pose_errors(a, b) is
+    the diagonal of pair_errors(a, b) and the restatement's, n_skipped and add_sum included.  Pose 1 has one vertex behind the camera
+    under the estimate (as test_poseerr_gpu's test_a_point_behind_the_camera has it)"""
+    pts, a, b, syms = _scene(1025, 3, 3, 129)
+    pts, a, b = pts.copy(), a.copy(), b.copy()
+    pts[40] = [0.0, 0.0, -6.5]
+    a[[0, 2], 2, 3] += F32(6.0)  # the other poses: far enough for every vertex
+    b[[0, 2], 2, 3] += F32(6.0)
+    a[1], b[1] = VR.pose((0.1, 0.0, 6.0), axis=(1.0, 0.0, 0.0), angle=0.05), VR.pose((0.0, 0.1, 10.0), angle=0.0)
+    want = PR.point_errors(pts, a, b, syms, INTR, F32(1.0 / UNIT))
+    assert want["n_skipped"].tolist() == [0, 1, 0]  # a skip cannot hide a failure
+    assert np.isfinite(want["mssd"]).all() and np.isfinite(want["mspd"]).all() and want["mssd_sym"].max() > 0
+    want["add"] = PR.add_of(want["add_sum"], F32(1.0 / UNIT), len(pts))
+    args = [_t(x, dev) for x in (pts, a[:, :, :3], a[:, :, 3], b[:, :, :3], b[:, :, 3])]
+    pose = poseerr.pose_errors(*args, INTR, syms=_t(syms, dev), unit=UNIT)
+    pair = posematch.pair_errors(*args, K=INTR, syms=_t(syms, dev), unit=UNIT)
+    for k, dt in dict(PAIR_OUT, add=torch.float32).items():
+        p, q = getattr(pose, k), getattr(pair, k)
+        assert p.dtype == q.dtype == dt and tuple(p.shape) == (3,) and tuple(q.shape) == (3, 3), k
+        assert np.array_equal(p.cpu().numpy(), want[k]) and torch.equal(q.diagonal(), p), (k, p.cpu().numpy(), q.cpu().numpy(), want[k])
+
+
 # ------------------------------------------------------------------------------------------------------------ matching
 POOL = np.array([0.0, -0.0, 0.125, 0.25, 0.25, 0.5, 0.75, 1.0, 2.0, -1.0, np.inf, NAN], F32)
 
