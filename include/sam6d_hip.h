@@ -1169,6 +1169,36 @@ size_t sam6d_pose_nms_workspace_bytes(int N);
 int sam6d_pose_nms(const float* err, const float* scores, int N, float thresh, long long* keep_idx, int* count, int* suppressed_by,
                    void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * All-pairs VSD: one render per pose, the pairs by the overlap of their windows (csrc/vsdpairs.hip, restated in
+ * tests/vsdpairs_ref.py).  (New entries only, so SAM6D_ABI_VERSION stays.)
+ * ------------------------------------------------------------------------------------------------------------ */
+/* The counts of BOP's Visible Surface Discrepancy of every estimate a[i] against every ground truth b[j] of one object.  Beside
+ * PEM/run_inference_custom_pytorch.py:460-471, where the reference writes its poses and leaves scoring to bop_toolkit.  For every
+ * (i, j) the row of counts is, bit for bit, what sam6d_pose_vsd gives for est = a[i], gt = b[j]; the roles are not symmetric.
+ * Mesh, camera, near, wave_area, depth_obs, delta, taus (ON THE HOST), T and inv_norm as in sam6d_pose_vsd.  view (A+B,3,4) f32: views
+ * 0 .. A-1 are a, A .. A+B-1 are b; box (A+B,4) i32 and offset (A+B+1) i64 on the device as in sam6d_pose_verify, EVERY VIEW WITH ITS
+ * OWN box (sam6d_pose_windows', not a pair's union); total: the host's copy of offset[A+B].
+ * Each view is rastered once.  Per view and window pixel, with D = r * c as in sam6d_pose_vsd: has (a key is there) and own = has &&
+ * (!reading || D - D_o <= delta); view_counts (A+B,2) i32 = n_render (#has), n_visible (#own).  Per pair, with E_i and G_j the
+ * n_visible of a[i] and b[j] and X the intersection rectangle of their two windows: n_visib_gt = G_j, n_inter = #X{has_e && own_g},
+ * n_visib_est = E_i + #X{has_e && !own_e && own_g}, n_union = n_visib_est + G_j - n_inter, cost_k = #X{has_e && own_g &&
+ * fabsf(D_g - D_e) * inv_norm >= taus[k]}: integer identities of sam6d_pose_vsd's sets (the recipe at the top of csrc/vsdpairs.hip
+ * says why).  counts (A, B, 4+T) i32 = n_union, n_inter, n_visib_est, n_visib_gt, cost_0 .. cost_{T-1}.  total == 0: every count and
+ * view count is 0 and no pass runs.  A pair whose windows do not meet costs no pixel work.
+ * 64-bit atomic minima (the raster) and 32-bit atomic adds (view_counts); a pair's row has one owner and is written by plain stores:
+ * a function of the inputs alone.  The kernels clamp every box to the image and address no word at or beyond `total`, whatever box
+ * and offset hold.
+ * Limits of sam6d_pose_windows with A, B 1 .. 1024 each, T 1 .. 16, wave_area >= 0, fx and fy not 0, delta and taus finite and >= 0,
+ * inv_norm finite and > 0, total 0 .. (A+B) H W, workspace 8-byte aligned and at least sam6d_pose_pair_vsd_workspace_bytes(total, A,
+ * B) = 8 total + 8 ceil(total / 2) + 32 (A+B) (the z-buffer words, the 32-bit image of D and own, and the raster pass's counter
+ * words; 0 for sizes outside the limits); anything else or a null pointer returns non-zero without a launch or a write. */
+size_t sam6d_pose_pair_vsd_workspace_bytes(long total, int A, int B);
+int sam6d_pose_pair_vsd(const float* vertices, int V, const int* faces, int F, const float* view, int A, int B, float fx, float fy,
+                        float cx, float cy, int H, int W, float near, int wave_area, const int* box, const long long* offset,
+                        long total, const float* depth_obs, float delta, const float* taus, int T, float inv_norm, int* counts,
+                        int* view_counts, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -56,12 +56,7 @@
 #define PE_MAX_N 1024
 #define PE_MAX_S 1024
 #define PE_MAX_PAIRS 512
-#define PE_MAX_T 16
 #define PE_VSD_WG 1024              // sixteen waves, as verify.hip's classify: one offer per workgroup at a pose's counters
-
-struct PeTaus {
-  float v[PE_MAX_T];
-};
 
 // ---------------------------------------------------------------------------------------------------------- a. point errors
 // The kernels are posematch.hip's: est[n] against gt[n] o syms[s] is the diagonal of its all-pairs walk (poseerr_point.h's pe_errors).
@@ -174,11 +169,7 @@ extern "C" int sam6d_pose_vsd(const float* vertices, int V, const int* faces, in
                               size_t workspace_bytes, void* stream) {
   const int bad = rs_limits("pose_vsd", V, F, "N", N, PE_MAX_PAIRS, H, W, near);
   if (bad) return bad;
-  SAM6D_REQUIRE(wave_area >= 0, "pose_vsd: wave_area = %d is negative", wave_area);
-  SAM6D_REQUIRE(delta >= 0.f && delta <= 3.4028234e38f, "pose_vsd: delta = %g is not a finite number >= 0", (double)delta);
-  SAM6D_REQUIRE(inv_norm > 0.f && inv_norm <= 3.4028234e38f, "pose_vsd: inv_norm = %g is not a finite number > 0", (double)inv_norm);
-  SAM6D_REQUIRE(fx != 0.f && fy != 0.f && fx == fx && fy == fy, "pose_vsd: fx, fy = %g, %g: zero or not a number", (double)fx, (double)fy);
-  SAM6D_REQUIRE(T >= 1 && T <= PE_MAX_T, "pose_vsd: T = %d is not in 1 .. %d", T, PE_MAX_T);
+  if (const int bad_tol = pe_check_vsd("pose_vsd", wave_area, delta, inv_norm, fx, fy, T)) return bad_tol;
   SAM6D_REQUIRE(total >= 0 && total <= 2L * N * H * W, "pose_vsd: total = %ld is not in 0 .. 2 N H W = %ld", total, 2L * N * H * W);
   SAM6D_POINTER("pose_vsd", vertices);
   SAM6D_POINTER("pose_vsd", faces);
@@ -190,10 +181,7 @@ extern "C" int sam6d_pose_vsd(const float* vertices, int V, const int* faces, in
   SAM6D_POINTER("pose_vsd", counts);
   SAM6D_POINTER("pose_vsd", workspace);
   PeTaus tv;
-  for (int k = 0; k < PE_MAX_T; ++k) {
-    tv.v[k] = k < T ? taus[k] : 0.f;
-    SAM6D_REQUIRE(tv.v[k] >= 0.f && tv.v[k] <= 3.4028234e38f, "pose_vsd: taus[%d] = %g is not a finite number >= 0", k, (double)tv.v[k]);
-  }
+  if (const int bad_tau = pe_check_taus("pose_vsd", taus, T, tv)) return bad_tau;
   const size_t need = sam6d_pose_vsd_workspace_bytes(total, N);
   SAM6D_REQUIRE(workspace_bytes >= need, "pose_vsd: workspace of %zu bytes is below sam6d_pose_vsd_workspace_bytes = %zu", workspace_bytes,
                 need);

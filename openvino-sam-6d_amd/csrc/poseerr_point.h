@@ -146,6 +146,32 @@ static inline int pe_check_inv_unit(const char* who, float inv_unit) {
   return 0;
 }
 
+// what the two VSD entries share (sam6d_pose_vsd in poseerr.hip, sam6d_pose_pair_vsd in vsdpairs.hip): the tolerances as a kernel
+// argument and their refusals, by name
+#define PE_MAX_T 16
+
+struct PeTaus {
+  float v[PE_MAX_T];
+};
+
+static inline int pe_check_vsd(const char* who, int wave_area, float delta, float inv_norm, float fx, float fy, int T) {
+  SAM6D_REQUIRE(wave_area >= 0, "%s: wave_area = %d is negative", who, wave_area);
+  SAM6D_REQUIRE(delta >= 0.f && delta <= 3.4028234e38f, "%s: delta = %g is not a finite number >= 0", who, (double)delta);
+  SAM6D_REQUIRE(inv_norm > 0.f && inv_norm <= 3.4028234e38f, "%s: inv_norm = %g is not a finite number > 0", who, (double)inv_norm);
+  SAM6D_REQUIRE(fx != 0.f && fy != 0.f && fx == fx && fy == fy, "%s: fx, fy = %g, %g: zero or not a number", who, (double)fx, (double)fy);
+  SAM6D_REQUIRE(T >= 1 && T <= PE_MAX_T, "%s: T = %d is not in 1 .. %d", who, T, PE_MAX_T);
+  return 0;
+}
+
+// taus (T floats on the host, not null) -> tv, zeros beyond T
+static inline int pe_check_taus(const char* who, const float* taus, int T, PeTaus& tv) {
+  for (int k = 0; k < PE_MAX_T; ++k) {
+    tv.v[k] = k < T ? taus[k] : 0.f;
+    SAM6D_REQUIRE(tv.v[k] >= 0.f && tv.v[k] <= 3.4028234e38f, "%s: taus[%d] = %g is not a finite number >= 0", who, k, (double)tv.v[k]);
+  }
+  return 0;
+}
+
 // Host side of the point errors, one copy for both entries (defined in posematch.hip): zeroes ws (A B S pairs of words), n_skipped
 // (pix) and add_sum in stream order, picks the run of matrices per workgroup, launches pair_errors_kernel<pix, diag> and
 // pair_errors_finish_kernel.  diag (with pix and B = 1 alone): a[i] is scored against b[i].  !pix: mspd, mspd_sym and n_skipped are

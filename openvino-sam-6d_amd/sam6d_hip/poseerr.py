@@ -369,16 +369,39 @@ def _vsd(vertices, faces, view, intr, H, W, near, depth, delta, taus, inv_norm):
     ws = _empty((need // 8,), vertices, torch.int64)
     counts = _empty((N, 4 + T), vertices, torch.int32)
     _lib.call("sam6d_pose_vsd", _p(vertices), int(vertices.shape[0]), _p(faces), int(faces.shape[0]), _p(view), N, *intr, H, W, near, 0,
-              _p(box), offset.data_ptr(), total, _p(depth), delta, (ctypes.c_float * T)(*taus), T, inv_norm, _p(counts), ws.data_ptr(), need,
-              _s())
+              _p(box), offset.data_ptr(), total, _p(depth), delta, _c_floats(taus), T, inv_norm, _p(counts), ws.data_ptr(), need, _s())
     return counts
 
 
+def _c_floats(values):
+    """the host array of floats an entry reads its taus from"""
+    return (ctypes.c_float * len(values))(*values)
+
+
 def vsd_from_counts(counts):
-    """counts (N, 4+T) i32 of sam6d_pose_vsd -> vsd (N,T) f32 = (cost_k + n_union - n_inter) / n_union, 1 where n_union is 0"""
-    union = counts[:, 0:1]
-    num = (counts[:, 4:] + (union - counts[:, 1:2])).to(torch.float32)
+    """counts (..., 4+T) i32 of sam6d_pose_vsd or sam6d_pose_pair_vsd ((N, 4+T) or (A, B, 4+T)) -> vsd (..., T) f32 =
+    (cost_k + n_union - n_inter) / n_union, 1 where n_union is 0"""
+    union = counts[..., 0:1]
+    num = (counts[..., 4:] + (union - counts[..., 1:2])).to(torch.float32)
     return torch.where(union > 0, num / union.to(torch.float32), torch.ones_like(num))
+
+
+def _tolerances(name, delta, taus, diameter):
+    """delta, taus and diameter of vsd and posematch.pair_vsd, checked -> delta, the list of taus, inv_norm"""
+    delta = float(delta)
+    if not (delta >= 0.0 and math.isfinite(delta)):
+        raise ValueError("%s: delta = %r is not a finite number >= 0" % (name, delta))
+    taus = [float(v) for v in np.asarray(taus.cpu() if torch.is_tensor(taus) else taus, np.float64).reshape(-1)]
+    if not 1 <= len(taus) <= MAX_TAUS:
+        raise ValueError("%s: taus: T = %d is not in 1 .. %d" % (name, len(taus), MAX_TAUS))
+    if not all(v >= 0.0 and math.isfinite(v) for v in taus):
+        raise ValueError("%s: taus = %r: every one must be a finite number >= 0" % (name, taus))
+    inv_norm = 1.0
+    if diameter is not None:
+        if not (float(diameter) > 0.0 and math.isfinite(float(diameter))):
+            raise ValueError("%s: diameter = %r is not a finite number > 0" % (name, diameter))
+        inv_norm = float(np.float32(1.0 / float(diameter)))
+    return delta, taus, inv_norm
 
 
 def vsd(mesh, R_est, t_est, R_gt, t_gt, K, depth, delta, taus, diameter=None, scale=1.0, near=NEAR):
@@ -398,19 +421,7 @@ def vsd(mesh, R_est, t_est, R_gt, t_gt, K, depth, delta, taus, diameter=None, sc
     vertices, faces, R_est, t_est, depth, _, intr, H, W = verify._pose_args(name, mesh, R_est, t_est, K, depth, None, near)
     N, R_est, t_est, R_gt, t_gt = _pair(name, R_est, t_est, R_gt, t_gt, MAX_PAIRS)
     _same_device(name, vertices, (("R_gt", R_gt), ("t_gt", t_gt)))
-    delta = float(delta)
-    if not (delta >= 0.0 and math.isfinite(delta)):
-        raise ValueError("%s: delta = %r is not a finite number >= 0" % (name, delta))
-    taus = [float(v) for v in np.asarray(taus.cpu() if torch.is_tensor(taus) else taus, np.float64).reshape(-1)]
-    if not 1 <= len(taus) <= MAX_TAUS:
-        raise ValueError("%s: taus: T = %d is not in 1 .. %d" % (name, len(taus), MAX_TAUS))
-    if not all(v >= 0.0 and math.isfinite(v) for v in taus):
-        raise ValueError("%s: taus = %r: every one must be a finite number >= 0" % (name, taus))
-    inv_norm = 1.0
-    if diameter is not None:
-        if not (float(diameter) > 0.0 and math.isfinite(float(diameter))):
-            raise ValueError("%s: diameter = %r is not a finite number > 0" % (name, diameter))
-        inv_norm = float(np.float32(1.0 / float(diameter)))
+    delta, taus, inv_norm = _tolerances(name, delta, taus, diameter)
     view = torch.cat([verify.pose_views(R_est, t_est, scale), verify.pose_views(R_gt, t_gt, scale)], dim=0).contiguous()
     counts = _vsd(vertices, faces, view, intr, H, W, float(near), depth, delta, taus, inv_norm)
     return vsd_from_counts(counts), counts

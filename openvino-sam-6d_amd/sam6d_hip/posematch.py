@@ -10,8 +10,12 @@ taking the nearest free target under the threshold -- and pose_nms is a greedy s
 written out at the top of csrc/posematch.hip and restated in tests/posematch_ref.py, and every comparison with that restatement is
 bit for bit.  Nothing here is pinned against bop_toolkit itself, which the suite does not have.
 
+pair_vsd is the third BOP error as a matrix: poseerr.vsd's counts for every (i, j), bit for bit, from one render per pose
+(csrc/vsdpairs.hip, restated in tests/vsdpairs_ref.py), and vsd_matches runs match_poses on it once per tolerance -- with
+instance_recall that is AR_VSD, beside the AR_MSSD and AR_MSPD that pair_errors' matrices give.
+
 Poses of different objects are separate calls, one mesh each (INTEGRATION.md has the loop over template_ids).  Left to the caller:
-symmetry-aware ADI and VSD as matrices, several meshes in one call, BOP's file formats and threshold lists.
+symmetry-aware ADI, ADI as a matrix, several meshes in one call, BOP's file formats and threshold lists.
 
 Imports poseerr, verify, runtime, _lib and torch only; the library is loaded at the first launch, not at import.  There is no
 CPU route: a CPU tensor raises RuntimeError.
@@ -20,12 +24,14 @@ import torch
 
 from . import _lib, verify
 from .poseerr import ADD_SCALE, MAX_POINTS, PoseErrors, _errors, _intrinsics, _inv_unit, _points, _same_device, _syms  # noqa: F401
+from .poseerr import MAX_TAUS, _c_floats, _tolerances, vsd_from_counts
 from .runtime import _empty, _p, _s, on_tensor_device
-from .verify import _tensor
+from .verify import NEAR, _tensor
 
 MAX_POSES = 1024             # A, B, S of pair_errors and match_poses, N of pose_nms
 MAX_TRIPLES = 1 << 22        # A B S: a workspace of 8 bytes per triple, 32 MiB at most
 MAX_THRESHOLDS = 64
+MAX_VSD_WORDS = 1 << 28      # pair_vsd: the window words of all A + B views, a z-buffer of 2 GiB at most
 NO_MSPD = 1                  # sam6d_pose_pair_errors flags bit 0
 
 
@@ -211,3 +217,78 @@ def nms_poses(mesh_or_points, R, t, scores, thresh, syms=None, scale=1.0):
     -> (PoseNms, the (N,N) mssd matrix)."""
     mssd = pair_errors(mesh_or_points, R, t, R, t, K=None, syms=syms, scale=scale).mssd
     return pose_nms(mssd, scores, thresh), mssd
+
+
+# ------------------------------------------------------------------------------------------------------------ VSD as a matrix
+class PairVsd:
+    """What pair_vsd returns; every tensor is on the device.  vsd (A,B,T) f32 and counts (A,B,4+T) i32 = n_union, n_inter, n_visib_est,
+    n_visib_gt, cost_0 .. cost_{T-1}: row i the estimate a[i], column j the ground truth b[j].  n_render_a, n_visible_a (A) and
+    n_render_b, n_visible_b (B) i32: per pose, the pixels its render covers and those of them that the depth image does not occlude."""
+
+    def __init__(self, vsd, counts, n_render_a, n_visible_a, n_render_b, n_visible_b):
+        self.vsd, self.counts = vsd, counts
+        self.n_render_a, self.n_visible_a, self.n_render_b, self.n_visible_b = n_render_a, n_visible_a, n_render_b, n_visible_b
+
+
+@on_tensor_device
+def _pair_vsd(vertices, faces, view, A, intr, H, W, near, depth, delta, taus, inv_norm):
+    B, T = int(view.shape[0]) - A, len(taus)
+    # every view's own window; sam6d_pose_windows takes 1024 views a call
+    box = torch.cat([verify._windows(vertices, faces, v, intr, H, W, near)[0] for v in (view[:A], view[A:])], dim=0).contiguous()
+    offset, total = verify.window_offsets(box)
+    total = int(total)  # the one read-back: 8 bytes, to size the workspace
+    if total > MAX_VSD_WORDS:
+        raise ValueError("pair_vsd: the windows of the %d + %d poses have %d words, above the cap of %d: split a or b" % (A, B, total, MAX_VSD_WORDS))
+    need = int(_lib.load().sam6d_pose_pair_vsd_workspace_bytes(total, A, B))
+    ws = _empty((need // 8,), vertices, torch.int64)
+    counts, view_counts = _empty((A, B, 4 + T), vertices, torch.int32), _empty((A + B, 2), vertices, torch.int32)
+    _lib.call("sam6d_pose_pair_vsd", _p(vertices), int(vertices.shape[0]), _p(faces), int(faces.shape[0]), _p(view), A, B, *intr, H, W, near, 0,
+              _p(box), offset.data_ptr(), total, _p(depth), delta, _c_floats(taus), T, inv_norm, _p(counts), _p(view_counts), ws.data_ptr(),
+              need, _s())
+    return counts, view_counts
+
+
+def pair_vsd(mesh, R_a, t_a, R_b, t_b, K, depth, delta, taus, diameter=None, scale=1.0, near=NEAR):
+    """BOP's Visible Surface Discrepancy of every estimate a[i] against every ground truth b[j] of one object, for every tolerance in
+    taus: for every (i, j), bit for bit, the counts poseerr.vsd gives for est = a[i], gt = b[j].
+
+    a is the estimate and b the ground truth, and the roles are NOT symmetric: the ground truth's visibility is decided by the depth
+    image alone, the estimate's also by the ground truth (BOP's `bop19` mode), so pair_vsd(.., a, b) is not the transpose of
+    pair_vsd(.., b, a).
+    mesh, K, depth, delta, taus, diameter, scale and near as poseerr.vsd has them.  R_a (A,3,3), t_a (A,3), R_b (B,3,3), t_b (B,3) f32
+    HIP tensors, A and B at most 1024 each; the windows of all A + B poses together at most 2^28 pixels (a z-buffer of 2 GiB).
+    Every pose is rendered once, into its own window; a pair costs a walk over the rectangle its two windows share and nothing at all
+    when they do not meet (csrc/vsdpairs.hip has the recipe and why it gives poseerr.vsd's integers).
+    -> PairVsd: vsd (A,B,T) f32 = (cost + n_union - n_inter) / n_union, 1 where nothing is visible; counts (A,B,4+T) i32; and per pose
+    n_render_a, n_visible_a (A), n_render_b, n_visible_b (B) i32.
+    A CPU tensor raises RuntimeError; a wrong shape or dtype ValueError naming the argument."""
+    name = "pair_vsd"
+    R_a, t_a = _poses(name, "a", R_a, t_a)
+    R_b, t_b = _poses(name, "b", R_b, t_b)
+    vertices, faces, R_a, t_a, depth, _, intr, H, W = verify._pose_args(name, mesh, R_a, t_a, K, depth, None, near)
+    _same_device(name, vertices, (("R_b", R_b), ("t_b", t_b)))
+    delta, taus, inv_norm = _tolerances(name, delta, taus, diameter)
+    A = int(R_a.shape[0])
+    view = torch.cat([verify.pose_views(R_a, t_a, scale), verify.pose_views(R_b, t_b, scale)], dim=0).contiguous()
+    counts, per_view = _pair_vsd(vertices, faces, view, A, intr, H, W, float(near), depth, delta, taus, inv_norm)
+    return PairVsd(vsd_from_counts(counts), counts, per_view[:A, 0], per_view[:A, 1], per_view[A:, 0], per_view[A:, 1])
+
+
+def vsd_matches(vsd, scores, thresholds, valid=None, max_ests=0):
+    """match_poses on a VSD matrix, once per misalignment tolerance: vsd (A,B,T) f32 HIP tensor (pair_vsd's), T 1 .. 16; scores,
+    thresholds (BOP: 0.05 .. 0.5, the correctness thresholds on the error), valid and max_ests as match_poses has them.
+    -> n_matched (T,K) i32 on the device, row k from match_poses(vsd[:, :, k], ..) with K the number of thresholds, and n_targets.
+    instance_recall(n_matched, n_targets) is BOP's recall per (tau, threshold) and its mean over both axes AR_VSD.  A host loop of at
+    most 16 launches; no kernel of its own.
+
+    valid is where BOP's rule "targets at least 10 % visible" goes: pair_vsd's n_visible_b / n_render_b >= 0.1.  That ratio is BOP's
+    visib_fract IN KIND: the package's rasteriser, and the silhouette inside the image as the denominator; it is not pinned against
+    bop_toolkit.
+    A CPU tensor raises RuntimeError; a wrong shape or dtype ValueError naming the argument."""
+    name = "vsd_matches"
+    vsd = _tensor(vsd, name, "vsd", torch.float32, (None, None, None))
+    T = int(vsd.shape[2])
+    if not 1 <= T <= MAX_TAUS:
+        raise ValueError("%s: vsd: T = %d is not in 1 .. %d" % (name, T, MAX_TAUS))
+    found = [match_poses(vsd[:, :, k].contiguous(), scores, thresholds, valid, max_ests) for k in range(T)]
+    return torch.stack([m.n_matched for m in found], dim=0), found[0].n_targets
