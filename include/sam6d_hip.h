@@ -396,7 +396,9 @@ int sam6d_weighted_sample(const float* weights, const float* rand, int B, int L,
  * ts (B,nh,3), dis (B,nh). */
 int sam6d_coarse_hypotheses(const int* idx, const float* pts1, const float* pts2, int B, int N1, int N2, int nh,
                             float* Rs, float* ts, float* dis, void* stream);
-/* torch.topk(k, largest=False) indices, ascending (PEM/utils/model_utils.py:258). */
+/* torch.topk(k, largest=False) indices, ascending (PEM/utils/model_utils.py:258).  Equal values (-0 equals +0) come in
+ * index order; a NaN of either sign ranks after +inf, lower index first, as torch.topk places it.  The order is total:
+ * every slot of sel is written exactly once for any row, whichever kernel n and k select. */
 int sam6d_select_smallest(const float* dis, int B, int n, int k, int* sel, void* stream);
 /* Hypothesis scoring + argmax (PEM/utils/model_utils.py:261-270); model (B,P,3) raw, radius (B).  P <= 8192 (16 bytes of LDS a CAD
  * point, reserved on first use). */
@@ -539,7 +541,8 @@ int sam6d_radius_normalize(const float* dense_po, const float* pts, int B, int N
 int sam6d_masked_patch_normalize(const float* feats, const float* masks, int N, int P, int D, int H, int W, int patch,
                                  float thresh, float* out, void* stream);
 /* replaces get_point_cloud_from_depth (PEM/utils/data_utils.py:92-110) on a resident depth map (H,W) f32, metres:
- * cloud (r1-r0, c1-c0, 3) for the crop bbox [rmin=r0, rmax=r1, cmin=c0, cmax=c1] (the whole image: 0,H,0,W). */
+ * cloud (r1-r0, c1-c0, 3) for the crop bbox [rmin=r0, rmax=r1, cmin=c0, cmax=c1] (the whole image: 0,H,0,W).  An empty
+ * window writes nothing and accepts a null cloud. */
 int sam6d_depth_to_cloud(const float* depth, int H, int W, int r0, int r1, int c0, int c1, float fx, float fy, float cx,
                          float cy, float* cloud, void* stream);
 /* replaces the test of Detections.remove_very_small_detections (ISM/model/utils.py:96-102): keep[i] (u8) =
@@ -547,7 +550,8 @@ int sam6d_depth_to_cloud(const float* depth, int H, int W, int r0, int r1, int c
  * thr_box = min_box_size**2, thr_mask = min_mask_size. */
 int sam6d_detections_small_keep(const long long* boxes, const float* masks, int N, int H, int W, float thr_box,
                                 float thr_mask, unsigned char* keep, void* stream);
-/* boolean-mask indexing (ISM/model/utils.py:104-105): idx (N) i64 = positions of the non-zero keep bytes, count[0] = K. */
+/* boolean-mask indexing (ISM/model/utils.py:104-105): idx (N) i64 = positions of the non-zero keep bytes, count[0] = K.
+ * Nothing is written to idx beyond K; N == 0 accepts a null keep and gives K = 0. */
 int sam6d_mask_to_indices(const unsigned char* keep, int N, long long* idx, int* count, void* stream);
 /* replaces `getattr(self, key)[idxs]` of Detections.filter / apply_nms* (ISM/model/utils.py:105,119,126,190) for a
  * tensor of any dtype: dst[j,:] = src[idx[j],:], rows of row_bytes bytes, idx (M) i64 (negative = from the end;
@@ -569,6 +573,9 @@ int sam6d_mask_rle_decode(const int* counts, const long long* offsets, int N, in
 /* replaces torchvision.ops.nms as Detections.apply_nms (ISM/model/utils.py:121-124, group == NULL) and
  * apply_nms_per_object_id (:107-117, group = object_ids) call it: boxes (N,4) f32 xyxy, scores (N) f32.
  * keep_idx (N) i64 receives the surviving indices, ids ascending, score descending inside an id (stable); count[0] = K.
+ * Inside an id the order is torch.sort(descending=True, stable=True)'s: a NaN score of either sign before every number,
+ * equal scores (-0 equals +0) by the lower index.  It is total, so keep_idx[:K] holds distinct indices in [0, N) for any
+ * scores.  A NaN IoU (0/0 of two empty boxes, NaN coordinates) never suppresses: the test is IoU > thresh.
  * ws: sam6d_nms_workspace_bytes(N) bytes of device memory. */
 size_t sam6d_nms_workspace_bytes(int N);
 int sam6d_nms(const float* boxes, const float* scores, const long long* group, int N, float thresh, long long* keep_idx,

@@ -64,7 +64,7 @@ __global__ __launch_bounds__(64) void mask_to_indices_kernel(const unsigned char
 }
 
 extern "C" int sam6d_mask_to_indices(const unsigned char* keep, int N, long long* idx, int* count, void* stream) {
-  SAM6D_REQUIRE(keep && idx && count, "mask_to_indices: null pointer");
+  SAM6D_REQUIRE(idx && count && (keep || N == 0), "mask_to_indices: null pointer");  // an empty mask has no bytes to point at
   SAM6D_REQUIRE(N >= 0, "mask_to_indices: bad size");
   hipLaunchKernelGGL(mask_to_indices_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, keep, N, idx, count);
   SAM6D_LAUNCH_CHECK("mask_to_indices");
@@ -113,17 +113,27 @@ extern "C" int sam6d_take_rows(const void* src, const long long* idx, long n_src
 // ------------------------------------------------------------------------------------------------- NMS
 // 1. order: position of box i in (group ascending, score descending, index ascending) -- torch.unique's ascending ids,
 //    then torchvision's stable descending sort inside each id.  Rank counting, O(N^2) over L2-resident scores.
+//    The scores are compared through an order-preserving integer key (posematch.hip's pm_key), so the rule is a total order
+//    for any input and every order[] slot is written exactly once: key(u) < key(v) exactly when u < v for numbers, a zero
+//    of either sign is +0, and a NaN of either sign takes the largest key -- torch.sort(descending=True, stable=True) puts
+//    NaN before every number, equal keys by the lower index.
+__device__ __forceinline__ unsigned nms_score_key(float v) {
+  if (v != v) return 0xffffffffu;
+  const unsigned w = v == 0.f ? 0u : __float_as_uint(v);
+  return (w & 0x80000000u) ? ~w : (w | 0x80000000u);
+}
+
 __global__ __launch_bounds__(256) void nms_order_kernel(const float* __restrict__ scores, const long long* __restrict__ group,
                                                         int N, int* __restrict__ order) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= N) return;
-  const float si = scores[i];
+  const unsigned ki = nms_score_key(scores[i]);
   const long long gi = group ? group[i] : 0;
   int pos = 0;
   for (int j = 0; j < N; ++j) {
-    const float sj = scores[j];
+    const unsigned kj = nms_score_key(scores[j]);
     const long long gj = group ? group[j] : 0;
-    pos += (gj < gi) || (gj == gi && (sj > si || (sj == si && j < i)));
+    pos += (gj < gi) || (gj == gi && (kj > ki || (kj == ki && j < i)));
   }
   order[pos] = i;
 }

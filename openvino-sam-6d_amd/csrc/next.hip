@@ -105,11 +105,12 @@ __global__ __launch_bounds__(256) void depth_to_cloud_kernel(const float* __rest
 
 extern "C" int sam6d_depth_to_cloud(const float* depth, int H, int W, int r0, int r1, int c0, int c1, float fx, float fy, float cx,
                                     float cy, float* cloud, void* stream) {
-  SAM6D_REQUIRE(depth && cloud, "depth_to_cloud: null pointer");
+  SAM6D_REQUIRE(depth, "depth_to_cloud: null pointer");
   SAM6D_REQUIRE(H > 0 && W > 0 && 0 <= r0 && r0 <= r1 && r1 <= H && 0 <= c0 && c0 <= c1 && c1 <= W,
                 "depth_to_cloud: bbox [%d,%d)x[%d,%d) outside the %dx%d depth map", r0, r1, c0, c1, H, W);
   const long total = (long)(r1 - r0) * (c1 - c0);
-  if (total == 0) return 0;
+  if (total == 0) return 0;  // an empty window has no output: its (0-byte) cloud may be a null pointer
+  SAM6D_REQUIRE(cloud, "depth_to_cloud: null pointer");
   hipLaunchKernelGGL(depth_to_cloud_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, depth, W,
                      r0, c0, r1 - r0, c1 - c0, fx, fy, cx, cy, cloud);
   SAM6D_LAUNCH_CHECK("depth_to_cloud");

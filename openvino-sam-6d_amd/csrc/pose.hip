@@ -823,55 +823,46 @@ extern "C" int sam6d_coarse_hypotheses(const int* idx, const float* pts1, const 
   SAM6D_LAUNCH_CHECK("coarse_hypotheses");
 }
 
-// k smallest of each row by rank counting: rank_i = #{j : d_j < d_i or (d_j == d_i and j < i)}; sel[rank] = i.
-// Output is sorted ascending (torch.topk(largest=False) order; tie order there is unspecified).
-// A wave holds 64 consecutive candidates i0 .. i0+63: every j below i0 precedes all of them (count d_j <= d_i), every j from
-// i0+64 on follows all of them (count d_j < d_i); only the 64 j inside the wave's own range need the full tie rule.  Two VALU
-// instructions per (i, j) pair instead of six, four j per broadcast LDS read.
+// The order of sam6d_select_smallest, both routes: the order-preserving integer image of the floats.  key(u) < key(v) exactly when
+// u < v for numbers (+-inf included), -0 and +0 share a key, and a NaN of either sign takes one key above +inf's -- torch.topk(largest=
+// False) puts every NaN after every number.  Equal keys rank by the lower index.
+__device__ __forceinline__ unsigned sr_key(float d) {
+  if (d != d) return 0xffc00000u;  // any NaN: the key of the positive quiet NaN, above +inf's 0xff800000
+  if (d == 0.0f) d = 0.0f;         // -0 and +0 compare equal in the rank rule
+  const unsigned u = __float_as_uint(d);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+#define SR_PAD_KEY 0xffffffffu  // above every key: the padding of the all-pairs route never counts
+
+// k smallest of each row by rank counting: rank_i = #{j : key_j < key_i or (key_j == key_i and j < i)}; sel[rank] = i.  A total order,
+// so every slot of sel is written exactly once.  Output is sorted ascending (torch.topk(largest=False) order; tie order there is
+// unspecified).
+// A wave holds 64 consecutive candidates i0 .. i0+63: every j below i0 precedes all of them (count key_j <= key_i), every j from
+// i0+64 on follows all of them (count key_j < key_i); only the 64 j inside the wave's own range need the full tie rule.  One compare
+// and one add-with-carry per (i, j) pair, four j per broadcast LDS read.
 __global__ __launch_bounds__(256) void select_smallest_kernel(const float* __restrict__ dis, int n, int k, int* __restrict__ sel) {
-  extern __shared__ __attribute__((aligned(16))) float sd[];  // n floats, padded with +inf to a multiple of 4
+  extern __shared__ __attribute__((aligned(16))) unsigned sk[];  // n keys, padded with SR_PAD_KEY to a multiple of 4
   const int b = blockIdx.y;
   const float* d = dis + (size_t)b * n;
   const int n4 = (n + 3) & ~3;
-  for (int i = threadIdx.x; i < n4; i += 256) sd[i] = (i < n) ? d[i] : INFINITY;
+  for (int i = threadIdx.x; i < n4; i += 256) sk[i] = (i < n) ? sr_key(d[i]) : SR_PAD_KEY;
   __syncthreads();
   const int i = blockIdx.x * 256 + threadIdx.x;
   const int i0 = i & ~63;  // first candidate of this wave (multiple of 64, so of 4)
   if (i0 >= n) return;
-  const float v = (i < n) ? sd[i] : INFINITY;
-  // sign bit of (v - o) = [o > v], of (o - v) = [o < v]: one v_sub_f32 and one v_alignbit_b32 (shift the bit into a 32-bit
-  // register) per pair, one popcount per 32 pairs -- compare + conditional add costs three VALU slots plus wait states
-  auto signs4 = [](unsigned int acc, float a, const float4& q, bool q_minus_a) {
-    const float d0 = q_minus_a ? q.x - a : a - q.x, d1 = q_minus_a ? q.y - a : a - q.y;
-    const float d2 = q_minus_a ? q.z - a : a - q.z, d3 = q_minus_a ? q.w - a : a - q.w;
-    acc = __builtin_amdgcn_alignbit(acc, __float_as_uint(d0), 31);
-    acc = __builtin_amdgcn_alignbit(acc, __float_as_uint(d1), 31);
-    acc = __builtin_amdgcn_alignbit(acc, __float_as_uint(d2), 31);
-    acc = __builtin_amdgcn_alignbit(acc, __float_as_uint(d3), 31);
-    return acc;
-  };
-  int gt_before = 0;  // #{j < i0 : d_j > v}; the j below the wave's range that count are the other i0 - gt_before
-  for (int j = 0; j < i0; j += 32) {
-    unsigned int acc = 0u;
-#pragma unroll
-    for (int u = 0; u < 8; ++u) acc = signs4(acc, v, *reinterpret_cast<const float4*>(&sd[j + 4 * u]), false);
-    gt_before += __popc(acc);
+  const unsigned v = (i < n) ? sk[i] : SR_PAD_KEY;
+  int rank = 0;
+  for (int j = 0; j < i0; j += 4) {  // i0 <= n: no padding below it
+    const uint4 o = *reinterpret_cast<const uint4*>(&sk[j]);
+    rank += (o.x <= v) + (o.y <= v) + (o.z <= v) + (o.w <= v);
   }
-  int rank = i0 - gt_before;
   const int i1 = min(i0 + 64, n4);
   for (int j = i0; j < i1; ++j) {
-    const float o = sd[j];
+    const unsigned o = sk[j];
     rank += (o < v || (o == v && j < i)) ? 1 : 0;
   }
-  int j = i1;
-  for (; j + 32 <= n4; j += 32) {
-    unsigned int acc = 0u;
-#pragma unroll
-    for (int u = 0; u < 8; ++u) acc = signs4(acc, v, *reinterpret_cast<const float4*>(&sd[j + 4 * u]), true);
-    rank += __popc(acc);
-  }
-  for (; j < n4; j += 4) {  // the +inf padding never counts: inf - v is +inf
-    const float4 o = *reinterpret_cast<const float4*>(&sd[j]);
+  for (int j = i1; j < n4; j += 4) {  // i1 and n4 are multiples of 4
+    const uint4 o = *reinterpret_cast<const uint4*>(&sk[j]);
     rank += (o.x < v) + (o.y < v) + (o.z < v) + (o.w < v);
   }
   if (i < n && rank < k) sel[(size_t)b * k + rank] = i;
@@ -883,11 +874,6 @@ __global__ __launch_bounds__(256) void select_smallest_kernel(const float* __res
 // the rank counting above: equal values in index order).  Identical output, one workgroup per row: 6000 -> 300 in ~15 us instead of
 // 72 us of all-pairs comparisons.
 #define SR_T 1024
-__device__ __forceinline__ unsigned sr_key(float d) {
-  if (d == 0.0f) d = 0.0f;  // -0 and +0 compare equal in the rank rule
-  const unsigned u = __float_as_uint(d);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 #define SR_STATIC_LDS (2048 * 4 + 64)  // hist[] + the three scalars of select_radix_kernel, padded
 __global__ __launch_bounds__(SR_T) void select_radix_kernel(const float* __restrict__ dis, int n, int k, int* __restrict__ sel) {
   extern __shared__ unsigned sr_keys[];        // n keys, then k candidate ids, then k candidate keys

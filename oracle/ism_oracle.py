@@ -145,11 +145,13 @@ def nms(boxes, scores, thresh):
     """torchvision.ops.nms, restated from torchvision's published CPU kernel (torchvision 0.15.1 / 0.20.x pinned by the
     reference's environment files; the package is NOT installed here -> PARITY UNPINNED for this function): stable
     descending sort by score; walk the order, keep a box unless suppressed, suppress every later box whose
-    IoU = inter / (area_i + area_j - inter) exceeds thresh.  Returns the kept indices in descending-score order."""
+    IoU = inter / (area_i + area_j - inter) exceeds thresh.  Returns the kept indices in descending-score order.
+    The sort is the kernel's own call, scores.sort(stable=True, descending=True): a NaN score of either sign comes before
+    every number, equal scores (-0 equals +0) keep their index order.  A NaN IoU never suppresses."""
     b = boxes.detach().cpu().numpy().astype(np.float32)
     s = scores.detach().cpu().numpy().astype(np.float32)
     n = b.shape[0]
-    order = np.argsort(-s, kind="stable")
+    order = torch.sort(torch.from_numpy(s), stable=True, descending=True).indices.numpy()
     areas = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
     dead = np.zeros(n, bool)
     keep = []

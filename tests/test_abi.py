@@ -28,6 +28,62 @@ def test_header_symbols_exported_and_bound():
     assert _lib.load().sam6d_abi_version() == ver == _lib.ABI_VERSION, "header, library and Python binding disagree on the ABI version"
 
 
+_C_TYPES = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t,
+            "unsigned": ctypes.c_uint, "unsigned int": ctypes.c_uint}
+
+
+def _ctype_of(decl, name):
+    """ctypes type of one C parameter or return type as the header spells it: any pointer is c_void_p, scalars by _C_TYPES."""
+    d = " ".join(decl.replace("*", " * ").split())
+    if "*" in d:
+        return ctypes.c_void_p
+    words = [w for w in d.split(" ") if w != "const"]
+    for n in (2, 1):  # "unsigned int x" / "unsigned x" / "int": the type, then at most one parameter name
+        t = " ".join(words[:n])
+        if t in _C_TYPES and len(words) - n <= 1 and (n == 1 or words[0] == "unsigned"):
+            return _C_TYPES[t]
+    raise AssertionError("%s: no ctypes mapping for '%s'" % (name, decl.strip()))
+
+
+def _prototypes():
+    """name -> (return type, [parameter types]) of every prototype in include/sam6d_hip.h, as the header's text spells them."""
+    txt = open(os.path.join(ROOT, "include", "sam6d_hip.h")).read()
+    txt = re.sub(r"/\*.*?\*/", " ", txt, flags=re.S)
+    txt = re.sub(r"//[^\n]*", " ", txt)
+    txt = re.sub(r"^\s*#.*$", " ", txt, flags=re.M)
+    txt = re.sub(r'extern\s+"C"\s*\{', " ", txt)
+    out = {}
+    for ret, name, args in re.findall(r"([A-Za-z_][A-Za-z0-9_ \*]*?)\b(sam6d_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", txt):
+        assert name not in out, "%s declared twice" % name
+        params = [] if args.strip() in ("", "void") else [a for a in args.split(",")]
+        out[name] = (ret.strip(), params)
+    return out
+
+
+def test_signatures_mirror_the_header_prototypes():
+    """Argument count, every argument's type and the return type of each binding equal the header's prototype (the names alone are
+    compared above).  A pointer is c_void_p; int / long / float / double / size_t / unsigned map to their ctypes."""
+    from sam6d_hip import _lib
+    protos = _prototypes()
+    assert set(protos) == set(_declared()), set(protos) ^ set(_declared())
+    assert len(protos) >= 176
+    lib = _lib.load()
+    for name, (ret, params) in sorted(protos.items()):
+        want_args = [_ctype_of(p, name) for p in params]
+        fn = getattr(lib, name)
+        if ret.replace(" ", "") == "constchar*":
+            want_ret = ctypes.c_char_p
+        else:
+            want_ret = _ctype_of(ret, name)
+        if name in _lib.SIGNATURES:
+            got = _lib.SIGNATURES[name]
+            assert len(got) == len(want_args), "%s: %d arguments bound, %d declared" % (name, len(got), len(want_args))
+            for k, (g, w) in enumerate(zip(got, want_args)):
+                assert g is w, "%s: argument %d bound as %s, declared '%s'" % (name, k, g.__name__, params[k].strip())
+        assert list(fn.argtypes) == want_args, "%s: loaded argtypes differ from the prototype" % name
+        assert fn.restype is want_ret, "%s: restype %s, declared '%s'" % (name, getattr(fn.restype, "__name__", fn.restype), ret)
+
+
 def test_every_declaration_cites_the_reference():
     txt = open(os.path.join(ROOT, "include", "sam6d_hip.h")).read()
     # each entry point's comment names the reference file:line it replaces

@@ -377,6 +377,13 @@ def test_nms_oracle_known_answers():
     assert IO.nms(b, s, 0.49).tolist() == [4, 1, 2]
     assert IO.nms_per_object_id(b, s, torch.tensor([1, 0, 1, 1, 0]), 0.5).tolist() == [4, 1, 0, 2]
     assert IO.nms(b[:0], s[:0], 0.5).tolist() == []
+    # NaN scores of either sign sort first, in index order (scores.sort(stable=True, descending=True)): order 1, 3, 4, 0, 2.
+    # box 1 overlaps 3 and 0 with IoU 81/119 = 0.68 and box 4 with 36/114 -> at 0.5 it kills 3 and 0; at 0.7 it kills neither, 3 stays
+    # and kills its duplicate 0 (IoU 1) but not 4 (IoU exactly 0.5)
+    nan = float("nan")
+    sn = torch.tensor([0.9, nan, 0.7, -nan, 0.95])
+    assert IO.nms(b, sn, 0.5).tolist() == [1, 4, 2]
+    assert IO.nms(b, sn, 0.7).tolist() == [1, 3, 4, 2]
 
 
 def test_small_detection_keep_oracle():
