@@ -1206,6 +1206,32 @@ int sam6d_pose_pair_vsd(const float* vertices, int V, const int* faces, int F, c
                         long total, const float* depth_obs, float delta, const float* taus, int T, float inv_norm, int* counts,
                         int* view_counts, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * All-pairs ADI, capped by the tile bounds (csrc/pairadi.hip over csrc/nearest_walk.h, restated in tests/pair_adi_ref.py).
+ * (New entries only, so SAM6D_ABI_VERSION stays.)
+ * ------------------------------------------------------------------------------------------------------------ */
+/* ADD-S / ADI of every pose a[i] against every pose b[j] of one object, over the model's vertices.  Beside
+ * PEM/run_inference_custom_pytorch.py:460-471, which writes all its poses out unmatched and has no evaluation; beside sam6d_pose_adi,
+ * which scores listed pairs, and sam6d_pose_pair_errors, which gives the other point errors as matrices.  The definition is the
+ * published one, restated by the package and pinned against its numpy restatement, not against bop_toolkit.
+ * points (V,3) f32; a (A,3,4), b (B,3,4) f32 row-major object -> camera; inv_unit > 0, finite; flags as in sam6d_pose_adi.
+ * For a pair that is computed, adi_sum[i][j] i64 is bit for bit what sam6d_pose_adi gives for est = a[i], gt = b[j] (the recipe at the
+ * top of csrc/nearest.hip, one copy of its steps in csrc/nearest_walk.h).  The boxes are built once per pose b[j].
+ * cap_sum >= 0 (the caller's cap as an integer sum: floor(cap * inv_unit * 2^30 * V)): per pair and point e_i = a[i] x_i, lb_i = the
+ * minimum over ALL tiles of b[j] of the tile bound of the skip rule (from +inf, fminf), and lower_sum[i][j] i64 = sum_i of
+ * sam6d_pose_adi's term of lb_i, with the same cap at 2^42 and the same 64-bit integer adds.  lower_sum <= adi_sum holds as integers
+ * (the proof is at the top of csrc/pairadi.hip), and a pair with lower_sum > cap_sum is SKIPPED: skipped[i][j] = 1, adi_sum[i][j] = -1,
+ * its V x V search is never started.  Every other pair has skipped = 0.  cap_sum < 0: no cap; lower_sum is neither read nor written
+ * and may be null.  skipped (A,B) bytes.  64-bit integer atomic adds only: every output is a function of the inputs alone.
+ * V 1 .. 2^20; A, B 1 .. 1024 each and A B ceil(V / 1024) <= 2^22 (the workgroups of a launch); workspace, adi_sum and lower_sum
+ * 8-byte aligned, the workspace at least sam6d_pose_pair_adi_workspace_bytes(V, A, B) = 24 B ceil(V / 256) (the boxes; 0 for sizes
+ * outside the limits); anything else, a null pointer or a non-finite inv_unit returns non-zero without a launch or a write, the
+ * argument named in sam6d_last_error(). */
+size_t sam6d_pose_pair_adi_workspace_bytes(int V, int A, int B);
+int sam6d_pose_pair_adi(const float* points, int V, const float* a, int A, const float* b, int B, float inv_unit, int flags, long cap_sum,
+                        long long* adi_sum, long long* lower_sum, unsigned char* skipped, void* workspace, size_t workspace_bytes,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

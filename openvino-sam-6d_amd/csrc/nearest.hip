@@ -59,38 +59,22 @@
 // before); the tile's g_j are formed once per workgroup into LDS and read from there as broadcasts, nine vector instructions per
 // pair.  At the end one wave_sum and one atomic per wave.  Diameter: nn_walk over the tile pairs (a, b) with b >= a, the column
 // tiles of a row chunk dealt to gridDim.y workgroups so that a small model still fills the chip; one atomic per wave.
+// nn_walk, the lower bound and ADI's walk of one chunk live in nearest_walk.h, because pairadi.hip (ADI of every pose against every
+// pose, sam6d_pose_pair_adi) runs the same walk per pair of the matrix and the same bound to leave far pairs out.
 //
 // WHAT THE HOST CANNOT SEE.  The seed indices are on the device: one outside [0, V) is ignored, never dereferenced.
-#include "poseerr_point.h"
+#include "nearest_walk.h"
 #include "../../include/sam6d_hip.h"
 
-#define NN_MAX_V (1 << 20)
 #define NN_MAX_N 1024
 #define NN_MAX_SEEDS 8
-#define NN_WG 256
-#define NN_PTS 4                    // points per thread
-#define NN_CHUNK (NN_WG * NN_PTS)   // points per workgroup
-#define NN_TILE 256                 // points per box and LDS tile
-#define NN_NO_PRUNE 1               // flags bit 0
 #define NN_INF 0x7f800000u
 #define NN_DIAM_WGS 2048            // the diameter's main launch aims at this many workgroups
 
-// The constants, the guarded point load (pe_load_point), d2 (pe_d2) and the ADD term (pe_add_term) are poseerr_point.h's.
+// The constants, the guarded point load (pe_load_point), d2 (pe_d2) and the ADD term (pe_add_term) are poseerr_point.h's; the sizes,
+// nn_point, the lower bound, nn_walk and ADI's walk of one chunk (nn_adi_chunk) are nearest_walk.h's, which pairadi.hip shares.
 // RECIPE maximum: the word the unsigned maximum of raw d2 bits stands for
 __device__ __forceinline__ unsigned nn_word(unsigned raw) { return raw > NN_INF ? PE_NAN : raw; }
-
-// the point idx under the (3,4) matrix M, or the raw point where M is null; zeros go in beyond V
-__device__ __forceinline__ void nn_point(const float* __restrict__ points, int V, int idx, const float* __restrict__ M, float (&g)[3]) {
-  float x[3];
-  pe_load_point(points, V, idx, x);
-  if (M) {  // (uniform)
-    rs_to_camera(M, x, g);
-  } else {
-    g[0] = x[0];
-    g[1] = x[1];
-    g[2] = x[2];
-  }
-}
 
 // ---------------------------------------------------------------------------------------------------------- the boxes
 // grid (T, N), four waves: point blockIdx.x * 256 + tid under gt[blockIdx.y], or the raw point where gt is null (N = 1).
@@ -121,79 +105,21 @@ __global__ __launch_bounds__(NN_TILE) void nn_boxes_kernel(const float* __restri
   }
 }
 
-// ---------------------------------------------------------------------------------------------------------- the walk
-// THE SKIPPING's protocol for a workgroup of four waves, in one copy.  tiles(s) is the s-th tile of the workgroup's sequence, below 0
-// after the last.  A tile is walked when flags has NN_NO_PRUNE or skips(lo, hi) is false in any thread: whether all of the thread's
-// points can do without a tile whose box is lo, hi (box (T,6), read only then).  point(idx, g) is the tile's point idx as it is
-// staged, and fold(c) takes one staged point into the thread's points.  Every thread of the workgroup calls it, with the same tiles
-template <class Tiles, class Skips, class Point, class Fold>
-__device__ __forceinline__ void nn_walk(int V, const float* __restrict__ box, int flags, Tiles tiles, Skips skips, Point point, Fold fold) {
-  __shared__ float4 tile[NN_TILE];
-  const int tid = threadIdx.x;
-  for (int s = 0, t; (t = tiles(s)) >= 0; ++s) {
-    bool walk = (flags & NN_NO_PRUNE) != 0;
-    if (!walk) {  // (uniform)
-      float lo[3], hi[3];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        lo[k] = box[(size_t)t * 6 + k];
-        hi[k] = box[(size_t)t * 6 + 3 + k];
-      }
-      walk = !skips(lo, hi);
-    }
-    if (!__syncthreads_or(walk)) continue;  // (uniform; the barrier also closes the reads of the tile before)
-    float g[3];
-    point(t * NN_TILE + tid, g);
-    tile[tid] = make_float4(g[0], g[1], g[2], 0.f);
-    __syncthreads();
-    const int cnt = min(NN_TILE, V - t * NN_TILE);
-#pragma unroll 4
-    for (int jj = 0; jj < cnt; ++jj) fold(tile[jj]);
-  }
+int nn_boxes(const char* who, const float* points, int V, const float* gt, int N, float* box, hipStream_t st) {
+  const int T = (V + NN_TILE - 1) / NN_TILE;
+  hipLaunchKernelGGL(nn_boxes_kernel, dim3(T, N), dim3(NN_TILE), 0, st, points, V, gt, T, box);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) sam6d_set_error("%s (boxes): launch failed: %s", who, hipGetErrorString(e));
+  return (int)e;
 }
 
 // ---------------------------------------------------------------------------------------------------------- a. ADI
-// grid (ceil(V / 1024), N), four waves: point blockIdx.x * 1024 + j * 256 + tid for j = 0 .. 3.  adi_sum (N) arrives zeroed
+// grid (ceil(V / 1024), N), four waves: chunk blockIdx.x of pose pair blockIdx.y (nn_adi_chunk).  adi_sum (N) arrives zeroed
 __global__ __launch_bounds__(NN_WG) void nn_adi_kernel(const float* __restrict__ points, int V, const float* __restrict__ est,
                                                        const float* __restrict__ gt, int T, const float* __restrict__ box, float inv_unit,
                                                        int flags, unsigned long long* __restrict__ adi_sum) {
-  const int n = blockIdx.y, tid = threadIdx.x;
-  const float* Gt = gt + (size_t)n * 12;
-  float e[NN_PTS][3], m[NN_PTS];
-  bool live[NN_PTS];
-#pragma unroll
-  for (int j = 0; j < NN_PTS; ++j) {
-    const int idx = blockIdx.x * NN_CHUNK + j * NN_WG + tid;  // below 2^20 + 1024
-    live[j] = idx < V;
-    nn_point(points, V, idx, est + (size_t)n * 12, e[j]);
-    m[j] = INFINITY;
-  }
-  const int first = blockIdx.x * NN_PTS;  // the tile of the workgroup's first point: below T
-  nn_walk(
-      V, box + (size_t)n * T * 6, flags, [&](int s) { return s < T ? (first + s < T ? first + s : first + s - T) : -1; },
-      [&](const float(&lo)[3], const float(&hi)[3]) {
-        bool all = true;
-#pragma unroll
-        for (int j = 0; j < NN_PTS; ++j) {
-          float gap[3];
-#pragma unroll
-          for (int k = 0; k < 3; ++k) gap[k] = fmaxf(fmaxf(e[j][k] - hi[k], lo[k] - e[j][k]), 0.f);  // the gap of the header, without a branch
-          const float lb = (gap[0] * gap[0] + gap[1] * gap[1]) + gap[2] * gap[2];
-          all = all && (!live[j] || lb > m[j]);
-        }
-        return all;
-      },
-      [&](int idx, float(&g)[3]) { nn_point(points, V, idx, Gt, g); },
-      [&](const float4 g) {
-#pragma unroll
-        for (int j = 0; j < NN_PTS; ++j) m[j] = fminf(m[j], pe_d2(e[j], g.x, g.y, g.z));  // m is never a NaN: d2 < m ? d2 : m
-      });
-  long long term = 0;
-#pragma unroll
-  for (int j = 0; j < NN_PTS; ++j)
-    if (live[j]) term += pe_add_term(m[j], inv_unit);
-  term = wave_sum(term);
-  if ((tid & 63) == 0 && term) __hip_atomic_fetch_add(adi_sum + n, (unsigned long long)term, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const int n = blockIdx.y;
+  nn_adi_chunk(points, V, blockIdx.x, est + (size_t)n * 12, gt + (size_t)n * 12, T, box + (size_t)n * T * 6, inv_unit, flags, adi_sum + n);
 }
 
 extern "C" size_t sam6d_pose_adi_workspace_bytes(int V, int N) {
@@ -220,8 +146,7 @@ extern "C" int sam6d_pose_adi(const float* points, int V, const float* est, cons
   SAM6D_MEMSET_CHECK("pose_adi", e);
   const int T = (V + NN_TILE - 1) / NN_TILE;
   float* box = (float*)workspace;
-  hipLaunchKernelGGL(nn_boxes_kernel, dim3(T, N), dim3(NN_TILE), 0, s, points, V, gt, T, box);
-  SAM6D_LAUNCH_CHECK_CONT("pose_adi (boxes)");
+  if (const int bad = nn_boxes("pose_adi", points, V, gt, N, box, s)) return bad;
   hipLaunchKernelGGL(nn_adi_kernel, dim3((V + NN_CHUNK - 1) / NN_CHUNK, N), dim3(NN_WG), 0, s, points, V, est, gt, T, (const float*)box, inv_unit,
                      flags, (unsigned long long*)adi_sum);
   SAM6D_LAUNCH_CHECK("pose_adi (points)");
@@ -316,8 +241,7 @@ extern "C" int sam6d_points_diameter(const float* points, int V, const int* seed
   const hipError_t e = hipMemsetAsync(words, 0, 2 * sizeof(unsigned), s);
   SAM6D_MEMSET_CHECK("points_diameter", e);
   const int T = (V + NN_TILE - 1) / NN_TILE, chunks = (V + NN_CHUNK - 1) / NN_CHUNK;
-  hipLaunchKernelGGL(nn_boxes_kernel, dim3(T, 1), dim3(NN_TILE), 0, s, points, V, (const float*)nullptr, T, box);
-  SAM6D_LAUNCH_CHECK_CONT("points_diameter (boxes)");
+  if (const int bad = nn_boxes("points_diameter", points, V, nullptr, 1, box, s)) return bad;
   hipLaunchKernelGGL(nn_seed_kernel, dim3(T), dim3(NN_WG), 0, s, points, V, seeds, n_seeds, words);
   SAM6D_LAUNCH_CHECK_CONT("points_diameter (seeds)");
   const int want = NN_DIAM_WGS / chunks, Y = want < 1 ? 1 : (want > T ? T : want);

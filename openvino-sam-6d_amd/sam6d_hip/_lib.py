@@ -196,6 +196,8 @@ SIGNATURES = {
     "sam6d_pose_pair_vsd_workspace_bytes": [c_l, c_i, c_i],
     "sam6d_pose_pair_vsd": [c_p, c_i, c_p, c_i, c_p, c_i, c_i] + [c_f] * 4 + [c_i, c_i, c_f, c_i, c_p, c_p, c_l, c_p, c_f, c_p, c_i, c_f,
                             c_p, c_p, c_p, ctypes.c_size_t, c_p],
+    "sam6d_pose_pair_adi_workspace_bytes": [c_i, c_i, c_i],
+    "sam6d_pose_pair_adi": [c_p, c_i, c_p, c_i, c_p, c_i, c_f, c_i, c_l, c_p, c_p, c_p, c_p, ctypes.c_size_t, c_p],
 }
 
 _lib = None

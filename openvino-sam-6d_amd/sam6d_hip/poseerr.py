@@ -268,6 +268,11 @@ def morton_order(points):
     return torch.argsort(_spread10(q[:, 0]) | (_spread10(q[:, 1]) << 1) | (_spread10(q[:, 2]) << 2), stable=True)
 
 
+def _adi_of(adi_sum, inv_unit, V):
+    """adi from its integer sum, the one copy of the expression (adi here, posematch.pair_adi): f32 in the unit of t"""
+    return (adi_sum.to(torch.float64) / ADD_SCALE / inv_unit / V).to(torch.float32)
+
+
 @on_tensor_device
 def _adi(points, est, gt, inv_unit, sort, prune):
     V, N = int(points.shape[0]), int(est.shape[0])
@@ -277,7 +282,7 @@ def _adi(points, est, gt, inv_unit, sort, prune):
     ws = _empty((need // 8,), points, torch.int64)
     adi_sum = _empty((N,), points, torch.int64)
     _lib.call("sam6d_pose_adi", _p(points), V, _p(est), _p(gt), N, inv_unit, 0 if prune else 1, adi_sum.data_ptr(), ws.data_ptr(), need, _s())
-    return AdiErrors((adi_sum.to(torch.float64) / ADD_SCALE / inv_unit / V).to(torch.float32), adi_sum)
+    return AdiErrors(_adi_of(adi_sum, inv_unit, V), adi_sum)
 
 
 def adi(mesh_or_points, R_est, t_est, R_gt, t_gt, scale=1.0, unit=None, sort=True, prune=True):

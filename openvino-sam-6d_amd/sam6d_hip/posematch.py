@@ -14,17 +14,24 @@ pair_vsd is the third BOP error as a matrix: poseerr.vsd's counts for every (i, 
 (csrc/vsdpairs.hip, restated in tests/vsdpairs_ref.py), and vsd_matches runs match_poses on it once per tolerance -- with
 instance_recall that is AR_VSD, beside the AR_MSSD and AR_MSPD that pair_errors' matrices give.
 
-Poses of different objects are separate calls, one mesh each (INTEGRATION.md has the loop over template_ids).  Left to the caller:
-symmetry-aware ADI, ADI as a matrix, several meshes in one call, BOP's file formats and threshold lists.
+pair_adi is ADD-S / ADI as a matrix: poseerr.adi's integer for every (i, j), bit for bit (csrc/pairadi.hip over the walk of
+csrc/nearest.hip, restated in tests/pair_adi_ref.py), and with a cap the pairs whose tile bounds already put them above it are
+answered +inf without their V x V search.  nms_poses_adi removes duplicate poses by it: ADI sees through a symmetry that nobody
+annotated, which MSSD without syms does not.  ADI is evaluated over the vertices, and is not pinned against bop_toolkit either.
 
-Imports poseerr, verify, runtime, _lib and torch only; the library is loaded at the first launch, not at import.  There is no
+Poses of different objects are separate calls, one mesh each (INTEGRATION.md has the loop over template_ids).  Left to the caller:
+symmetry-aware ADI, several meshes in one call, BOP's file formats and threshold lists.
+
+Imports poseerr, verify, runtime, _lib, torch and math only; the library is loaded at the first launch, not at import.  There is no
 CPU route: a CPU tensor raises RuntimeError.
 """
+import math
+
 import torch
 
 from . import _lib, verify
 from .poseerr import ADD_SCALE, MAX_POINTS, PoseErrors, _errors, _intrinsics, _inv_unit, _points, _same_device, _syms  # noqa: F401
-from .poseerr import MAX_TAUS, _c_floats, _tolerances, vsd_from_counts
+from .poseerr import MAX_TAUS, _adi_of, _c_floats, _tolerances, morton_order, vsd_from_counts
 from .runtime import _empty, _p, _s, on_tensor_device
 from .verify import NEAR, _tensor
 
@@ -33,6 +40,8 @@ MAX_TRIPLES = 1 << 22        # A B S: a workspace of 8 bytes per triple, 32 MiB 
 MAX_THRESHOLDS = 64
 MAX_VSD_WORDS = 1 << 28      # pair_vsd: the window words of all A + B views, a z-buffer of 2 GiB at most
 NO_MSPD = 1                  # sam6d_pose_pair_errors flags bit 0
+MAX_ADI_WORKGROUPS = 1 << 22 # pair_adi: A B ceil(V / 1024), the workgroups of one launch
+ADI_NMS_MARGIN = 2.0 ** -20  # nms_poses_adi: cap = thresh * (1 + margin)
 
 
 class PairErrors(PoseErrors):
@@ -63,13 +72,13 @@ class PoseNms:
 
 
 # ------------------------------------------------------------------------------------------------------------ pair errors
-def _poses(name, what, R, t):
+def _poses(name, what, R, t, least=1):
     if not torch.is_tensor(R) or R.dim() != 3:
         raise ValueError("%s: R_%s must be an (N,3,3) float32 tensor" % (name, what))
     N = int(R.shape[0])
     R, t = _tensor(R, name, "R_" + what, torch.float32, (N, 3, 3)), _tensor(t, name, "t_" + what, torch.float32, (N, 3))
-    if not 1 <= N <= MAX_POSES:
-        raise ValueError("%s: R_%s: %s = %d is not in 1 .. %d" % (name, what, what.upper(), N, MAX_POSES))
+    if not least <= N <= MAX_POSES:
+        raise ValueError("%s: R_%s: %s = %d is not in %d .. %d" % (name, what, what.upper(), N, least, MAX_POSES))
     return R, t
 
 
@@ -217,6 +226,103 @@ def nms_poses(mesh_or_points, R, t, scores, thresh, syms=None, scale=1.0):
     -> (PoseNms, the (N,N) mssd matrix)."""
     mssd = pair_errors(mesh_or_points, R, t, R, t, K=None, syms=syms, scale=scale).mssd
     return pose_nms(mssd, scores, thresh), mssd
+
+
+# ------------------------------------------------------------------------------------------------------------ ADI as a matrix
+class PairAdi:
+    """What pair_adi returns; every tensor is on the device and (A,B): row i the pose a[i], column j the pose b[j].  adi f32 in the
+    unit of t and adi_sum i64 the integer it is formed from, poseerr.AdiErrors' fields for est = a[i], gt = b[j]; lower_sum i64 the
+    tile bounds' sum that never exceeds adi_sum (None without a cap); skipped bool: the pair is above the cap by its lower_sum, its
+    adi is +inf and its adi_sum -1."""
+
+    def __init__(self, adi, adi_sum, lower_sum, skipped):
+        self.adi, self.adi_sum, self.lower_sum, self.skipped = adi, adi_sum, lower_sum, skipped
+
+
+def _cap_sum(name, cap, inv_unit, V):
+    """the cap as the integer the kernels compare lower_sum with: floor(cap * inv_unit * 2^30 * V) in float64, at most 2^63 - 1"""
+    cap = float(cap)
+    if not (cap >= 0.0 and math.isfinite(cap)):
+        raise ValueError("%s: cap = %r is not a finite number >= 0" % (name, cap))
+    x = ((cap * inv_unit) * ADD_SCALE) * V
+    return (1 << 63) - 1 if x >= 2.0 ** 63 else int(math.floor(x))
+
+
+@on_tensor_device
+def _pair_adi(points, a, b, inv_unit, cap_sum, sort, prune):
+    V, A, B = int(points.shape[0]), int(a.shape[0]), int(b.shape[0])
+    if sort:
+        points = points[morton_order(points)].contiguous()
+    need = int(_lib.load().sam6d_pose_pair_adi_workspace_bytes(V, A, B))
+    ws = _empty((need // 8,), points, torch.int64)
+    adi_sum, skipped = _empty((A, B), points, torch.int64), _empty((A, B), points, torch.bool)
+    lower_sum = _empty((A, B), points, torch.int64) if cap_sum >= 0 else None
+    _lib.call("sam6d_pose_pair_adi", _p(points), V, _p(a), A, _p(b), B, inv_unit, 0 if prune else 1, cap_sum, adi_sum.data_ptr(),
+              None if lower_sum is None else lower_sum.data_ptr(), skipped.data_ptr(), ws.data_ptr(), need, _s())
+    adi = torch.where(skipped, torch.full_like(adi_sum, float("inf"), dtype=torch.float32), _adi_of(adi_sum, inv_unit, V))
+    return PairAdi(adi, adi_sum, lower_sum, skipped)
+
+
+def pair_adi(mesh_or_points, R_a, t_a, R_b, t_b, scale=1.0, unit=None, cap=None, sort=True, prune=True):
+    """ADD-S / ADI of every pose a[i] against every pose b[j] of one object, over the model's vertices: for every (i, j) that is
+    computed, bit for bit, what poseerr.adi gives for est = a[i], gt = b[j].  The roles are not symmetric (the nearest vertex is
+    searched under b[j]), so pair_adi(.., a, b) is not the transpose of pair_adi(.., b, a).  No symmetry transforms are needed or
+    applied; nothing is pinned against bop_toolkit.
+
+    mesh_or_points, scale, unit, sort and prune as poseerr.adi has them; R_a (A,3,3), t_a (A,3), R_b (B,3,3), t_b (B,3) f32 HIP
+    tensors, A and B 0 .. 1024 each, V 1 .. 2^20, and A B ceil(V / 1024) at most 2^22 (the workgroups of one launch: split a or b, or
+    pass fewer vertices).  An empty side gives empty tensors without a launch.
+    cap: a distance in the unit of t, or None.  With a cap, every pair gets lower_sum, the sum of the terms of each vertex's
+    distance to the nearest tile box of b[j]: V / 256 box tests per vertex where the search costs V distances.  lower_sum <=
+    adi_sum holds exactly (csrc/pairadi.hip has the proof), so a pair whose lower_sum is above floor(cap * (1 / unit) * 2^30 * V) has
+    an ADI above the cap: it is skipped, its search is never started, skipped is True, adi +inf and adi_sum -1.  Every other pair is
+    computed in full, also where its ADI turns out above the cap.  Use it where only errors below a threshold matter: for
+    match_poses under the ADD(-S) protocol pass cap = the largest threshold * (1 + 2^-20) (nms_poses_adi derives the margin), and
+    the matching is the uncapped matrix's.  For a dense mesh pass a subset of the vertices (ops.furthest_point_sampling): the cost of
+    a computed pair grows with V^2.
+    Neither sort nor prune changes a bit of any output; lower_sum belongs to the tiles of the order the search runs in (sorted or
+    as given).  There is no read-back.
+    -> PairAdi: adi (A,B) f32, adi_sum (A,B) i64, lower_sum (A,B) i64 or None, skipped (A,B) bool.
+    A CPU tensor raises RuntimeError; a wrong shape or dtype ValueError naming the argument, and so does a cap that is negative or
+    not finite."""
+    name = "pair_adi"
+    R_a, t_a = _poses(name, "a", R_a, t_a, least=0)
+    R_b, t_b = _poses(name, "b", R_b, t_b, least=0)
+    points = _points(name, mesh_or_points, R_a)
+    inv_unit = _inv_unit(name, unit)
+    V, A, B = int(points.shape[0]), int(R_a.shape[0]), int(R_b.shape[0])
+    cap_sum = -1 if cap is None else _cap_sum(name, cap, inv_unit, V)
+    groups = A * B * ((V + 1023) // 1024)
+    if groups > MAX_ADI_WORKGROUPS:
+        raise ValueError("%s: A B ceil(V / 1024) = %d x %d x %d = %d is above the cap of %d workgroups a launch: split a or b, or pass fewer "
+                         "vertices" % (name, A, B, (V + 1023) // 1024, groups, MAX_ADI_WORKGROUPS))
+    _device_only(name, points, R_a, t_a, R_b, t_b)
+    _same_device(name, points, (("R_a", R_a), ("t_a", t_a), ("R_b", R_b), ("t_b", t_b)))
+    if A == 0 or B == 0:
+        dev = points.device
+        return PairAdi(torch.empty((A, B), dtype=torch.float32, device=dev), torch.empty((A, B), dtype=torch.int64, device=dev),
+                       None if cap is None else torch.empty((A, B), dtype=torch.int64, device=dev), torch.empty((A, B), dtype=torch.bool, device=dev))
+    return _pair_adi(points, verify.pose_views(R_a, t_a, scale), verify.pose_views(R_b, t_b, scale), inv_unit, cap_sum, bool(sort), bool(prune))
+
+
+def nms_poses_adi(mesh_or_points, R, t, scores, thresh, scale=1.0, unit=None):
+    """pose_nms on the ADI of the poses against themselves, capped just above thresh: duplicate poses of an object whose symmetries
+    nobody annotated (a CAD file without models_info.json) are the same pose under ADI, where nms_poses without syms keeps both.
+    thresh is a length in the unit of t, at least 0 (a fraction of the model's diameter is a good one); the other arguments as
+    pair_adi and pose_nms have them.  -> (PoseNms, the (N,N) adi matrix, +inf where a pair was skipped).
+
+    What is kept is what pose_nms keeps on the uncapped matrix.  The cap is thresh * (1 + 2^-20).  A skipped pair has adi_sum >=
+    cap_sum + 1, and cap_sum + 1 is above the float64 product cap * inv_unit * 2^30 * V that floor() cut, which is off from the real
+    product by a few units of 2^-53 relative.  The adi that pair_adi would report is fl32 of the float64 quotient adi_sum / 2^30 /
+    inv_unit / V, again a few 2^-53 off: it is at least cap * (1 - 2^-50) > thresh, and rounding to float32 (2^-24) is monotone, so
+    the reported adi is not below fl32(thresh), the number pose_nms compares with.  pose_nms asks err < thresh, strictly: +inf in the
+    place of such an entry never changes an answer."""
+    name = "nms_poses_adi"
+    thresh = float(thresh)
+    if not (thresh >= 0.0 and math.isfinite(thresh)):
+        raise ValueError("%s: thresh = %r is not a finite number >= 0" % (name, thresh))
+    adi = pair_adi(mesh_or_points, R, t, R, t, scale=scale, unit=unit, cap=thresh * (1.0 + ADI_NMS_MARGIN)).adi
+    return pose_nms(adi, scores, thresh), adi
 
 
 # ------------------------------------------------------------------------------------------------------------ VSD as a matrix
